@@ -11,6 +11,10 @@ base + global frame index as in tools/test_waveform_simple.cpp).  N>1: `python -
 are sharded over ranks (weak scaling, per-GPU batch fixed), RCCL only broadcasts the seed and
 all-reduces counters/timing.
 
+A plain run sets up, warms up, times --steps steps and prints the line; --dump-outputs DIR also writes what the last timed
+step returned (a fixed sample of its frames, see dump_outputs).  --full adds what takes work of its own: the last step's
+correctness counters, the per-kernel timing and roofline figures, and the CPU baseline.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -37,6 +41,8 @@ RECOVERY_STAGE = ("recovery_list_kernel", "recovery_stage1_kernel", "recovery_fi
 DEMOD_STAGE = ("demod_fft_kernel", "demod_decide_kernel", "demod_walk_kernel", "demod_est_kernel", "demod_frames_kernel")
 DECODE_STAGE = ("fast_primary_kernel", "fast_mark_kernel", "fast_stage_kernel", "fast_phase0_kernel", "fast_chain_kernel",
                 "fast_cascade_kernel", "fast_finalize_kernel", "frame_validate_kernel", "dual_phase0_kernel", "dual_cascade_kernel")
+DUMP_FRAMES = 65536       # frames of the last step --dump-outputs writes: 65536 x 174 float32 + 65536 float64 = 46 MB
+DUMP_SEED = 1             # fixes which frames those are, for every build and run
 
 
 def host_cores():
@@ -135,6 +141,26 @@ def cpu_baseline(frames_host, seconds_budget=20.0):
                       f"decodeFixedFrame incl. retry cascade and CRC recovery"}
 
 
+def dump_outputs(out_dir, e, out, first_frame):
+    """What ria_gpu_rx_batch returned in the last timed step, as DIR/<name>.npy: the payload bytes and every field of the
+    decode status (engine.DECODE_STATUS) as float32, for a fixed sample of DUMP_FRAMES frames (all of them in a smaller
+    batch), and frame_index (float64), the global index of each sampled frame."""
+    import torch
+    B = out[0].shape[0]
+    rows = np.arange(B) if B <= DUMP_FRAMES else np.sort(np.random.default_rng(DUMP_SEED).choice(B, DUMP_FRAMES, replace=False))
+    sel = rows.astype(np.int64)
+    idx = torch.from_numpy(sel).to(out[0].device)
+    arrays = {"frame_index": (first_frame + sel).astype(np.float64),
+              "payload": out[0].index_select(0, idx).cpu().numpy().astype(np.float32)}
+    st = e.decode_status(out[1].index_select(0, idx))
+    for name in st.dtype.names:
+        arrays[name] = st[name].astype(np.float32)
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main(argv=None, engine_factory=None):
     """engine_factory: tests/test_bench_gloo.py passes a CPU stand-in for RxEngine to run this function's N > 1 control
     flow (seed broadcast, global frame indices, barrier, max-over-ranks time, counter all-reduce, rank-0 JSON line) with
@@ -147,14 +173,16 @@ def main(argv=None, engine_factory=None):
     ap.add_argument("--channel", type=int, default=2, help="0 awgn 1 good 2 moderate 3 poor 4 flutter")
     ap.add_argument("--snr", type=float, default=20.0)
     ap.add_argument("--seed", type=int, default=20261004)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--steps-only", action="store_true",
-                    help="profiling passes: only the warm-up + timed steps run on the GPU (no per-kernel timing section, no CPU leg), "
-                         "so that a counter summed over the run divides by warmup + steps")
+    ap.add_argument("--full", action="store_true",
+                    help="also the last step's correctness counters, per-kernel timing + roofline and the CPU baseline; without it "
+                         "only the warm-up + timed steps run on the GPU, so that a counter summed over a profiled run divides by warmup + steps")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0's frames) as DIR/<name>.npy")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     stub = engine_factory is not None
-    if stub:
-        args.steps_only = True
 
     import torch
     import torch.distributed as dist
@@ -235,11 +263,17 @@ def main(argv=None, engine_factory=None):
     barrier()
     elapsed = time.perf_counter() - t0
 
-    # correctness counters of the last step (outside the timed region)
-    st = e.decode_status(out[1])
-    frames_ok = int((st["cw_ok"].all(axis=1) & st["frame_valid"].astype(bool)).sum())
-    bytes_ok = int((out[0] == infos[(n_sets - 1) % n_pool]).all(dim=1).sum().item())
-    cnt = torch.tensor([B * args.steps, frames_ok, bytes_ok, int(st["iterations"].sum())], dtype=torch.int64, device=cdev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, e, out, ((n_sets - 1) % n_pool * world + rank) * B)
+
+    counts = [B * args.steps]
+    if args.full:
+        # correctness counters of the last step (outside the timed region)
+        st = e.decode_status(out[1])
+        frames_ok = int((st["cw_ok"].all(axis=1) & st["frame_valid"].astype(bool)).sum())
+        bytes_ok = int((out[0] == infos[(n_sets - 1) % n_pool]).all(dim=1).sum().item())
+        counts += [frames_ok, bytes_ok, int(st["iterations"].sum())]
+    cnt = torch.tensor(counts, dtype=torch.int64, device=cdev)
     tmax = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
     if collectives:
         dist.all_reduce(cnt, op=dist.ReduceOp.SUM)
@@ -250,7 +284,7 @@ def main(argv=None, engine_factory=None):
     # live per-kernel durations with HIP events on the stream the kernels are launched on
     # (torch's current stream is the stream handed to the C ABI).
     t_demod = t_decode = None
-    if not args.steps_only:
+    if args.full and not stub:
         x = batches[-1]
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
         llr, _ = e.demod(x, want_status=False)
@@ -356,12 +390,13 @@ def main(argv=None, engine_factory=None):
                             f"{total_frames} frames ({B} per step per GPU), full decodeFixedFrame",
                 "frame_samples": int(e.geo.frame_samples), "batch_per_gpu": B,
                 "channel": args.channel, "snr_db": args.snr,
-                "frames_decoded_last_step": int(cnt[1].item()), "frames_bytes_equal_tx_last_step": int(cnt[2].item()),
-                "fused_path_GBps": round(total_frames / elapsed * ALGO_BYTES_FRAME / 1e9, 2),
             },
             "roofline": roof,
         }
-        if world == 1 and not args.no_cpu_baseline and not args.steps_only:
+        if args.full:
+            res["config"].update(frames_decoded_last_step=int(cnt[1].item()), frames_bytes_equal_tx_last_step=int(cnt[2].item()))
+        res["config"]["fused_path_GBps"] = round(total_frames / elapsed * ALGO_BYTES_FRAME / 1e9, 2)
+        if world == 1 and args.full and not args.no_cpu_baseline and not stub:
             # bounded sample of the same workload: the last batch, as many of its frames as the host cores finish in ~20 s
             res["cpu_baseline"] = cpu_baseline(batches[-1][:24576].cpu().numpy(), seconds_budget=20.0)
         else:

@@ -3,7 +3,8 @@
 deterministic CPU stand-in whose outputs are functions of the GLOBAL frame / buffer content only.  What must hold for
 N > 1: every rank works on its own global indices, rank 0's seed is the one used, the counters all-reduce to the sums
 of the 1-rank runs over the same global indices, the time is the max over ranks, only rank 0 prints.
-(The config-5 driver's sharding is sweep.run_sweep, covered by tests/test_sweep_gloo.py.)"""
+(The config-5 driver's sharding is sweep.run_sweep, covered by tests/test_sweep_gloo.py.)  The same stand-in runs bench.py's
+plain one-rank path with --dump-outputs."""
 import json
 import os
 import socket
@@ -80,7 +81,8 @@ def _bench_worker(rank, world, port, q):
         made.append(StubEngine(batch))
         return made[-1]
     # rank 1 is started with a different --seed: only rank 0's may count
-    res = bench.main(["--gpus", str(world), "--steps", "3", "--warmup", "1", "--batch", "500", "--seed", str(777 if rank == 0 else 5)], factory)
+    res = bench.main(["--gpus", str(world), "--steps", "3", "--warmup", "1", "--batch", "500", "--seed", str(777 if rank == 0 else 5), "--full"],
+                     factory)
     q.put((rank, res, made[0].rx_calls, made[0].seed))
 
 
@@ -120,6 +122,37 @@ def test_bench_control_flow_world_size_2():
     assert res0["config"]["frames_decoded_last_step"] == exp_ok == res0["config"]["frames_bytes_equal_tx_last_step"]
     assert res0["cpu_baseline"] is None and res0["vs_baseline"] is None
     json.dumps(res0)
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path, monkeypatch):
+    """One rank, no --full: --steps timed steps after --warmup, the line without the --full figures, and --dump-outputs
+    writing the last step's payload + decode-status fields for the frames of the fixed sample, the same in every run."""
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "RIA_BENCH_FORCE_DIST", "RIA_BENCH_REHEARSE"):
+        monkeypatch.delenv(k, raising=False)
+    import bench
+    B, steps, warm = 70000, 2, 1
+    monkeypatch.setattr(bench, "DUMP_FRAMES", 4096)
+    runs = []
+    for d in ("a", "b"):
+        made = []
+        res = bench.main(["--steps", str(steps), "--warmup", str(warm), "--batch", str(B), "--seed", "31", "--dump-outputs",
+                          str(tmp_path / d)], lambda batch: made.append(StubEngine(batch)) or made[-1])
+        runs.append({f.name[:-4]: np.load(f) for f in sorted((tmp_path / d).glob("*.npy"))})
+        assert len(made[0].rx_calls) == steps + warm
+    assert res["steps"] == steps and abs(res["value"] - B * steps / (res["ms_per_step"] * steps * 1e-3)) < 0.05 * res["value"]
+    assert res["roofline"] is None and res["cpu_baseline"] is None and "frames_decoded_last_step" not in res["config"]
+    a = runs[0]
+    assert sorted(a) == sorted(["frame_index", "payload"] + list(DSTAT.names))
+    assert all(v.dtype == (np.float64 if k == "frame_index" else np.float32) for k, v in a.items())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert all(np.array_equal(a[k], runs[1][k]) for k in a)
+    idx = a["frame_index"].astype(np.int64)
+    last = (steps + warm - 1) * B                      # first global frame of the last step's batch
+    assert len(idx) == 4096 and len(np.unique(idx)) == 4096 and idx.min() >= last and idx.max() < last + B
+    good = (StubEngine._h(31, idx) % 5) != 0
+    exp = np.stack([StubEngine(1).make_frames(31, int(i), 1).numpy()[0] for i in idx]) * good[:, None]
+    assert np.array_equal(a["payload"], exp.astype(np.float32))
+    assert np.array_equal(a["frame_valid"], good.astype(np.float32)) and np.array_equal(a["iterations"][:, 0], (idx % 7).astype(np.float32))
 
 
 class StubSync:

@@ -44,6 +44,23 @@ def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
+def reference_answers(golden, key, n, live):
+    """The compiled unmodified reference's answers (a dict of arrays over n frames / buffers) for one test's inputs: from the
+    library itself where oracle/_ref is present, else as recorded from it on the same inputs in
+    tests/golden/ref_library_parity.npz (entries '<key>__<name>').  RIA_RECORD_REF_PARITY=DIR writes each live answer
+    to DIR/<key>.npz, the pieces that file is merged from."""
+    if po.Ref.available():
+        ans = live()
+        if os.environ.get("RIA_RECORD_REF_PARITY"):
+            os.makedirs(os.environ["RIA_RECORD_REF_PARITY"], exist_ok=True)
+            np.savez_compressed(os.path.join(os.environ["RIA_RECORD_REF_PARITY"], key + ".npz"), **ans)
+        return ans
+    g = golden("ref_library_parity")
+    ans = {k[len(key) + 2:]: g[k] for k in g.files if k.startswith(key + "__")}
+    assert ans and all(len(v) == n for v in ans.values()), f"tests/golden/ref_library_parity.npz holds no answers for {key} x {n}"
+    return ans
+
+
 def test_native_library_is_loaded():
     from ria_amd import capi
     L = capi.load()
@@ -428,15 +445,11 @@ def test_cox_sync_matches_oracle_batch(oracle, golden):
 
 def test_cox_sync_vs_the_reference_library(golden):
     """Schmidl-Cox searchForSync on 320 capture buffers (two pilot layouts, random offsets / SNR / CFO, tone bursts and
-    truncated preambles in front, noise-only buffers) decided by the GPU and by the UNMODIFIED reference (oracle/_ref)
-    on the host cores: found / position / CFO / noise floor must agree bit for bit."""
+    truncated preambles in front, noise-only buffers) decided by the GPU and by the UNMODIFIED reference (oracle/_ref, or
+    its answers recorded on these buffers) on the host cores: found / position / CFO / noise floor must agree bit for bit."""
     import threading
     import gen_golden
-    if not po.Ref.available():
-        pytest.skip("oracle/_ref/libria_ref.so not present on this box")
     g = golden("cox_sync")
-    ref = po.Ref()
-    ref.cox_search(np.zeros(12000, np.float32))          # static-table warm-up before threading
     rng = np.random.default_rng(4711)
     for mod, rate, pm, pr, tx in (("QAM16", "R1_2", po.QAM16, po.R1_2, g["tx"]), ("DQPSK", "R1_4", po.DQPSK, po.R1_4, g["preamble_dqpsk_r14"])):
         e = engine(mod, rate)
@@ -450,15 +463,21 @@ def test_cox_sync_vs_the_reference_library(golden):
             X[t], _ = gen_golden.cox_buffer(tx, case, 5000 + t)
             nf[t] = (0.0, 0.0, 3e-4)[t % 3]
         out = _cox_fields(e.sync_cox(dev(X), 0.8, dev(nf)))
-        exp = np.zeros((n, 4), np.float32)
 
-        def work(lo, hi):
-            for i in range(lo, hi):
-                o3, nfa = ref.cox_search(X[i], 0.8, float(nf[i]), pm, pr)
-                exp[i, :3] = o3; exp[i, 3] = nfa
-        nt = 16
-        th = [threading.Thread(target=work, args=(k * n // nt, (k + 1) * n // nt)) for k in range(nt)]
-        [t.start() for t in th]; [t.join() for t in th]
+        def live():
+            ref = po.Ref()
+            ref.cox_search(np.zeros(12000, np.float32))          # static-table warm-up before threading
+            exp = np.zeros((n, 4), np.float32)
+
+            def work(lo, hi):
+                for i in range(lo, hi):
+                    o3, nfa = ref.cox_search(X[i], 0.8, float(nf[i]), pm, pr)
+                    exp[i, :3] = o3; exp[i, 3] = nfa
+            nt = 16
+            th = [threading.Thread(target=work, args=(k * n // nt, (k + 1) * n // nt)) for k in range(nt)]
+            [t.start() for t in th]; [t.join() for t in th]
+            return {"found_pos_cfo_floor": exp}
+        exp = reference_answers(golden, f"cox_{mod}_{rate}", n, live)["found_pos_cfo_floor"]
         bad = [i for i in range(n) if not np.array_equal(out[i].view(np.uint32), exp[i].view(np.uint32))]
         assert not bad, (mod, len(bad), bad[:5], out[bad[0]], exp[bad[0]])
         assert n // 3 <= int(exp[:, 0].sum()) < n
@@ -697,14 +716,35 @@ def test_burst_interleaver_matches_reference_permutation(golden):
         assert np.array_equal(np.packbits(back.astype(np.uint8), axis=1), exp)
 
 
-def test_thousands_of_bench_frames_vs_the_reference_library():
-    """2 048 frames of the bench workload decoded by the GPU and by the UNMODIFIED reference (oracle/_ref,
-    compiled from /root/reference in the build container and shipped as a .so) on the host cores: payload bytes
-    and per-codeword success must agree frame for frame (rare paths included: CRC recovery stage 2, the 0xD5
-    reassembly quirk, factor leak)."""
+def reference_decode_answers(golden, key, pm, pr, bpc, bps, y):
+    """decodeFixedFrame of the reference after its own rx_process on every frame of y, on the host cores: per-codeword
+    success and the decoded bytes of the codewords it decoded (zero elsewhere)."""
     import threading
-    if not po.Ref.available():
-        pytest.skip("oracle/_ref/libria_ref.so not present on this box")
+    n = len(y)
+
+    def live():
+        ref = po.Ref()
+        ref.rx_process(pm, pr, y[0])          # static-table warm-up before threading
+        exp_d = np.zeros((n, 4 * bpc), np.uint8); exp_ok = np.zeros((n, 4), np.uint8)
+
+        def work(lo, hi):
+            for f in range(lo, hi):
+                llr = ref.rx_process(pm, pr, y[f])[0]
+                d, ok = ref.decode_fixed_frame(llr, pr, True, bps)
+                exp_d[f] = d[:4 * bpc]; exp_ok[f] = ok
+        nt = 16
+        th = [threading.Thread(target=work, args=(k * n // nt, (k + 1) * n // nt)) for k in range(nt)]
+        [t.start() for t in th]; [t.join() for t in th]
+        return {"cw_ok": exp_ok, "bytes": exp_d * np.repeat(exp_ok != 0, bpc, axis=1)}
+    ans = reference_answers(golden, key, n, live)
+    return ans["bytes"], ans["cw_ok"]
+
+
+def test_thousands_of_bench_frames_vs_the_reference_library(golden):
+    """2 048 frames of the bench workload decoded by the GPU and by the UNMODIFIED reference (oracle/_ref, compiled
+    from the reference's sources and shipped as a .so, or its answers recorded on these frames) on the host cores: payload
+    bytes and per-codeword success must agree frame for frame (rare paths included: CRC recovery stage 2, the 0xD5
+    reassembly quirk, factor leak)."""
     e = engine("QAM16", "R1_2")
     import os
     n, seed, first = int(os.environ.get("RIA_BIG_SAMPLE", "2048")), 20261004, 25000 * 2 + 4096
@@ -713,19 +753,7 @@ def test_thousands_of_bench_frames_vs_the_reference_library():
     e.channel_exact_(x, 2, 20.0, seed, first_frame=first)
     out, st = e.rx(x)
     out, s = out.cpu().numpy(), e.decode_status(st)
-    y = x.cpu().numpy()
-    ref = po.Ref()
-    ref.rx_process(po.QAM16, po.R1_2, y[0])          # static-table warm-up before threading
-    exp_d = np.zeros((n, 160), np.uint8); exp_ok = np.zeros((n, 4), np.uint8)
-
-    def work(lo, hi):
-        for f in range(lo, hi):
-            llr = ref.rx_process(po.QAM16, po.R1_2, y[f])[0]
-            d, ok = ref.decode_fixed_frame(llr, po.R1_2, True, 188)
-            exp_d[f] = d[:160]; exp_ok[f] = ok
-    nt = 16
-    th = [threading.Thread(target=work, args=(k * n // nt, (k + 1) * n // nt)) for k in range(nt)]
-    [t.start() for t in th]; [t.join() for t in th]
+    exp_d, exp_ok = reference_decode_answers(golden, "bench_QAM16_R1_2", po.QAM16, po.R1_2, 40, 188, x.cpu().numpy())
     # CodewordStatus of the reference after recovery: a recovered frame reports all codewords decoded
     bad = [f for f in range(n) if not np.array_equal(s["cw_ok"][f], exp_ok[f])]
     assert not bad, f"{len(bad)} frames differ in codeword success, first {bad[:5]}"
@@ -740,13 +768,11 @@ def test_thousands_of_bench_frames_vs_the_reference_library():
     ("DBPSK", "R1_4", 2, 4.0), ("DQPSK", "R1_4", 2, 7.0), ("DQPSK", "R1_2", 3, 12.0), ("QPSK", "R1_2", 2, 11.0),
     ("D8PSK", "R1_2", 1, 16.0), ("QAM16", "R3_4", 1, 21.0), ("QAM32", "R3_4", 0, 19.0), ("QAM64", "R3_4", 1, 27.0),
     ("QAM16", "R2_3", 4, 22.0), ("QAM64", "R5_6", 0, 24.0), ("BPSK", "R1_2", 2, 8.0)])
-def test_other_modes_vs_the_reference_library(mod, rate, kind, snr):
-    """The same frame-for-frame comparison with the unmodified reference (oracle/_ref) for the other modulation /
-    code-rate modes at marginal SNRs on AWGN and the Watterson presets: generated frames -> TX -> reference-identical
-    channel -> full RX chain; per-codeword success and decoded bytes must agree for every frame."""
-    import threading
-    if not po.Ref.available():
-        pytest.skip("oracle/_ref/libria_ref.so not present on this box")
+def test_other_modes_vs_the_reference_library(golden, mod, rate, kind, snr):
+    """The same frame-for-frame comparison with the unmodified reference (oracle/_ref, or its answers recorded on these
+    frames) for the other modulation / code-rate modes at marginal SNRs on AWGN and the Watterson presets: generated
+    frames -> TX -> reference-identical channel -> full RX chain; per-codeword success and decoded bytes must agree for
+    every frame."""
     from ria_amd import capi
     e = engine(mod, rate)
     pm, pr = capi.MOD[mod], capi.RATE[rate]
@@ -757,19 +783,7 @@ def test_other_modes_vs_the_reference_library(mod, rate, kind, snr):
     e.channel_exact_(x, kind, snr, seed, first_frame=first)
     out, st = e.rx(x)
     out, s = out.cpu().numpy(), e.decode_status(st)
-    y = x.cpu().numpy()
-    ref = po.Ref()
-    ref.rx_process(pm, pr, y[0])
-    exp_d = np.zeros((n, 4 * bpc), np.uint8); exp_ok = np.zeros((n, 4), np.uint8)
-
-    def work(lo, hi):
-        for f in range(lo, hi):
-            llr = ref.rx_process(pm, pr, y[f])[0]
-            d, ok = ref.decode_fixed_frame(llr, pr, True, bps)
-            exp_d[f] = d[:4 * bpc]; exp_ok[f] = ok
-    nt = 16
-    th = [threading.Thread(target=work, args=(k * n // nt, (k + 1) * n // nt)) for k in range(nt)]
-    [t.start() for t in th]; [t.join() for t in th]
+    exp_d, exp_ok = reference_decode_answers(golden, f"modes_{mod}_{rate}_{kind}_{snr:g}", pm, pr, bpc, bps, x.cpu().numpy())
     bad = [f for f in range(n) if not np.array_equal(s["cw_ok"][f], exp_ok[f])]
     assert not bad, f"{len(bad)} frames differ in codeword success, first {bad[:5]}"
     for f in range(n):

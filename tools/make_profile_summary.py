@@ -6,7 +6,7 @@ import collections, csv, glob, json, os, shutil, sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, root)
 from ria_amd.srchash import csrc_sha256  # noqa: E402
-# the PMC passes run `bench.py --steps-only --steps 1 --warmup 1`: two whole steps and nothing else on the GPU
+# the PMC passes run a plain `bench.py --steps 1 --warmup 1`: two whole steps and nothing else on the GPU
 BATCH = int(os.environ.get("RIA_PROFILE_BATCH", "100000"))   # bench.py's default frames per step
 META = {"tag": None, "source_sha256": csrc_sha256(), "steps_counted": 2, "frames_per_step": BATCH, "frames_per_launch": BATCH,
         "note": "source_sha256 = sha256 over ria_amd/csrc/* at the time of the measurement (ria_amd/srchash.py); bench.py quotes "
@@ -73,9 +73,9 @@ del sq["_meta"]
 rows = list(csv.DictReader(open(os.path.join(P, f"{tag}_bench_kernel_stats.csv"))))
 L = [f"# {tag} — bench, kernel trace and PMC summaries\n",
      "Commands (MI355X box, repo root, after `cd /tmp && export TMPDIR=/tmp`):\n",
-     f"* `python bench.py` -> `{tag}_bench.json`",
-     f"* `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --no-cpu-baseline` -> `{tag}_bench_kernel_stats.csv`",
-     f"* `rocprofv3 --kernel-trace --pmc FETCH_SIZE -- python3 bench.py --steps-only --steps 1 --warmup 1`, same with `WRITE_SIZE` (separate passes) -> `{tag}_hbm_traffic_pmc.json` (both passes with `RIA_NO_SPLIT=1`, so one launch = one whole {BATCH}-frame step, the unit `bench.py`'s roofline uses; FETCH_SIZE x 2 for gfx950; Infinity-Cache hits are counted)",
+     f"* `python bench.py --full` -> `{tag}_bench.json`",
+     f"* `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --no-cpu-baseline` -> `{tag}_bench_kernel_stats.csv`",
+     f"* `rocprofv3 --kernel-trace --pmc FETCH_SIZE -- python3 bench.py --steps 1 --warmup 1`, same with `WRITE_SIZE` (separate passes) -> `{tag}_hbm_traffic_pmc.json` (both passes with `RIA_NO_SPLIT=1`, so one launch = one whole {BATCH}-frame step, the unit `bench.py`'s roofline uses; FETCH_SIZE x 2 for gfx950; Infinity-Cache hits are counted)",
      f"* `rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE -- python3 bench.py ...` -> `{tag}_sq_utilisation_pmc.json`\n",
      f"Bench line: **{bench['value']:.0f} frames/s** on 1 MI355X ({bench['ms_per_step']} ms per {BATCH}-frame step); reference CPU path on the same box: {bench['cpu_baseline']['value']} frames/s on {bench['cpu_baseline']['cores']} threads ({bench['cpu_baseline']['kind']}).\n",
      "| kernel | calls | avg ms | % of GPU time |", "|---|---|---|---|"]

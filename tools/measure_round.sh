@@ -11,9 +11,9 @@ step() { local name=$1; shift; "$@"; local rc=$?; echo "$name rc=$rc" | tee -a "
 run_pytest() { timeout -k 10 900 python -m pytest tests -m gpu -x -q > "$O/pytest_gpu.log" 2>&1; }
 run_latency() { timeout -k 10 400 python tools/bench_latency.py --out "$O/latency.json" > "$O/latency.log" 2>&1; }
 run_smoke() { timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > "$O/smoke.log" 2>&1; }
-run_bench() { timeout -k 10 400 python bench.py > "$O/bench.log" 2>&1; }
-run_stats() { timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/stats" -- python3 bench.py --no-cpu-baseline --steps 4 --warmup 1 > "$O/stats.log" 2>&1; }
-run_pmc() { local d=$1; shift; timeout -k 10 300 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d "$O/$d" -- python3 bench.py --steps-only --steps 1 --warmup 1 > "$O/$d.log" 2>&1; }
+run_bench() { timeout -k 10 400 python bench.py --full > "$O/bench.log" 2>&1; }
+run_stats() { timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/stats" -- python3 bench.py --full --no-cpu-baseline --steps 4 --warmup 1 > "$O/stats.log" 2>&1; }
+run_pmc() { local d=$1; shift; timeout -k 10 300 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d "$O/$d" -- python3 bench.py --steps 1 --warmup 1 > "$O/$d.log" 2>&1; }
 run_sync() { timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/sync" -- python3 tools/bench_sync.py > "$O/sync.log" 2>&1; }
 run_ladder() { timeout -k 10 400 python tools/run_ladder_sweep.py --trials 65536 --out "$O/ladder.jsonl" > "$O/ladder.log" 2>&1; }
 run_grid() { timeout -k 10 300 python tools/run_acquisition_grid.py --preambles 20000 > "$O/acq_grid.log" 2>&1; }
