@@ -412,6 +412,70 @@ int ria_gpu_burst_deinterleave_batch(ria_gpu_handle h, const float* physical_llr
 int ria_gpu_burst_interleave_batch(ria_gpu_handle h, const uint8_t* logical_bytes_dev, int burst_frames, int n_groups,
                                    uint8_t* physical_bytes_out_dev, void* stream);
 
+/* ---- acquire + decode: connected-mode OFDM-CHIRP data frames with timing recovery ------------------
+ * ria_gpu_rx_acquire_batch replaces what gui::StreamingDecoder does with one search window of a connected-mode DATA frame
+ * (src/gui/modem/streaming_decoder.cpp): detectDataSync on the window with the known CFO (:723-735), the acceptance test
+ * against light_sync_min_confidence (:679-699, :752-771), setAbsoluteTrainingPosition + setFrequencyOffset + process()
+ * at the found position (:891-897, :1345-1349), decodeFixedFrame (:2936-2940), and multi-candidate timing recovery
+ * (:1855-1965): when no codeword decodes, the frame is demodulated and decoded again at +8, -8, +16, -16, +24, -24, +32,
+ * -32 samples and the first candidate that decodes anything is kept.
+ *
+ * Window geometry: window b starts at samples_dev + b*stride and holds window_len samples; the detector sees its first
+ * search_len (search_len <= window_len <= stride).  A candidate starting at s runs only if s >= 0 and
+ * s + frame_samples <= window_len.  If the primary candidate (s = sync_start) does not fit, the window is not accepted.
+ * A recovery candidate that does not fit is skipped and not counted (the reference reads older ring-buffer samples
+ * there instead).
+ *
+ * Primary candidate: delta 0, meta.flags bit0 = the detector's burst marker, abs_position = abs_base + sync_start,
+ * CFO = known_cfo_hz.  Recovery runs only when the primary's decode status has no cw_ok set (the reference's
+ * `!success && codewords_ok == 0`); every recovery candidate has meta.flags 0 (process() consumes the burst marker as a
+ * one-shot, ofdm_chirp_waveform.cpp:421-427, and reset() does not re-arm it, :474-485), abs_position = abs_base +
+ * sync_start + delta and the same known CFO.  The first candidate with any cw_ok is reported (its bytes, decode status
+ * and demod status); if none decodes anything, the primary's outputs are reported with delta 0.  Windows that are not
+ * accepted get zero bytes and zero statuses; detected, sync_start and correlation are still filled in.
+ *
+ * flags: the RIA_DECODE_* bits (RIA_DECODE_NO_CHANNEL_DEINTERLEAVE included) plus RIA_ACQ_NO_TIMING_RETRY (primary
+ * candidate only); RIA_RX_DEMOD_ONLY is RIA_ERR_INVALID.  A decode work-queue fault in any internal part of any round
+ * fails the whole call with RIA_ERR_HIP.  The call synchronises its stream once per round for one small device-to-host
+ * read (the length of the round's work list); no samples, soft bits or payloads go to the host.  Work grows with the
+ * number of windows that fail: each round demodulates and decodes only the windows still failing, each at its own next
+ * candidate.  Workspaces live on the handle and grow with n_windows.
+ *
+ * Not covered (the caller's side or other paths): control-frame hypotheses (R1/4 fast path, CW0 peek and salvage,
+ * :1268-1335, :1505-1575, :2866-2990), the weak-accept and reject-streak state (fold them into min_confidence), the PING
+ * energy check, chase combining, dual-chirp and Schmidl-Cox acquisition, OFDM-COX, ring-buffer wrap-around, and the
+ * +-2 Hz clamp of the reported CFO the host applies before it feeds it back (:1912-1918). */
+typedef struct ria_acq_params {      /* one per window, 32 bytes */
+    float    known_cfo_hz;           /* detectDataSync's known CFO (last_cfo_, :726) and the CFO every candidate is demodulated with */
+    float    detect_threshold;       /* detectDataSync threshold (CORR_DETECT_THRESHOLD 0.15 for OFDM, streaming_decoder.hpp:457) */
+    float    min_confidence;         /* accepted iff detected && correlation >= min_confidence (light_sync_min_confidence) */
+    uint32_t reserved0;
+    uint64_t abs_base;               /* absolute sample index of window sample 0 (ringPosToAbsolute) */
+    uint32_t reserved[2];
+} ria_acq_params;
+
+typedef struct ria_acq_result {      /* 32 bytes */
+    int32_t detected;                /* the LTS detector's result */
+    int32_t accepted;                /* detected && correlation >= min_confidence && the primary candidate fits the window */
+    int32_t sync_start;              /* detector start_sample, -1 if not detected */
+    int32_t frame_start;             /* start of the reported candidate = sync_start + delta, -1 if not accepted */
+    float   correlation;
+    float   cfo_hz;                  /* ria_frame_status.cfo_hz of the reported candidate (the estimatedCFO the host clamps), 0 if not accepted */
+    int16_t delta;                   /* 0 = primary, else the recovery delta that was accepted */
+    uint8_t candidates;              /* candidates demodulated and decoded: 0 (not accepted) .. 9 */
+    uint8_t burst_interleaved;       /* detector's burst marker */
+    int32_t reserved;
+} ria_acq_result;
+
+#define RIA_ACQ_NO_TIMING_RETRY 0x400u   /* primary candidate only */
+
+/* info_out_dev: n_windows * info_bytes_per_frame; decode_status_dev, acq_dev: n_windows entries; demod_status_dev
+ * (nullable): n_windows entries; params_dev: n_windows entries. */
+int ria_gpu_rx_acquire_batch(ria_gpu_handle h, const float* samples_dev, int64_t stride, int search_len, int window_len,
+                             int n_windows, const ria_acq_params* params_dev, uint32_t flags,
+                             uint8_t* info_out_dev, ria_decode_status* decode_status_dev, ria_acq_result* acq_dev,
+                             ria_frame_status* demod_status_dev, void* stream);
+
 /* ---- debug / test hooks ----------------------------------------------------------------------- */
 /* op: 0 sinf 1 cosf 2 logf 3 atan2f(a,b) 4 hypotf(a,b) 5 a/b 6 sqrtf(a); evaluates the device
  * math the kernels use on n arguments (tests compare against the host libm). */

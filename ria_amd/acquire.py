@@ -1,0 +1,109 @@
+"""Connected-mode OFDM data frames from capture windows: the acceptance rule, the Monte-Carlo window recipe and the
+counter driver around RxEngine.rx_acquire (ria_gpu_rx_acquire_batch).
+
+A window is what gui::StreamingDecoder searches for one DATA frame: silence, the frame at some offset, the channel
+over the whole window.  The detector sees the first `search_len` samples; the window holds search_len + frame_samples,
+so that every detected frame fits in it.
+"""
+import numpy as np
+import torch
+
+from . import capi
+from .sweep import reduce_counters, shard_range, trial_seed32
+
+SEARCH_LEN = 21000          # span of the LTS sync bench and the burst tests
+DETECT_THRESHOLD = 0.15     # CORR_DETECT_THRESHOLD (streaming_decoder.hpp:457)
+ACQ_COUNTERS = ("windows", "detected", "accepted", "primary_ok", "recovered", "frame_err", "byte_err", "decodes")
+
+_PSK = (capi.MOD["BPSK"], capi.MOD["QPSK"])
+_QAM = (capi.MOD["QAM16"], capi.MOD["QAM32"], capi.MOD["QAM64"], capi.MOD["QAM256"])
+
+
+def lts_min_confidence(modulation, fading_hint=0.0, snr_hint=99.0, reject_streak=0):
+    """light_sync_min_confidence of connected-mode OFDM (streaming_decoder.cpp:679-699): PSK 0.90, QAM 0.78,
+    differential 0.72 lowered to 0.68 / 0.65 / 0.62 by the fading and SNR hints, then relaxed by 0.015 per rejection
+    beyond the 7th (at most 0.12, never below 0.56).  Stateless: the caller keeps the hints and the reject streak.
+    Float32 arithmetic, as the reference computes it."""
+    mod = capi.MOD[modulation] if isinstance(modulation, str) else int(modulation)
+    f32 = np.float32
+    if mod in _PSK:
+        return f32(0.90)
+    if mod in _QAM:
+        return f32(0.78)
+    fading, snr = f32(fading_hint), f32(snr_hint)
+    conf = f32(0.72)
+    if fading >= f32(1.00) or snr < f32(10.0):
+        conf = f32(0.62)
+    elif fading >= f32(0.70) or snr < f32(14.0):
+        conf = f32(0.65)
+    elif fading >= f32(0.50) or snr < f32(18.0):
+        conf = f32(0.68)
+    if reject_streak >= 8:
+        relax = min(f32(0.12), f32(0.015) * f32(reject_streak - 7))
+        conf = max(f32(0.56), f32(conf - relax))
+    return f32(conf)
+
+
+def window_recipe(base_seed, point_index, trials, search_len=SEARCH_LEN):
+    """(frame offsets int64, mt19937 channel seeds uint32) of the windows `trials` (global trial numbers) of one sweep
+    point.  The offset is uniform over [0, search_len - 4 symbols], so that the frame's two LTS symbols lie inside the
+    detector's span; both values depend on (base seed, point, trial) only, never on chunking or rank."""
+    idx = np.asarray(trials, dtype=np.uint64)
+    max_off = int(search_len) - 4 * 1152
+    seeds = trial_seed32(base_seed, point_index, 2, idx)
+    offs = trial_seed32(base_seed, point_index, 3, idx).astype(np.int64) % np.int64(max_off + 1)
+    return offs, seeds
+
+
+def make_windows(engine, base_seed, point, point_index, start, n, search_len=SEARCH_LEN, tx_cfo=None):
+    """Windows of trials [start, start + n) of one sweep point on the engine's device: make_frames (seq = trial) ->
+    tx(peak 0.8) -> [transmitter CFO] -> placed at the recipe offset in a zero window of search_len + frame_samples
+    samples -> the reference-identical channel over the whole window (one mt19937 seed per trial).
+    Returns (windows float32 [n, window_len], sent info uint8 [n, info_bytes], offsets int64 [n])."""
+    fs = engine.geo.frame_samples
+    offs, seeds = window_recipe(base_seed, point_index, np.arange(start, start + n), search_len)
+    info = engine.make_frames(base_seed, start, n)
+    x = engine.tx(info, peak=0.8)
+    if tx_cfo is not None:
+        x = engine.tx_cfo(x, float(tx_cfo))
+    win = torch.zeros((n, search_len + fs), dtype=torch.float32, device=engine.device)
+    offs_t = torch.from_numpy(offs).to(engine.device)
+    win.scatter_(1, offs_t[:, None] + torch.arange(fs, device=engine.device)[None, :], x)   # placement only
+    engine.channel_exact_seeded_(win, point.channel, point.snr_db, seeds)
+    return win, info, offs
+
+
+def tally(info, st, res, sent):
+    """Counter row (ACQ_COUNTERS) of one chunk from rx_acquire's outputs and the sent payloads."""
+    ok = st["cw_ok"].all(axis=1) & st["frame_valid"].astype(bool)
+    same = (info == sent).all(dim=1).cpu().numpy()
+    acc = res["accepted"] != 0
+    any_primary = acc & (res["delta"] == 0) & st["cw_ok"].any(axis=1)
+    return np.array([len(res), int((res["detected"] != 0).sum()), int(acc.sum()), int(any_primary.sum()),
+                     int((acc & (res["delta"] != 0)).sum()), int((~(ok & same)).sum()), int((info != sent).sum().item()),
+                     int(res["candidates"].sum())], dtype=np.int64)
+
+
+def run_acquire_point(engine, point, base_seed, point_index, start, n, search_len=SEARCH_LEN, min_confidence=None,
+                      tx_cfo=None):
+    """One chunk of trials of one sweep point through ria_gpu_rx_acquire_batch.  Returns the counter row:
+    windows, detected, accepted, primary_ok (the primary candidate decoded a codeword), recovered (a recovery candidate
+    was reported), frame_err (not every codeword decoded, frame CRC failed or payload differs), byte_err (payload bytes
+    that differ from the sent ones, undecoded windows included), decodes (candidates demodulated + decoded)."""
+    win, sent, _ = make_windows(engine, base_seed, point, point_index, start, n, search_len, tx_cfo)
+    info, st, res = engine.rx_acquire(win, search_len, known_cfo=0.0 if tx_cfo is None else float(tx_cfo),
+                                      detect_threshold=DETECT_THRESHOLD, min_confidence=min_confidence)
+    return tally(info, engine.decode_status(st), res, sent)
+
+
+def run_acquire_sweep(engine, points, n_trials, base_seed, chunk=4096, **kw):
+    """run_acquire_point over every point, trials sharded over ranks as sweep.run_sweep shards them; counters summed
+    over ranks.  Returns int64 [n_points, len(ACQ_COUNTERS)]."""
+    import torch.distributed as dist
+    rank = dist.get_rank() if dist.is_initialized() else 0
+    world = dist.get_world_size() if dist.is_initialized() else 1
+    local = np.zeros((len(points), len(ACQ_COUNTERS)), dtype=np.int64)
+    for pi, p in enumerate(points):
+        for start, n in shard_range(n_trials, rank, world, chunk):
+            local[pi] += run_acquire_point(engine, p, base_seed, pi, start, n, **kw)
+    return reduce_counters(local, engine.device)

@@ -13,6 +13,7 @@ DECODE_NO_CHANNEL_DEINTERLEAVE = 0x100
 RX_DEMOD_ONLY = 0x200
 OPT_SPLIT_PARTS = 1
 OPT_DUAL_DECODER = 2
+ACQ_NO_TIMING_RETRY = 0x400
 
 # every symbol include/ria_gpu.h declares
 EXPORTS = [
@@ -21,6 +22,7 @@ EXPORTS = [
     "ria_gpu_rx_batch", "ria_gpu_rx_frames_host", "ria_gpu_decode_frames_host", "ria_gpu_tx_batch", "ria_gpu_make_frames",
     "ria_gpu_channel_batch", "ria_gpu_channel_exact_batch", "ria_gpu_channel_exact_seeded_batch", "ria_gpu_debug_math", "ria_gpu_debug_queue_fault", "ria_gpu_sync_zc_batch", "ria_gpu_zc_preamble", "ria_gpu_sync_chirp_batch", "ria_gpu_chirp_preamble", "ria_gpu_mcdpsk_demod_batch",
     "ria_gpu_mcdpsk_modulate_host", "ria_gpu_chase_combine_batch", "ria_gpu_sync_lts_batch", "ria_gpu_sync_host", "ria_gpu_ldpc_encode_host", "ria_gpu_burst_deinterleave_batch", "ria_gpu_burst_interleave_batch",
+    "ria_gpu_rx_acquire_batch",
     "ria_gpu_sync_cox_batch", "ria_gpu_cox_preamble", "ria_gpu_channel_exact_cfo_batch", "ria_gpu_tx_cfo_batch",
     "ria_gpu_mcdpsk_demod_host", "ria_gpu_ldpc_decode_robust_host", "ria_gpu_mcdpsk_modulate_batch",
     "ria_link_recommend", "ria_link_data_mode", "ria_link_ofdm_code_rate", "ria_link_cap_initial_rate",
@@ -62,6 +64,17 @@ class FrameStatus(C.Structure):
 class DecodeStatus(C.Structure):
     _fields_ = [("cw_ok", C.c_uint8 * 4), ("iterations", C.c_uint16 * 4), ("attempts", C.c_uint8 * 4),
                 ("frame_valid", C.c_uint8), ("needs_recovery", C.c_uint8), ("reserved", C.c_uint8 * 2)]
+
+
+class AcqParams(C.Structure):
+    _fields_ = [("known_cfo_hz", C.c_float), ("detect_threshold", C.c_float), ("min_confidence", C.c_float),
+                ("reserved0", C.c_uint32), ("abs_base", C.c_uint64), ("reserved", C.c_uint32 * 2)]
+
+
+class AcqResult(C.Structure):
+    _fields_ = [("detected", C.c_int32), ("accepted", C.c_int32), ("sync_start", C.c_int32), ("frame_start", C.c_int32),
+                ("correlation", C.c_float), ("cfo_hz", C.c_float), ("delta", C.c_int16), ("candidates", C.c_uint8),
+                ("burst_interleaved", C.c_uint8), ("reserved", C.c_int32)]
 
 
 _lib = None
@@ -129,6 +142,7 @@ def load(build_if_needed=True):
     L.ria_gpu_ldpc_encode_host.argtypes = [vp, vp, i32, vp]
     L.ria_gpu_burst_deinterleave_batch.argtypes = [vp, vp, i32, i32, i32, vp, vp]
     L.ria_gpu_burst_interleave_batch.argtypes = [vp, vp, i32, i32, vp, vp]
+    L.ria_gpu_rx_acquire_batch.argtypes = [vp, vp, C.c_int64, i32, i32, i32, vp, u32, vp, vp, vp, vp, vp]
     L.ria_link_recommend.argtypes = [f32, f32, C.POINTER(LinkRecommendation)]
     L.ria_link_recommend.restype = None
     L.ria_link_data_mode.argtypes = [f32, i32, f32, C.POINTER(LinkRecommendation)]

@@ -32,6 +32,7 @@
 #include "mcdpsk_kernels.hip.h"
 #include "cox_kernels.hip.h"
 #include "cfo_kernels.hip.h"
+#include "acquire_kernels.hip.h"
 
 using namespace ria;
 
@@ -99,6 +100,9 @@ struct ria_gpu {
     uint8_t* p_redec_ok = nullptr; uint8_t* p_redec_bytes = nullptr; ria_decode_status* p_st_c = nullptr;
     int rec_frames = 0, rec_host_frames = 0;
     Crc16Tables crc;
+    // ria_gpu_rx_acquire_batch: detector results, two work lists, the compact outputs of one round and the control block
+    // (device + pinned mirror), one block sized for acq_windows windows, grown on demand
+    unsigned char* d_acq_ws = nullptr; int acq_windows = 0; AcqCtl* p_acq_ctl = nullptr;
 };
 
 namespace {
@@ -428,6 +432,8 @@ void ria_gpu_destroy(ria_gpu_handle h) {
     if (h->d_mc_ws) (void)hipFree(h->d_mc_ws);
     for (void* p : {h->d_cox_tI, h->d_cox_tQ, h->d_cox_ws, h->d_txcfo_ws, h->d_zc_ws, static_cast<void*>(h->d_chan_nstd)}) if (p) (void)hipFree(p);
     for (void* p : h->d_demod_ws) if (p) (void)hipFree(p);
+    if (h->d_acq_ws) (void)hipFree(h->d_acq_ws);
+    if (h->p_acq_ctl) (void)hipHostFree(h->p_acq_ctl);
     for (void* p : {(void*)h->d_rctl, (void*)h->d_flagged, (void*)h->d_list2, (void*)h->d_stage2, (void*)h->d_info_c, (void*)h->d_rows_c,
                     (void*)h->d_redec_ok, (void*)h->d_redec_bytes, (void*)h->d_st_c, (void*)h->d_overflow}) if (p) (void)hipFree(p);
     for (void* p : {(void*)h->p_rctl, (void*)h->p_flagged, (void*)h->p_info_c, (void*)h->p_rows_c, (void*)h->p_redec_ok,
@@ -1238,6 +1244,16 @@ int ria_gpu_chirp_preamble(ria_gpu_handle h, float* out_host, int max_n) {
     return static_cast<int>(p.size());
 }
 
+// the LTS detector's tables and LDS opt-in, made once per handle
+static int lts_prepare(ria_gpu_handle h) {
+    if (!h->d_hilbert65) { std::vector<float> hc = build_hilbert(65); HIP_TRY(h, upload(&h->d_hilbert65, hc)); }
+    if (!h->lts_lds_opted) {
+        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(lts_sync_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lts_lds_bytes()));
+        h->lts_lds_opted = 1;
+    }
+    return RIA_OK;
+}
+
 int ria_gpu_sync_lts_batch(ria_gpu_handle h, const float* samples_dev, int64_t stride, int buf_len, int n_buffers,
                            const float* known_cfo_dev, float threshold, ria_lts_result* out_dev, void* stream) {
     if (!h) return RIA_ERR_INVALID;
@@ -1245,11 +1261,7 @@ int ria_gpu_sync_lts_batch(ria_gpu_handle h, const float* samples_dev, int64_t s
     if (!samples_dev || !out_dev || n_buffers < 0 || buf_len < 0 || stride < buf_len)
         return fail(h, RIA_ERR_INVALID, "ria_gpu_sync_lts_batch: bad arguments");
     HIP_TRY(h, hipSetDevice(h->device));
-    if (!h->d_hilbert65) { std::vector<float> hc = build_hilbert(65); HIP_TRY(h, upload(&h->d_hilbert65, hc)); }
-    if (!h->lts_lds_opted) {
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(lts_sync_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lts_lds_bytes()));
-        h->lts_lds_opted = 1;
-    }
+    if (int rc = lts_prepare(h)) return rc;
     LtsArgs A{};
     A.samples = samples_dev; A.stride = stride; A.buf_len = buf_len; A.n_buffers = n_buffers; A.known_cfo = known_cfo_dev;
     A.threshold = threshold; A.hilbert = static_cast<const float*>(h->d_hilbert65); A.out = out_dev;
@@ -1313,6 +1325,107 @@ int ria_gpu_cox_preamble(ria_gpu_handle h, float* out_host, int max_n) {
     if (static_cast<int>(p.size()) > max_n) return -static_cast<int>(p.size());
     std::memcpy(out_host, p.data(), p.size() * sizeof(float));
     return static_cast<int>(p.size());
+}
+
+// ------------------------------------------------------------------------------------------------ acquire + decode
+// layout of the acquisition workspace for n windows (offsets from d_acq_ws)
+struct AcqLayout {
+    size_t lts, list[2], info, dst, fst, ctl, total;
+};
+static AcqLayout acq_layout(size_t n, size_t info_bytes) {
+    AcqLayout L{};
+    size_t o = 0;
+    L.lts = o; o = up256(o + n * sizeof(ria_lts_result));
+    for (int q = 0; q < 2; ++q) { L.list[q] = o; o = up256(o + n * (sizeof(uint64_t) + sizeof(ria_frame_meta) + sizeof(uint32_t) + 1)); }
+    L.info = o; o = up256(o + n * info_bytes);
+    L.dst = o; o = up256(o + n * sizeof(ria_decode_status));
+    L.fst = o; o = up256(o + n * sizeof(ria_frame_status));
+    L.ctl = o; o = up256(o + sizeof(AcqCtl));
+    L.total = o;
+    return L;
+}
+static AcqList acq_list(unsigned char* base, size_t n) {   // the four arrays of one list, widest first
+    AcqList l;
+    l.offset = reinterpret_cast<uint64_t*>(base);
+    l.meta = reinterpret_cast<ria_frame_meta*>(base + n * sizeof(uint64_t));
+    l.window = reinterpret_cast<uint32_t*>(base + n * (sizeof(uint64_t) + sizeof(ria_frame_meta)));
+    l.cand = base + n * (sizeof(uint64_t) + sizeof(ria_frame_meta) + sizeof(uint32_t));
+    return l;
+}
+
+int ria_gpu_rx_acquire_batch(ria_gpu_handle h, const float* samples_dev, int64_t stride, int search_len, int window_len,
+                             int n_windows, const ria_acq_params* params_dev, uint32_t flags,
+                             uint8_t* info_out_dev, ria_decode_status* decode_status_dev, ria_acq_result* acq_dev,
+                             ria_frame_status* demod_status_dev, void* stream) {
+    if (!h) return RIA_ERR_INVALID;
+    const uint32_t known_flags = RIA_DECODE_FULL | RIA_DECODE_NO_CHANNEL_DEINTERLEAVE | RIA_ACQ_NO_TIMING_RETRY;
+    if (n_windows < 0 || search_len < 0 || window_len < search_len || stride < window_len || (flags & ~known_flags) != 0)
+        return fail(h, RIA_ERR_INVALID, "ria_gpu_rx_acquire_batch: bad argument (0 <= search_len <= window_len <= stride; flags: RIA_DECODE_* and RIA_ACQ_NO_TIMING_RETRY only)");
+    if (n_windows == 0) return RIA_OK;
+    if (!samples_dev || !params_dev || !info_out_dev || !decode_status_dev || !acq_dev)
+        return fail(h, RIA_ERR_INVALID, "ria_gpu_rx_acquire_batch: null pointer");
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = lts_prepare(h)) return rc;
+    const size_t n = static_cast<size_t>(n_windows), ib = static_cast<size_t>(h->geo.info_bytes_per_frame);
+    if (n_windows > h->acq_windows) {   // nothing of an earlier call is in flight: every call ends on a stream sync
+        if (h->d_acq_ws) (void)hipFree(h->d_acq_ws);
+        h->d_acq_ws = nullptr; h->acq_windows = 0;
+        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&h->d_acq_ws), acq_layout(n, ib).total));
+        h->acq_windows = n_windows;
+    }
+    if (!h->p_acq_ctl) HIP_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&h->p_acq_ctl), sizeof(AcqCtl), hipHostMallocDefault));
+    const size_t cap = static_cast<size_t>(h->acq_windows);
+    const AcqLayout L = acq_layout(cap, ib);
+    unsigned char* W = h->d_acq_ws;
+    HIP_TRY(h, hipMemsetAsync(info_out_dev, 0, n * ib, s));
+    HIP_TRY(h, hipMemsetAsync(decode_status_dev, 0, n * sizeof(ria_decode_status), s));
+    if (demod_status_dev) HIP_TRY(h, hipMemsetAsync(demod_status_dev, 0, n * sizeof(ria_frame_status), s));
+
+    // 1. LTS detection with each window's threshold and known CFO
+    LtsArgs S{};
+    S.samples = samples_dev; S.stride = stride; S.buf_len = search_len; S.n_buffers = n_windows;
+    S.known_cfo = &params_dev->known_cfo_hz; S.threshold_dev = &params_dev->detect_threshold;
+    S.param_stride = static_cast<int>(sizeof(ria_acq_params) / sizeof(float));
+    S.hilbert = static_cast<const float*>(h->d_hilbert65);
+    S.out = reinterpret_cast<ria_lts_result*>(W + L.lts);
+    hipLaunchKernelGGL(lts_sync_kernel, dim3(n_windows), dim3(kLtsThreads), lts_lds_bytes(), s, S);
+    // 2. acceptance + the round-0 list
+    AcqArgs A{};
+    A.lts = S.out; A.params = params_dev; A.n_windows = n_windows; A.window_len = window_len;
+    A.frame_samples = h->geo.frame_samples; A.stride = stride; A.acq = acq_dev;
+    A.ctl = reinterpret_cast<AcqCtl*>(W + L.ctl);
+    AcqList lists[2] = {acq_list(W + L.list[0], cap), acq_list(W + L.list[1], cap)};
+    A.next = lists[0];
+    hipLaunchKernelGGL(acq_plan_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A);
+    HIP_TRY(h, hipGetLastError());
+    A.info_c = W + L.info; A.dst_c = reinterpret_cast<const ria_decode_status*>(W + L.dst);
+    A.fst_c = reinterpret_cast<const ria_frame_status*>(W + L.fst);
+    A.info_bytes = static_cast<int>(ib); A.info_out = info_out_dev; A.dst_out = decode_status_dev; A.fst_out = demod_status_dev;
+    const uint32_t dflags = flags & ~RIA_ACQ_NO_TIMING_RETRY;
+    // 3./4. rounds: round 0 runs every accepted window at its primary candidate, round r >= 1 the windows whose previous
+    // candidate decoded nothing at their next candidate that fits; at most 8 recovery rounds (each advances every window
+    // it holds by at least one of the 8 deltas)
+    for (int round = 0;; ++round) {
+        HIP_TRY(h, hipMemcpyAsync(h->p_acq_ctl, A.ctl, sizeof(AcqCtl), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        if (h->p_acq_ctl->fault) return fail(h, RIA_ERR_HIP, "decode work-queue fault in round %d: no window of this call was decoded", round - 1);
+        const int n_list = static_cast<int>(h->p_acq_ctl->n_list);
+        if (n_list == 0) break;
+        if (n_list > n_windows || round >= kAcqCandidates) return fail(h, RIA_ERR_HIP, "ria_gpu_rx_acquire_batch: work list of round %d broke its bound (%d)", round, n_list);
+        A.cur = lists[round & 1];
+        A.next = lists[(round + 1) & 1];
+        A.n_cur = n_list;
+        A.round = round;
+        A.retry = !(flags & RIA_ACQ_NO_TIMING_RETRY) && round + 1 < kAcqCandidates;
+        int rc = ria_gpu_rx_batch(h, samples_dev, A.cur.offset, A.cur.meta, n_list, dflags, W + L.info,
+                                  reinterpret_cast<ria_decode_status*>(W + L.dst), nullptr, reinterpret_cast<ria_frame_status*>(W + L.fst), s);
+        if (rc != RIA_OK) return rc;
+        hipLaunchKernelGGL(acq_scatter_kernel, dim3(std::min((n_list + 3) / 4, 4096)), dim3(256), 0, s, A);
+        hipLaunchKernelGGL(acq_next_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A);
+        HIP_TRY(h, hipGetLastError());
+    }
+    return RIA_OK;
 }
 
 int ria_gpu_sync_host(ria_gpu_handle h, int kind, const float* samples_host, int n_samples, float threshold, float param,

@@ -613,6 +613,9 @@ struct LtsArgs {
     const float* known_cfo; float threshold;
     const float* hilbert;       // [65]
     ria_lts_result* out;
+    // ria_gpu_rx_acquire_batch: per-buffer threshold and known CFO read from its ria_acq_params records (buffer b at
+    // threshold_dev[b * param_stride], known_cfo[b * param_stride]); threshold_dev null = `threshold` for every buffer
+    const float* threshold_dev = nullptr; int param_stride = 1;
 };
 
 // The analytic signal sits in LDS with one empty slot after every 8 samples (sample i at slot i + (i >> 3)): the coarse
@@ -654,7 +657,8 @@ __global__ __launch_bounds__(kLtsThreads) void lts_sync_kernel(LtsArgs A) {
     const int tid = threadIdx.x, n = A.buf_len, L = kLtsSym;
     const float* x = A.samples + static_cast<long long>(blockIdx.x) * A.stride;
     ria_lts_result* out = A.out + blockIdx.x;
-    const float known = A.known_cfo ? A.known_cfo[blockIdx.x] : 0.0f;
+    const float known = A.known_cfo ? A.known_cfo[static_cast<long long>(blockIdx.x) * A.param_stride] : 0.0f;
+    const float threshold = A.threshold_dev ? A.threshold_dev[static_cast<long long>(blockIdx.x) * A.param_stride] : A.threshold;
     if (n < 3 * L) {
         if (tid == 0) { out->detected = 0; out->start_sample = 0; out->correlation = 0.f; out->cfo_hz = known; out->burst_interleaved = 0; out->reserved[0] = out->reserved[1] = out->reserved[2] = 0; }
         return;
@@ -724,7 +728,7 @@ __global__ __launch_bounds__(kLtsThreads) void lts_sync_kernel(LtsArgs A) {
     __syncthreads();
     float best = sh_best; int boff = sh_off;
     // +-4 refinement (:322-353)
-    if (best > A.threshold) {
+    if (best > threshold) {
         const int rs = (signal_start > boff - 4) ? signal_start : boff - 4;
         const int re = (search_end < boff + 5) ? search_end : boff + 5;
         if (tid < 9) {
@@ -747,7 +751,7 @@ __global__ __launch_bounds__(kLtsThreads) void lts_sync_kernel(LtsArgs A) {
         ria_lts_result o;
         o.detected = 0; o.start_sample = 0; o.correlation = best; o.cfo_hz = known; o.burst_interleaved = 0;
         o.reserved[0] = o.reserved[1] = o.reserved[2] = 0;
-        if (best > A.threshold) {
+        if (best > threshold) {
             o.detected = 1; o.start_sample = boff;
             const float cfo_phase = static_cast<float>(static_cast<double>(2.0f) * 3.14159265358979323846 * static_cast<double>(known) * static_cast<double>(L) / static_cast<double>(48000.0f));
             const float cr = cosf_glibc(-cfo_phase), ci = sinf_glibc(-cfo_phase);

@@ -241,6 +241,41 @@ class RxEngine:
                                                     _ptr(out), _stream_ptr()))
         return self._status_array(out, self.LTS_RESULT)
 
+    ACQ_PARAMS = np.dtype([("known_cfo_hz", "<f4"), ("detect_threshold", "<f4"), ("min_confidence", "<f4"), ("reserved0", "<u4"),
+                           ("abs_base", "<u8"), ("reserved", "<u4", 2)])
+    ACQ_RESULT = np.dtype([("detected", "<i4"), ("accepted", "<i4"), ("sync_start", "<i4"), ("frame_start", "<i4"),
+                           ("correlation", "<f4"), ("cfo_hz", "<f4"), ("delta", "<i2"), ("candidates", "u1"),
+                           ("burst_interleaved", "u1"), ("reserved", "<i4")])
+
+    def rx_acquire(self, windows, search_len, known_cfo=None, detect_threshold=0.15, min_confidence=None, abs_base=None,
+                   flags=capi.DECODE_FULL, retry=True, want_demod_status=False):
+        """Connected-mode OFDM data frames from capture windows (ria_gpu_rx_acquire_batch): LTS detection on the first
+        search_len samples of each row of `windows` (float32 [n, window_len] on the device), the acceptance test,
+        demodulation + decodeFixedFrame at the detected start and, where no codeword decodes, the reference's timing
+        recovery at +-8 .. +-32 samples.  known_cfo / detect_threshold / min_confidence / abs_base: scalars or one value per
+        window (min_confidence None: acquire.lts_min_confidence of the handle's modulation without fading or SNR hints).
+        Returns (info, decode_status, acq_result[, frame_status]); acq_result is a structured array (ACQ_RESULT)."""
+        from .acquire import lts_min_confidence
+        n, window_len = windows.shape
+        assert windows.dtype == torch.float32 and windows.is_contiguous()
+        if min_confidence is None:
+            min_confidence = lts_min_confidence(self.modulation)
+        p = np.zeros(n, self.ACQ_PARAMS)
+        p["known_cfo_hz"] = 0.0 if known_cfo is None else known_cfo
+        p["detect_threshold"] = detect_threshold
+        p["min_confidence"] = min_confidence
+        p["abs_base"] = 0 if abs_base is None else abs_base
+        params = torch.from_numpy(p.view(np.uint8).reshape(n, 32)).to(self.device)
+        info = torch.empty((n, self.geo.info_bytes_per_frame), dtype=torch.uint8, device=self.device)
+        st = torch.empty((n, 20), dtype=torch.uint8, device=self.device)
+        acq = torch.empty((n, 32), dtype=torch.uint8, device=self.device)
+        fst = torch.empty((n, 32), dtype=torch.uint8, device=self.device) if want_demod_status else None
+        fl = int(flags) | (0 if retry else capi.ACQ_NO_TIMING_RETRY)
+        self._check(self.lib.ria_gpu_rx_acquire_batch(self.h, _ptr(windows), window_len, int(search_len), window_len, n, _ptr(params), fl,
+                                                      _ptr(info), _ptr(st), _ptr(acq), _ptr(fst), _stream_ptr()))
+        res = self._status_array(acq, self.ACQ_RESULT)
+        return (info, st, res, fst) if want_demod_status else (info, st, res)
+
     COX_RESULT = np.dtype([("found", "<i4"), ("start_sample", "<i4"), ("cfo_hz", "<f4"), ("noise_floor", "<f4"),
                            ("sts_position", "<i4"), ("reserved", "<i4", 3)])
 
