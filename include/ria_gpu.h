@@ -443,8 +443,9 @@ int ria_gpu_burst_interleave_batch(ria_gpu_handle h, const uint8_t* logical_byte
  *
  * Not covered (the caller's side or other paths): control-frame hypotheses (R1/4 fast path, CW0 peek and salvage,
  * :1268-1335, :1505-1575, :2866-2990), the weak-accept and reject-streak state (fold them into min_confidence), the PING
- * energy check, chase combining, dual-chirp and Schmidl-Cox acquisition, OFDM-COX, ring-buffer wrap-around, and the
- * +-2 Hz clamp of the reported CFO the host applies before it feeds it back (:1912-1918). */
+ * energy check, chase combining, Schmidl-Cox acquisition, OFDM-COX, ring-buffer wrap-around, and the
+ * +-2 Hz clamp of the reported CFO the host applies before it feeds it back (:1912-1918).  MC-DPSK frames (ZC and
+ * dual-chirp acquisition, the disconnected handshake fallbacks) are ria_gpu_mcdpsk_acquire_batch's. */
 typedef struct ria_acq_params {      /* one per window, 32 bytes */
     float    known_cfo_hz;           /* detectDataSync's known CFO (last_cfo_, :726) and the CFO every candidate is demodulated with */
     float    detect_threshold;       /* detectDataSync threshold (CORR_DETECT_THRESHOLD 0.15 for OFDM, streaming_decoder.hpp:457) */
@@ -475,6 +476,90 @@ int ria_gpu_rx_acquire_batch(ria_gpu_handle h, const float* samples_dev, int64_t
                              int n_windows, const ria_acq_params* params_dev, uint32_t flags,
                              uint8_t* info_out_dev, ria_decode_status* decode_status_dev, ria_acq_result* acq_dev,
                              ria_frame_status* demod_status_dev, void* stream);
+
+/* ---- acquire + decode: MC-DPSK frames with the disconnected-handshake fallbacks ------------------------
+ * ria_gpu_mcdpsk_acquire_batch replaces what gui::StreamingDecoder does with one search window of an MC-DPSK frame
+ * (src/gui/modem/streaming_decoder.cpp), in the reference's order:
+ *   1. detection on the first search_len samples: MCDPSKWaveform::detectDataSync (ZC, roots DATA | CONTROL, the window's
+ *      known CFO, mc_dpsk_waveform.cpp:227-292) or, with RIA_MACQ_SYNC_CHIRP, detectSync (dual chirp, training start =
+ *      down_chirp_start + 24000 + 4800, :176-225).  Accepted iff detected, correlation >= min_confidence and the primary
+ *      frame [sync_start, sync_start + frame_len) lies in the window (the disconnected chirp path has no confidence test,
+ *      :829-834: pass min_confidence 0).
+ *   2. the CFO: the detector's; when connected, the known CFO instead if |known| > 0.01 Hz and the measurement differs
+ *      from it by more than 1 Hz (:903-917).  Every candidate is demodulated by a fresh demodulator with this CFO and
+ *      phase 0 over frame_len samples, frame_len = getMinSamplesForCWCount(frame_cw) of the PRIMARY modulation
+ *      (mc_dpsk_waveform.cpp:470-485) = 4608 + frame_cw * ceil(648 / (carriers * bps)) * 512 * spreading.
+ *   3. decodeMCDPSKFrame at R1/4 (:2595-2819, raw path): robustDecodeSingleCW of CW0, magic 0x55 0x4C, truncation to
+ *      20 bytes, parseHeader (control CRC over 18 bytes / data-header CRC over 15), a CONNECT / CONNECT_ACK /
+ *      CONNECT_NAK with total_cw < 3 rejected (:2713-2722); total_cw 1 is a success; fewer soft bits than total_cw
+ *      codewords is a partial result (CW0's 20 bytes, codewords_ok 1); else CW1..total_cw-1 robustly decoded and the
+ *      frame reassembled (CodewordStatus::reassemble, frame_v2.cpp:1030-1063).  A data header with total_cw 0 (undefined
+ *      behaviour in the reference) is treated as an invalid header.
+ *   4. connected, RIA_MACQ_NO_RETRY, a success or codewords_ok > 0 (header salvage: header_total_cw tells the caller how
+ *      many codewords to wait for): done.
+ *   5. RIA_MACQ_DISCONNECTED: the alternate modulation (DBPSK <-> DQPSK) over the same samples, accepted only as a full
+ *      success (:1646-1690); then timing recovery at +8, -8, +16, -16, +24, -24, +32, -32, +48, -48, +64, -64 samples,
+ *      each with the primary and then the alternate modulation; the first full success wins (:1692-1797).  A candidate
+ *      whose samples do not lie in the window (s < 0 or s + frame_len > window_len) is skipped and not counted (the
+ *      reference reads older ring-buffer samples there instead).  If nothing succeeds, the primary is reported.
+ *
+ * Window geometry as ria_gpu_rx_acquire_batch: window b at samples_dev + b*stride, window_len samples, the detector sees
+ * the first search_len (search_len <= window_len <= stride).  The handle's code rate must be RIA_RATE_1_4 (MC-DPSK is
+ * always R1/4, so decodeMCDPSKFrame's R1/4 fallbacks do not arise); cfg gives the carriers, spreading and the PRIMARY
+ * modulation.  frame_cw 1..8; a frame length the MC-DPSK demodulator cannot take is RIA_ERR_UNSUPPORTED.
+ *
+ * Outputs (every window, accepted or not): acq_dev; frame_out_dev rows of RIA_MACQ_FRAME_BYTES(frame_cw) bytes (a
+ * DQPSK alternate over a DBPSK frame length carries up to 2 * frame_cw codewords) holding the DecodeResult's frame_data
+ * (frame_bytes of them), zero elsewhere; llr_out_dev (nullable) rows of llr_stride floats with the reported candidate's
+ * soft bits (n_llr of them, the rest zero; llr_stride must hold every candidate that can run), e.g. for
+ * ria_gpu_chase_combine_batch.  The chase cache itself, channel interleaving (RIA_MACQ_CHANNEL_INTERLEAVE is
+ * RIA_ERR_UNSUPPORTED), PING/PONG classification and the CW0-peek escalation stay with the caller.
+ *
+ * Work: round r demodulates and decodes the list of windows still searching, each at its own next candidate that fits,
+ * with two small device-to-host reads (the round's codeword-row count and the next list's length); no samples, soft bits
+ * or payloads go to the host.  The robust decoder has no work queue, so the call has no work-queue fault path.
+ * Workspaces live on the handle and grow with n_windows. */
+typedef struct ria_mcdpsk_acq_params {   /* one per window, 32 bytes */
+    float    known_cfo_hz;               /* connected: detectDataSync's known CFO and the CFO rule's reference */
+    float    detect_threshold;           /* ZC 0.2 / chirp 0.15 in the reference's MC-DPSK calls */
+    float    min_confidence;             /* accepted iff detected && correlation >= min_confidence && the frame fits */
+    uint32_t reserved0;
+    uint64_t abs_base;                   /* absolute sample index of window sample 0: reported only (not used) */
+    uint32_t reserved[2];
+} ria_mcdpsk_acq_params;
+
+typedef struct ria_mcdpsk_acq_result {   /* 64 bytes */
+    int32_t detected;
+    int32_t accepted;
+    int32_t sync_start;                  /* training start (ZC start_sample / down chirp + 28800), -1 if not detected */
+    int32_t frame_start;                 /* start of the reported candidate = sync_start + delta, -1 if not accepted */
+    float   correlation;                 /* ZC correlation / max(up, down) chirp correlation */
+    float   cfo_hz;                      /* CFO every candidate was demodulated with, 0 if not accepted */
+    float   fading_index;                /* the reported candidate's demodulator getFadingIndex() */
+    int16_t delta;                       /* 0 primary / alternate, else the recovery delta that was accepted */
+    uint8_t modulation;                  /* RIA_MOD_DBPSK / RIA_MOD_DQPSK of the reported candidate */
+    uint8_t candidates;                  /* candidates demodulated + decoded: 0 (not accepted) .. 26 */
+    uint8_t success;                     /* DecodeResult of the reported candidate: success, codewords_ok, codewords_failed, */
+    uint8_t codewords_ok;                /* frame_type (0x10 PROBE = DecodeResult's default when no header was parsed) */
+    uint8_t codewords_failed;
+    uint8_t frame_type;
+    int32_t header_total_cw;             /* total_cw of a valid CW0 header, 0 if none */
+    int32_t frame_bytes;                 /* frame_data length: reassembled on success, 20 for a partial frame, else 0 */
+    int32_t n_llr;                       /* soft bits of the reported candidate */
+    int32_t reserved[4];
+} ria_mcdpsk_acq_result;
+
+#define RIA_MACQ_SYNC_CHIRP           0x1u   /* dual-chirp detectSync instead of ZC detectDataSync */
+#define RIA_MACQ_DISCONNECTED         0x2u   /* handshake fallbacks on, connected CFO rule off (ZC + DISCONNECTED: RIA_ERR_INVALID) */
+#define RIA_MACQ_NO_RETRY             0x4u   /* primary candidate only */
+#define RIA_MACQ_CHANNEL_INTERLEAVE   0x8u   /* use_mc_dpsk_channel_interleave_: RIA_ERR_UNSUPPORTED */
+#define RIA_MACQ_FRAME_BYTES(frame_cw) (40 * (frame_cw))
+
+int ria_gpu_mcdpsk_acquire_batch(ria_gpu_handle h, const ria_mcdpsk_config* cfg, const float* samples_dev, int64_t stride,
+                                 int search_len, int window_len, int n_windows, int frame_cw,
+                                 const ria_mcdpsk_acq_params* params_dev, uint32_t flags,
+                                 uint8_t* frame_out_dev, ria_mcdpsk_acq_result* acq_dev,
+                                 float* llr_out_dev /* nullable */, int llr_stride, void* stream);
 
 /* ---- debug / test hooks ----------------------------------------------------------------------- */
 /* op: 0 sinf 1 cosf 2 logf 3 atan2f(a,b) 4 hypotf(a,b) 5 a/b 6 sqrtf(a); evaluates the device

@@ -107,3 +107,52 @@ def run_acquire_sweep(engine, points, n_trials, base_seed, chunk=4096, **kw):
         for start, n in shard_range(n_trials, rank, world, chunk):
             local[pi] += run_acquire_point(engine, p, base_seed, pi, start, n, **kw)
     return reduce_counters(local, engine.device)
+
+
+# ---- MC-DPSK (ria_gpu_mcdpsk_acquire_batch)
+def _zc_relax(streak):
+    return min(np.float32(0.15), np.float32(0.025) * np.float32(streak - 3)) if streak >= 4 else np.float32(0.0)
+
+
+def zc_min_confidence(reject_streak=0):
+    """light_sync_min_confidence of connected ZC mode (streaming_decoder.cpp:679-717): 0.40, relaxed after 4 consecutive
+    rejects by 0.025 per reject beyond the 3rd (at most 0.15), never below 0.25.  Float32 arithmetic."""
+    return np.float32(max(np.float32(0.25), np.float32(np.float32(0.40) - _zc_relax(reject_streak))))
+
+
+def zc_weak_floor(reject_streak=0):
+    """weak_sync_floor of connected ZC mode: 0.30 with the same relaxation, never below 0.20."""
+    return np.float32(max(np.float32(0.20), np.float32(np.float32(0.30) - _zc_relax(reject_streak))))
+
+
+def mcdpsk_frame_len(frame_cw, carriers=10, bits_per_symbol=1, spreading=1):
+    """MCDPSKWaveform::getMinSamplesForCWCount (mc_dpsk_waveform.cpp:470-485): training + reference + frame_cw codewords"""
+    return 9 * 512 + int(frame_cw) * -(-648 // (int(carriers) * int(bits_per_symbol))) * 512 * int(spreading)
+
+
+def mcdpsk_window_recipe(preamble_len, frame_cw, lead=2000, tail=2000, carriers=10, bits_per_symbol=1, spreading=1):
+    """(search_len, window_len) of an MC-DPSK test / bench window: `lead` samples of silence, the preamble, the frame of
+    frame_cw codewords, `tail` samples.  The detector sees the lead-in, the preamble and the first 8 symbols after it."""
+    fl = mcdpsk_frame_len(frame_cw, carriers, bits_per_symbol, spreading)
+    return lead + preamble_len + 8 * 512, lead + preamble_len + fl + tail
+
+
+def make_mcdpsk_windows(engine, coded, preamble, n, frame_cw, kind, snr_db, seeds, lead=2000, tail=2000, carriers=10,
+                        bits_per_symbol=1, spreading=1, gap=0):
+    """n windows on the engine's device: the frame(s) `coded` (uint8 [m, n_bytes] coded bytes, row i % m for window i)
+    modulated on the device behind `preamble` (float32 host array: engine.chirp_preamble() or a ZC preamble), peak 0.8,
+    at sample `lead` of a zero window, then the reference-identical channel (one mt19937 seed per window).  gap > 0 puts
+    that many zero samples between the preamble and the frame (windows that need the timing recovery).
+    Returns (windows float32 [n, window_len], search_len)."""
+    coded = np.ascontiguousarray(coded, np.uint8)
+    body = engine.mcdpsk_modulate_batch(coded, carriers, bits_per_symbol, spreading)
+    pre = torch.from_numpy(np.ascontiguousarray(preamble, np.float32)).to(engine.device)
+    tx = torch.cat([pre[None, :].expand(body.shape[0], -1),
+                    torch.zeros((body.shape[0], int(gap)), dtype=torch.float32, device=engine.device), body], dim=1)
+    tx = tx * (0.8 / tx.abs().amax(dim=1, keepdim=True))
+    search_len, window_len = mcdpsk_window_recipe(len(preamble), frame_cw, lead, tail, carriers, bits_per_symbol, spreading)
+    win = torch.zeros((n, window_len), dtype=torch.float32, device=engine.device)
+    m = min(tx.shape[1], window_len - lead)
+    win[:, lead:lead + m] = tx[torch.arange(n, device=engine.device) % tx.shape[0], :m]
+    engine.channel_exact_seeded_(win, kind, snr_db, np.ascontiguousarray(seeds, np.uint32))
+    return win, search_len

@@ -14,6 +14,10 @@ RX_DEMOD_ONLY = 0x200
 OPT_SPLIT_PARTS = 1
 OPT_DUAL_DECODER = 2
 ACQ_NO_TIMING_RETRY = 0x400
+MACQ_SYNC_CHIRP = 0x1
+MACQ_DISCONNECTED = 0x2
+MACQ_NO_RETRY = 0x4
+MACQ_CHANNEL_INTERLEAVE = 0x8
 
 # every symbol include/ria_gpu.h declares
 EXPORTS = [
@@ -22,7 +26,7 @@ EXPORTS = [
     "ria_gpu_rx_batch", "ria_gpu_rx_frames_host", "ria_gpu_decode_frames_host", "ria_gpu_tx_batch", "ria_gpu_make_frames",
     "ria_gpu_channel_batch", "ria_gpu_channel_exact_batch", "ria_gpu_channel_exact_seeded_batch", "ria_gpu_debug_math", "ria_gpu_debug_queue_fault", "ria_gpu_sync_zc_batch", "ria_gpu_zc_preamble", "ria_gpu_sync_chirp_batch", "ria_gpu_chirp_preamble", "ria_gpu_mcdpsk_demod_batch",
     "ria_gpu_mcdpsk_modulate_host", "ria_gpu_chase_combine_batch", "ria_gpu_sync_lts_batch", "ria_gpu_sync_host", "ria_gpu_ldpc_encode_host", "ria_gpu_burst_deinterleave_batch", "ria_gpu_burst_interleave_batch",
-    "ria_gpu_rx_acquire_batch",
+    "ria_gpu_rx_acquire_batch", "ria_gpu_mcdpsk_acquire_batch",
     "ria_gpu_sync_cox_batch", "ria_gpu_cox_preamble", "ria_gpu_channel_exact_cfo_batch", "ria_gpu_tx_cfo_batch",
     "ria_gpu_mcdpsk_demod_host", "ria_gpu_ldpc_decode_robust_host", "ria_gpu_mcdpsk_modulate_batch",
     "ria_link_recommend", "ria_link_data_mode", "ria_link_ofdm_code_rate", "ria_link_cap_initial_rate",
@@ -75,6 +79,24 @@ class AcqResult(C.Structure):
     _fields_ = [("detected", C.c_int32), ("accepted", C.c_int32), ("sync_start", C.c_int32), ("frame_start", C.c_int32),
                 ("correlation", C.c_float), ("cfo_hz", C.c_float), ("delta", C.c_int16), ("candidates", C.c_uint8),
                 ("burst_interleaved", C.c_uint8), ("reserved", C.c_int32)]
+
+
+class McAcqParams(C.Structure):
+    _fields_ = [("known_cfo_hz", C.c_float), ("detect_threshold", C.c_float), ("min_confidence", C.c_float),
+                ("reserved0", C.c_uint32), ("abs_base", C.c_uint64), ("reserved", C.c_uint32 * 2)]
+
+
+class McAcqResult(C.Structure):
+    _fields_ = [("detected", C.c_int32), ("accepted", C.c_int32), ("sync_start", C.c_int32), ("frame_start", C.c_int32),
+                ("correlation", C.c_float), ("cfo_hz", C.c_float), ("fading_index", C.c_float), ("delta", C.c_int16),
+                ("modulation", C.c_uint8), ("candidates", C.c_uint8), ("success", C.c_uint8), ("codewords_ok", C.c_uint8),
+                ("codewords_failed", C.c_uint8), ("frame_type", C.c_uint8), ("header_total_cw", C.c_int32),
+                ("frame_bytes", C.c_int32), ("n_llr", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+def macq_frame_bytes(frame_cw):
+    """RIA_MACQ_FRAME_BYTES: bytes of one frame_out row of ria_gpu_mcdpsk_acquire_batch"""
+    return 40 * int(frame_cw)
 
 
 _lib = None
@@ -143,6 +165,7 @@ def load(build_if_needed=True):
     L.ria_gpu_burst_deinterleave_batch.argtypes = [vp, vp, i32, i32, i32, vp, vp]
     L.ria_gpu_burst_interleave_batch.argtypes = [vp, vp, i32, i32, vp, vp]
     L.ria_gpu_rx_acquire_batch.argtypes = [vp, vp, C.c_int64, i32, i32, i32, vp, u32, vp, vp, vp, vp, vp]
+    L.ria_gpu_mcdpsk_acquire_batch.argtypes = [vp, vp, vp, C.c_int64, i32, i32, i32, i32, vp, u32, vp, vp, vp, i32, vp]
     L.ria_link_recommend.argtypes = [f32, f32, C.POINTER(LinkRecommendation)]
     L.ria_link_recommend.restype = None
     L.ria_link_data_mode.argtypes = [f32, i32, f32, C.POINTER(LinkRecommendation)]

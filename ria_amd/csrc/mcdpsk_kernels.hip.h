@@ -44,7 +44,11 @@ struct McArgs {
     float* scale;              // [n_frames]
     float* llr; int llr_stride;
     ria_mcdpsk_status* status;
+    // offset-list form (ria_gpu_mcdpsk_acquire_batch): frame first+f at samples + offset[first+f] with bits per symbol
+    // bps_list[first+f]; null = samples + (first+f)*stride and `bps` for every frame
+    const uint64_t* offset; const uint8_t* bps_list;
 };
+__device__ __forceinline__ int mc_bps(const McArgs& A, size_t f) { return A.bps_list ? A.bps_list[A.first + f] : A.bps; }
 
 __device__ __forceinline__ float2 mc_cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 
@@ -75,7 +79,7 @@ __global__ __launch_bounds__(256) void mcdpsk_corr_kernel(McArgs A) {
     float2* Y = reinterpret_cast<float2*>(smem);                           // [n_sym][nc]  running sums
     float* xs_l = reinterpret_cast<float*>(smem + ((n_sym * nc * 8 + 15) & ~15));   // [CH][S4]
     float2* mx_l = reinterpret_cast<float2*>(xs_l + CH * S4);              // [nc][mrow]
-    const float* x = A.samples + static_cast<long long>(A.first + f) * A.stride;
+    const float* x = A.offset ? A.samples + A.offset[A.first + f] : A.samples + static_cast<long long>(A.first + f) * A.stride;
     const float cfo = A.cfo ? A.cfo[A.first + f] : 0.0f;
     if (mc_corrects(cfo, n)) {
         float* xc = A.ws + static_cast<size_t>(f) * 2 * n;
@@ -166,12 +170,13 @@ __global__ __launch_bounds__(256) void mcdpsk_corr_kernel(McArgs A) {
 // data symbols, so one LANE per (carrier, frame), frames adjacent
 __global__ __launch_bounds__(256) void mcdpsk_chain_kernel(McArgs A) {
     const McShape g = mc_shape(A);
-    const int nc = A.nc, bps = A.bps, sp = A.spreading, num_rx = g.num_rx, nds = g.nds;
+    const int nc = A.nc, sp = A.spreading, num_rx = g.num_rx, nds = g.nds;
     const size_t F = static_cast<size_t>(A.n_frames);
     const size_t idx = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x;
     if (idx >= F * nc) return;
     const int c = static_cast<int>(idx / F);
     const size_t f = idx - static_cast<size_t>(c) * F;
+    const int bps = mc_bps(A, f);
     auto Y = [&](int item) { return A.Yg[static_cast<size_t>(item) * F + f]; };
     {
         float2 prev = Y(2 * nc + c);
@@ -215,10 +220,11 @@ __global__ __launch_bounds__(256) void mcdpsk_chain_kernel(McArgs A) {
 // and the fading indices (:404-437, :705-733): short serial loops over a frame's symbols, so one LANE per frame
 __global__ __launch_bounds__(64) void mcdpsk_stats_kernel(McArgs A) {
     const McShape g = mc_shape(A);
-    const int nc = A.nc, bps = A.bps, nds = g.nds;
+    const int nc = A.nc, nds = g.nds;
     const size_t F = static_cast<size_t>(A.n_frames);
     const size_t f = static_cast<size_t>(blockIdx.x) * 64 + threadIdx.x;
     if (f >= F) return;
+    const int bps = mc_bps(A, f);
     auto Y = [&](int item) { return A.Yg[static_cast<size_t>(item) * F + f]; };
     auto cmag = [&](int item) { return A.cmag[static_cast<size_t>(item) * F + f]; };
     const float cfo_in = A.cfo ? A.cfo[A.first + f] : 0.0f;
@@ -335,11 +341,12 @@ __global__ __launch_bounds__(64) void mcdpsk_stats_kernel(McArgs A) {
 // ---- kernel 4: LLRs (:650-667), one lane per (frame, data symbol, carrier)
 __global__ __launch_bounds__(256) void mcdpsk_llr_kernel(McArgs A) {
     const McShape g = mc_shape(A);
-    const int nc = A.nc, bps = A.bps, per = g.nds * nc;
+    const int nc = A.nc, per = g.nds * nc;
     const size_t F = static_cast<size_t>(A.n_frames);
     const size_t idx = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x;
     if (idx >= F * per) return;
     const size_t f = idx / per;
+    const int bps = mc_bps(A, f);
     const int i = static_cast<int>(idx - f * per), c = i % nc;
     const float phase = A.cph[static_cast<size_t>(i) * F + f];
     const float cs = A.scale[f] * A.rel[static_cast<size_t>(c) * F + f];

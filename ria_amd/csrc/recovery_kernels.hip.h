@@ -38,11 +38,15 @@ struct RecCtx {            // wave-uniform view of one frame's working set (all 
     int lane;
 };
 
+// isControlFrame (frame_v2.hpp): the 1-codeword types whose CRC covers 18 bytes
+__device__ __forceinline__ bool rec_is_control(int t) {
+    return t == 0x10 || t == 0x11 || t == 0x16 || t == 0x17 || t == 0x20 || t == 0x21 || t == 0x15 || t == 0x40;
+}
 __device__ inline bool rec_parse_header(const RecCtx& x, const uint8_t* d, int len, bool* ctl, int* plen) {  // frame_v2.cpp:1195-1252
     if (len < 20) return false;
     if (d[0] != 0x55 || d[1] != 0x4C) return false;
     const int t = d[2];
-    *ctl = (t == 0x10 || t == 0x11 || t == 0x16 || t == 0x17 || t == 0x20 || t == 0x21 || t == 0x15 || t == 0x40);
+    *ctl = rec_is_control(t);
     if (*ctl) {
         if (crc16_wave(d, 18, x.crc_bit, x.crc_init, x.lane) != static_cast<uint32_t>((d[18] << 8) | d[19])) return false;
         *plen = 0;
@@ -52,23 +56,30 @@ __device__ inline bool rec_parse_header(const RecCtx& x, const uint8_t* d, int l
     }
     return true;
 }
+// reassembleCodewords (frame_v2.cpp:959-989) of n_cw decoded codewords of bpc bytes (cw_at(i): codeword i) for a header
+// already parsed (control: 20 bytes, data: 17 + payload + 2); one wave, returns the length
+template <class CwAt>
+__device__ inline int rec_reassemble_cws(bool ctl, int plen, CwAt cw_at, int n_cw, int bpc, int lane, uint8_t* out) {
+    const int expected = ctl ? 20 : 17 + plen + 2;
+    int n = 0;
+    for (int i = 0; i < n_cw; ++i) {
+        const int remaining = expected - n;
+        if (remaining == 0) break;
+        const uint8_t* src = cw_at(i);
+        int avail = bpc;
+        if (i != 0 && src[0] == 0xD5) { src += 2; avail -= 2; }
+        const int c = remaining < avail ? remaining : avail;
+        for (int b = lane; b < c; b += 64) out[n + b] = src[b];
+        n += c;
+    }
+    return n;
+}
 // CodewordStatus::reassemble + reassembleCodewords (frame_v2.cpp:1030-1063, :959-989), all CWs decoded
 __device__ inline int rec_reassemble(const RecCtx& x, uint8_t* out) {
     bool ctl; int plen;
     wave_sync();
     if (!rec_parse_header(x, x.cw, x.bpc, &ctl, &plen)) return 0;
-    const int expected = ctl ? 20 : 17 + plen + 2;
-    int n = 0;
-    for (int i = 0; i < 4; ++i) {
-        const int remaining = expected - n;
-        if (remaining == 0) break;
-        const uint8_t* src = x.cw + i * 68;
-        int avail = x.bpc;
-        if (i != 0 && src[0] == 0xD5) { src += 2; avail -= 2; }
-        const int c = remaining < avail ? remaining : avail;
-        for (int b = x.lane; b < c; b += 64) out[n + b] = src[b];
-        n += c;
-    }
+    const int n = rec_reassemble_cws(ctl, plen, [&](int i) { return x.cw + i * 68; }, 4, x.bpc, x.lane, out);
     wave_sync();
     return n;
 }

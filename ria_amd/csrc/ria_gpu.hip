@@ -33,6 +33,7 @@
 #include "cox_kernels.hip.h"
 #include "cfo_kernels.hip.h"
 #include "acquire_kernels.hip.h"
+#include "mcdpsk_acquire_kernels.hip.h"
 
 using namespace ria;
 
@@ -103,6 +104,9 @@ struct ria_gpu {
     // ria_gpu_rx_acquire_batch: detector results, two work lists, the compact outputs of one round and the control block
     // (device + pinned mirror), one block sized for acq_windows windows, grown on demand
     unsigned char* d_acq_ws = nullptr; int acq_windows = 0; AcqCtl* p_acq_ctl = nullptr;
+    // ria_gpu_mcdpsk_acquire_batch: detector results, two work lists, one round's soft bits, codeword rows, decoder outputs and
+    // header state, and the control block (device + pinned mirror), grown on demand
+    unsigned char* d_macq_ws = nullptr; size_t macq_bytes = 0; MacqCtl* p_macq_ctl = nullptr;
 };
 
 namespace {
@@ -434,6 +438,8 @@ void ria_gpu_destroy(ria_gpu_handle h) {
     for (void* p : h->d_demod_ws) if (p) (void)hipFree(p);
     if (h->d_acq_ws) (void)hipFree(h->d_acq_ws);
     if (h->p_acq_ctl) (void)hipHostFree(h->p_acq_ctl);
+    if (h->d_macq_ws) (void)hipFree(h->d_macq_ws);
+    if (h->p_macq_ctl) (void)hipHostFree(h->p_macq_ctl);
     for (void* p : {(void*)h->d_rctl, (void*)h->d_flagged, (void*)h->d_list2, (void*)h->d_stage2, (void*)h->d_info_c, (void*)h->d_rows_c,
                     (void*)h->d_redec_ok, (void*)h->d_redec_bytes, (void*)h->d_st_c, (void*)h->d_overflow}) if (p) (void)hipFree(p);
     for (void* p : {(void*)h->p_rctl, (void*)h->p_flagged, (void*)h->p_info_c, (void*)h->p_rows_c, (void*)h->p_redec_ok,
@@ -1009,9 +1015,10 @@ __global__ void debug_math_kernel(int op, const float* a, const float* b, int n,
     out[i] = r;
 }
 
-int ria_gpu_sync_zc_batch(ria_gpu_handle h, const float* samples_dev, int64_t stride, int buf_len, int n_buffers,
-                          float threshold, uint32_t root_mask, const float* known_cfo_dev, ria_zc_result* out_dev,
-                          void* stream) {
+// threshold_dev / param_stride: per-buffer threshold and known CFO records (ZcArgs); null / 1 = the public call
+static int sync_zc_impl(ria_gpu_handle h, const float* samples_dev, int64_t stride, int buf_len, int n_buffers,
+                        float threshold, uint32_t root_mask, const float* known_cfo_dev, ria_zc_result* out_dev,
+                        void* stream, const float* threshold_dev, int param_stride) {
     if (!h) return RIA_ERR_INVALID;
     if (n_buffers == 0) return RIA_OK;
     if (!samples_dev || !out_dev || n_buffers < 0 || buf_len < 0 || buf_len > kZcMaxBuf || stride < buf_len)
@@ -1019,6 +1026,7 @@ int ria_gpu_sync_zc_batch(ria_gpu_handle h, const float* samples_dev, int64_t st
     ZcArgs A{};
     A.samples = samples_dev; A.stride = stride; A.buf_len = buf_len; A.n_buffers = n_buffers; A.threshold = threshold;
     A.root_mask = root_mask & 15u; A.known_cfo = known_cfo_dev; A.ref = static_cast<const float2*>(h->d_zc_ref); A.out = out_dev;
+    A.threshold_dev = threshold_dev; A.param_stride = param_stride;
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (buf_len <= kZcLdsBuf) {   // the mixed-down buffer fits one workgroup's LDS
@@ -1040,12 +1048,19 @@ int ria_gpu_sync_zc_batch(ria_gpu_handle h, const float* samples_dev, int64_t st
         A.bb_ws = static_cast<float2*>(h->d_zc_ws);
         for (int first = 0; first < n_buffers; first += chunk) {
             A.samples = samples_dev + static_cast<int64_t>(first) * stride; A.n_buffers = std::min(chunk, n_buffers - first);
-            A.known_cfo = known_cfo_dev ? known_cfo_dev + first : nullptr; A.out = out_dev + first;
+            A.known_cfo = known_cfo_dev ? known_cfo_dev + static_cast<int64_t>(first) * param_stride : nullptr; A.out = out_dev + first;
+            A.threshold_dev = threshold_dev ? threshold_dev + static_cast<int64_t>(first) * param_stride : nullptr;
             hipLaunchKernelGGL(zc_detect_kernel<false>, dim3(A.n_buffers), dim3(256), 4 * static_cast<int>(sizeof(ZcRootOut)), s, A);
         }
     }
     HIP_TRY(h, hipGetLastError());
     return RIA_OK;
+}
+
+int ria_gpu_sync_zc_batch(ria_gpu_handle h, const float* samples_dev, int64_t stride, int buf_len, int n_buffers,
+                          float threshold, uint32_t root_mask, const float* known_cfo_dev, ria_zc_result* out_dev,
+                          void* stream) {
+    return sync_zc_impl(h, samples_dev, stride, buf_len, n_buffers, threshold, root_mask, known_cfo_dev, out_dev, stream, nullptr, 1);
 }
 
 int ria_gpu_zc_preamble(ria_gpu_handle h, int root, float* out_host, int max_n) {
@@ -1125,8 +1140,15 @@ static int chirp_prepare(ria_gpu_handle h, int chunk, int outer, hipStream_t s) 
     return RIA_OK;
 }
 
+static int sync_chirp_impl(ria_gpu_handle h, const float* samples_dev, int64_t stride, int buf_len, int n_buffers,
+                           float threshold, ria_chirp_result* out_dev, void* stream, const float* threshold_dev, int param_stride);
 int ria_gpu_sync_chirp_batch(ria_gpu_handle h, const float* samples_dev, int64_t stride, int buf_len, int n_buffers,
                              float threshold, ria_chirp_result* out_dev, void* stream) {
+    return sync_chirp_impl(h, samples_dev, stride, buf_len, n_buffers, threshold, out_dev, stream, nullptr, 1);
+}
+
+static int sync_chirp_impl(ria_gpu_handle h, const float* samples_dev, int64_t stride, int buf_len, int n_buffers,
+                           float threshold, ria_chirp_result* out_dev, void* stream, const float* threshold_dev, int param_stride) {
     if (!h) return RIA_ERR_INVALID;
     if (n_buffers == 0) return RIA_OK;
     if (!samples_dev || !out_dev || n_buffers < 0 || buf_len < 0 || stride < buf_len)
@@ -1150,6 +1172,7 @@ int ria_gpu_sync_chirp_batch(ria_gpu_handle h, const float* samples_dev, int64_t
     A.tmpl = static_cast<const float*>(h->d_ch_tmpl); A.tmpl_energy[0] = h->ch_energy[0]; A.tmpl_energy[1] = h->ch_energy[1];
     A.w1 = static_cast<float2*>(h->d_ch_w1); A.w2 = static_cast<float2*>(h->d_ch_w2); A.best = static_cast<unsigned long long*>(h->d_ch_mag);
     A.cum = static_cast<float*>(h->d_ch_cum); A.st = static_cast<ChirpBufState*>(h->d_ch_st); A.out = out_dev;
+    A.threshold_dev = threshold_dev; A.param_stride = param_stride;
     for (int first = 0; first < n_buffers; first += outer) {
         const int nb = std::min(outer, n_buffers - first);
         A.first = first; A.n_buffers = nb;
@@ -1461,6 +1484,13 @@ static bool mcdpsk_config_ok(const ria_mcdpsk_config* c) {
            (c->spreading == 1 || c->spreading == 2 || c->spreading == 4);
 }
 
+// offsets_dev / bps_dev (nullable): the offset-list form (McArgs::offset, bps_list) of ria_gpu_mcdpsk_acquire_batch, whose
+// caller has checked the arguments (llr_stride for two bits per symbol)
+static int mcdpsk_demod_impl(ria_gpu_handle h, const ria_mcdpsk_config* cfg, const float* samples_dev, int64_t stride,
+                             const uint64_t* offsets_dev, const uint8_t* bps_dev,
+                             int frame_samples, int n_frames, const float* cfo_hz_dev, const float* phase0_dev,
+                             float* llr_out_dev, int llr_stride, ria_mcdpsk_status* status_dev, void* stream);
+
 int ria_gpu_mcdpsk_demod_batch(ria_gpu_handle h, const ria_mcdpsk_config* cfg, const float* samples_dev, int64_t stride,
                                int frame_samples, int n_frames, const float* cfo_hz_dev, const float* phase0_dev,
                                float* llr_out_dev, int llr_stride, ria_mcdpsk_status* status_dev, void* stream) {
@@ -1472,6 +1502,16 @@ int ria_gpu_mcdpsk_demod_batch(ria_gpu_handle h, const ria_mcdpsk_config* cfg, c
     const int nc = cfg->num_carriers, num_rx = (frame_samples - (kMcTrain + 1) * kMcSps) / kMcSps;
     const int nds = std::max(1, num_rx / cfg->spreading);
     if (llr_stride < nds * nc * cfg->bits_per_symbol) return fail(h, RIA_ERR_INVALID, "ria_gpu_mcdpsk_demod_batch: llr_stride too small");
+    return mcdpsk_demod_impl(h, cfg, samples_dev, stride, nullptr, nullptr, frame_samples, n_frames, cfo_hz_dev, phase0_dev,
+                             llr_out_dev, llr_stride, status_dev, stream);
+}
+
+static int mcdpsk_demod_impl(ria_gpu_handle h, const ria_mcdpsk_config* cfg, const float* samples_dev, int64_t stride,
+                             const uint64_t* offsets_dev, const uint8_t* bps_dev,
+                             int frame_samples, int n_frames, const float* cfo_hz_dev, const float* phase0_dev,
+                             float* llr_out_dev, int llr_stride, ria_mcdpsk_status* status_dev, void* stream) {
+    const int nc = cfg->num_carriers, num_rx = (frame_samples - (kMcTrain + 1) * kMcSps) / kMcSps;
+    const int nds = std::max(1, num_rx / cfg->spreading);
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (!h->d_mc_mixer.count(nc)) {
@@ -1505,6 +1545,7 @@ int ria_gpu_mcdpsk_demod_batch(ria_gpu_handle h, const ria_mcdpsk_config* cfg, c
     A.spreading = cfg->spreading; A.cfo = cfo_hz_dev; A.phase0 = phase0_dev; A.mixer = static_cast<const float2*>(h->d_mc_mixer[nc]);
     A.hilbert = static_cast<const float*>(h->d_mc_hilbert); A.llr = llr_out_dev;
     A.llr_stride = llr_stride; A.status = status_dev; A.chunk = mcdpsk_corr_chunk(nc, frame_samples);
+    A.offset = offsets_dev; A.bps_list = bps_dev;
     const size_t n_sym = static_cast<size_t>(3 + num_rx);
     for (int first = 0; first < n_frames; first += chunk) {
         A.first = first; A.n_frames = std::min(chunk, n_frames - first);
@@ -1619,6 +1660,174 @@ int ria_gpu_mcdpsk_modulate_host(ria_gpu_handle h, const ria_mcdpsk_config* cfg,
     if (static_cast<int>(f.size()) > max_n) return -static_cast<int>(f.size());
     std::memcpy(out_host, f.data(), f.size() * sizeof(float));
     return static_cast<int>(f.size());
+}
+
+// ------------------------------------------------------------------------------------------------ MC-DPSK acquire + decode
+static_assert(sizeof(ria_mcdpsk_acq_params) == 32, "ria_mcdpsk_acq_params is 32 bytes (include/ria_gpu.h)");
+static_assert(sizeof(ria_mcdpsk_acq_result) == 64, "ria_mcdpsk_acq_result is 64 bytes (include/ria_gpu.h)");
+static_assert(offsetof(ria_mcdpsk_acq_params, abs_base) == 16 && offsetof(ria_mcdpsk_acq_result, delta) == 28 &&
+              offsetof(ria_mcdpsk_acq_result, header_total_cw) == 36, "ria_mcdpsk_acq_* field offsets");
+// layout of the MC-DPSK acquisition workspace for n windows, llr_ws soft bits and max_cw codewords per candidate
+struct MacqLayout {
+    size_t det, list[2], mst, llr, rows, row_entry, row_cw, out_a, ok_a, it_a, out_b, ok_b, it_b, hdr, need, base, done, ctl, total;
+};
+static MacqLayout macq_layout(size_t n, size_t llr_ws, size_t max_cw, size_t dec_bytes) {
+    MacqLayout L{};
+    size_t o = 0;
+    const size_t nr = n * max_cw;   // rows of round A (n) and round B (n * (max_cw - 1))
+    L.det = o; o = up256(o + n * 32);
+    for (int q = 0; q < 2; ++q) { L.list[q] = o; o = up256(o + n * (sizeof(uint64_t) + sizeof(float) + sizeof(uint32_t) + 2)); }
+    L.mst = o; o = up256(o + n * sizeof(ria_mcdpsk_status));
+    L.llr = o; o = up256(o + n * llr_ws * sizeof(float));
+    L.rows = o; o = up256(o + nr * kMacqLdpcBlock * sizeof(float));
+    L.row_entry = o; o = up256(o + nr * sizeof(uint32_t));
+    L.row_cw = o; o = up256(o + nr);
+    L.out_a = o; o = up256(o + n * dec_bytes);
+    L.ok_a = o; o = up256(o + n);
+    L.it_a = o; o = up256(o + n * sizeof(uint16_t));
+    L.out_b = o; o = up256(o + nr * dec_bytes);
+    L.ok_b = o; o = up256(o + nr);
+    L.it_b = o; o = up256(o + nr * sizeof(uint16_t));
+    L.hdr = o; o = up256(o + n * sizeof(int));
+    L.need = o; o = up256(o + n * sizeof(int));
+    L.base = o; o = up256(o + n * sizeof(uint32_t));
+    L.done = o; o = up256(o + n);
+    L.ctl = o; o = up256(o + sizeof(MacqCtl));
+    L.total = o;
+    return L;
+}
+static MacqList macq_list(unsigned char* base, size_t n) {   // the five arrays of one list, widest first
+    MacqList l;
+    l.offset = reinterpret_cast<uint64_t*>(base);
+    l.cfo = reinterpret_cast<float*>(base + n * sizeof(uint64_t));
+    l.window = reinterpret_cast<uint32_t*>(base + n * (sizeof(uint64_t) + sizeof(float)));
+    l.cand = base + n * (sizeof(uint64_t) + sizeof(float) + sizeof(uint32_t));
+    l.bps = l.cand + n;
+    return l;
+}
+
+int ria_gpu_mcdpsk_acquire_batch(ria_gpu_handle h, const ria_mcdpsk_config* cfg, const float* samples_dev, int64_t stride,
+                                 int search_len, int window_len, int n_windows, int frame_cw,
+                                 const ria_mcdpsk_acq_params* params_dev, uint32_t flags,
+                                 uint8_t* frame_out_dev, ria_mcdpsk_acq_result* acq_dev,
+                                 float* llr_out_dev, int llr_stride, void* stream) {
+    if (!h) return RIA_ERR_INVALID;
+    const uint32_t known_flags = RIA_MACQ_SYNC_CHIRP | RIA_MACQ_DISCONNECTED | RIA_MACQ_NO_RETRY | RIA_MACQ_CHANNEL_INTERLEAVE;
+    const bool chirp = (flags & RIA_MACQ_SYNC_CHIRP) != 0, disconnected = (flags & RIA_MACQ_DISCONNECTED) != 0;
+    if (!mcdpsk_config_ok(cfg) || n_windows < 0 || search_len < 0 || window_len < search_len || stride < window_len ||
+        frame_cw < 1 || frame_cw > 8 || (flags & ~known_flags) != 0 || (disconnected && !chirp) || (!chirp && search_len > kZcMaxBuf))
+        return fail(h, RIA_ERR_INVALID, "ria_gpu_mcdpsk_acquire_batch: bad argument (config, 0 <= search_len <= window_len <= stride, "
+                                        "frame_cw 1..8, known flags, ZC only when connected)");
+    if (h->cfg.code_rate != RIA_RATE_1_4) return fail(h, RIA_ERR_INVALID, "ria_gpu_mcdpsk_acquire_batch: MC-DPSK frames are R1/4: the handle's rate must be RIA_RATE_1_4");
+    if (flags & RIA_MACQ_CHANNEL_INTERLEAVE) return fail(h, RIA_ERR_UNSUPPORTED, "ria_gpu_mcdpsk_acquire_batch: MC-DPSK channel interleaving is not implemented");
+    const int nc = cfg->num_carriers, bps = cfg->bits_per_symbol, sp = cfg->spreading;
+    const bool retry = disconnected && !(flags & RIA_MACQ_NO_RETRY);
+    const int sym_per_cw = (kMacqLdpcBlock + nc * bps - 1) / (nc * bps);
+    const int frame_len = (kMcTrain + 1) * kMcSps + frame_cw * sym_per_cw * kMcSps * sp;      // getMinSamplesForCWCount
+    if (mcdpsk_lds_bytes(nc, frame_len) > 160 * 1024)
+        return fail(h, RIA_ERR_UNSUPPORTED, "ria_gpu_mcdpsk_acquire_batch: frame of %d samples too long for the MC-DPSK demodulator", frame_len);
+    const int nds = frame_cw * sym_per_cw;
+    const int llr_ws = nds * nc * 2;                                   // either modulation
+    const int llr_need = nds * nc * (retry ? 2 : bps);                 // candidates that can run
+    const int max_cw = llr_ws / kMacqLdpcBlock;                        // <= 2 * frame_cw
+    if (llr_out_dev && llr_stride < llr_need)
+        return fail(h, RIA_ERR_INVALID, "ria_gpu_mcdpsk_acquire_batch: llr_stride %d < %d soft bits", llr_stride, llr_need);
+    if (max_cw > 2 * frame_cw) return fail(h, RIA_ERR_UNSUPPORTED, "ria_gpu_mcdpsk_acquire_batch: codeword bound broken");
+    if (n_windows == 0) return RIA_OK;
+    if (!samples_dev || !params_dev || !frame_out_dev || !acq_dev)
+        return fail(h, RIA_ERR_INVALID, "ria_gpu_mcdpsk_acquire_batch: null pointer");
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t n = static_cast<size_t>(n_windows), dec_bytes = static_cast<size_t>((h->geo.ldpc_k + 7) / 8);
+    const MacqLayout L = macq_layout(n, static_cast<size_t>(llr_ws), static_cast<size_t>(max_cw), dec_bytes);
+    if (L.total > h->macq_bytes) {   // nothing of an earlier call is in flight: every call ends on a stream sync
+        if (h->d_macq_ws) (void)hipFree(h->d_macq_ws);
+        h->d_macq_ws = nullptr; h->macq_bytes = 0;
+        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&h->d_macq_ws), L.total));
+        h->macq_bytes = L.total;
+    }
+    if (!h->p_macq_ctl) HIP_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&h->p_macq_ctl), sizeof(MacqCtl), hipHostMallocDefault));
+    unsigned char* W = h->d_macq_ws;
+    const int frame_row = RIA_MACQ_FRAME_BYTES(frame_cw);
+    HIP_TRY(h, hipMemsetAsync(frame_out_dev, 0, n * frame_row, s));
+    if (llr_out_dev) HIP_TRY(h, hipMemsetAsync(llr_out_dev, 0, n * static_cast<size_t>(llr_stride) * sizeof(float), s));
+
+    // 1. detection with each window's threshold (and known CFO for ZC)
+    const int pstride = static_cast<int>(sizeof(ria_mcdpsk_acq_params) / sizeof(float));
+    MacqArgs A{};
+    if (chirp) {
+        A.chirp = reinterpret_cast<const ria_chirp_result*>(W + L.det);
+        int rc = sync_chirp_impl(h, samples_dev, stride, search_len, n_windows, 0.15f, reinterpret_cast<ria_chirp_result*>(W + L.det), s,
+                                 &params_dev->detect_threshold, pstride);
+        if (rc != RIA_OK) return rc;
+    } else {
+        A.zc = reinterpret_cast<const ria_zc_result*>(W + L.det);
+        int rc = sync_zc_impl(h, samples_dev, stride, search_len, n_windows, 0.2f, 12u /* DATA | CONTROL */, &params_dev->known_cfo_hz,
+                              reinterpret_cast<ria_zc_result*>(W + L.det), s, &params_dev->detect_threshold, pstride);
+        if (rc != RIA_OK) return rc;
+    }
+    // 2. acceptance + the round-0 list
+    A.params = params_dev; A.n_windows = n_windows; A.window_len = window_len; A.frame_len = frame_len; A.stride = stride;
+    A.connected = !disconnected; A.retry = retry; A.bps = bps; A.acq = acq_dev;
+    A.ctl = reinterpret_cast<MacqCtl*>(W + L.ctl);
+    MacqList lists[2] = {macq_list(W + L.list[0], n), macq_list(W + L.list[1], n)};
+    A.next = lists[0];
+    hipLaunchKernelGGL(macq_plan_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A);
+    HIP_TRY(h, hipGetLastError());
+    A.mst = reinterpret_cast<const ria_mcdpsk_status*>(W + L.mst);
+    A.llr = reinterpret_cast<const float*>(W + L.llr); A.llr_ws = llr_ws;
+    A.rows = reinterpret_cast<float*>(W + L.rows);
+    A.row_entry = reinterpret_cast<uint32_t*>(W + L.row_entry); A.row_cw = W + L.row_cw;
+    A.out_a = W + L.out_a; A.ok_a = W + L.ok_a; A.out_b = W + L.out_b; A.ok_b = W + L.ok_b;
+    A.dec_bytes = static_cast<int>(dec_bytes);
+    A.hdr_total = reinterpret_cast<int*>(W + L.hdr); A.need_rows = reinterpret_cast<int*>(W + L.need);
+    A.row_base = reinterpret_cast<uint32_t*>(W + L.base); A.done = W + L.done;
+    A.crc_bit = static_cast<const uint16_t*>(h->d_crc_bit); A.crc_init = static_cast<const uint16_t*>(h->d_crc_init);
+    A.frame_out = frame_out_dev; A.frame_row = frame_row; A.llr_out = llr_out_dev; A.llr_stride = llr_stride;
+    const ria_mcdpsk_config c = *cfg;
+    // 3.-5. rounds: round 0 runs every accepted window at its primary candidate, round r >= 1 the windows still searching at
+    // their next candidate that fits (at most 25 more rounds: each advances every window it holds by at least one candidate)
+    for (int round = 0;; ++round) {
+        HIP_TRY(h, hipMemcpyAsync(h->p_macq_ctl, A.ctl, sizeof(MacqCtl), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        const int n_list = static_cast<int>(h->p_macq_ctl->n_list);
+        if (n_list == 0) break;
+        if (n_list > n_windows || round >= kMacqCandidates)
+            return fail(h, RIA_ERR_HIP, "ria_gpu_mcdpsk_acquire_batch: work list of round %d broke its bound (%d)", round, n_list);
+        A.cur = lists[round & 1];
+        A.next = lists[(round + 1) & 1];
+        A.n_cur = n_list;
+        int rc = mcdpsk_demod_impl(h, &c, samples_dev, stride, A.cur.offset, A.cur.bps, frame_len, n_list, A.cur.cfo, nullptr,
+                                   const_cast<float*>(A.llr), llr_ws, const_cast<ria_mcdpsk_status*>(A.mst), s);
+        if (rc != RIA_OK) return rc;
+        // round A: CW0 of every entry, then the headers and the round-B row list
+        MacqArgs G = A;
+        G.row_entry = nullptr;
+        hipLaunchKernelGGL(macq_gather_kernel, dim3(static_cast<unsigned>(std::min<size_t>((static_cast<size_t>(n_list) * kMacqLdpcBlock + 255) / 256, 16384))),
+                           dim3(256), 0, s, G, n_list);
+        rc = ria_gpu_ldpc_decode_robust_batch(h, A.rows, n_list, W + L.out_a, W + L.ok_a, reinterpret_cast<uint16_t*>(W + L.it_a), nullptr, s);
+        if (rc != RIA_OK) return rc;
+        const unsigned waves = static_cast<unsigned>(std::min((n_list + 3) / 4, 4096));
+        hipLaunchKernelGGL(macq_header_kernel, dim3(waves), dim3(256), 0, s, A);
+        hipLaunchKernelGGL(macq_rows_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A);
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(h->p_macq_ctl, A.ctl, sizeof(MacqCtl), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        const int n_rows = static_cast<int>(h->p_macq_ctl->n_rows);
+        if (n_rows < 0 || n_rows > n_list * (max_cw - 1))
+            return fail(h, RIA_ERR_HIP, "ria_gpu_mcdpsk_acquire_batch: codeword rows of round %d broke their bound (%d)", round, n_rows);
+        // round B: CW1..total_cw-1 of the entries whose header asks for them
+        if (n_rows > 0) {
+            hipLaunchKernelGGL(macq_gather_kernel, dim3(static_cast<unsigned>(std::min<size_t>((static_cast<size_t>(n_rows) * kMacqLdpcBlock + 255) / 256, 16384))),
+                               dim3(256), 0, s, A, n_rows);
+            rc = ria_gpu_ldpc_decode_robust_batch(h, A.rows, n_rows, W + L.out_b, W + L.ok_b, reinterpret_cast<uint16_t*>(W + L.it_b), nullptr, s);
+            if (rc != RIA_OK) return rc;
+        }
+        hipLaunchKernelGGL(macq_finish_kernel, dim3(waves), dim3(256), 0, s, A);
+        hipLaunchKernelGGL(macq_next_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A);
+        HIP_TRY(h, hipGetLastError());
+    }
+    return RIA_OK;
 }
 
 int ria_gpu_chase_combine_batch(ria_gpu_handle h, float* acc_dev, int32_t* count_dev, const uint8_t* decoded_dev,

@@ -35,6 +35,9 @@ struct ZcArgs {
     const float2* ref;         // [4][1016] interpolated ZC reference per root (host_tables.hpp build_zc_reference)
     ria_zc_result* out;
     float2* bb_ws;             // [n_buffers][buf_len] baseband workspace of the long-buffer form (kLds = false)
+    // ria_gpu_mcdpsk_acquire_batch: per-buffer threshold and known CFO read from its parameter records (buffer b at
+    // threshold_dev[b * param_stride], known_cfo[b * param_stride]); threshold_dev null = `threshold` for every buffer
+    const float* threshold_dev = nullptr; int param_stride = 1;
 };
 
 struct ZcRootOut { float combined; int timing; int has_cfo; float cfo; };
@@ -84,7 +87,8 @@ __global__ __launch_bounds__(256) void zc_detect_kernel(ZcArgs A) {
         if (tid == 0) { out->detected = 0; out->frame_type = 255; out->start_sample = -1; out->root_detected = -1; out->correlation = 0.f; out->cfo_hz = 0.f; out->snr_estimate = 0.f; out->reserved = 0.f; }
         return;
     }
-    const float known = A.known_cfo ? A.known_cfo[blockIdx.x] : 0.0f;
+    const float known = A.known_cfo ? A.known_cfo[static_cast<long long>(blockIdx.x) * A.param_stride] : 0.0f;
+    const float zc_thr = A.threshold_dev ? A.threshold_dev[static_cast<long long>(blockIdx.x) * A.param_stride] : A.threshold;
     const float f = 1500.0f + known;
     // baseband[i] = rx[i] * (cos(phase), sin(phase)), phase = -2*pi*f*t in double, rounded to float (:503-508)
     for (int i = tid; i < n; i += 256) {
@@ -151,7 +155,7 @@ __global__ __launch_bounds__(256) void zc_detect_kernel(ZcArgs A) {
         const float sr_l = __shfl(s3.sr, 2), si_l = __shfl(s3.si, 2);
         int timing = peak_pos;
         bool at_earlier = false;
-        if (peak_mag > A.threshold && peak_pos >= kZcRep) {
+        if (peak_mag > zc_thr && peak_pos >= kZcRep) {
             if (cm_e > peak_mag * 0.4f) { timing = peak_pos - kZcRep; at_earlier = true; }
         }
         float combined = peak_mag;
@@ -191,7 +195,7 @@ __global__ __launch_bounds__(256) void zc_detect_kernel(ZcArgs A) {
         ria_zc_result o;
         o.detected = 0; o.frame_type = (best_root >= 0) ? (best_root - 1) / 2 : 255; o.start_sample = -1; o.root_detected = best_root;
         o.correlation = best_corr; o.cfo_hz = 0.0f; o.snr_estimate = 0.0f; o.reserved = 0.0f;
-        if (best_corr > A.threshold && best_root >= 0) {
+        if (best_corr > zc_thr && best_root >= 0) {
             o.detected = 1; o.cfo_hz = best_cfo; o.start_sample = best_pos + kZcPreamble;
             float snr;
             if (best_corr <= 0.01f) snr = -10.0f;
@@ -253,7 +257,12 @@ struct ChirpArgs {
     ChirpBufState* st;         // [outer chunk]
     ria_chirp_result* out;     // [all buffers]
     int down;                  // stage: 0 up, 1 down
+    // ria_gpu_mcdpsk_acquire_batch: per-buffer threshold (buffer b at threshold_dev[b * param_stride]); null = `threshold`
+    const float* threshold_dev = nullptr; int param_stride = 1;
 };
+__device__ __forceinline__ float chirp_threshold(const ChirpArgs& A, int buffer) {
+    return A.threshold_dev ? A.threshold_dev[static_cast<long long>(buffer) * A.param_stride] : A.threshold;
+}
 
 __device__ __forceinline__ void wave_lds_fence() {   // single-wave workgroup: DS ops execute in order
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -489,7 +498,7 @@ __global__ void chirp_peak_kernel(ChirpArgs A) {
     const float corr = key ? u2f(static_cast<uint32_t>(key >> 32)) : 0.0f;
     const int pos = key ? static_cast<int>(0xFFFFFFFFu - static_cast<uint32_t>(key & 0xFFFFFFFFull)) : -1;
     s.corr = corr;
-    s.pos = (pos >= 0 && !(corr < A.threshold)) ? pos : -1;
+    s.pos = (pos >= 0 && !(corr < chirp_threshold(A, A.first + A.sub + b))) ? pos : -1;
 }
 
 // time-domain path of detectChirpTemplate (:759-817) for short windows: one workgroup per buffer,
@@ -539,7 +548,8 @@ __global__ __launch_bounds__(256) void chirp_td_kernel(ChirpArgs A) {
         if (v > best) { best = v; best_pos = idx; }
     }
     int pos_out = -1;
-    if (!(best_pos < 0 || best < A.threshold * 0.3f)) {
+    const float thr = chirp_threshold(A, A.first + b);
+    if (!(best_pos < 0 || best < thr * 0.3f)) {
         const int fine_start = best_pos - 48 < 0 ? 0 : best_pos - 48;
         const int fine_end = best_pos + 48 > search_len ? search_len : best_pos + 48;
         {   // fine search, inclusive range of at most 97 positions (:788-795)
@@ -569,7 +579,7 @@ __global__ __launch_bounds__(256) void chirp_td_kernel(ChirpArgs A) {
             __syncthreads();
             best_pos = spos;
         }
-        pos_out = (best >= A.threshold) ? best_pos : -1;
+        pos_out = (best >= thr) ? best_pos : -1;
     }
     if (tid == 0) { s.corr = best; s.pos = pos_out; }
 }

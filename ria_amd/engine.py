@@ -312,6 +312,49 @@ class RxEngine:
                                                         _ptr(llr), n_llr, _ptr(st), _stream_ptr()))
         return llr, self._status_array(st, self.MCDPSK_STATUS)
 
+    MCACQ_PARAMS = ACQ_PARAMS
+    MCACQ_RESULT = np.dtype([("detected", "<i4"), ("accepted", "<i4"), ("sync_start", "<i4"), ("frame_start", "<i4"),
+                             ("correlation", "<f4"), ("cfo_hz", "<f4"), ("fading_index", "<f4"), ("delta", "<i2"),
+                             ("modulation", "u1"), ("candidates", "u1"), ("success", "u1"), ("codewords_ok", "u1"),
+                             ("codewords_failed", "u1"), ("frame_type", "u1"), ("header_total_cw", "<i4"),
+                             ("frame_bytes", "<i4"), ("n_llr", "<i4"), ("reserved", "<i4", 4)])
+
+    def mcdpsk_acquire(self, windows, search_len, frame_cw, carriers=10, modulation="DBPSK", spreading=1, sync="chirp",
+                       disconnected=None, known_cfo=None, detect_threshold=None, min_confidence=None, abs_base=None, retry=True,
+                       want_llr=False):
+        """MC-DPSK frames from capture windows (ria_gpu_mcdpsk_acquire_batch): ZC ("zc") or dual-chirp ("chirp") detection
+        on the first search_len samples of each row of `windows` (float32 [n, window_len] on the device), the acceptance
+        test, demodulation + decodeMCDPSKFrame at R1/4 and, when `disconnected` (default: chirp), the handshake fallbacks.
+        The handle must be R1/4.  known_cfo / detect_threshold / min_confidence / abs_base: scalars or one value per window
+        (defaults: 0, the reference's 0.2 ZC / 0.15 chirp, acquire.zc_min_confidence(0) for ZC and 0 for chirp).
+        Returns (frames uint8 [n, 40 * frame_cw], acq_result structured array (MCACQ_RESULT)[, llr float32 [n, stride]])."""
+        from .acquire import zc_min_confidence
+        n, window_len = windows.shape
+        assert windows.dtype == torch.float32 and windows.is_contiguous()
+        chirp = {"chirp": True, "zc": False}[sync]
+        if disconnected is None:
+            disconnected = chirp
+        bps = {"DBPSK": 1, "DQPSK": 2}[modulation] if isinstance(modulation, str) else int(modulation)
+        p = np.zeros(n, self.MCACQ_PARAMS)
+        p["known_cfo_hz"] = 0.0 if known_cfo is None else known_cfo
+        p["detect_threshold"] = (0.15 if chirp else 0.2) if detect_threshold is None else detect_threshold
+        p["min_confidence"] = (0.0 if chirp else zc_min_confidence(0)) if min_confidence is None else min_confidence
+        p["abs_base"] = 0 if abs_base is None else abs_base
+        params = torch.from_numpy(p.view(np.uint8).reshape(n, 32)).to(self.device)
+        fl = (capi.MACQ_SYNC_CHIRP if chirp else 0) | (capi.MACQ_DISCONNECTED if disconnected else 0) | (0 if retry else capi.MACQ_NO_RETRY)
+        frames = torch.empty((n, capi.macq_frame_bytes(frame_cw)), dtype=torch.uint8, device=self.device)
+        acq = torch.empty((n, 64), dtype=torch.uint8, device=self.device)
+        llr, stride = None, 0
+        if want_llr:
+            stride = frame_cw * -(-648 // (carriers * bps)) * carriers * 2        # room for either modulation
+            llr = torch.empty((n, stride), dtype=torch.float32, device=self.device)
+        cfg = capi.McdpskConfig(carriers, bps, spreading, 0)
+        self._check(self.lib.ria_gpu_mcdpsk_acquire_batch(self.h, C.byref(cfg), _ptr(windows), window_len, int(search_len), window_len, n,
+                                                          int(frame_cw), _ptr(params), fl, _ptr(frames), _ptr(acq), _ptr(llr), stride,
+                                                          _stream_ptr()))
+        res = self._status_array(acq, self.MCACQ_RESULT)
+        return (frames, res, llr) if want_llr else (frames, res)
+
     def mcdpsk_modulate(self, data, carriers=10, bits_per_symbol=1, spreading=1):
         data = np.ascontiguousarray(data, np.uint8)
         cfg = capi.McdpskConfig(carriers, bits_per_symbol, spreading, 0)

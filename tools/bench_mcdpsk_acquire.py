@@ -1,0 +1,98 @@
+"""Throughput of ria_gpu_mcdpsk_acquire_batch (RxEngine.mcdpsk_acquire) on one GPU; prints one JSON line.
+
+Workloads (all windows built and channelled on the device, ria_amd.acquire.make_mcdpsk_windows):
+  connect_awgn / connect_moderate: disconnected CONNECT windows (dual chirp, DBPSK, 10 carriers, frame_cw 3) at low SNR
+  connect_recovery: connect_awgn with the frame 288 samples behind the preamble (timing recovery)
+  zc_connected: connected ZC windows of a 1-CW control frame
+  host_chain: the connect_awgn windows through the separate calls driven from the host, primary candidate only, with
+              the time of each stage (sync_chirp, mcdpsk_demod, ldpc_decode_robust of every codeword)
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "oracle"))
+
+
+def timed(fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    for _ in range(reps):
+        out = fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t) / reps, out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--windows", type=int, default=1024)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--snr", type=float, default=0.0)
+    ap.add_argument("--zc-snr", type=float, default=15.0)
+    a = ap.parse_args()
+    from mcdpsk_acquire_restatement import ACK, CONNECT, control_frame, data_frame, encode_frame
+    from ria_amd.acquire import make_mcdpsk_windows, mcdpsk_frame_len
+    from ria_amd.engine import RxEngine
+    from ria_amd.srchash import csrc_sha256
+    e = RxEngine("DQPSK", "R1_4", max_batch=64)
+    n = a.windows
+    seeds = np.arange(1, n + 1, dtype=np.uint32) * np.uint32(2654435761)
+    connect = encode_frame(data_frame(CONNECT, 7, np.arange(25, dtype=np.uint8)))[None, :]
+    chirp = e.chirp_preamble()
+    out = {"metric": "mcdpsk_acquire_windows_per_s", "windows": n, "snr_db": a.snr, "source_hash": csrc_sha256()}
+    for name, kind in (("connect_awgn", 0), ("connect_moderate", 2)):
+        w, sl = make_mcdpsk_windows(e, connect, chirp, n, 3, kind, a.snr, seeds)
+        dt, (frames, res) = timed(lambda: e.mcdpsk_acquire(w, sl, 3), a.reps)
+        out[name] = {"windows_per_s": n / dt, "ms": dt * 1e3, "success": int(res["success"].sum()),
+                     "recovered": int(((res["success"] != 0) & (res["candidates"] > 1)).sum()),
+                     "candidates": int(res["candidates"].sum())}
+        if kind == 0:
+            # the same windows through the separate calls, stage by stage (primary candidate only): detection, demodulation
+            # at the detected starts, robust decode of every codeword; windows are gathered between the stages
+            fl = mcdpsk_frame_len(3)
+            dt_sync, ch = timed(lambda: e.sync_chirp(w[:, :sl].contiguous(), 0.15), a.reps)
+            ok = np.nonzero(ch["success"] != 0)[0]
+            starts = ch["down_chirp_start"][ok].astype(np.int64) + 28800
+            fit = ok[starts + fl <= w.shape[1]]
+            starts = ch["down_chirp_start"][fit].astype(np.int64) + 28800
+            idx = torch.from_numpy(fit).to(e.device)
+            cols = torch.from_numpy(starts).to(e.device)[:, None] + torch.arange(fl, device=e.device)[None, :]
+            frames_ = torch.gather(w[idx], 1, cols).contiguous()
+            cfo = torch.from_numpy(ch["cfo_hz"][fit].astype(np.float32)).to(e.device)
+            dt_demod, (llr, _) = timed(lambda: e.mcdpsk_demod(frames_, 10, 1, 1, cfo_hz=cfo), a.reps)
+            rows = llr[:, :3 * 648].reshape(-1, 648).contiguous()
+            dt_dec, _ = timed(lambda: e.ldpc_decode_robust(rows), a.reps)
+            out["host_chain"] = {"detect_ms": dt_sync * 1e3, "demod_ms": dt_demod * 1e3, "decode_ms": dt_dec * 1e3,
+                                 "sum_ms": (dt_sync + dt_demod + dt_dec) * 1e3,
+                                 "windows_per_s": n / (dt_sync + dt_demod + dt_dec), "windows_decoded": len(fit)}
+            del frames_, llr, rows
+        del w
+    # windows whose frame sits 288 samples behind the preamble: the primary and the alternate fail, the timing recovery
+    # decodes them (at +48 samples in the restatement's AWGN windows)
+    w, sl = make_mcdpsk_windows(e, connect, chirp, n, 3, 0, a.snr, seeds, gap=288)
+    dt, (frames, res) = timed(lambda: e.mcdpsk_acquire(w, sl, 3), a.reps)
+    out["connect_recovery"] = {"windows_per_s": n / dt, "ms": dt * 1e3, "success": int(res["success"].sum()),
+                               "recovered": int(((res["success"] != 0) & (res["candidates"] > 1)).sum()),
+                               "candidates": int(res["candidates"].sum())}
+    del w
+    # connected ZC windows at an SNR where the detector accepts them (at 0 dB the ZC correlation stays below 0.25 and the
+    # call is detection only)
+    ack = encode_frame(control_frame(ACK, 3))[None, :]
+    zc = e.zc_preamble(5)
+    w, sl = make_mcdpsk_windows(e, ack, zc, n, 1, 0, a.zc_snr, seeds)
+    dt, (frames, res) = timed(lambda: e.mcdpsk_acquire(w, sl, 1, sync="zc", min_confidence=0.25), a.reps)
+    out["zc_connected"] = {"snr_db": a.zc_snr, "windows_per_s": n / dt, "ms": dt * 1e3, "accepted": int(res["accepted"].sum()),
+                           "candidates": int(res["candidates"].sum())}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
