@@ -151,6 +151,17 @@ int ria_gpu_demod_batch(ria_gpu_handle h, const float* samples_dev, const uint64
                         const ria_frame_meta* meta_dev, int n_frames,
                         float* llr_out_dev, ria_frame_status* status_dev, void* stream);
 
+/* ---- LLR input domain of every LDPC decode (ria_gpu_ldpc_decode_batch, ria_gpu_ldpc_decode_robust_batch,
+ * ria_gpu_decode_batch, ria_gpu_rx_batch, ria_gpu_rx_acquire_batch, ria_gpu_mcdpsk_acquire_batch) -----------------
+ * Each LLR x goes through canon(x) before the first iteration:
+ *   NaN -> +1e30;  x > +1e30 (+inf included) -> +1e30;  x < -1e30 (-inf included) -> -1e30;  -0.0 -> +0.0;
+ *   every other value unchanged (f32 denormals are kept, not flushed).
+ * Bit-exact with LDPCDecoder::decodeBP (ok, lastIterations(), bytes) for every finite |x| <= 1e30, zeros and
+ * denormals included, at any max_iterations >= 0 and any min-sum factor in (0, 1]: the reference itself treats -0.0 and
+ * +0.0 alike (it only tests x < 0 and |x|).  For NaN, +-inf and finite |x| > 1e30 the result is the reference's
+ * answer on canon(x), which differs from its answer on the raw value where the raw value would turn its sums into
+ * inf or NaN.  max_iterations 0: ok 0, iterations 0, bytes = the hard bits (x < 0) of the input. */
+
 /* ---- RX: decode  (protocol::v2::decodeFixedFrame, frame_v2.hpp:848, frame_v2.cpp:1335-1883) --- */
 /* llr_dev: frame f at llr_dev + f*llr_stride (first 2592 used).  info_out_dev: n_frames *
  * info_bytes_per_frame.  status_dev: n_frames entries. */

@@ -158,6 +158,24 @@ def main():
                 n_succ += ok_r
         check(f"ldpc_decode rate={rate} ({n_succ}/80 converged)", ok)
 
+    # 6b. the decoders over their whole input domain (tests/ldpc_domain_inputs.py): erasures, ties, clamp edge, denormals,
+    # out-of-contract values, every factor x max_iterations, robustDecodeSingleCW and decodeFixedFrame on frame families
+    sys.path.insert(0, os.path.join(os.path.dirname(po.HERE), "tests"))
+    import ldpc_domain_inputs as L
+    for rn, rate in L.RATES.items():
+        for fam in L.FAMILIES + (L.OOC,):
+            X = L.family(O, rate, fam)
+            a, b = L.decode_answers(R, rate, X), L.decode_answers(O, rate, X)
+            ra, rb = L.robust_answers(R, rate, X), L.robust_answers(O, rate, X)
+            same = all(np.array_equal(a[k], b[k]) for k in a) and all(np.array_equal(ra[k], rb[k]) for k in ra)
+            conv = int(a["res"][:, L.CONFIGS.index((0.9375, 200)), 0].sum())
+            check(f"ldpc domain {fam:9s} rate={rn} ({len(X)} rows, {conv} converged at 200 iterations)", same)
+    for mod, rate, shape, n, seed in L.FRAME_SETS:
+        llr, _ = L.frames(O, mod, rate, shape, n, seed)
+        a, b = L.frame_answers(R, mod, rate, llr), L.frame_answers(O, mod, rate, llr)
+        check(f"ldpc domain frames {mod} rate={rate} {shape} ({int(a['ok'].all(1).sum())}/{n} decoded by ref)",
+              all(np.array_equal(a[k], b[k]) for k in a))
+
     # 8. ZC acquisition (sync::ZCSync): preamble synthesis and detect() over SNR x CFO x offset x root
     for root in (1, 3, 5, 7):
         check(f"zc_generate root={root}", bits_equal(O.zc_generate(root), R.zc_generate(root)))

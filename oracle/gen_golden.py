@@ -303,6 +303,41 @@ HARQ_CASES = [(10, 1, 4, 0, -22.0), (10, 1, 4, 0, -20.0), (10, 1, 2, 0, -19.0), 
 HARQ_TRIALS, HARQ_SEED = 192, 424242
 
 
+def ldpc_domain_fixture(R):
+    """LDPCDecoder, robustDecodeSingleCW and decodeFixedFrame of the reference over the decoder's input domain
+    (tests/ldpc_domain_inputs.py builds the inputs; only their sha256 is kept here, next to the answers)."""
+    sys.path.insert(0, os.path.join(os.path.dirname(po.HERE), "tests"))
+    import ldpc_domain_inputs as L
+    O = po.Oracle()
+    rec = {"configs": np.array(L.CONFIGS, np.float32)}
+    for rn, rate in L.RATES.items():
+        for fam in L.FAMILIES + (L.OOC,):
+            X = L.family(O, rate, fam)
+            key = f"{fam}_{rn}"
+            rec[f"sha_{key}"] = np.array(L.digest(X))
+            for k, v in {**L.decode_answers(R, rate, X), **L.robust_answers(R, rate, X)}.items():
+                rec[f"{k}_{key}"] = v
+            if fam == L.OOC:     # the same rows mapped as include/ria_gpu.h states (the GPU's answers where raw ones differ)
+                for k, v in {**L.decode_answers(R, rate, L.canon(X)), **L.robust_answers(R, rate, L.canon(X))}.items():
+                    rec[f"{k}_canon_{key}"] = v
+            if fam == "waterfall":
+                ans = {"res": rec[f"res_{key}"]}
+                rows, factors = L.boundary_rows(rate, X, ans)
+                rec[f"bnd_rows_{key}"], rec[f"bnd_factors_{key}"] = rows, factors
+                for k, v in L.boundary_answers(R, rate, X, rows, factors).items():
+                    rec[f"{k}_{key}"] = v
+            print("ldpc domain", key, "rows", len(X), "converged at (0.9375, 200):",
+                  int(rec[f"res_{key}"][:, L.CONFIGS.index((0.9375, 200)), 0].sum()), flush=True)
+    for mod, rate, shape, n, seed in L.FRAME_SETS:
+        llr, _ = L.frames(O, mod, rate, shape, n, seed)
+        key = f"{mod}_{[k for k, v in L.RATES.items() if v == rate][0]}_{shape}"
+        rec[f"sha_frm_{key}"] = np.array(L.digest(llr))
+        for k, v in L.frame_answers(R, mod, rate, llr).items():
+            rec[f"frm_{k}_{key}"] = v
+        print("ldpc domain frames", key, "all ok", int(rec[f"frm_ok_{key}"].all(axis=1).sum()), "of", n, flush=True)
+    return rec
+
+
 def harq_inputs(case_index, n=HARQ_TRIALS):
     """(info [n, 21], seeds [n, 4]) of a HARQ case: the sweep's own per-trial recipe (ria_amd/sweep.py)"""
     sys.path.insert(0, os.path.dirname(po.HERE))
@@ -584,6 +619,9 @@ def main():
     if only == "harq":
         np.savez_compressed(os.path.join(OUT, "harq_trials.npz"), **harq_fixture(R))
         return 0
+    if only == "ldpc_domain":
+        np.savez_compressed(os.path.join(OUT, "ldpc_domain.npz"), **ldpc_domain_fixture(R))
+        return 0
     if only == "robust":
         np.savez_compressed(os.path.join(OUT, "robust_ldpc.npz"), **robust_fixture(R))
         return 0
@@ -669,6 +707,7 @@ def main():
     np.savez_compressed(os.path.join(OUT, "burst_chain.npz"), **burst_fixture(R, O))
     np.savez_compressed(os.path.join(OUT, "burst_interleaver.npz"), **burst_interleaver_fixture(R))
     np.savez_compressed(os.path.join(OUT, "robust_ldpc.npz"), **robust_fixture(R))
+    np.savez_compressed(os.path.join(OUT, "ldpc_domain.npz"), **ldpc_domain_fixture(R))
     np.savez_compressed(os.path.join(OUT, "harq_trials.npz"), **harq_fixture(R))
     np.savez_compressed(os.path.join(OUT, "cfo_impairment.npz"), **cfo_fixture(R))
     np.savez_compressed(os.path.join(OUT, "mcdpsk_waveform.npz"), **mcwf_fixture(R))
