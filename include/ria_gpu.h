@@ -77,7 +77,25 @@ typedef struct ria_gpu_geometry {
 } ria_gpu_geometry;
 
 /* Per-frame input of the demodulator: the three setters the host calls before process()
- * (streaming_decoder.cpp:896 setAbsoluteTrainingPosition, :1347 setFrequencyOffset). */
+ * (streaming_decoder.cpp:896 setAbsoluteTrainingPosition, :1347 setFrequencyOffset).
+ *
+ * Limit: |cfo_hz * abs_position| <= 1.025e12 Hz*samples (2^27 * 48000 / (2 pi); at 60 Hz about 99 hours of samples).
+ * The correction phase at the first sample is -2 pi cfo_hz abs_position / 48000 rounded to float and wrapped into
+ * [-pi, pi] by repeated subtraction of 2 pi on that float (ofdm_chirp_waveform.cpp:402-411).  Up to |phase| = 2^27
+ * every step changes the float and the library reproduces the reference's wrap bit for bit (ria_amd/csrc/cfo_theta0.h;
+ * about |cfo_hz * abs_position| / 48000 steps of one lane, fewer than 2.3e7 at the limit).  Above 2^27, and
+ * for an infinite phase (cfo_hz +-inf), the float no longer changes and the reference's loop does not return at all; the
+ * library starts such a frame at phase 0 instead, at once.  For a NaN phase (cfo_hz NaN, or +-inf at position 0) the
+ * reference's loops end at once with a NaN phase; the library deliberately starts that frame at phase 0 too.  Apart
+ * from that cfo_hz is not validated: a non-finite value gives non-finite outputs.  flags bits 1..31 are ignored.
+ *
+ * Non-finite samples.  Samples may be NaN, +-inf or so large that sums overflow.  The demodulator then follows the
+ * reference bit for bit, including what its std::complex arithmetic does there: operator* and operator/ recover an
+ * infinity where both parts of a result come out NaN (C99 Annex G.5.1, libgcc __mulsc3 / __divsc3), and hypotf(inf, NaN)
+ * is +inf.  The LLRs stay finite in every case the tests record: the demappers clamp to [-20, 20] with std::min / std::max, which turn a NaN into the
+ * bound.  The float status words (ria_frame_status: fading_index, noise_variance, lts_phase_slope, snr_linear,
+ * corr_phase, snr_db) can be NaN or inf for such a frame; a NaN there is a NaN in the reference, but its sign and payload
+ * are the GPU's (0x7FC00000), not the host's. */
 typedef struct ria_frame_meta {
     float    cfo_hz;          /* IWaveform::setFrequencyOffset */
     uint32_t flags;           /* bit0: first LTS symbol is negated (burst marker, ofdm_chirp_waveform.cpp:421-440) */
@@ -122,6 +140,10 @@ typedef struct ria_gpu* ria_gpu_handle;
 
 /* ---- lifecycle ------------------------------------------------------------------------------ */
 int  ria_gpu_abi_version(void);
+/* Which implementation of the demodulator this process uses (fixed at the first call of any entry point that
+ * demodulates, or of this function): 0 the split pipeline (demod_fft / decide / walk / est kernels), 1 the
+ * one-wave-per-frame demod_frames_kernel (environment RIA_DEMOD_FUSED=1).  Both give the same bits. */
+int  ria_gpu_demod_variant(void);
 void ria_gpu_default_config(ria_gpu_config* cfg);
 /* replaces: std::make_unique<OFDMChirpWaveform>(config) + configure(mod, rate)
  * (streaming_decoder.cpp:2299,2328; ofdm_chirp_waveform.cpp:81-107) */

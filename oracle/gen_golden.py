@@ -338,6 +338,30 @@ def ldpc_domain_fixture(R):
     return rec
 
 
+def demod_domain_fixture(R):
+    """OFDMChirpWaveform::process + getSoftBits of the reference (OFDM-COX object for QAM256) over the demodulator's
+    input domain (tests/demod_domain_inputs.py builds the inputs; only their sha256 is kept here).  Per (mode, family):
+    aux_* uint32 [n, 6] bit patterns of cfo_hz, fading_index, noise_variance, lts_phase_slope, snr_linear, corr_phase;
+    snr_* float32 [n] (display value); n_llr_* int32 [n]; llr0_* the first frame's LLR bits; dig_* uint8 [n, 32] sha256
+    of every frame's LLR bits (NaN canonical)."""
+    sys.path.insert(0, os.path.join(os.path.dirname(po.HERE), "tests"))
+    import demod_domain_inputs as D
+    O = po.Oracle()
+    rec = {}
+    for mode, fam in D.CASES:
+        F = D.family(O, mode, fam)
+        key = f"{mode}_{fam}"
+        llr, aux, snr = D.reference_answers(R, mode, F)
+        rec[f"sha_{key}"] = np.array(D.digest(F))
+        rec[f"aux_{key}"], rec[f"snr_{key}"] = aux, snr
+        rec[f"n_llr_{key}"] = np.array([len(l) for l in llr], np.int32)
+        rec[f"llr0_{key}"] = llr[0].view(np.uint32)
+        rec[f"dig_{key}"] = np.stack([np.frombuffer(bytes.fromhex(D.llr_digest(l)), np.uint8) for l in llr])
+        print("demod domain", key, "frames", len(llr), "NaN LLRs", sum(int(np.isnan(l).sum()) for l in llr),
+              "inf LLRs", sum(int(np.isinf(l).sum()) for l in llr), flush=True)
+    return rec
+
+
 def harq_inputs(case_index, n=HARQ_TRIALS):
     """(info [n, 21], seeds [n, 4]) of a HARQ case: the sweep's own per-trial recipe (ria_amd/sweep.py)"""
     sys.path.insert(0, os.path.dirname(po.HERE))
@@ -622,6 +646,9 @@ def main():
     if only == "ldpc_domain":
         np.savez_compressed(os.path.join(OUT, "ldpc_domain.npz"), **ldpc_domain_fixture(R))
         return 0
+    if only == "demod_domain":
+        np.savez_compressed(os.path.join(OUT, "demod_domain.npz"), **demod_domain_fixture(R))
+        return 0
     if only == "robust":
         np.savez_compressed(os.path.join(OUT, "robust_ldpc.npz"), **robust_fixture(R))
         return 0
@@ -708,6 +735,7 @@ def main():
     np.savez_compressed(os.path.join(OUT, "burst_interleaver.npz"), **burst_interleaver_fixture(R))
     np.savez_compressed(os.path.join(OUT, "robust_ldpc.npz"), **robust_fixture(R))
     np.savez_compressed(os.path.join(OUT, "ldpc_domain.npz"), **ldpc_domain_fixture(R))
+    np.savez_compressed(os.path.join(OUT, "demod_domain.npz"), **demod_domain_fixture(R))
     np.savez_compressed(os.path.join(OUT, "harq_trials.npz"), **harq_fixture(R))
     np.savez_compressed(os.path.join(OUT, "cfo_impairment.npz"), **cfo_fixture(R))
     np.savez_compressed(os.path.join(OUT, "mcdpsk_waveform.npz"), **mcwf_fixture(R))

@@ -26,15 +26,57 @@ static inline cf cf_mk(float re, float im) { cf z = { re, im }; return z; }
 static inline cf cf_add(cf a, cf b) { return cf_mk(a.re + b.re, a.im + b.im); }
 static inline cf cf_sub(cf a, cf b) { return cf_mk(a.re - b.re, a.im - b.im); }
 static inline cf cf_conj(cf a) { return cf_mk(a.re, -a.im); }
+/* std::complex<float> operator* compiles to libgcc's __mulsc3: the plain products, and where both parts come out NaN the
+ * recovery of C99 Annex G.5.1 (an infinite operand gives an infinite product).  Finite operands never reach it. */
+static cf cf_mul_recover(float a, float b, float c, float d, cf z) {
+    float ac = a * c, bd = b * d, ad = a * d, bc = b * c;
+    int recalc = 0;
+    if (isinf(a) || isinf(b)) {
+        a = copysignf(isinf(a) ? 1.0f : 0.0f, a); b = copysignf(isinf(b) ? 1.0f : 0.0f, b);
+        if (isnan(c)) c = copysignf(0.0f, c);
+        if (isnan(d)) d = copysignf(0.0f, d);
+        recalc = 1;
+    }
+    if (isinf(c) || isinf(d)) {
+        c = copysignf(isinf(c) ? 1.0f : 0.0f, c); d = copysignf(isinf(d) ? 1.0f : 0.0f, d);
+        if (isnan(a)) a = copysignf(0.0f, a);
+        if (isnan(b)) b = copysignf(0.0f, b);
+        recalc = 1;
+    }
+    if (!recalc && (isinf(ac) || isinf(bd) || isinf(ad) || isinf(bc))) {
+        if (isnan(a)) a = copysignf(0.0f, a);
+        if (isnan(b)) b = copysignf(0.0f, b);
+        if (isnan(c)) c = copysignf(0.0f, c);
+        if (isnan(d)) d = copysignf(0.0f, d);
+        recalc = 1;
+    }
+    if (recalc) { z.re = INFINITY * (a * c - b * d); z.im = INFINITY * (a * d + b * c); }
+    return z;
+}
 static inline cf cf_mul(cf a, cf b) {
-    return cf_mk(a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re);
+    cf z = cf_mk(a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re);
+    if (isnan(z.re) && isnan(z.im)) z = cf_mul_recover(a.re, a.im, b.re, b.im, z);
+    return z;
 }
 static inline cf cf_scale(float s, cf a) { return cf_mk(s * a.re, s * a.im); }
 static inline cf cf_divf(cf a, float s) { return cf_mk(a.re / s, a.im / s); }
 static inline cf cf_div(cf x, cf y) { /* libgcc __divsc3, wide-type path */
     double a = x.re, b = x.im, c = y.re, d = y.im;
     double denom = c * c + d * d;
-    return cf_mk((float)((a * c + b * d) / denom), (float)((b * c - a * d) / denom));
+    float x_ = (float)((a * c + b * d) / denom), y_ = (float)((b * c - a * d) / denom);
+    if (isnan(x_) && isnan(y_)) {   /* Annex G.5.1 recovery, as __divsc3 does it on the float operands */
+        float fa = x.re, fb = x.im, fc = y.re, fd = y.im;
+        if (fc == 0.0f && fd == 0.0f && (!isnan(fa) || !isnan(fb))) {
+            x_ = copysignf(INFINITY, fc) * fa; y_ = copysignf(INFINITY, fc) * fb;
+        } else if ((isinf(fa) || isinf(fb)) && isfinite(fc) && isfinite(fd)) {
+            fa = copysignf(isinf(fa) ? 1.0f : 0.0f, fa); fb = copysignf(isinf(fb) ? 1.0f : 0.0f, fb);
+            x_ = INFINITY * (fa * fc + fb * fd); y_ = INFINITY * (fb * fc - fa * fd);
+        } else if ((isinf(fc) || isinf(fd)) && isfinite(fa) && isfinite(fb)) {
+            fc = copysignf(isinf(fc) ? 1.0f : 0.0f, fc); fd = copysignf(isinf(fd) ? 1.0f : 0.0f, fd);
+            x_ = 0.0f * (fa * fc + fb * fd); y_ = 0.0f * (fb * fc - fa * fd);
+        }
+    }
+    return cf_mk(x_, y_);
 }
 static inline float cf_abs(cf a) { return hypotf(a.re, a.im); }
 static inline float cf_norm(cf a) { return a.re * a.re + a.im * a.im; }
@@ -42,6 +84,12 @@ static inline float cf_arg(cf a) { return atan2f(a.im, a.re); }
 static inline cf cf_expj(float phi) { return cf_mk(cosf(phi), sinf(phi)); }
 static inline float fmaxf_(float a, float b) { return (a < b) ? b : a; } /* std::max */
 static inline float fminf_(float a, float b) { return (b < a) ? b : a; } /* std::min */
+
+/* How often the last ro_rx_process_flags() of this thread took each data-dependent branch of the demodulator
+ * (ro_branch_counts; order: RO_BC_* in ria_oracle.h).  Test instrumentation only: no result depends on it. */
+static _Thread_local unsigned ro_bc[RO_BC_N];
+#define BC(i) (ro_bc[i]++)
+void ro_branch_counts(unsigned* out) { memcpy(out, ro_bc, sizeof(ro_bc)); }
 
 /* ------------------------------------------------------------------ mt19937 / normal */
 void ro_mt_seed(ro_mt* m, uint32_t seed) {
@@ -728,14 +776,16 @@ static void ro_estimate_lts(ro_rx* r, const float* x) { /* channel_equalizer.cpp
         if (cf_abs(h0) > 0.01f && cf_abs(h1) > 0.01f) {
             cf diff = cf_mul(h1, cf_conj(h0));
             float mag = cf_abs(diff);
-            if (mag > 1e-6f) { sum = cf_add(sum, cf_divf(diff, mag)); valid++; }
-        }
+            if (mag > 1e-6f) { sum = cf_add(sum, cf_divf(diff, mag)); valid++; } else BC(RO_BC_MAG_SMALL);
+        } else BC(RO_BC_H_SMALL);
     }
+    if (valid <= 10) BC(RO_BC_CNT_SMALL);
     if (valid > 10) {
         float avg = atan2f(sum.im, sum.re);
         float dur = (float)RO_SYM / (float)48000u;
         float res = (float)((double)avg / (2.0f * M_PI * (double)dur));
         if (fabsf(res) > 0.3f && fabsf(res) < 5.0f) {
+            BC(RO_BC_RERUN);
             r->cfo_hz += res;
             r->mixer.phase = 0.0f;
             r->corr_phase = phase0;
@@ -753,8 +803,8 @@ static void ro_estimate_lts(ro_rx* r, const float* x) { /* channel_equalizer.cpp
         if (cf_abs(h0) > 0.01f && cf_abs(h1) > 0.01f) {
             cf diff = cf_mul(h1, cf_conj(h0));
             float mag = cf_abs(diff);
-            if (mag > 1e-6f) { ss = cf_add(ss, cf_divf(diff, mag)); sc++; }
-        }
+            if (mag > 1e-6f) { ss = cf_add(ss, cf_divf(diff, mag)); sc++; } else BC(RO_BC_MAG_SMALL);
+        } else BC(RO_BC_H_SMALL);
     }
     if (sc > 0) r->slope = cf_arg(cf_divf(ss, (float)sc));
 
@@ -772,6 +822,8 @@ static void ro_estimate_lts(ro_rx* r, const float* x) { /* channel_equalizer.cpp
         float nv = noise_sum / (4.0f * (float)count);
         float sp = signal_sum / (float)count;
         float snr = sp / fmaxf_(nv, 1e-10f);
+        if (snr < 3.16f) BC(RO_BC_SNR_LOW);
+        if (10000.0f < snr) BC(RO_BC_SNR_HIGH);
         snr = fmaxf_(3.16f, fminf_(10000.0f, snr));
         r->noise_var = nv;
         r->snr_lin = snr;
@@ -813,6 +865,7 @@ static void ro_update_channel(ro_rx* r, const cf* fd) { /* channel_equalizer.cpp
         for (int p = 0; p < np; ++p) {
             cf hold = r->H[g->pilot_idx[p]];
             float hm = cf_abs(hold);
+            if (!(hm > 0.01f)) BC(RO_BC_HM_SMALL);
             if (hm > 0.01f) {
                 cf ratio = cf_mul(hls[p], cf_conj(hold));
                 float mag = cf_abs(ratio);
@@ -949,13 +1002,15 @@ static void ro_equalize(ro_rx* r, const cf* fd, cf* eq) { /* channel_equalizer.c
         avg /= (float)nd;
         float thr = 0.25f * avg;
         float snv = r->noise_var;
-        if (snv < 1e-6f) snv = avg / 31.6f;
+        if (snv < 1e-6f) { BC(RO_BC_SNV_SMALL); snv = avg / 31.6f; }
         for (int i = 0; i < nd; ++i) {
             cf h = r->H[g->data_idx[i]];
             float hp = cf_norm(h), den = hp + snv;
-            if (den < 1e-10f) { eq[i] = cf_mk(0, 0); r->cnv[i] = 100.0f; }
+            if (den < 1e-10f) { BC(RO_BC_DEN_SMALL); eq[i] = cf_mk(0, 0); r->cnv[i] = 100.0f; }
             else { eq[i] = cf_divf(cf_mul(fd[g->data_idx[i]], cf_conj(h)), den); r->cnv[i] = snv / (hp + snv); }
             if (hp < thr) r->cnv[i] = 100.0f;
+            if (r->cnv[i] < 1e-6f) BC(RO_BC_CNV_LOW);
+            if (100.0f < r->cnv[i]) BC(RO_BC_CNV_HIGH);
             r->cnv[i] = fmaxf_(1e-6f, fminf_(100.0f, r->cnv[i]));
         }
         return;
@@ -963,9 +1018,11 @@ static void ro_equalize(ro_rx* r, const cf* fd, cf* eq) { /* channel_equalizer.c
     for (int i = 0; i < nd; ++i) {
         cf h = r->H[g->data_idx[i]];
         float hp = cf_norm(h), den = hp + r->noise_var;
-        if (den < 1e-10f) { eq[i] = cf_mk(0, 0); r->cnv[i] = 100.0f; }
+        if (den < 1e-10f) { BC(RO_BC_DEN_SMALL); eq[i] = cf_mk(0, 0); r->cnv[i] = 100.0f; }
         else {
             eq[i] = cf_divf(cf_mul(cf_conj(h), fd[g->data_idx[i]]), den);
+            if (r->noise_var / den < 1e-6f) BC(RO_BC_CNV_LOW);
+            if (100.0f < r->noise_var / den) BC(RO_BC_CNV_HIGH);
             r->cnv[i] = fmaxf_(1e-6f, fminf_(100.0f, r->noise_var / den));
         }
     }
@@ -1064,7 +1121,7 @@ static int ro_demap(int mod, cf sym, cf prev, float nv, float* o) { /* soft_dema
             cf diff = cf_mul(sym, cf_conj(prev));
             float pd = atan2f(diff.im, diff.re);
             float sp = cf_abs(sym) * cf_abs(prev);
-            if (sp < 1e-6f) { o[0] = 0.0f; return 1; }
+            if (sp < 1e-6f) { BC(RO_BC_SP_SMALL); o[0] = 0.0f; return 1; }
             float dnv = 2.0f * nv;
             float conf = 2.0f * sp / dnv;
             o[0] = ro_clip(conf * cosf(pd));
@@ -1119,6 +1176,7 @@ static int ro_demod_symbol(ro_rx* r, const cf* eq, float* soft) { /* demodulator
         for (int i = 0; i < nd; ++i) r->dprev[i] = cf_mk(1, 0);
         r->have_dprev = 1;
     }
+    if (mod == RO_D8PSK && r->fading_index > 0.30f) BC(RO_BC_D8PSK_TWO_PASS);
     if (mod == RO_D8PSK && r->fading_index > 0.30f) {
         /* demodulateD8PSKTwoPass (demodulator.cpp:533-620): common phase error from the embedded DQPSK grid,
          * half of it removed before the D8PSK demap; the corrected symbol becomes the next reference */
@@ -1175,6 +1233,15 @@ static int ro_demod_symbol(ro_rx* r, const cf* eq, float* soft) { /* demodulator
     return n;
 }
 
+/* initial correction phase (ofdm_chirp_waveform.cpp:402-411).  As in the reference, the wrap does not end once |init|
+ * exceeds 2^27 (a float no longer changes when 2 pi is subtracted) or is infinite. */
+float ro_theta0(float cfo_hz, long long abs_pos) {
+    float init = (float)(-2.0f * M_PI * (double)cfo_hz * (double)(unsigned long long)abs_pos / (double)48000u);
+    while ((double)init > M_PI) init = (float)((double)init - 2.0f * M_PI);
+    while ((double)init < -M_PI) init = (float)((double)init + 2.0f * M_PI);
+    return init;
+}
+
 int ro_rx_process(const ro_geom* g, const float* samples, int n, float cfo_hz, long long abs_pos,
                   float* llr_out, int max_llr, ro_rx_aux* aux) {
     return ro_rx_process_flags(g, samples, n, cfo_hz, abs_pos, 0, llr_out, max_llr, aux);
@@ -1198,10 +1265,9 @@ int ro_rx_process_flags(const ro_geom* g, const float* samples_in, int n, float 
     }
     static _Thread_local ro_rx r;
     memset(&r, 0, sizeof(r));
+    memset(ro_bc, 0, sizeof(ro_bc));
     r.g = g;
-    float init = (float)(-2.0f * M_PI * (double)cfo_hz * (double)(unsigned long long)abs_pos / (double)48000u);
-    while ((double)init > M_PI) init = (float)((double)init - 2.0f * M_PI);
-    while ((double)init < -M_PI) init = (float)((double)init + 2.0f * M_PI);
+    float init = ro_theta0(cfo_hz, abs_pos);
     r.cfo_hz = cfo_hz;
     r.corr_phase = init;
     ro_nco_init(&r.mixer, 1500.0f, 48000.0f);

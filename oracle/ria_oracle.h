@@ -94,6 +94,18 @@ typedef struct ro_rx_aux {
 } ro_rx_aux;
 int ro_rx_process(const ro_geom* g, const float* samples, int n, float cfo_hz, long long abs_pos,
                   float* llr_out, int max_llr, ro_rx_aux* aux);
+/* the correction phase at the first sample, wrapped into [-pi, pi] as OFDMChirpWaveform::process does; like the
+ * reference it does not return for |2 pi cfo_hz abs_pos / 48000| above 2^27 or infinite */
+float ro_theta0(float cfo_hz, long long abs_pos);
+/* test instrumentation: how often the last ro_rx_process[_flags]() of the calling thread took each data-dependent branch.
+ * H_SMALL: a training pair failed |H| > 0.01; MAG_SMALL: failed mag > 1e-6; CNT_SMALL: 10 or fewer pairs for the residual
+ * CFO; RERUN: the 0.3 .. 5 Hz re-run; SNR_LOW / SNR_HIGH: the training SNR clamped at 3.16 / 10000; HM_SMALL: a pilot's
+ * previous |H| failed hm > 0.01; SNV_SMALL: noise variance below 1e-6 replaced; DEN_SMALL: den < 1e-10; CNV_LOW / CNV_HIGH:
+ * the per-carrier noise clamped at 1e-6 / 100; D8PSK_TWO_PASS: symbols through the fading > 0.30 gate; SP_SMALL: the
+ * 1-bit demapper's sp < 1e-6 */
+enum { RO_BC_H_SMALL, RO_BC_MAG_SMALL, RO_BC_CNT_SMALL, RO_BC_RERUN, RO_BC_SNR_LOW, RO_BC_SNR_HIGH, RO_BC_HM_SMALL, RO_BC_SNV_SMALL,
+       RO_BC_DEN_SMALL, RO_BC_CNV_LOW, RO_BC_CNV_HIGH, RO_BC_D8PSK_TWO_PASS, RO_BC_SP_SMALL, RO_BC_N };
+void ro_branch_counts(unsigned* out /* [RO_BC_N] */);
 
 /* the same with OFDMChirpWaveform's one-shot burst marker: flags bit0 = the first LTS symbol was negated on air
  * (ofdm_chirp_waveform.cpp:421-440) */

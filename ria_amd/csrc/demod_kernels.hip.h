@@ -23,9 +23,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "../../include/ria_gpu.h"
 #include "devmath.h"
+#include "cfo_theta0.h"
 #include "host_tables.hpp"
 
 namespace ria {
@@ -106,13 +108,67 @@ struct DemodArgs {
 };
 
 // ---------------------------------------------------------------- complex helpers (reference semantics)
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) {  // naive, no FMA
+// std::complex<float> operator* and operator/ compile to libgcc's __mulsc3 / __divsc3: the plain formulas, and where BOTH
+// parts of the result are NaN the recovery of C99 Annex G.5.1 (an infinite operand gives an infinite product, a finite
+// value over an infinite one gives zero).  Finite operands never take the recovery.  cmul_plain is the multiplication
+// without it: the butterflies and the mixer of the transform (see fft_bins_have_nan; "Non-finite samples" in include/ria_gpu.h).
+__device__ __forceinline__ bool isinf_(float v) { return (f2u(v) & 0x7fffffffu) == 0x7f800000u; }
+__device__ __forceinline__ bool isnan_(float v) { return v != v; }
+__device__ __forceinline__ float csign_(float mag, float s) { return u2f((f2u(mag) & 0x7fffffffu) | (f2u(s) & 0x80000000u)); }
+__device__ __forceinline__ float2 cmul_plain(float2 a, float2 b) {  // naive, no FMA
     return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
+}
+__device__ __noinline__ float2 cmul_recover(float a, float b, float c, float d, float2 z) {
+    const float ac = a * c, bd = b * d, ad = a * d, bc = b * c;
+    const float inf = u2f(0x7f800000u);
+    bool recalc = false;
+    if (isinf_(a) || isinf_(b)) {
+        a = csign_(isinf_(a) ? 1.0f : 0.0f, a); b = csign_(isinf_(b) ? 1.0f : 0.0f, b);
+        if (isnan_(c)) c = csign_(0.0f, c);
+        if (isnan_(d)) d = csign_(0.0f, d);
+        recalc = true;
+    }
+    if (isinf_(c) || isinf_(d)) {
+        c = csign_(isinf_(c) ? 1.0f : 0.0f, c); d = csign_(isinf_(d) ? 1.0f : 0.0f, d);
+        if (isnan_(a)) a = csign_(0.0f, a);
+        if (isnan_(b)) b = csign_(0.0f, b);
+        recalc = true;
+    }
+    if (!recalc && (isinf_(ac) || isinf_(bd) || isinf_(ad) || isinf_(bc))) {
+        if (isnan_(a)) a = csign_(0.0f, a);
+        if (isnan_(b)) b = csign_(0.0f, b);
+        if (isnan_(c)) c = csign_(0.0f, c);
+        if (isnan_(d)) d = csign_(0.0f, d);
+        recalc = true;
+    }
+    if (recalc) { z.x = inf * (a * c - b * d); z.y = inf * (a * d + b * c); }
+    return z;
+}
+__device__ __forceinline__ float2 cmul(float2 a, float2 b) {  // __mulsc3
+    float2 z = cmul_plain(a, b);
+    if (__builtin_expect(isnan_(z.x) && isnan_(z.y), 0)) z = cmul_recover(a.x, a.y, b.x, b.y, z);
+    return z;
+}
+__device__ __noinline__ float2 cdivc_recover(float a, float b, float c, float d, float2 z) {
+    const float inf = u2f(0x7f800000u);
+    const bool fin_cd = !isinf_(c) && !isnan_(c) && !isinf_(d) && !isnan_(d), fin_ab = !isinf_(a) && !isnan_(a) && !isinf_(b) && !isnan_(b);
+    if (c == 0.0f && d == 0.0f && (!isnan_(a) || !isnan_(b))) {
+        z.x = csign_(inf, c) * a; z.y = csign_(inf, c) * b;
+    } else if ((isinf_(a) || isinf_(b)) && fin_cd) {
+        a = csign_(isinf_(a) ? 1.0f : 0.0f, a); b = csign_(isinf_(b) ? 1.0f : 0.0f, b);
+        z.x = inf * (a * c + b * d); z.y = inf * (b * c - a * d);
+    } else if ((isinf_(c) || isinf_(d)) && fin_ab) {
+        c = csign_(isinf_(c) ? 1.0f : 0.0f, c); d = csign_(isinf_(d) ? 1.0f : 0.0f, d);
+        z.x = 0.0f * (a * c + b * d); z.y = 0.0f * (b * c - a * d);
+    }
+    return z;
 }
 __device__ __forceinline__ float2 cdivc(float2 x, float2 y) {  // libgcc __divsc3: double, one rounding
     double a = x.x, b = x.y, c = y.x, d = y.y;
     double den = c * c + d * d;
-    return make_float2(static_cast<float>((a * c + b * d) / den), static_cast<float>((b * c - a * d) / den));
+    float2 z = make_float2(static_cast<float>((a * c + b * d) / den), static_cast<float>((b * c - a * d) / den));
+    if (__builtin_expect(isnan_(z.x) && isnan_(z.y), 0)) z = cdivc_recover(x.x, x.y, y.x, y.y, z);
+    return z;
 }
 __device__ __forceinline__ float cabs_(float2 a) { return hypotf_glibc(a.x, a.y); }
 __device__ __forceinline__ float cnorm(float2 a) { return a.x * a.x + a.y * a.y; }
@@ -192,8 +248,9 @@ __device__ __forceinline__ float lane_read(float v, int l) { return __shfl(v, l)
 // ---------------------------------------------------------------- 1024-point FFT by one wavefront
 constexpr int kFftBufFloats2 = 1088;  // 1024 + 64 padding slots (index i lives at i + (i >> 4))
 
+template <bool kRecover = false>
 __device__ __forceinline__ void bfly(float2& a, float2& b, float2 w) {  // fft.cpp:113-117
-    float2 t = cmul(w, b);
+    float2 t = kRecover ? cmul(w, b) : cmul_plain(w, b);
     b = make_float2(a.x - t.x, a.y - t.y);
     a = make_float2(a.x + t.x, a.y + t.y);
 }
@@ -233,7 +290,8 @@ __device__ __forceinline__ FftLaneTw fft_load_lane_tw(const float2* __restrict__
 // addresses are contiguous over the lanes (no bank conflict: the natural order puts the lanes' pairs 32 bytes apart, 2-way),
 // and pass 1's bit-reversed gather then reads 32 consecutive slots per half wave (natural order: every other slot, 2-way).
 __device__ __forceinline__ constexpr int fft_in_slot(int i) { return 2 * ((i >> 2) & 63) + ((i >> 1) & 1) + 128 * (i & 1) + 256 * (i >> 8); }
-template <bool kLaneTw = false, bool kSlotOrder = false>
+// kRecover: every multiplication is the full __mulsc3 (see fft_bins_have_nan).
+template <bool kLaneTw = false, bool kSlotOrder = false, bool kRecover = false>
 __device__ inline void fft1024_wave(float2* buf, const float2* __restrict__ tw, const FftUniformTw& utw, float2* Yrow, int lane, const FftLaneTw* ltw = nullptr) {
     float2 x[16];
     // pass 1: bit-reversed gather, stages 1-4 on indices 16*lane + r
@@ -255,7 +313,7 @@ __device__ inline void fft1024_wave(float2* buf, const float2* __restrict__ tw, 
         for (int r = 0; r < 16; ++r) {
             if ((r & half) == 0) {
                 int k = r & (half - 1);
-                bfly(x[r], x[r + half], utw.w[half - 1 + k]);
+                bfly<kRecover>(x[r], x[r + half], utw.w[half - 1 + k]);
             }
         }
     }
@@ -275,8 +333,8 @@ __device__ inline void fft1024_wave(float2* buf, const float2* __restrict__ tw, 
             for (int r = 0; r < 16; ++r) {
                 if ((r & hr) == 0) {
                     int k = a + 16 * (r & (hr - 1));
-                    if constexpr (kLaneTw) bfly(x[r], x[r + hr], ltw->ws[hr - 1 + (r & (hr - 1))]);
-                    else bfly(x[r], x[r + hr], tw[k << (10 - s)]);
+                    if constexpr (kLaneTw) bfly<kRecover>(x[r], x[r + hr], ltw->ws[hr - 1 + (r & (hr - 1))]);
+                    else bfly<kRecover>(x[r], x[r + hr], tw[k << (10 - s)]);
                 }
             }
         }
@@ -293,14 +351,27 @@ __device__ inline void fft1024_wave(float2* buf, const float2* __restrict__ tw, 
         int pa = b + (b >> 4);
         float2 y0 = buf[pa], y1 = buf[pa + 272], y2 = buf[pa + 544], y3 = buf[pa + 816];
         const float2 w9 = tw[b << 1];
-        bfly(y0, y1, w9);
-        bfly(y2, y3, w9);
-        bfly(y0, y2, tw[b]);
-        bfly(y1, y3, tw[b + 256]);
+        bfly<kRecover>(y0, y1, w9);
+        bfly<kRecover>(y2, y3, w9);
+        bfly<kRecover>(y0, y2, tw[b]);
+        bfly<kRecover>(y1, y3, tw[b + 256]);
         if (t == 0) { if (lane >= 1 && lane <= 30) Yrow[28 + lane] = y0; }      // bins 1..30  -> logical 29..58
         else        { if (lane >= 35) Yrow[lane - 35] = y3; }                    // bins 995..1023 -> logical 0..28
     }
     wave_sync();
+}
+
+// The mixer and the butterflies multiply without the Annex G recovery (cmul_plain): with finite data the recovery is never
+// taken, and a product whose parts are both NaN makes both parts of every bin that depends on it NaN.  So a symbol whose 59
+// used bins hold no NaN never needed the recovery; a symbol with a NaN among them (an infinite sample, or sums that
+// overflowed) is mixed and transformed again with the full multiplication, which then equals the reference's.  A NaN sample
+// takes the second pass too although it can never take the recovery: telling it from an infinity would cost the finite path
+// a second test, and the second pass only ever falls on a frame that holds non-finite values.
+// Cost on the finite path: one ballot per symbol.  demod_fft_kernel 156 -> 159 VGPRs, no scratch, 3 waves per SIMD as
+// before; demod_est_kernel<QAM16> 128 VGPRs as before plus a 16-byte call frame for the out-of-line recovery.
+__device__ __forceinline__ bool fft_bins_have_nan(const float2* Yrow, int lane) {
+    const float2 y = Yrow[lane < kCarriers ? lane : 0];
+    return __any(isnan_(y.x) || isnan_(y.y)) != 0;
 }
 
 // ---------------------------------------------------------------- soft demappers (soft_demap.hpp)
@@ -496,32 +567,14 @@ __device__ __forceinline__ void demod_prefetch_symbol(const float* __restrict__ 
                                          (__attribute__((address_space(3))) void*)(raw + 256 * c), 16, 0, 0);
 }
 
-__device__ __forceinline__ void demod_fft_symbol(const DemodArgs& A, const float* __restrict__ x, int s, int next_s, float2* buf, float2* Yrow,
-                                                 DemodShared* sh, int lane, float& th_walk, int& pf_sym, const FftUniformTw& utw) {
-    const float cfo = sh->cfo;
-    const bool use_cfo = fabs_(cfo) > 0.01f;
-    const float inc = static_cast<float>(-2.0f * 3.14159265358979323846 * static_cast<double>(cfo) / 48000.0);
-    const bool aligned = (reinterpret_cast<uintptr_t>(x) & 15u) == 0;
-    if (pf_sym >= 0) {   // a prefetch is in flight or has landed: it must be complete before the tile is read or rewritten
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        wave_sync();
-    }
+// 16 lanes re-walk the correction phases from the markers, the wave mixes the 1024 samples down into the tile and transforms
+// them.  from_tile: the samples were prefetched into the tile (demod_prefetch_symbol), else they are read from memory.
+template <bool kRecover>
+__device__ __forceinline__ void demod_stage_and_fft(const DemodArgs& A, const float* __restrict__ x, int s, float2* buf, float2* Yrow, DemodShared* sh,
+                                                    int lane, bool use_cfo, float inc, bool aligned, bool from_tile, const FftUniformTw& utw) {
     float th_reg[16];
     if (use_cfo) {
-        // channel_equalizer.cpp:132-144: float phase recurrence over EVERY sample (CP included), wrapped
-        // with double-precision pi.  Inherently serial: lane 0 walks the symbol once, dropping a
-        // marker every 72 samples; 16 lanes then re-walk 72 samples each into the (still free) tile.
         float* thb = reinterpret_cast<float*>(buf);
-        if (lane == 0) {
-            float th = th_walk;
-            for (int q = 0; q < 16; ++q) {
-                sh->sub_theta[q] = th;
-#pragma unroll 1
-                for (int g = 0; g < 9; ++g) th = cfo_phase_step8(th, inc);
-            }
-            th_walk = th;
-        }
-        wave_sync();
         if (lane < 16) {
             float th = sh->sub_theta[lane];
             for (int i = 0; i < 72; ++i) { thb[72 * lane + i] = th; th = cfo_phase_step(th, inc); }
@@ -533,11 +586,8 @@ __device__ __forceinline__ void demod_fft_symbol(const DemodArgs& A, const float
             for (int e = 0; e < 4; ++e) th_reg[4 * c + e] = thb[kCP + 4 * lane + 256 * c + e];
         wave_sync();
     }
-    // stage + downconvert 1024 samples (cyclic prefix dropped): 16 B per lane per load, coalesced; from the tile when the
-    // previous symbol's step prefetched them (all 16 floats of the lane are read before the tile is written below)
-    const float* xs = x + s * kSym + kCP;
-    const float2* osc = A.nco + s * kSym + kCP;
-    const bool from_tile = (pf_sym == s);
+    // from the tile when the previous symbol's step prefetched the samples: all 16 floats of the lane are read before the
+    // tile is written below (the phases live in front of them)
     float xa[16];
     if (from_tile) {
         const float* raw = reinterpret_cast<const float*>(buf) + kRawOff;
@@ -548,7 +598,9 @@ __device__ __forceinline__ void demod_fft_symbol(const DemodArgs& A, const float
         }
         wave_sync();
     }
-    pf_sym = -1;
+    // stage + downconvert 1024 samples (cyclic prefix dropped): 16 B per lane per load, coalesced
+    const float* xs = x + s * kSym + kCP;
+    const float2* osc = A.nco + s * kSym + kCP;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         int j = 4 * lane + 256 * c;
@@ -561,12 +613,46 @@ __device__ __forceinline__ void demod_fft_symbol(const DemodArgs& A, const float
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             float2 m = make_float2(xv[e] * ov[e].x, xv[e] * -ov[e].y);  // samples[i] * conj(osc)
-            if (use_cfo) m = cmul(m, cexpj(th_reg[4 * c + e]));
+            if (use_cfo) m = kRecover ? cmul(m, cexpj(th_reg[4 * c + e])) : cmul_plain(m, cexpj(th_reg[4 * c + e]));
             buf[j + e] = m;
         }
     }
     wave_sync();
-    fft1024_wave(buf, A.twiddle, utw, Yrow, lane);
+    fft1024_wave<false, false, kRecover>(buf, A.twiddle, utw, Yrow, lane);
+}
+
+__device__ __forceinline__ void demod_fft_symbol(const DemodArgs& A, const float* __restrict__ x, int s, int next_s, float2* buf, float2* Yrow,
+                                                 DemodShared* sh, int lane, float& th_walk, int& pf_sym, const FftUniformTw& utw) {
+    const float cfo = sh->cfo;
+    const bool use_cfo = fabs_(cfo) > 0.01f;
+    const float inc = static_cast<float>(-2.0f * 3.14159265358979323846 * static_cast<double>(cfo) / 48000.0);
+    const bool aligned = (reinterpret_cast<uintptr_t>(x) & 15u) == 0;
+    if (pf_sym >= 0) {   // a prefetch is in flight or has landed: it must be complete before the tile is read or rewritten
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wave_sync();
+    }
+    if (use_cfo) {
+        // channel_equalizer.cpp:132-144: float phase recurrence over EVERY sample (CP included), wrapped
+        // with double-precision pi.  Inherently serial: lane 0 walks the symbol once, dropping a
+        // marker every 72 samples; 16 lanes then re-walk 72 samples each into the (still free) tile.
+        if (lane == 0) {
+            float th = th_walk;
+            for (int q = 0; q < 16; ++q) {
+                sh->sub_theta[q] = th;
+#pragma unroll 1
+                for (int g = 0; g < 9; ++g) th = cfo_phase_step8(th, inc);
+            }
+            th_walk = th;
+        }
+        wave_sync();
+    }
+    const bool from_tile = (pf_sym == s);
+    pf_sym = -1;
+    demod_stage_and_fft<false>(A, x, s, buf, Yrow, sh, lane, use_cfo, inc, aligned, from_tile, utw);
+    if (fft_bins_have_nan(Yrow, lane)) {   // wave-uniform; see fft_bins_have_nan
+        wave_sync();
+        demod_stage_and_fft<true>(A, x, s, buf, Yrow, sh, lane, use_cfo, inc, aligned, false, utw);
+    }
     if (aligned && next_s >= 0) { demod_prefetch_symbol(x, next_s, buf, lane); pf_sym = next_s; }
 }
 
@@ -588,12 +674,7 @@ __global__ __launch_bounds__(kDemodThreads) __attribute__((amdgpu_waves_per_eu(3
         if (A.meta) {
             cfo = A.meta[frame].cfo_hz;
             fl = A.meta[frame].flags;
-            // ofdm_chirp_waveform.cpp:402-411
-            float ip = static_cast<float>(-2.0f * 3.14159265358979323846 * static_cast<double>(cfo) *
-                                          static_cast<double>(A.meta[frame].abs_position) / 48000.0);
-            while (static_cast<double>(ip) > 3.14159265358979323846) ip = static_cast<float>(static_cast<double>(ip) - 2.0f * 3.14159265358979323846);
-            while (static_cast<double>(ip) < -3.14159265358979323846) ip = static_cast<float>(static_cast<double>(ip) + 2.0f * 3.14159265358979323846);
-            init = ip;
+            init = cfo_theta0(cfo, A.meta[frame].abs_position);   // ofdm_chirp_waveform.cpp:402-411
         }
         (void)fl;
         sh->cfo = cfo;
@@ -986,12 +1067,7 @@ __device__ __forceinline__ void demod_frame_start(const DemodArgs& A, int frame,
     cfo = 0.0f; theta0 = 0.0f;
     if (A.meta) {
         cfo = A.meta[frame].cfo_hz;
-        // ofdm_chirp_waveform.cpp:402-411
-        float ip = static_cast<float>(-2.0f * 3.14159265358979323846 * static_cast<double>(cfo) *
-                                      static_cast<double>(A.meta[frame].abs_position) / 48000.0);
-        while (static_cast<double>(ip) > 3.14159265358979323846) ip = static_cast<float>(static_cast<double>(ip) - 2.0f * 3.14159265358979323846);
-        while (static_cast<double>(ip) < -3.14159265358979323846) ip = static_cast<float>(static_cast<double>(ip) + 2.0f * 3.14159265358979323846);
-        theta0 = ip;
+        theta0 = cfo_theta0(cfo, A.meta[frame].abs_position);   // ofdm_chirp_waveform.cpp:402-411
     }
 }
 
@@ -1047,16 +1123,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void de
                 for (int e = 0; e < 4; ++e) xv[4 * c + e] = xs[4 * lane + 256 * c + e];
         }
     };
-    float xn[16];
-    int q = list ? list[i] : i;
-    fetch(q, xn);
-    for (;;) {
-        float (&xv)[16] = xn;                              // mixed into the tile first; the next frame's samples are fetched right after
-        const int qc = q;
-        float cfo = 0.0f;
-        if (use_final) cfo = S.ws.cfo[qc];
-        else if (A.meta) cfo = A.meta[S.first + qc].cfo_hz;
-        const bool use_cfo = fabs_(cfo) > 0.01f;           // wave-uniform
+    // the 16 samples of a lane mixed down into the tile at fft_in_slot(i), i = 4 lane + 256 c + e
+    auto mix = [&](const float (&xv)[16], int qc, bool use_cfo, float cfo, auto recover) {
         if (use_cfo) {
             // 16 lanes re-walk 72 samples each from their marker (demod_walk_kernel) into the UPPER half of the tile (floats
             // 1024..2175).  The mixed samples then fill the tile from the bottom, a quarter (256 samples per wave) at a time:
@@ -1078,7 +1146,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void de
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const float2 m = make_float2(xv[4 * c + e] * ov[4 * c + e].x, xv[4 * c + e] * -ov[4 * c + e].y);
-                    tile[2 * lane + 256 * c + (e >> 1) + 128 * (e & 1)] = cmul(m, cexpj(tv[e]));   // fft_in_slot(4 lane + 256 c + e)
+                    tile[2 * lane + 256 * c + (e >> 1) + 128 * (e & 1)] = decltype(recover)::value ? cmul(m, cexpj(tv[e])) : cmul_plain(m, cexpj(tv[e]));
                 }
                 wave_sync();
             }
@@ -1086,14 +1154,34 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void de
 #pragma unroll
             for (int c = 0; c < 4; ++c)
 #pragma unroll
-                for (int e = 0; e < 4; ++e)   // samples[i] * conj(osc) at fft_in_slot(i), i = 4 lane + 256 c + e
+                for (int e = 0; e < 4; ++e)   // samples[i] * conj(osc)
                     tile[2 * lane + 256 * c + (e >> 1) + 128 * (e & 1)] = make_float2(xv[4 * c + e] * ov[4 * c + e].x, xv[4 * c + e] * -ov[4 * c + e].y);
         }
+    };
+    float xn[16];
+    int q = list ? list[i] : i;
+    fetch(q, xn);
+    for (;;) {
+        // xn is mixed into the tile first; the next frame's samples are fetched right after
+        const int qc = q;
+        float cfo = 0.0f;
+        if (use_final) cfo = S.ws.cfo[qc];
+        else if (A.meta) cfo = A.meta[S.first + qc].cfo_hz;
+        const bool use_cfo = fabs_(cfo) > 0.01f;           // wave-uniform
+        mix(xn, qc, use_cfo, cfo, std::false_type{});
         i += F;
         const bool more = i < count;
         if (more) { q = list ? list[i] : i; fetch(q, xn); }   // in flight during the whole transform below
         wave_sync();
         fft1024_wave<true, true>(tile, A.twiddle, utw, Yl, lane, &ltw);
+        if (fft_bins_have_nan(Yl, lane)) {   // wave-uniform; see fft_bins_have_nan: this frame's symbol again, the next frame's fetch after it
+            wave_sync();
+            fetch(qc, xn);
+            mix(xn, qc, use_cfo, cfo, std::true_type{});
+            wave_sync();
+            fft1024_wave<true, true, true>(tile, A.twiddle, utw, Yl, lane, &ltw);
+            if (more) fetch(q, xn);
+        }
         S.ws.Y[(static_cast<size_t>(qc) * S.n_sym + s) * 64 + lane] = Yl[lane];
         if (!more) break;
         wave_sync();

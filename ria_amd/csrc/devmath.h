@@ -297,7 +297,10 @@ RIA_HD float atan2f_glibc(float y, float x) {
 // ---------------------------------------------------------------- hypotf
 RIA_HD float hypotf_glibc(float x, float y) {
     double dx = x, dy = y;
-    return (float)dsqrt(dx * dx + dy * dy);
+    float r = (float)dsqrt(dx * dx + dy * dy);
+    // an infinite argument gives +inf even when the other one is NaN (C99 F.9.4.3; glibc tests it first)
+    if (r != r && ((f2u(x) & 0x7fffffffu) == 0x7f800000u || (f2u(y) & 0x7fffffffu) == 0x7f800000u)) r = u2f(0x7f800000u);
+    return r;
 }
 
 }  // namespace ria

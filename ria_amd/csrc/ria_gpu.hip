@@ -395,6 +395,11 @@ static int run_crc_recovery_host(ria_gpu_handle h, const FastDecodeArgs& D, hipS
 extern "C" {
 
 int ria_gpu_abi_version(void) { return RIA_GPU_ABI_VERSION; }
+static bool demod_fused_selected() {   // read once per process
+    static const bool fused = getenv("RIA_DEMOD_FUSED") && getenv("RIA_DEMOD_FUSED")[0] == '1';
+    return fused;
+}
+int ria_gpu_demod_variant(void) { return demod_fused_selected() ? 1 : 0; }
 
 void ria_gpu_default_config(ria_gpu_config* cfg) {
     std::memset(cfg, 0, sizeof(*cfg));
@@ -736,8 +741,7 @@ static int demod_batch_slot(ria_gpu_handle h, const float* samples_dev, const ui
 #ifdef RIA_DEBUG_STAMPS
     if (const char* e = getenv("RIA_DEBUG_DEMOD_STAMPS")) A.dbg = reinterpret_cast<unsigned long long*>(strtoull(e, nullptr, 0));
 #endif
-    static const bool fused = getenv("RIA_DEMOD_FUSED") && getenv("RIA_DEMOD_FUSED")[0] == '1';
-    if (fused) launch_demod_fused(A, stream);
+    if (demod_fused_selected()) launch_demod_fused(A, stream);
     else {
         if (!h->d_demod_ws[slot]) HIP_TRY(h, hipMalloc(&h->d_demod_ws[slot], demod_ws_bytes(2 + h->geo.n_data_symbols)));
         launch_demod(A, h->geo, h->cfg.modulation, h->d_demod_ws[slot], stream);

@@ -32,6 +32,16 @@ int main(int argc, char** argv) {
         bad += f2u(hypotf_glibc(a, b)) != f2u(hypotf(a, b));
         n += 2;
     }
+    // hypotf of zeros, infinities, NaN, the largest and the smallest floats: hypotf(inf, NaN) is +inf (a NaN's sign and
+    // payload are not compared)
+    const uint32_t sp[] = {0x00000000u, 0x80000000u, 0x7f800000u, 0xff800000u, 0x7fc00000u, 0xffc00000u, 0x7f7fffffu, 0xff7fffffu,
+                           0x00000001u, 0x007fffffu, 0x00800000u, 0x3f800000u, 0xbf800000u, 0x7e967699u, 0x5f000000u};
+    for (uint32_t ua : sp)
+        for (uint32_t ub : sp) {
+            float a = u2f(ua), b = u2f(ub), want = hypotf(a, b), got = hypotf_glibc(a, b);
+            bad += !((want != want && got != got) || f2u(want) == f2u(got));
+            ++n;
+        }
     printf("%ld %ld\n", bad, n);
     return bad != 0;
 }

@@ -854,11 +854,16 @@ def test_edge_cases():
     # empty batch
     info, st = e.rx(torch.empty((0, e.geo.frame_samples), dtype=torch.float32, device="cuda"))
     assert info.shape[0] == 0
-    # all-zero frame: no NaNs in LLRs, nothing decodes as a valid frame
+    # all-zero frame: the oracle's LLRs bit for bit (no NaN among them), nothing decodes as a valid frame
+    # (silence of every kind in every mode: tests/test_gpu_demod_domain.py, family "silence")
     z = torch.zeros((2, e.geo.frame_samples), dtype=torch.float32, device="cuda")
     info, st, llr, fst = e.rx(z, want_llr=True)
     s = e.decode_status(st)
     assert not s["frame_valid"].any()
+    llr_o, _ = po.Oracle().rx_process(po.QAM16, po.R1_2, np.zeros(e.geo.frame_samples, np.float32))
+    assert not np.isnan(llr_o).any()
+    for f in range(2):
+        assert np.array_equal(bits(llr[f].cpu().numpy()), bits(llr_o))
     # saturated LLRs decode instantly with 0 iterations
     cw = torch.full((4, 648), 20.0, device="cuda")
     out, ok, it = e.ldpc_decode(cw, 80, 0.9375)
