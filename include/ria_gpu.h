@@ -250,7 +250,19 @@ int ria_gpu_channel_batch(ria_gpu_handle h, int kind, float snr_db, uint64_t see
  * known_cfo_dev: per-buffer known CFO in Hz, or NULL for 0.  Results are bit-identical to the reference's
  * ZCSyncResult for every field (snr_estimate included).  buf_len <= 1048576: buffers up to 16384 samples are mixed down
  * into the workgroup's LDS (the batched acquisition sweeps), longer ones (the host's connected-mode search windows of
- * 31 000 - 48 000 samples, streaming_decoder.cpp:424-431) into a device workspace the handle keeps. */
+ * 31 000 - 48 000 samples, streaming_decoder.cpp:424-431) into a device workspace the handle keeps.
+ *
+ * Input domain of the four detectors (ZC, dual chirp, LTS light sync, Schmidl-Cox).  Samples may be any float32: NaN,
+ * +-inf, denormals, +-FLT_MAX or so large that the window energies overflow.  The threshold, the known CFO and the initial
+ * noise floor may be any float32 too, NaN and +-inf included.  None of these makes the reference undefined: it converts no
+ * float of the data to an index, every compare with a NaN is false, and its complex products go through std::complex's
+ * operator* (C99 Annex G: an infinite factor gives an infinite product), so nothing is out of contract and the answer is
+ * the reference's in every case.  What follows from that: a correlation that comes out NaN never wins a maximum search;
+ * std::max(combined, peak) keeps a NaN combined metric (zc_sync.hpp:289), which drops that root; a NaN threshold detects
+ * nothing where the compare is `corr > threshold` (ZC, LTS, Schmidl-Cox) and rejects nothing where it is
+ * `corr < threshold` (the chirp transform path, chirp_sync.hpp:707); a NaN noise floor fails every energy gate of
+ * searchForSync and is returned as it came.  A float field of a result may be NaN; the sign and payload of such a NaN are
+ * not part of the contract.  tests/sync_domain_inputs.py holds the buffers these statements are tested on. */
 typedef struct ria_zc_result {
     int32_t detected;        /* ZCSyncResult::detected */
     int32_t frame_type;      /* ZCFrameType: 0 PING 1 PONG 2 DATA 3 CONTROL 255 UNKNOWN */

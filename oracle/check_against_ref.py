@@ -291,6 +291,23 @@ def main():
             worst = f"snr={snr} seed={seed}"
     check("tools/test_zc_dbpsk.cpp testAtSNR (130 cases: signal, ZC result, stage reached, soft bits, decode)", ok, worst)
 
+    # the four acquisition detectors over their input domain (tests/sync_domain_inputs.py), NaN rule of same_bits
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import sync_domain_inputs as S
+    for det in S.DETECTORS:
+        ok, worst, n = True, "", 0
+        for fam in S.FAMILIES:
+            if (det, fam) not in S.CASES:
+                continue
+            F = S.family(O, det, fam)
+            a, b = S.answers(O, det, F), S.answers(R, det, F)
+            n += len(a)
+            for i in range(len(a)):
+                if not S.same_bits(a[i], b[i]):
+                    ok = False
+                    worst = worst or f"{fam}: {F['labels'][i]}: oracle {a[i]} reference {b[i]}"
+        check(f"{det} detector over its input domain ({n} buffers)", ok, worst)
+
     print("\n%s: %d failing group(s)" % ("PINNED" if fails == 0 else "MISMATCH", fails))
     return 1 if fails else 0
 

@@ -362,6 +362,22 @@ def demod_domain_fixture(R):
     return rec
 
 
+def sync_domain_fixture(R):
+    """ZCSync::detect, ChirpSync::detectDualChirp, OFDMChirpWaveform::detectDataSync and OFDMDemodulator::searchForSync of the
+    reference over the detectors' input domain (tests/sync_domain_inputs.py builds the buffers; only their sha256 is kept
+    here).  Per (detector, family): sha_* and ans_* float32 [n, 8] (32 bytes a buffer, fields of sync_domain_inputs.FIELDS)."""
+    sys.path.insert(0, os.path.join(os.path.dirname(po.HERE), "tests"))
+    import sync_domain_inputs as S
+    O = po.Oracle()
+    rec = {}
+    for det, fam in S.CASES:
+        F = S.family(O, det, fam)
+        rec[f"sha_{det}_{fam}"] = np.array(S.digest(F))
+        rec[f"ans_{det}_{fam}"] = a = S.answers(R, det, F)
+        print("sync domain", det, fam, "buffers", len(a), "detected", int((a[:, 0] == 1).sum()), "NaN fields", int(np.isnan(a).sum()), flush=True)
+    return rec
+
+
 def harq_inputs(case_index, n=HARQ_TRIALS):
     """(info [n, 21], seeds [n, 4]) of a HARQ case: the sweep's own per-trial recipe (ria_amd/sweep.py)"""
     sys.path.insert(0, os.path.dirname(po.HERE))
@@ -649,6 +665,9 @@ def main():
     if only == "demod_domain":
         np.savez_compressed(os.path.join(OUT, "demod_domain.npz"), **demod_domain_fixture(R))
         return 0
+    if only == "sync_domain":
+        np.savez_compressed(os.path.join(OUT, "sync_domain.npz"), **sync_domain_fixture(R))
+        return 0
     if only == "robust":
         np.savez_compressed(os.path.join(OUT, "robust_ldpc.npz"), **robust_fixture(R))
         return 0
@@ -736,6 +755,7 @@ def main():
     np.savez_compressed(os.path.join(OUT, "robust_ldpc.npz"), **robust_fixture(R))
     np.savez_compressed(os.path.join(OUT, "ldpc_domain.npz"), **ldpc_domain_fixture(R))
     np.savez_compressed(os.path.join(OUT, "demod_domain.npz"), **demod_domain_fixture(R))
+    np.savez_compressed(os.path.join(OUT, "sync_domain.npz"), **sync_domain_fixture(R))
     np.savez_compressed(os.path.join(OUT, "harq_trials.npz"), **harq_fixture(R))
     np.savez_compressed(os.path.join(OUT, "cfo_impairment.npz"), **cfo_fixture(R))
     np.savez_compressed(os.path.join(OUT, "mcdpsk_waveform.npz"), **mcwf_fixture(R))

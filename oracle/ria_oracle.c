@@ -58,6 +58,7 @@ static inline cf cf_mul(cf a, cf b) {
     if (isnan(z.re) && isnan(z.im)) z = cf_mul_recover(a.re, a.im, b.re, b.im, z);
     return z;
 }
+void ro_cmul(float a, float b, float c, float d, float* re, float* im) { cf z = cf_mul(cf_mk(a, b), cf_mk(c, d)); *re = z.re; *im = z.im; }
 static inline cf cf_scale(float s, cf a) { return cf_mk(s * a.re, s * a.im); }
 static inline cf cf_divf(cf a, float s) { return cf_mk(a.re / s, a.im / s); }
 static inline cf cf_div(cf x, cf y) { /* libgcc __divsc3, wide-type path */
@@ -1689,7 +1690,7 @@ static float cox_metric(const float* x, int n, int offset) { /* measureSchmidlCo
         R2 += cf_norm(an[i + half]);
     }
     float norm = sqrtf(R1 * R2);
-    if (norm < 1e-10f) return 0.0f;
+    if (SBC(COX_NORM, norm < 1e-10f)) return 0.0f;
     return cf_abs(P) / norm;
 }
 static int cox_has_energy(const float* x, int n, int offset, int window, float* nf) { /* hasMinimumEnergy */
@@ -1698,10 +1699,10 @@ static int cox_has_energy(const float* x, int n, int offset, int window, float* 
     int count = 0;
     for (int i = 0; i < window; i += 16) { float s = x[offset + i]; sum_sq += s * s; ++count; }
     float energy = sum_sq / (float)count;
-    if (*nf < 1e-20f) *nf = energy * 0.1f;
+    if (SBC(COX_NF_INIT, *nf < 1e-20f)) *nf = energy * 0.1f;
     if (energy < *nf) *nf = energy;
     else if (energy < *nf * 3.0f) *nf = (1.0f - 0.01f) * *nf + 0.01f * energy;
-    return energy >= *nf * 4.0f;
+    return SBC(COX_ENERGY, energy >= *nf * 4.0f);
 }
 static float cox_coarse_cfo(const float* x, int n, int sync_offset) { /* estimateCoarseCFO */
     const int cp = RO_SYM - RO_FFT, half = RO_FFT / 2;
@@ -1741,7 +1742,7 @@ static float cox_lts_corr(const float* x, int n, long long offset, const float* 
         erx += s * s;
     }
     float mag = sqrtf(cI * cI + cQ * cQ), norm = sqrtf(erx * eref);
-    return (norm > 1e-6f) ? mag / norm : 0.0f;
+    return SBC(COX_LTS_NORM, norm > 1e-6f) ? mag / norm : 0.0f;
 }
 /* returns refined LTS start, or -1 for the reference's SIZE_MAX */
 static long long cox_refine_lts(const float* x, int n, int coarse_sts, const float* tI, const float* tQ) {
@@ -1755,22 +1756,23 @@ static long long cox_refine_lts(const float* x, int n, int coarse_sts, const flo
     long long best_off = coarse;
     for (int d = -BACK; d <= FWD; ++d) {
         float c = cox_lts_corr(x, n, coarse + d, tI, tQ, eref);
-        if (c > best) { best = c; best_off = coarse + d; }
+        if (c > best) { best = c; best_off = coarse + d; } else if (c == best && c > 0.0f) ro_sbc[RO_SBC_COX_TIE]++;
     }
     if (best_off >= L) {
         long long prev = best_off - L;
         if (prev >= coarse - BACK) {
             float pc = cox_lts_corr(x, n, prev, tI, tQ, eref);
-            if (pc >= best * 0.92f) { best_off = prev; best = pc; }
+            if (SBC(COX_EARLIER_LTS, pc >= best * 0.92f)) { best_off = prev; best = pc; }
         }
     }
-    if (best < 0.05f) return -1;
+    if (SBC(COX_CONFIRM, best < 0.05f)) return -1;
     return best_off;
 }
 /* out3 = {found, position (first LTS symbol), cfo_hz}; *noise_floor is Impl::noise_floor_energy (0 for a fresh demodulator)
  * and is updated as the reference's member would be. */
 int ro_cox_search(const ro_geom* g, const float* x, int n, float threshold, float* noise_floor, float* out3) {
     out3[0] = out3[1] = out3[2] = 0.0f;
+    memset(ro_sbc, 0, sizeof(ro_sbc));
     const int L = RO_SYM, total = 6 * L, window = 2 * L;
     if (n < 4000) return 0;
     if (n < total + window) return 0;
@@ -1782,15 +1784,15 @@ int ro_cox_search(const ro_geom* g, const float* x, int n, float threshold, floa
     for (int i = 0; i < search_end; i += 64) {
         if (!cox_has_energy(x, n, i, window, &nf)) { i += window / 2 - 64; continue; }
         float corr = cox_metric(x, n, i);
-        if (corr > threshold) {
+        if (SBC(COX_THR, corr > threshold)) {
             int plateau = 0, peak_pos = i;
             float peak = corr;
             for (int j = 0; j <= 300 && i + j + total < n; j += 8) {
                 float c = cox_metric(x, n, i + j);
-                if (c >= 0.90f) ++plateau;
-                if (c > peak) { peak = c; peak_pos = i + j; }
+                if (SBC(COX_PLATEAU, c >= 0.90f)) ++plateau;
+                if (c > peak) { peak = c; peak_pos = i + j; } else if (c == peak && c > 0.0f && j > 0) ro_sbc[RO_SBC_COX_TIE]++;
             }
-            if (plateau >= 15) {
+            if (SBC(COX_RULE, plateau >= 15)) {
                 long long lts = cox_refine_lts(x, n, peak_pos, tI, tQ);
                 if (lts >= 0) {
                     found = 1;

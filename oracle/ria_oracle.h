@@ -107,6 +107,35 @@ enum { RO_BC_H_SMALL, RO_BC_MAG_SMALL, RO_BC_CNT_SMALL, RO_BC_RERUN, RO_BC_SNR_L
        RO_BC_DEN_SMALL, RO_BC_CNV_LOW, RO_BC_CNV_HIGH, RO_BC_D8PSK_TWO_PASS, RO_BC_SP_SMALL, RO_BC_N };
 void ro_branch_counts(unsigned* out /* [RO_BC_N] */);
 
+/* (a + bi)(c + di) as std::complex<float> operator* computes it (libgcc __mulsc3: C99 Annex G.5.1 recovery of infinities);
+ * ria_oracle.c's cf_mul for the other translation unit */
+void ro_cmul(float a, float b, float c, float d, float* re, float* im);
+
+/* The same for the four acquisition detectors: how often the last ro_zc_detect / ro_chirp_detect / ro_detect_data_sync /
+ * ro_cox_search of this thread found each data-dependent condition true (_T) and false (_F), and how often a maximum search
+ * met a lag whose metric equals the running maximum bit for bit (_TIE: the first-maximum rule decided).
+ * ZC: DENOM denom > 1e-10 (:556), PEAK peak > threshold at a peak >= 1016 (:262), EARLIER earlier repetition > 0.4 peak (:268),
+ * COMBINE 0 < peak < 0.25 with room for the second repetition (:280), CFO_OK both repetitions above 0.1 (:349), DETECT
+ * best > threshold (:375), SNR_LOW corr <= 0.01, SNR_HIGH corr >= 0.99 (:628-633).
+ * CH: FFT transform path (_F: time-domain path, chirp_sync.hpp:735), DENOM denom > 1e-10 (:686), THR best < threshold (:707),
+ * TD_DENOM denom < 1e-10 (:847), TD_COARSE no coarse candidate or below 0.3 threshold (:777), TD_THR best >= threshold (:812),
+ * CFO_REJ |cfo| > 100 Hz (:489).
+ * LTS: NOISE noise floor < 0.05 (ofdm_chirp_waveform.cpp:241), ENERGY a 64-sample window above the gate (:252), EXIT
+ * corr > 0.95 (:312), DETECT best > threshold (:320, :356), MARKER compensated peak negative (:372).
+ * COX: NF_INIT floor < 1e-20, ENERGY energy >= 4 floors (ofdm_sync.cpp:36-49), NORM norm < 1e-10 (:156), THR corr > threshold
+ * (demodulator.cpp:1494), PLATEAU c >= 0.90 (:1502), RULE plateau >= 15 (:1509), LTS_NORM norm > 1e-6 (ofdm_sync.cpp:437),
+ * EARLIER_LTS previous copy >= 0.92 best (:460), CONFIRM best < 0.05 (:470). */
+#define RO_SBC_PAIRS(X) X(ZC_DENOM) X(ZC_PEAK) X(ZC_EARLIER) X(ZC_COMBINE) X(ZC_CFO_OK) X(ZC_DETECT) X(ZC_SNR_LOW) X(ZC_SNR_HIGH) \
+    X(CH_FFT) X(CH_DENOM) X(CH_THR) X(CH_TD_DENOM) X(CH_TD_COARSE) X(CH_TD_THR) X(CH_CFO_REJ) \
+    X(LTS_NOISE) X(LTS_ENERGY) X(LTS_EXIT) X(LTS_DETECT) X(LTS_MARKER) \
+    X(COX_NF_INIT) X(COX_ENERGY) X(COX_NORM) X(COX_THR) X(COX_PLATEAU) X(COX_RULE) X(COX_LTS_NORM) X(COX_EARLIER_LTS) X(COX_CONFIRM)
+#define RO_SBC_ENUM(n) RO_SBC_##n##_T, RO_SBC_##n##_F,
+enum { RO_SBC_PAIRS(RO_SBC_ENUM) RO_SBC_ZC_TIE, RO_SBC_CH_TIE, RO_SBC_LTS_TIE, RO_SBC_COX_TIE, RO_SBC_N };
+extern _Thread_local unsigned ro_sbc[RO_SBC_N];
+#define SBC(n, cond) ((cond) ? (ro_sbc[RO_SBC_##n##_T]++, 1) : (ro_sbc[RO_SBC_##n##_F]++, 0))
+void ro_sync_branch_counts(unsigned* out /* [RO_SBC_N] */);
+int ro_sync_branch_n(void);
+
 /* the same with OFDMChirpWaveform's one-shot burst marker: flags bit0 = the first LTS symbol was negated on air
  * (ofdm_chirp_waveform.cpp:421-440) */
 int ro_rx_process_flags(const ro_geom* g, const float* samples, int n, float cfo_hz, long long abs_pos, int flags,

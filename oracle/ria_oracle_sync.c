@@ -25,6 +25,11 @@
 #define ZC_PREAMBLE (2 * ZC_REP + ZC_GAP)  /* 2512 */
 static const float kZcFs = 48000.0f, kZcFc = 1500.0f;
 
+_Thread_local unsigned ro_sbc[RO_SBC_N];   /* test instrumentation only: no result depends on it */
+void ro_sync_branch_counts(unsigned* out) { memcpy(out, ro_sbc, sizeof(ro_sbc)); }
+int ro_sync_branch_n(void) { return RO_SBC_N; }
+#define SBC_RESET() memset(ro_sbc, 0, sizeof(ro_sbc))
+
 static void zc_sequence(int root, float* re, float* im) { /* zc_sync.hpp:420-436 (N odd) */
     for (int n = 0; n < ZC_N; ++n) {
         float phase = (float)(-M_PI * root * n * (n + 1) / ZC_N);
@@ -88,10 +93,11 @@ static void zc_corr_at(const float* rx, int lag, float f, const float* tre, cons
     for (int i = 0; i < ZC_REP; ++i) {
         float br, bi;
         zc_mix(rx, lag + i, f, &br, &bi);
-        /* bb * conj(z) with std::complex<float> operator*: (a+bi)(c+di'), d' = -d */
-        float c = tre[i], d = -tim[i];
-        sr += br * c - bi * d;
-        si += br * d + bi * c;
+        /* bb * conj(z) with std::complex<float> operator* (an infinite sample on a zero of z: Annex G recovery) */
+        float pr, pi_;
+        ro_cmul(br, bi, tre[i], -tim[i], &pr, &pi_);
+        sr += pr;
+        si += pi_;
         e += br * br + bi * bi;
     }
     *sre = sr; *sim_ = si; *energy = e;
@@ -104,8 +110,8 @@ static float zc_corr_mag(const float* rx, int n, int lag, float f, const float* 
     return (denom > 1e-10f) ? hypotf(sr, si) / denom : 0.0f;
 }
 static float zc_corr_to_snr(float corr) { /* :628-633 */
-    if (corr <= 0.01f) return -10.0f;
-    if (corr >= 0.99f) return 30.0f;
+    if (SBC(ZC_SNR_LOW, corr <= 0.01f)) return -10.0f;
+    if (SBC(ZC_SNR_HIGH, corr >= 0.99f)) return 30.0f;
     float snr = 20.0f * log10f(corr / (1.0f - corr + 0.01f));
     if (snr < -10.0f) snr = -10.0f;
     if (snr > 30.0f) snr = 30.0f;
@@ -116,6 +122,7 @@ static float zc_corr_to_snr(float corr) { /* :628-633 */
 int ro_zc_detect(const float* rx, int n, float threshold, int root_mask, float known_cfo_hz, float* out7) { /* :192-391 */
     static const int roots[4] = {1, 3, 5, 7};
     out7[0] = 0.f; out7[1] = 255.f; out7[2] = -1.f; out7[3] = 0.f; out7[4] = 0.f; out7[5] = 0.f; out7[6] = -1.f;
+    SBC_RESET();
     if (n < ZC_REP) return 0;
     const float f = kZcFc + known_cfo_hz;
     const int corr_len = n - ZC_REP + 1, step = ZC_REP / 32; /* 31 */
@@ -136,8 +143,8 @@ int ro_zc_detect(const float* rx, int n, float threshold, int root_mask, float k
             float sr, si, e;
             zc_corr_at(rx, lag, f, tre, tim, &sr, &si, &e);
             float denom = sqrtf(e * (float)ZC_REP);
-            float mag = (denom > 1e-10f) ? hypotf(sr, si) / denom : 0.0f;
-            if (mag > coarse_mag) { coarse_mag = mag; coarse_pos = lag; }
+            float mag = SBC(ZC_DENOM, denom > 1e-10f) ? hypotf(sr, si) / denom : 0.0f;
+            if (mag > coarse_mag) { coarse_mag = mag; coarse_pos = lag; } else if (mag == coarse_mag && mag > 0.0f) ro_sbc[RO_SBC_ZC_TIE]++;
             if (denom > 1e-10f) { cre[lag] = sr / denom; cim[lag] = si / denom; }
         }
         int fine_start = coarse_pos - step < 0 ? 0 : coarse_pos - step;
@@ -153,23 +160,20 @@ int ro_zc_detect(const float* rx, int n, float threshold, int root_mask, float k
         int peak_pos = 0;
         for (int i = 0; i < corr_len; ++i) {
             float mag = hypotf(cre[i], cim[i]);
-            if (mag > peak_mag) { peak_mag = mag; peak_pos = i; }
+            if (mag > peak_mag) { peak_mag = mag; peak_pos = i; } else if (mag == peak_mag && mag > 0.0f) ro_sbc[RO_SBC_ZC_TIE]++;
         }
         int timing_pos = peak_pos;
-        if (peak_mag > threshold && peak_pos >= ZC_REP) {
+        if (SBC(ZC_PEAK, peak_mag > threshold && peak_pos >= ZC_REP)) {
             int earlier = peak_pos - ZC_REP;
             float em = zc_corr_mag(rx, n, earlier, f, tre, tim);
-            if (em > peak_mag * 0.4f) timing_pos = earlier;
+            if (SBC(ZC_EARLIER, em > peak_mag * 0.4f)) timing_pos = earlier;
         }
         float combined = peak_mag;
-        if (peak_mag > 0.0f && peak_mag < 0.25f) {
-            int rep2 = timing_pos + ZC_REP;
-            if (rep2 + ZC_REP <= n) {
-                float m1 = zc_corr_mag(rx, n, timing_pos, f, tre, tim);
-                float m2 = zc_corr_mag(rx, n, rep2, f, tre, tim);
-                combined = sqrtf(m1 * m1 + m2 * m2) / sqrtf(2.0f);
-                if (!(combined > peak_mag)) combined = peak_mag; /* std::max(combined, peak) */
-            }
+        if (SBC(ZC_COMBINE, peak_mag > 0.0f && peak_mag < 0.25f && timing_pos + 2 * ZC_REP <= n)) {
+            float m1 = zc_corr_mag(rx, n, timing_pos, f, tre, tim);
+            float m2 = zc_corr_mag(rx, n, timing_pos + ZC_REP, f, tre, tim);
+            combined = sqrtf(m1 * m1 + m2 * m2) / sqrtf(2.0f);
+            if (combined < peak_mag) combined = peak_mag; /* std::max(combined, peak): a NaN combined stays (:289) */
         }
         if (combined > best_corr) {
             best_corr = combined;
@@ -181,10 +185,10 @@ int ro_zc_detect(const float* rx, int n, float threshold, int root_mask, float k
                 zc_corr_at(rx, timing_pos, f, tre, tim, &r1, &i1, &e1);
                 zc_corr_at(rx, rep2, f, tre, tim, &r2, &i2, &e2);
                 float m1 = hypotf(r1, i1) / ZC_REP, m2 = hypotf(r2, i2) / ZC_REP;
-                if (m1 > 0.1f && m2 > 0.1f) {
+                if (SBC(ZC_CFO_OK, m1 > 0.1f && m2 > 0.1f)) {
                     /* corr2 * conj(corr1) */
-                    float c = r1, d = -i1;
-                    float pr = r2 * c - i2 * d, pi_ = r2 * d + i2 * c;
+                    float pr, pi_;
+                    ro_cmul(r2, i2, r1, -i1, &pr, &pi_);
                     float phase_diff = atan2f(pi_, pr);
                     float rep_duration = (float)ZC_REP / kZcFs;
                     best_cfo = (float)(phase_diff / (2.0f * M_PI * rep_duration));
@@ -196,7 +200,7 @@ int ro_zc_detect(const float* rx, int n, float threshold, int root_mask, float k
     out7[3] = best_corr;
     out7[6] = (float)best_root;
     if (best_root >= 0) out7[1] = (float)((best_root - 1) / 2); /* roots 1,3,5,7 -> PING, PONG, DATA, CONTROL */
-    if (best_corr > threshold && best_root >= 0) {
+    if (SBC(ZC_DETECT, best_corr > threshold && best_root >= 0)) {
         out7[0] = 1.f;
         out7[4] = best_cfo;
         out7[2] = (float)(best_pos + ZC_PREAMBLE);
@@ -318,7 +322,7 @@ static float ch_td_corr(const float* s, int n, int offset, const float* tsin, co
         e += x * x;
     }
     float denom = sqrtf(e * tmpl_energy);
-    if (denom < 1e-10f) return 0.0f;
+    if (SBC(CH_TD_DENOM, denom < 1e-10f)) return 0.0f;
     return sqrtf(ci * ci + cq * cq) / denom;
 }
 
@@ -329,7 +333,7 @@ static int ch_detect_template(const float* s, int n, int down, float threshold, 
     const float tmpl_energy = down ? g_ch_dn_energy : g_ch_up_energy;
     *corr_out = 0.0f;
     if (n < CH_LEN) return -1;
-    if (n >= 2 * CH_LEN) { /* detectChirpTemplateFFT :627-712 */
+    if (SBC(CH_FFT, n >= 2 * CH_LEN)) { /* detectChirpTemplateFFT :627-712 */
         const scf* tf = down ? g_ch_dn_fft : g_ch_up_fft;
         const int fft_in = n < CH_FFT ? n : CH_FFT;
         const int search_len = fft_in - CH_LEN;
@@ -351,12 +355,12 @@ static int ch_detect_template(const float* s, int n, int down, float threshold, 
             float mag = hypotf(buf[pos].re, buf[pos].im);
             float se = cum[pos + CH_LEN] - cum[pos];
             float denom = sqrtf(se * tmpl_energy);
-            float nc = (denom > 1e-10f) ? mag / denom : 0.0f;
-            if (nc > best) { best = nc; best_pos = pos; }
+            float nc = SBC(CH_DENOM, denom > 1e-10f) ? mag / denom : 0.0f;
+            if (nc > best) { best = nc; best_pos = pos; } else if (nc == best && nc > 0.0f) ro_sbc[RO_SBC_CH_TIE]++;
         }
         free(buf); free(cum);
         *corr_out = best;
-        return (best < threshold) ? -1 : best_pos;
+        return SBC(CH_THR, best < threshold) ? -1 : best_pos;
     }
     /* time-domain fallback :759-817 */
     const int search_len = n - CH_LEN;
@@ -364,10 +368,10 @@ static int ch_detect_template(const float* s, int n, int down, float threshold, 
     int best_pos = -1;
     for (int pos = 0; pos < search_len; pos += 48) {
         float c = ch_td_corr(s, n, pos, tsin, tcos, tmpl_energy);
-        if (c > best) { best = c; best_pos = pos; }
+        if (c > best) { best = c; best_pos = pos; } else if (c == best && c > 0.0f) ro_sbc[RO_SBC_CH_TIE]++;
     }
     *corr_out = best;
-    if (best_pos < 0 || best < threshold * 0.3f) return -1;
+    if (SBC(CH_TD_COARSE, best_pos < 0 || best < threshold * 0.3f)) return -1;
     int fine_start = best_pos - 48 < 0 ? 0 : best_pos - 48;
     int fine_end = best_pos + 48 > search_len ? search_len : best_pos + 48;
     for (int pos = fine_start; pos <= fine_end; ++pos) {
@@ -387,12 +391,13 @@ static int ch_detect_template(const float* s, int n, int down, float threshold, 
         }
     }
     *corr_out = best;
-    return (best >= threshold) ? best_pos : -1;
+    return SBC(CH_TD_THR, best >= threshold) ? best_pos : -1;
 }
 
 /* out6 = {success, up_chirp_start, down_chirp_start, cfo_hz, up_correlation, down_correlation} */
 int ro_chirp_detect(const float* s, int n, float threshold, float* out6) { /* detectDualChirp :352-512 */
     ch_init();
+    SBC_RESET();
     out6[0] = 0.f; out6[1] = -1.f; out6[2] = -1.f; out6[3] = 0.f; out6[4] = 0.f; out6[5] = 0.f;
     if (n < 2 * CH_LEN + CH_GAP) return 0;
     float up_corr, down_corr;
@@ -423,7 +428,7 @@ int ro_chirp_detect(const float* s, int n, float threshold, float* out6) { /* de
     float gap_error = (float)(actual_gap - expected_gap);
     float cfo = gap_error / (2.0f * cfo_to_samples);
     out6[3] = cfo;
-    if (fabsf(cfo) > 100.0f) return 0;
+    if (SBC(CH_CFO_REJ, fabsf(cfo) > 100.0f)) return 0;
     float up_correction = cfo * cfo_to_samples;
     float down_correction = -cfo * cfo_to_samples;
     out6[1] = (float)(int)roundf((float)up_pos + up_correction);
@@ -784,6 +789,7 @@ int ro_chase_store(float* existing, int* combine_count, int decoded, const float
 int ro_detect_data_sync(const float* x, int n, float known_cfo_hz, float threshold, float* out4) {
     const int L = RO_SYM; /* 1152 */
     out4[0] = 0.f; out4[1] = 0.f; out4[2] = 0.f; out4[3] = 0.f;
+    SBC_RESET();
     const int search_window = L * 4;
     if (n < L * 3) return 0;
     float noise_floor = 0.0f;
@@ -792,14 +798,16 @@ int ro_detect_data_sync(const float* x, int n, float known_cfo_hz, float thresho
     noise_floor = sqrtf(noise_floor / noise_samples);
     float energy_threshold = noise_floor * 3.0f + 0.01f;
     int signal_start = 0;
-    int signal_in_noise = noise_floor < 0.05f;
+    int signal_in_noise = SBC(LTS_NOISE, noise_floor < 0.05f);
     if (signal_in_noise) {
+        int gate = 0;
         for (int i = 0; i < n - L * 2; ++i) {
             float energy = 0.0f;
             for (int j = 0; j < 64; ++j) if (i + j < n) energy += x[i + j] * x[i + j];
             energy = sqrtf(energy / 64);
-            if (energy > energy_threshold) { signal_start = i; break; }
+            if (energy > energy_threshold) { signal_start = i; gate = 1; break; }
         }
+        (void)SBC(LTS_ENERGY, gate);
     }
     enum { TAPS = 65, M = 32 };
     float coeff[TAPS];
@@ -843,8 +851,8 @@ int ro_detect_data_sync(const float* x, int n, float known_cfo_hz, float thresho
     for (int offset = signal_start; offset < search_end; offset += 8) {
         float corr, pr, pi;
         RO_LTS_CORR(offset, corr, pr, pi);
-        if (corr > best_corr) { best_corr = corr; best_offset = offset; bpr = pr; bpi = pi; }
-        if (corr > 0.95f) break;
+        if (corr > best_corr) { best_corr = corr; best_offset = offset; bpr = pr; bpi = pi; } else if (corr == best_corr && corr > 0.0f) ro_sbc[RO_SBC_LTS_TIE]++;
+        if (SBC(LTS_EXIT, corr > 0.95f)) break;
     }
     if (best_corr > threshold) {
         int rs = signal_start > best_offset - 4 ? signal_start : best_offset - 4;
@@ -854,18 +862,18 @@ int ro_detect_data_sync(const float* x, int n, float known_cfo_hz, float thresho
             if (offset == center) continue;
             float corr, pr, pi;
             RO_LTS_CORR(offset, corr, pr, pi);
-            if (corr > best_corr) { best_corr = corr; best_offset = offset; bpr = pr; bpi = pi; }
+            if (corr > best_corr) { best_corr = corr; best_offset = offset; bpr = pr; bpi = pi; } else if (corr == best_corr && corr > 0.0f) ro_sbc[RO_SBC_LTS_TIE]++;
         }
     }
     free(ar); free(ai);
     out4[2] = best_corr;
-    if (best_corr > threshold) {
+    if (SBC(LTS_DETECT, best_corr > threshold)) {
         out4[0] = 1.f;
         out4[1] = (float)best_offset;
         float cfo_phase = (float)(2.0f * M_PI * known_cfo_hz * L / 48000.0f);
         float cr = cosf(-cfo_phase), ci = sinf(-cfo_phase);
         float mr = bpr * cr - bpi * ci;
-        out4[3] = (mr < 0.0f) ? 1.f : 0.f;
+        out4[3] = SBC(LTS_MARKER, mr < 0.0f) ? 1.f : 0.f;
         return 1;
     }
     return 0;

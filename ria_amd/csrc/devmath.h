@@ -127,7 +127,8 @@ RIA_HD float sinf_glibc(float y) {
         if (abstop12(y) < 0x398) return y;  // |y| < 2^-12 : abstop12(0x1p-12f) = 0x398
         return sincos_eval(x, s, false, 0);
     }
-    if (abstop12(y) >= 0x42f) {  // |y| >= 120 (finite)
+    if (abstop12(y) >= 0x42f) {  // |y| >= 120
+        if (abstop12(y) >= 0x7f8) return y - y;  // inf or NaN -> NaN (glibc: __math_invalidf); a non-finite known CFO gets here
         const uint32_t xi = f2u(y);
         int n;
         x = sincos_reduce_large(xi, &n);
@@ -149,7 +150,8 @@ RIA_HD float cosf_glibc(float y) {
         if (abstop12(y) < 0x398) return 1.0f;
         return sincos_eval(x, x2, false, 1);
     }
-    if (abstop12(y) >= 0x42f) {  // |y| >= 120 (finite)
+    if (abstop12(y) >= 0x42f) {  // |y| >= 120
+        if (abstop12(y) >= 0x7f8) return y - y;  // inf or NaN -> NaN (glibc: __math_invalidf); a non-finite known CFO gets here
         const uint32_t xi = f2u(y);
         int n;
         x = sincos_reduce_large(xi, &n);

@@ -43,8 +43,12 @@ struct ZcArgs {
 struct ZcRootOut { float combined; int timing; int has_cfo; float cfo; };
 
 // (value, index) arg-max over the wave: larger value wins, equal values -> smaller index (= first maximum
-// of a left-to-right scan with a strict '>')
+// of a left-to-right scan with a strict '>').  Such a scan never takes a NaN, so a NaN enters as -1: a lane that kept
+// its own NaN would leave the lanes with different answers after the xor butterfly.  -1 is below every candidate of the
+// four users (the ZC coarse and fine scans and chirp_td_kernel reduce normalised correlations >= 0 and mark lanes without
+// a candidate with -1 themselves; the Schmidl-Cox LTS refinement starts every lane's own scan at -1).
 __device__ inline void wave_argmax_first(float& v, int& idx) {
+    if (!(v == v)) v = -1.0f;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         float ov = __shfl_xor(v, off);
@@ -67,10 +71,22 @@ __device__ inline ZcSum zc_corr_at(const float2* __restrict__ bb, const float2* 
         si += x.x * d + x.y * c;
         e += x.x * x.x + x.y * x.y;
     }
+    // The reference multiplies with std::complex's operator* (C99 Annex G: an infinite sample on a zero of the reference gives
+    // an infinite product where the plain formula gives NaN + NaN i).  Such a term leaves both plain sums NaN, so only then
+    // is the lag summed again with the full multiply; finite buffers never get here.
+    if (__builtin_expect(sr != sr && si != si, 0)) {
+        sr = 0.0f; si = 0.0f;
+        for (int i = 0; i < kZcRep; ++i) {
+            const float2 z = ref[i];
+            const float2 p = cmul(b[i], make_float2(z.x, -z.y));
+            sr += p.x;
+            si += p.y;
+        }
+    }
     return {sr, si, e};
 }
 
-// kLds: the mixed-down buffer lives in LDS (buffers up to ~19 000 samples: the batched acquisition sweeps); otherwise in a
+// kLds: the mixed-down buffer lives in LDS (buffers up to kZcLdsBuf = 16 384 samples: the batched acquisition sweeps); otherwise in a
 // global workspace served by L1 / L2 (the host's connected-mode search windows: 31 000 - 48 000 samples,
 // streaming_decoder.cpp:424-431).  Same arithmetic, same order.
 template <bool kLds>
@@ -163,7 +179,7 @@ __global__ __launch_bounds__(256) void zc_detect_kernel(ZcArgs A) {
         if (peak_mag > 0.0f && peak_mag < 0.25f && rep2 + kZcRep <= n) {
             const float m1 = at_earlier ? cm_e : cm_p, m2 = at_earlier ? cm_p : cm_l;
             combined = fdiv(fsqrt(m1 * m1 + m2 * m2), fsqrt(2.0f));
-            if (!(combined > peak_mag)) combined = peak_mag;
+            if (combined < peak_mag) combined = peak_mag;   // std::max(combined, peak_mag): a NaN combined stays (:289)
         }
         int has_cfo = 0; float cfo = 0.0f;
         if (rep2 + kZcRep <= n) {
@@ -171,8 +187,8 @@ __global__ __launch_bounds__(256) void zc_detect_kernel(ZcArgs A) {
             const float r2 = at_earlier ? sr_p : sr_l, i2 = at_earlier ? si_p : si_l;
             const float m1 = fdiv(hypotf_glibc(r1, i1), static_cast<float>(kZcRep)), m2 = fdiv(hypotf_glibc(r2, i2), static_cast<float>(kZcRep));
             if (m1 > 0.1f && m2 > 0.1f) {
-                const float c = r1, d = -i1;
-                const float pr = r2 * c - i2 * d, pi_ = r2 * d + i2 * c;   // corr2 * conj(corr1)
+                const float2 pp = cmul(make_float2(r2, i2), make_float2(r1, -i1));   // corr2 * conj(corr1), std::complex operator*
+                const float pr = pp.x, pi_ = pp.y;
                 const float phase_diff = atan2f_glibc(pi_, pr);
                 const float rep_duration = fdiv(static_cast<float>(kZcRep), 48000.0f);
                 cfo = static_cast<float>(static_cast<double>(phase_diff) / (static_cast<double>(2.0f) * 3.14159265358979323846 * static_cast<double>(rep_duration)));
