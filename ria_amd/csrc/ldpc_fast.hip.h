@@ -507,6 +507,7 @@ struct FastDecodeArgs {
     float* staged;           // [4*n_frames][kStageFloats]  de-interleaved decoder input of list1 entry i, in register order
     unsigned int* l1idx;     // [4*n_frames]  codeword -> its list1 index (valid for listed codewords only)
     unsigned int* l1hash;    // [4*n_frames]  list1 entry -> hash of its first 16 soft bits (seed of the perturbation RNG)
+    uint32_t* seed_ws;       // [cascade grid][kSeedWsWords]  seeded mt19937 states of the attempt group a cascade workgroup is on (this stream slot's)
 };
 
 // A codeword that needs more than its first decode is decoded up to 4 + 34 more times.  Its soft bits are gathered
@@ -711,14 +712,30 @@ __global__ void fast_chain_kernel(FastDecodeArgs A) {
     }
 }
 
-// perturbed decoder input of cascade attempt a (frame_v2.cpp:1415-1546) into st.li/st.lp
+// Attempts of one cascade entry that one wave takes in one queue unit (RIA_CASCADE_GROUP: build-time, measured at 2, 4, 8).
+#ifndef RIA_CASCADE_GROUP
+#define RIA_CASCADE_GROUP 4
+#endif
+constexpr int kCascadeGroup = RIA_CASCADE_GROUP;
+constexpr unsigned kCascadeGroups = (kRetryAttempts + kCascadeGroup - 1) / kCascadeGroup;
+constexpr size_t kSeedWsWords = static_cast<size_t>(kCascadeGroup) * 624;   // per workgroup of the persistent grid
+
+// perturbed decoder input of cascade attempt a (frame_v2.cpp:1415-1546) into st.li/st.lp; the attempt is the j-th of its
+// group, whose seeded mt19937 states are in ws (mt_seed_group)
 template <class S>
 __device__ inline float fast_perturb(FastState<S>& st, const FastCode& c, const float* base_i, const float* base_p,
-                                     uint32_t* mt, float* normal, int a, uint32_t h, int lane) {
+                                     uint32_t* mt, float* normal, const uint32_t* ws, int j, int a, int lane) {
     uint32_t seed; float sigma, factor; int kind;
     lane = opaque_lane(lane);
-    retry_transform_params(a, h, &seed, &sigma, &factor, &kind);
-    normal648_wave(mt, normal, seed, lane);
+    retry_transform_params(a, 0u, &seed, &sigma, &factor, &kind);
+    // sigma == 0.0f (attempt 26 only) needs no noise: the 648 normals are finite (r2 lies in (0, 1], so the logarithm and
+    // the quotient under the root are finite), and nz * 0.0f + 0.0f is +0.0f for every finite nz, whatever its sign.
+    // Seeding, twisting and drawing are skipped and nz is taken as 0: the same bits.
+    const bool noise = sigma != 0.0f;
+    if (noise) {
+        mt_load_group_state<kCascadeGroup>(mt, ws, j, lane);
+        normal648_state(mt, normal, lane);
+    }
     auto tf = [&](float v, float nz) {
         if (kind == 1) { v = (v < 10.0f) ? v : 10.0f; v = (-10.0f < v) ? v : -10.0f; }
         else if (kind == 2) v = v * 0.5f;
@@ -729,20 +746,27 @@ __device__ inline float fast_perturb(FastState<S>& st, const FastCode& c, const 
     };
 #pragma unroll
     for (int r = 0; r < S::NC; ++r) {
-        const uint32_t j = c.col_at[lane + 64 * r];
-        st.li[r] = (j != 0xFFFFu) ? llr_canon(tf(base_i[r], normal[j])) : 0.0f;
+        const uint32_t q = c.col_at[lane + 64 * r];
+        const float nz = (noise && q != 0xFFFFu) ? normal[q] : 0.0f;
+        st.li[r] = (q != 0xFFFFu) ? llr_canon(tf(base_i[r], nz)) : 0.0f;
     }
 #pragma unroll
     for (int r = 0; r < S::NR; ++r) {
         const uint32_t i = c.check_at[lane + 64 * r];
-        st.lp[r] = (i != 0xFFFFu) ? llr_canon(tf(base_p[r], normal[c.k + i])) : kIdleRowLlr;
+        const float nz = (noise && i != 0xFFFFu) ? normal[c.k + i] : 0.0f;
+        st.lp[r] = (i != 0xFFFFu) ? llr_canon(tf(base_p[r], nz)) : kIdleRowLlr;
     }
     wave_sync();
     return factor;
 }
 
 // ------------------------------------------------------------------------------------------------ kernel D2
-// persistent single-wave workgroups; unit u = attempt-major (a = u / n_entries, e = u % n_entries)
+// persistent single-wave workgroups; unit u = group-major (g = u / n_entries, e = u % n_entries): the wave runs attempts
+// g*G .. min(g*G + G, 34) - 1 of entry e in ascending order.  The entry's soft bits and seed hash are loaded once per
+// unit and the group's mt19937 states are seeded in lockstep (mt_seed_group) into seed_ws[blockIdx.x], which no other
+// wave touches.  best[e] is still the smallest successful attempt: an attempt runs unless a smaller one has been
+// published, a success ends the group (its later attempts can never win), and the result slot is written under the
+// lock by the current best only.  No wave waits for another.
 template <class S>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(S::kCascadeWaves))) void fast_cascade_kernel(FastDecodeArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -750,7 +774,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(S::kCascadeW
     const int lane = threadIdx.x;
     float* msg = reinterpret_cast<float*>(smem);
     const unsigned int n_entries = A.ctl->n_entries;
-    const unsigned int total = n_entries * 34u;
+    const unsigned int total = n_entries * kCascadeGroups;
     if (total == 0) return;
     FastState<S> st;
     fast_load_tables(st, c, smem, lane);
@@ -760,23 +784,34 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(S::kCascadeW
         unsigned int u = atomicAdd(&A.ctl->next_unit, lane == 0 ? 1u : 0u);   // all lanes take part: see RIA_QUEUE_GUARD
         u = __builtin_amdgcn_readfirstlane(u);   // scalar: the loop control and every address derived from u stay uniform
         if (u >= total) break;
-        const unsigned int a = u / n_entries, e = u - a * n_entries;
+        const unsigned int g = u / n_entries, e = u - g * n_entries, a0 = g * kCascadeGroup;
         unsigned int b = __hip_atomic_load(&A.best[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         b = __builtin_amdgcn_readfirstlane(b);
-        if (b < a) continue;  // an earlier attempt already succeeded: this one can never be chosen
-        const unsigned int fc = A.entries[e];
-        const unsigned int li = A.l1idx[fc];
-        fast_load_staged(st, A.staged + static_cast<size_t>(li) * kStageFloats, lane);
-        float bi[S::NC], bp[S::NR];
+        if (b < a0) continue;  // an earlier attempt already succeeded: none of this group can be chosen
+        const unsigned int li = A.l1idx[A.entries[e]];
+        uint32_t* ws = A.seed_ws + static_cast<size_t>(blockIdx.x) * kSeedWsWords;
+        mt_seed_group<kCascadeGroup>(ws, A.l1hash[li], a0, opaque_lane(lane));
+#pragma unroll 1
+        for (int j = 0; j < kCascadeGroup; ++j) {
+            const unsigned int a = a0 + static_cast<unsigned>(j);
+            if (a >= kRetryAttempts) break;
+            if (j > 0) {   // a smaller attempt may have been published while this wave decoded
+                b = __hip_atomic_load(&A.best[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                b = __builtin_amdgcn_readfirstlane(b);
+                if (b < a) break;
+            }
+            // the soft bits come back from the cache for every attempt that runs: held in registers they would be 11-12 VGPRs
+            // live across the decode, which the three-waves-per-SIMD budget does not have
+            fast_load_staged(st, A.staged + static_cast<size_t>(li) * kStageFloats, lane);
+            float bi[S::NC], bp[S::NR];
 #pragma unroll
-        for (int r = 0; r < S::NC; ++r) bi[r] = st.li[r];
+            for (int r = 0; r < S::NC; ++r) bi[r] = st.li[r];
 #pragma unroll
-        for (int r = 0; r < S::NR; ++r) bp[r] = st.lp[r];
-        const uint32_t h = A.l1hash[li];
-        float factor = fast_perturb(st, c, bi, bp, reinterpret_cast<uint32_t*>(msg), msg + 640, static_cast<int>(a), h, lane);
-        bool ok;
-        const int it = fast_decode<S>(st, c, smem, factor, c.max_iter, lane, &ok);
-        if (ok) {
+            for (int r = 0; r < S::NR; ++r) bp[r] = st.lp[r];
+            float factor = fast_perturb(st, c, bi, bp, reinterpret_cast<uint32_t*>(msg), msg + 640, ws, j, static_cast<int>(a), lane);
+            bool ok;
+            const int it = fast_decode<S>(st, c, smem, factor, c.max_iter, lane, &ok);
+            if (!ok) continue;
             // all-lane forms here too (no lane-0-only atomic inside the loop): only lane 0's operand can change the word
             unsigned int prev = atomicMin(&A.best[e], lane == 0 ? a : 0xFFFFFFFFu);
             prev = __builtin_amdgcn_readfirstlane(prev);
@@ -791,7 +826,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(S::kCascadeW
                     if (got == 0u) { mine = true; break; }
                     __builtin_amdgcn_s_sleep(1);
                 }
-                if (!mine) { if (lane == 0) atomicExch(&A.ctl->queue_fault, 1u); continue; }
+                if (!mine) { if (lane == 0) atomicExch(&A.ctl->queue_fault, 1u); break; }
                 __threadfence();
                 unsigned int cur = __hip_atomic_load(&A.best[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 cur = __builtin_amdgcn_readfirstlane(cur);
@@ -802,6 +837,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(S::kCascadeW
                 __threadfence();
                 if (lane == 0) atomicExch(&w->lock, 0u);
             }
+            break;   // this attempt succeeded: the group's later attempts can never be chosen
         }
     }
 }

@@ -86,10 +86,10 @@ __device__ __forceinline__ float mt_canonical(uint32_t y) {  // tempering + gene
     float r = __uint2float_rn(y) * 2.3283064365386963e-10f;  // / 2^32, exact scaling
     return (r >= 1.0f) ? u2f(0x3f7fffffu) : r;
 }
-// Fills normal[0..647] with the first 648 values of normal_distribution<float>(0,1) on mt19937(seed).
+// Fills normal[0..647] with the first 648 values of normal_distribution<float>(0,1) on the mt19937 whose freshly
+// seeded (not yet twisted) state is in st.
 template <int W = 1>
-__device__ inline void normal648_wave(uint32_t* st, float* normal, uint32_t seed, int lane) {
-    mt_seed_wave<W>(st, seed, lane);
+__device__ inline void normal648_state(uint32_t* st, float* normal, int lane) {
     int accepted = 0;  // accepted pairs so far (wave-uniform)
     while (accepted < 324) {
         mt_twist_wave<W>(st, lane);
@@ -114,6 +114,12 @@ __device__ inline void normal648_wave(uint32_t* st, float* normal, uint32_t seed
         }
         wave_sync();
     }
+}
+// Fills normal[0..647] with the first 648 values of normal_distribution<float>(0,1) on mt19937(seed).
+template <int W = 1>
+__device__ inline void normal648_wave(uint32_t* st, float* normal, uint32_t seed, int lane) {
+    mt_seed_wave<W>(st, seed, lane);
+    normal648_state<W>(st, normal, lane);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -155,6 +161,38 @@ __device__ inline void retry_transform_params(int a, uint32_t h, uint32_t* seed,
     else if (a < 26) { *kind = 3; *sigma = s3[a - 23]; *factor = 0.875f; *seed = h + static_cast<uint32_t>(a * 997 + 99999); }
     else if (a < 31) { *kind = 4; *sigma = s5[a - 26]; *factor = 0.875f; *seed = h + static_cast<uint32_t>(a * 997 + 33333); }
     else { *kind = 5; *sigma = s6[a - 31]; *factor = 0.875f; *seed = h + static_cast<uint32_t>(a * 997 + 77777); }
+}
+
+
+// The retry cascade seeds the mt19937 of up to G attempts of one codeword at once: the seeding recurrence is serial, but
+// the attempts' seeds differ by constants only (retry_transform_params), so lane j < G runs the recurrence of attempt
+// a0 + j in plain VALU code and the G chains cost the issue slots of one.  Word i of attempt j goes to ws[i * G + j]
+// (each step stores G adjacent words), a global-memory area that belongs to this workgroup alone.
+constexpr unsigned kRetryAttempts = 34;
+template <int G>
+__device__ inline void mt_seed_group(uint32_t* ws, uint32_t h, unsigned a0, int lane) {
+    static_assert(G >= 1 && G <= 64, "one lane per attempt of the group");
+    const unsigned a = a0 + static_cast<unsigned>(lane);
+    if (lane < G && a < kRetryAttempts) {
+        uint32_t x; float sigma, factor; int kind;
+        retry_transform_params(static_cast<int>(a), h, &x, &sigma, &factor, &kind);
+        uint32_t* w = ws + lane;
+        w[0] = x;
+        for (uint32_t i = 1; i < 624; ++i) {
+            x = 1812433253u * (x ^ (x >> 30)) + i;
+            w[i * G] = x;
+        }
+    }
+    // the wave reads these words back itself (other lanes than the ones that wrote them)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+// state of the group's attempt j into the LDS area normal648_state works on
+template <int G>
+__device__ inline void mt_load_group_state(uint32_t* st, const uint32_t* ws, int j, int lane) {
+    for (int i = lane; i < 624; i += 64) st[i] = ws[i * G + j];
+    wave_sync();
 }
 
 }  // namespace ria

@@ -86,6 +86,7 @@ struct ria_gpu {
     float* d_staged = nullptr;            // [4 * ws_frames][kStageFloats]
     unsigned int* d_l1idx = nullptr;      // [4 * ws_frames]
     unsigned int* d_l1hash = nullptr;     // [4 * ws_frames]
+    uint32_t* d_seed_ws = nullptr;        // [kMaxParts][cascade grid][kSeedWsWords]: per stream slot, per persistent workgroup
     int ws_frames = 0;
     int split_parts = 0;                  // RIA_OPT_SPLIT_PARTS (0 = library default)
     int dual_decoder = 0;                 // RIA_OPT_DUAL_DECODER: 0 = default (environment RIA_DUAL, else off), 1 = on, -1 = off
@@ -175,14 +176,21 @@ static bool shape_fits(int rate, const CoreTables& t, int* wave_lds) {
     });
     return ok;
 }
+// workgroups of the persistent retry kernels (256 CUs x 12 waves); RIA_PERSIST_GRID overrides it for experiments
+static int persist_grid_size(bool dual) {
+    static const int grid_env = getenv("RIA_PERSIST_GRID") ? std::max(64, atoi(getenv("RIA_PERSIST_GRID"))) : 0;
+    return grid_env ? grid_env : (dual ? 2048 : 3072);
+}
 static hipError_t ensure_decode_ws(ria_gpu_handle h, int n_frames) {
-    if (n_frames <= h->ws_frames && h->d_ctl && h->d_l1hash) return hipSuccess;
+    if (n_frames <= h->ws_frames && h->d_ctl && h->d_l1hash && h->d_seed_ws) return hipSuccess;
     h->ws_frames = 0;   // nothing is valid until every allocation below has succeeded
     for (void* p_ : {(void*)h->d_entries, (void*)h->d_best, (void*)h->d_list1, (void*)h->d_res, (void*)h->d_res_bytes, (void*)h->d_win, (void*)h->d_staged, (void*)h->d_l1idx, (void*)h->d_l1hash})
         if (p_) (void)hipFree(p_);
     h->d_entries = h->d_best = h->d_list1 = nullptr; h->d_res = nullptr; h->d_res_bytes = nullptr; h->d_win = nullptr; h->d_staged = nullptr; h->d_l1idx = nullptr; h->d_l1hash = nullptr;
     hipError_t e;
     if (!h->d_ctl && (e = hipMalloc(reinterpret_cast<void**>(&h->d_ctl), kMaxParts * sizeof(DecodeCtl))) != hipSuccess) return e;   // one per stream slot
+    // the cascade's seeded RNG states: one area per workgroup of its grid and per stream slot (the parts of a batch run concurrently)
+    if (!h->d_seed_ws && (e = hipMalloc(reinterpret_cast<void**>(&h->d_seed_ws), static_cast<size_t>(kMaxParts) * persist_grid_size(false) * kSeedWsWords * sizeof(uint32_t))) != hipSuccess) return e;
     if ((e = hipMalloc(reinterpret_cast<void**>(&h->d_entries), static_cast<size_t>(n_frames) * 4 * sizeof(unsigned))) != hipSuccess) return e;
     if ((e = hipMalloc(reinterpret_cast<void**>(&h->d_best), static_cast<size_t>(n_frames) * 4 * sizeof(unsigned))) != hipSuccess) return e;
     if ((e = hipMalloc(reinterpret_cast<void**>(&h->d_list1), static_cast<size_t>(n_frames) * 4 * sizeof(unsigned))) != hipSuccess) return e;
@@ -422,7 +430,7 @@ void ria_gpu_destroy(ria_gpu_handle h) {
     (void)hipSetDevice(h->device);
     void* ptrs[] = {h->d_row_deg, h->d_row_var, h->d_col_deg, h->d_col_slot, h->d_gather, h->d_gather_nochan,
                     h->d_crc_bit, h->d_crc_init, h->d_zc_ref, h->d_ch_tw, h->d_ch_tmpl, h->d_ch_tmpl_fft, h->d_ch_w1, h->d_ch_w2, h->d_ch_mag, h->d_ch_cum, h->d_ch_st, h->d_twiddle, h->d_nco, h->d_demod_const, h->d_tx_const, h->d_llr_ws,
-                    h->d_ctl, h->d_entries, h->d_best, h->d_list1, h->d_res, h->d_res_bytes, h->d_win, h->d_staged, h->d_l1idx, h->d_l1hash,
+                    h->d_ctl, h->d_entries, h->d_best, h->d_list1, h->d_res, h->d_res_bytes, h->d_win, h->d_staged, h->d_l1idx, h->d_l1hash, h->d_seed_ws,
                     h->d_f_row_addr, h->d_f_col_addr, h->d_f_check_at, h->d_f_col_at, h->d_f_col_pos};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (auto& st_ : h->aux_stream) if (st_) (void)hipStreamDestroy(st_);
@@ -653,6 +661,7 @@ static int launch_decode(ria_gpu_handle h, const float* llr_dev, int llr_stride,
     A.staged = h->d_staged + o4 * kStageFloats;
     A.l1idx = h->d_l1idx + o4;
     A.l1hash = h->d_l1hash + o4;
+    A.seed_ws = h->d_seed_ws + static_cast<size_t>(slot) * persist_grid_size(false) * kSeedWsWords;
     if ((e = hipMemsetAsync(A.ctl, 0, sizeof(DecodeCtl), s)) != hipSuccess)
         return fail(h, RIA_ERR_HIP, "hipMemsetAsync: %s", hipGetErrorString(e));
     const int wb = h->wave_lds;
@@ -665,8 +674,7 @@ static int launch_decode(ria_gpu_handle h, const float* llr_dev, int llr_stride,
 #else
     const bool dual = false;
 #endif
-    static const int grid_env = getenv("RIA_PERSIST_GRID") ? std::max(64, atoi(getenv("RIA_PERSIST_GRID"))) : 0;
-    const int persist_grid = grid_env ? grid_env : (dual ? 2048 : 3072);
+    const int persist_grid = persist_grid_size(dual);
     static const bool dbg = getenv("RIA_DEBUG_SYNC") != nullptr;   // stage-by-stage sync + trace on stderr
     auto stage = [&](const char* name) {
         if (!dbg) return;
