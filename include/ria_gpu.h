@@ -230,6 +230,12 @@ int ria_gpu_decode_frames_host(ria_gpu_handle h, const float* llr_host, int llr_
  * (0 = leave the modulator's output_scale 40 level; tools/test_waveform_simple.cpp:365-371 uses 0.8) */
 int ria_gpu_tx_batch(ria_gpu_handle h, const uint8_t* info_dev, int n_frames, float peak_normalize,
                      float* samples_out_dev, void* stream);
+/* The same in two steps, split at the coded bytes where the burst interleaver works (streaming_encoder.cpp:302-389):
+ * encodeFixedFrame alone (coded_out_dev: n_frames * 324 bytes, channel interleaved, MSB first), and the modulator on such
+ * bytes (e.g. ria_gpu_burst_interleave_batch's output).  tx_coded(encode_frames(info)) is ria_gpu_tx_batch(info) bit for bit. */
+int ria_gpu_encode_frames_batch(ria_gpu_handle h, const uint8_t* info_dev, int n_frames, uint8_t* coded_out_dev, void* stream);
+int ria_gpu_tx_coded_batch(ria_gpu_handle h, const uint8_t* coded_dev, int n_frames, float peak_normalize,
+                           float* samples_out_dev, void* stream);
 
 /* Builds serialized v2 data frames (makeFixedDataFrame("TEST","RX",seq,payload).serialize(),
  * frame_v2.cpp:1890-1912, :502-554) with payload bytes drawn from a counter RNG: seq = first_seq + f. */
@@ -488,9 +494,10 @@ int ria_gpu_burst_interleave_batch(ria_gpu_handle h, const uint8_t* logical_byte
  *
  * Not covered (the caller's side or other paths): control-frame hypotheses (R1/4 fast path, CW0 peek and salvage,
  * :1268-1335, :1505-1575, :2866-2990), the weak-accept and reject-streak state (fold them into min_confidence), the PING
- * energy check, chase combining, Schmidl-Cox acquisition, OFDM-COX, ring-buffer wrap-around, and the
- * +-2 Hz clamp of the reported CFO the host applies before it feeds it back (:1912-1918).  MC-DPSK frames (ZC and
- * dual-chirp acquisition, the disconnected handshake fallbacks) are ria_gpu_mcdpsk_acquire_batch's. */
+ * energy check, burst groups and burst continuation (ria_gpu_rx_burst_batch), chase combining, Schmidl-Cox
+ * acquisition, OFDM-COX, ring-buffer wrap-around, and the +-2 Hz clamp of the reported CFO the host applies before it
+ * feeds it back (:1912-1918).  MC-DPSK frames (ZC and dual-chirp acquisition, the disconnected handshake fallbacks) are
+ * ria_gpu_mcdpsk_acquire_batch's. */
 typedef struct ria_acq_params {      /* one per window, 32 bytes */
     float    known_cfo_hz;           /* detectDataSync's known CFO (last_cfo_, :726) and the CFO every candidate is demodulated with */
     float    detect_threshold;       /* detectDataSync threshold (CORR_DETECT_THRESHOLD 0.15 for OFDM, streaming_decoder.hpp:457) */
@@ -521,6 +528,98 @@ int ria_gpu_rx_acquire_batch(ria_gpu_handle h, const float* samples_dev, int64_t
                              int n_windows, const ria_acq_params* params_dev, uint32_t flags,
                              uint8_t* info_out_dev, ria_decode_status* decode_status_dev, ria_acq_result* acq_dev,
                              ria_frame_status* demod_status_dev, void* stream);
+
+/* ---- burst groups and burst continuation: what the receiver does behind the first data frame of a window -------------
+ * ria_gpu_rx_burst_batch continues where ria_gpu_rx_acquire_batch stops (src/gui/modem/streaming_decoder.cpp).  Window
+ * geometry, ria_acq_params, the detector, the acceptance rule (steps 1-2 above) and the RIA_DECODE_* /
+ * RIA_DECODE_NO_CHANNEL_DEINTERLEAVE / RIA_ACQ_NO_TIMING_RETRY flags are ria_gpu_rx_acquire_batch's; two flags are new.
+ * Every per-frame output has RIA_BURST_MAX_FRAMES slots per window (window b, slot f at index b * 9 + f); every slot of
+ * every output the call does not fill is zero.
+ *
+ * Positions.  Physical frame f of a window starts at s_f = sync_start + f * frame_samples.  Frame 0's abs_position is
+ * abs_base + sync_start and every later frame of the window is demodulated with the SAME abs_position: between the frames
+ * of a burst the reference calls neither setAbsoluteTrainingPosition nor reset() (group path :3173-3175; continuation path
+ * :2066-2067 - nothing between :1434 and :2015 on the path of a successful 4-codeword data frame calls either: the only
+ * calls are in the timing-recovery candidates, :1891-1897, which such a frame does not reach).
+ *
+ * Energy gate of frame f >= 1 (:3154-3171 = :2047-2059): sum of x[s_f + 1024 + i]^2 for i < min(frame_samples - 1024, 5000),
+ * in float32, ascending i, each product rounded before it is added (the library is built with -ffp-contract=off);
+ * rms = sqrtf(sum / (float)len); the gate fails iff rms < 0.04f (a NaN passes).  rms_dev holds the value bit for bit, also
+ * that of the frame the gate stopped.
+ *
+ * CFO chain (:1397-1406, :3190-3197, :2075-2082): c_0 = known_cfo_hz.  After frame f was demodulated with c_f and reports
+ * e = ria_frame_status.cfo_hz: d = e - c_f; c_{f+1} = |d| > 2 ? c_f + copysignf(2, d) : e (a NaN drift leaves e).
+ * cfo_used_dev[f] = c_f; ria_burst_result.cfo_hz = the last c computed = what the host would hold in last_cfo_.
+ *
+ * Group mode (mode 2): RIA_BURST_INTERLEAVE (use_burst_interleave_) is set and the accepted window's detector reports the
+ * negated-LTS marker (:1378-1410, accumulateBurstFrames / tryDemodulateNextBurstFrame :3065-3208).  Frame 0 is
+ * demodulated once with meta.flags = 1 and no timing recovery (nothing is decoded yet); n_llr == 0 is STOP_PROCESS.  Then
+ * for f = 1 .. group_size - 1, in this order: the frame must lie in the window (s_f + frame_samples <= window_len, else
+ * STOP_WINDOW: the reference would wait for samples), pass the gate (else STOP_ENERGY), be demodulated with flags 0 and
+ * c_f (n_llr == 0: STOP_PROCESS), chain step.  Any stop aborts the group as the reference discards it (:3093-3108):
+ * frames = the physical frames demodulated so far, frames_decoded = 0, no bytes and no decode status; the demod status,
+ * cfo_used and rms slots of the frames that ran stay filled.  A complete group goes through
+ * ria_gpu_burst_deinterleave_batch's permutation (finalizeBurstGroup :3210-3239) and decodeFixedFrame with the call's
+ * decode flags on each logical frame: logical frame i in slot i of the bytes and decode status, frames_decoded =
+ * group_size; the demod status slots hold the PHYSICAL frames.
+ *
+ * Continuation mode (mode 1): every other accepted window (:2015-2114).  Frame 0 is exactly what ria_gpu_rx_acquire_batch
+ * reports for the window, timing recovery included, in slot 0 (a marked window without RIA_BURST_INTERLEAVE still has its
+ * first LTS un-negated).  A frame 0 whose reported candidate has no soft bits (n_llr == 0) is STOP_PROCESS with frames = 0,
+ * whatever RIA_BURST_NO_CONTINUE says: slot 0 and frames_decoded = 1 stay what the acquire rounds report, and the chain
+ * does not step (cfo_hz = known_cfo_hz).  Continuation runs only if RIA_BURST_NO_CONTINUE is clear (else STOP_NONE), frame 0 is a success -
+ * all four cw_ok and frame_valid, which is CodewordStatus::allSuccess() with a non-empty reassemble() for a fixed frame
+ * (frame_v2.cpp:1030-1063) (else STOP_DECODE), byte 2 of the frame is neither a control nor a connect type
+ * (frame_v2.hpp:222-228, :348-351; streaming_decoder.cpp:1994-1998) (else STOP_NOT_DATA), and delta == 0 (else
+ * STOP_RECOVERED: the reference runs its recovery candidates with a sync_cfo_ the primary has already moved, :1433, :1903,
+ * while ria_gpu_rx_acquire_batch deliberately uses the known CFO for them, so the chain's start would not be the
+ * reference's; the caller continues such a window itself).  c_1 comes from frame 0's cfo_hz by the chain rule (:1412-1434).
+ * For k = 1 .. 8 (MAX_BURST_BLOCKS, streaming_decoder.hpp:418), in this order: fit (else STOP_WINDOW), gate (else
+ * STOP_ENERGY), demodulate with c_k (n_llr == 0: STOP_PROCESS, the block is not counted), chain step, decodeFixedFrame into
+ * slot k; a block that decodes no codeword is kept and counted as the reference counts it, and ends the burst
+ * (STOP_DECODE, :2112); after block 8 STOP_LIMIT.
+ *
+ * Scope as ria_gpu_rx_acquire_batch: decodeFrame is decodeFixedFrame only; the control-frame hypotheses (:2866-3000), the
+ * burst timeout (:3066-3088), the frame queue and statistics stay with the caller.  A decode work-queue fault in any round
+ * fails the whole call with RIA_ERR_HIP; so does a work list that breaks its bound (the call never loops on one).  The call
+ * synchronises its stream once per round for one small device-to-host read; rounds <= 9 (acquire) + 9.  No samples, soft
+ * bits or payloads go to the host.  Workspaces live on the handle, grow with n_windows (and group_size) and are allocated
+ * before anything of the call is in flight. */
+#define RIA_BURST_MAX_FRAMES 9            /* 1 + MAX_BURST_BLOCKS; an interleaved group uses group_size <= 8 of them */
+#define RIA_BURST_INTERLEAVE   0x800u     /* use_burst_interleave_: a marked window is accumulated as a group */
+#define RIA_BURST_NO_CONTINUE  0x1000u    /* unmarked windows: first frame only (= ria_gpu_rx_acquire_batch) */
+
+typedef struct ria_burst_result {         /* 64 bytes, one per window */
+    int32_t detected, accepted, sync_start, frame_start;   /* as ria_acq_result; frame_start of frame 0 */
+    float   correlation;
+    float   cfo_hz;            /* the value the host would hold in last_cfo_ after the window (0 if not accepted) */
+    int16_t delta;             /* timing-recovery delta of frame 0 (continuation mode), 0 in group mode */
+    uint8_t candidates;        /* as ria_acq_result, frame 0 only (0 in group mode) */
+    uint8_t burst_interleaved; /* detector's marker */
+    uint8_t mode;              /* 0 not accepted, 1 single frame / continuation, 2 interleaved group */
+    uint8_t frames;            /* physical frames demodulated (soft bits produced) */
+    uint8_t frames_decoded;    /* logical frames / blocks handed to decodeFixedFrame: slots 0..frames_decoded-1 are valid */
+    uint8_t stop;              /* RIA_BURST_STOP_* */
+    int32_t reserved[8];
+} ria_burst_result;
+enum { RIA_BURST_STOP_NONE = 0,        /* group complete / not accepted / RIA_BURST_NO_CONTINUE */
+       RIA_BURST_STOP_ENERGY = 1,      /* rms < 0.04 */
+       RIA_BURST_STOP_PROCESS = 2,     /* process() false or no soft bits (n_llr == 0) */
+       RIA_BURST_STOP_WINDOW = 3,      /* next block does not lie in the window (the reference would wait) */
+       RIA_BURST_STOP_DECODE = 4,      /* block decoded nothing (continuation) / frame 0 not a success */
+       RIA_BURST_STOP_NOT_DATA = 5,    /* frame 0 is a control / connect frame (frame_v2.hpp:222-228, :348-351) */
+       RIA_BURST_STOP_LIMIT = 6,       /* MAX_BURST_BLOCKS reached */
+       RIA_BURST_STOP_RECOVERED = 7 }; /* frame 0 came from timing recovery (delta != 0): no continuation */
+
+int ria_gpu_rx_burst_batch(ria_gpu_handle h, const float* samples_dev, int64_t stride, int search_len, int window_len,
+                           int n_windows, int group_size /* 2..8 */, const ria_acq_params* params_dev, uint32_t flags,
+                           uint8_t* info_out_dev,               /* n_windows * 9 * info_bytes_per_frame */
+                           ria_decode_status* decode_status_dev,/* n_windows * 9 */
+                           ria_burst_result* burst_dev,         /* n_windows */
+                           ria_frame_status* demod_status_dev,  /* nullable, n_windows * 9: physical frame f */
+                           float* cfo_used_dev,                 /* nullable, n_windows * 9: CFO handed to process() of frame f */
+                           float* rms_dev,                      /* nullable, n_windows * 9: the gate's rms of frame f (slot 0 = 0) */
+                           void* stream);
 
 /* ---- acquire + decode: MC-DPSK frames with the disconnected-handshake fallbacks ------------------------
  * ria_gpu_mcdpsk_acquire_batch replaces what gui::StreamingDecoder does with one search window of an MC-DPSK frame

@@ -1,5 +1,6 @@
 """Connected-mode OFDM data frames from capture windows: the acceptance rule, the Monte-Carlo window recipe and the
-counter driver around RxEngine.rx_acquire (ria_gpu_rx_acquire_batch).
+counter driver around RxEngine.rx_acquire (ria_gpu_rx_acquire_batch), and the same for bursts of frames around
+RxEngine.rx_burst (ria_gpu_rx_burst_batch).
 
 A window is what gui::StreamingDecoder searches for one DATA frame: silence, the frame at some offset, the channel
 over the whole window.  The detector sees the first `search_len` samples; the window holds search_len + frame_samples,
@@ -107,6 +108,70 @@ def run_acquire_sweep(engine, points, n_trials, base_seed, chunk=4096, **kw):
         for start, n in shard_range(n_trials, rank, world, chunk):
             local[pi] += run_acquire_point(engine, p, base_seed, pi, start, n, **kw)
     return reduce_counters(local, engine.device)
+
+
+# ---- burst groups and burst continuation (ria_gpu_rx_burst_batch)
+BURST_STOPS = ("none", "energy", "process", "window", "decode", "not_data", "limit", "recovered")   # RIA_BURST_STOP_*
+BURST_COUNTERS = ("windows", "detected", "accepted") + tuple(f"mode{m}_{s}" for m in (1, 2) for s in BURST_STOPS) + \
+    ("frames", "frames_decoded", "frames_ok")
+
+
+def make_burst_windows(engine, base_seed, point, point_index, start, n, n_frames, interleaved=True, marker=None,
+                       search_len=SEARCH_LEN, window_frames=None, peak=0.5):
+    """Burst windows of trials [start, start + n) of one sweep point on the engine's device, as the air interface carries
+    them (streaming_encoder.cpp:302-389): make_frames (seq = trial * n_frames + f) -> encodeFixedFrame -> [BurstInterleaver::
+    interleave over the n_frames frames of a window] -> modulator per physical frame -> [first LTS of the burst negated:
+    the marker] -> the whole burst scaled to `peak` -> placed at the recipe offset in a zero window of search_len +
+    window_frames * frame_samples samples (window_frames >= n_frames, default n_frames + 1: room for the block behind the
+    burst, which ends a continuation at the energy gate) -> the reference-identical channel over the whole window (one
+    mt19937 seed per trial).  marker None: as `interleaved`.
+    Returns (windows float32 [n, window_len], sent info uint8 [n, n_frames, info_bytes], offsets int64 [n])."""
+    fs, N = engine.geo.frame_samples, int(n_frames)
+    marker = bool(interleaved) if marker is None else bool(marker)
+    window_frames = N + 1 if window_frames is None else int(window_frames)
+    assert N >= 1 and window_frames >= N and (not interleaved or 2 <= N <= 8)
+    offs, seeds = window_recipe(base_seed, point_index, np.arange(start, start + n), search_len)
+    info = engine.make_frames(base_seed, start * N, n * N)
+    coded = engine.encode_frames(info)
+    if interleaved:
+        coded = engine.burst_interleave(coded, N)
+    x = engine.tx_coded(coded, peak=0.0).reshape(n, N * fs)
+    if marker:
+        x[:, :1152] = -x[:, :1152]
+    x = x * (np.float32(peak) / x.abs().amax(dim=1, keepdim=True))
+    win = torch.zeros((n, search_len + window_frames * fs), dtype=torch.float32, device=engine.device)
+    offs_t = torch.from_numpy(offs).to(engine.device)
+    win.scatter_(1, offs_t[:, None] + torch.arange(N * fs, device=engine.device)[None, :], x)   # placement only
+    engine.channel_exact_seeded_(win, point.channel, point.snr_db, seeds)
+    return win, info.reshape(n, N, -1), offs
+
+
+def burst_tally(out, sent):
+    """Counter row (BURST_COUNTERS) of one chunk from rx_burst's host-side outputs and the sent payloads
+    (uint8 [n, n_frames, info_bytes], numpy or tensor): windows per mode and stop reason, physical frames demodulated,
+    logical frames / blocks decoded, and those of them that are complete, CRC-valid and equal to what was sent."""
+    res, st = out["result"], out["decode_status"]
+    sent = sent.cpu().numpy() if torch.is_tensor(sent) else np.asarray(sent)
+    row = dict.fromkeys(BURST_COUNTERS, 0)
+    row.update(windows=len(res), detected=int((res["detected"] != 0).sum()), accepted=int((res["accepted"] != 0).sum()))
+    for m in (1, 2):
+        for k, name in enumerate(BURST_STOPS):
+            row[f"mode{m}_{name}"] = int(((res["mode"] == m) & (res["stop"] == k)).sum())
+    nf = min(sent.shape[1], out["info"].shape[1])
+    valid = np.arange(nf)[None, :] < res["frames_decoded"][:, None]
+    ok = st["cw_ok"][:, :nf].all(axis=2) & (st["frame_valid"][:, :nf] != 0) & (out["info"][:, :nf] == sent[:, :nf]).all(axis=2)
+    row.update(frames=int(res["frames"].sum()), frames_decoded=int(res["frames_decoded"].sum()), frames_ok=int((ok & valid).sum()))
+    return np.array([row[k] for k in BURST_COUNTERS], dtype=np.int64)
+
+
+def run_burst_point(engine, point, base_seed, point_index, start, n, n_frames, interleaved=True, search_len=SEARCH_LEN,
+                    min_confidence=None, **kw):
+    """One chunk of trials of one sweep point through ria_gpu_rx_burst_batch (group_size = n_frames for interleaved
+    bursts).  Returns the counter row (BURST_COUNTERS)."""
+    win, sent, _ = make_burst_windows(engine, base_seed, point, point_index, start, n, n_frames, interleaved, search_len=search_len)
+    out = engine.rx_burst(win, search_len, group_size=max(2, int(n_frames)), detect_threshold=DETECT_THRESHOLD,
+                          min_confidence=min_confidence, interleave=bool(interleaved), **kw)
+    return burst_tally(out, sent)
 
 
 # ---- MC-DPSK (ria_gpu_mcdpsk_acquire_batch)

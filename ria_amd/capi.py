@@ -14,6 +14,10 @@ RX_DEMOD_ONLY = 0x200
 OPT_SPLIT_PARTS = 1
 OPT_DUAL_DECODER = 2
 ACQ_NO_TIMING_RETRY = 0x400
+BURST_MAX_FRAMES = 9
+BURST_INTERLEAVE = 0x800
+BURST_NO_CONTINUE = 0x1000
+BURST_STOP = {"NONE": 0, "ENERGY": 1, "PROCESS": 2, "WINDOW": 3, "DECODE": 4, "NOT_DATA": 5, "LIMIT": 6, "RECOVERED": 7}
 MACQ_SYNC_CHIRP = 0x1
 MACQ_DISCONNECTED = 0x2
 MACQ_NO_RETRY = 0x4
@@ -26,7 +30,7 @@ EXPORTS = [
     "ria_gpu_rx_batch", "ria_gpu_rx_frames_host", "ria_gpu_decode_frames_host", "ria_gpu_tx_batch", "ria_gpu_make_frames",
     "ria_gpu_channel_batch", "ria_gpu_channel_exact_batch", "ria_gpu_channel_exact_seeded_batch", "ria_gpu_debug_math", "ria_gpu_debug_queue_fault", "ria_gpu_sync_zc_batch", "ria_gpu_zc_preamble", "ria_gpu_sync_chirp_batch", "ria_gpu_chirp_preamble", "ria_gpu_mcdpsk_demod_batch",
     "ria_gpu_mcdpsk_modulate_host", "ria_gpu_chase_combine_batch", "ria_gpu_sync_lts_batch", "ria_gpu_sync_host", "ria_gpu_ldpc_encode_host", "ria_gpu_burst_deinterleave_batch", "ria_gpu_burst_interleave_batch",
-    "ria_gpu_rx_acquire_batch", "ria_gpu_mcdpsk_acquire_batch",
+    "ria_gpu_rx_acquire_batch", "ria_gpu_mcdpsk_acquire_batch", "ria_gpu_rx_burst_batch", "ria_gpu_encode_frames_batch", "ria_gpu_tx_coded_batch",
     "ria_gpu_sync_cox_batch", "ria_gpu_cox_preamble", "ria_gpu_channel_exact_cfo_batch", "ria_gpu_tx_cfo_batch",
     "ria_gpu_mcdpsk_demod_host", "ria_gpu_ldpc_decode_robust_host", "ria_gpu_mcdpsk_modulate_batch",
     "ria_link_recommend", "ria_link_data_mode", "ria_link_ofdm_code_rate", "ria_link_cap_initial_rate",
@@ -79,6 +83,13 @@ class AcqResult(C.Structure):
     _fields_ = [("detected", C.c_int32), ("accepted", C.c_int32), ("sync_start", C.c_int32), ("frame_start", C.c_int32),
                 ("correlation", C.c_float), ("cfo_hz", C.c_float), ("delta", C.c_int16), ("candidates", C.c_uint8),
                 ("burst_interleaved", C.c_uint8), ("reserved", C.c_int32)]
+
+
+class BurstResult(C.Structure):
+    _fields_ = [("detected", C.c_int32), ("accepted", C.c_int32), ("sync_start", C.c_int32), ("frame_start", C.c_int32),
+                ("correlation", C.c_float), ("cfo_hz", C.c_float), ("delta", C.c_int16), ("candidates", C.c_uint8),
+                ("burst_interleaved", C.c_uint8), ("mode", C.c_uint8), ("frames", C.c_uint8), ("frames_decoded", C.c_uint8),
+                ("stop", C.c_uint8), ("reserved", C.c_int32 * 8)]
 
 
 class McAcqParams(C.Structure):
@@ -139,6 +150,8 @@ def load(build_if_needed=True):
     L.ria_gpu_rx_frames_host.argtypes = [vp, vp, vp, i32, u32, vp, vp, vp, vp]
     L.ria_gpu_decode_frames_host.argtypes = [vp, vp, i32, i32, u32, vp, vp]
     L.ria_gpu_tx_batch.argtypes = [vp, vp, i32, f32, vp, vp]
+    L.ria_gpu_encode_frames_batch.argtypes = [vp, vp, i32, vp, vp]
+    L.ria_gpu_tx_coded_batch.argtypes = [vp, vp, i32, f32, vp, vp]
     L.ria_gpu_make_frames.argtypes = [vp, u64, i32, i32, vp, vp]
     L.ria_gpu_channel_batch.argtypes = [vp, i32, f32, u64, u64, vp, i32, vp]
     L.ria_gpu_debug_math.argtypes = [vp, i32, vp, vp, i32, vp, vp]
@@ -165,6 +178,7 @@ def load(build_if_needed=True):
     L.ria_gpu_burst_deinterleave_batch.argtypes = [vp, vp, i32, i32, i32, vp, vp]
     L.ria_gpu_burst_interleave_batch.argtypes = [vp, vp, i32, i32, vp, vp]
     L.ria_gpu_rx_acquire_batch.argtypes = [vp, vp, C.c_int64, i32, i32, i32, vp, u32, vp, vp, vp, vp, vp]
+    L.ria_gpu_rx_burst_batch.argtypes = [vp, vp, C.c_int64, i32, i32, i32, i32, vp, u32, vp, vp, vp, vp, vp, vp, vp]
     L.ria_gpu_mcdpsk_acquire_batch.argtypes = [vp, vp, vp, C.c_int64, i32, i32, i32, i32, vp, u32, vp, vp, vp, i32, vp]
     L.ria_link_recommend.argtypes = [f32, f32, C.POINTER(LinkRecommendation)]
     L.ria_link_recommend.restype = None

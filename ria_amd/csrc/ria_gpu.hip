@@ -34,6 +34,7 @@
 #include "cfo_kernels.hip.h"
 #include "acquire_kernels.hip.h"
 #include "mcdpsk_acquire_kernels.hip.h"
+#include "burst_kernels.hip.h"
 
 using namespace ria;
 
@@ -108,6 +109,9 @@ struct ria_gpu {
     // ria_gpu_mcdpsk_acquire_batch: detector results, two work lists, one round's soft bits, codeword rows, decoder outputs and
     // header state, and the control block (device + pinned mirror), grown on demand
     unsigned char* d_macq_ws = nullptr; size_t macq_bytes = 0; MacqCtl* p_macq_ctl = nullptr;
+    // ria_gpu_rx_burst_batch: frame-0 rows of the acquire rounds, the round lists, the groups' soft bits and decode batch,
+    // and the control block (device + pinned mirror), grown on demand
+    unsigned char* d_burst_ws = nullptr; size_t burst_bytes = 0; BurstCtl* p_burst_ctl = nullptr;
 };
 
 namespace {
@@ -453,6 +457,8 @@ void ria_gpu_destroy(ria_gpu_handle h) {
     if (h->p_acq_ctl) (void)hipHostFree(h->p_acq_ctl);
     if (h->d_macq_ws) (void)hipFree(h->d_macq_ws);
     if (h->p_macq_ctl) (void)hipHostFree(h->p_macq_ctl);
+    if (h->d_burst_ws) (void)hipFree(h->d_burst_ws);
+    if (h->p_burst_ctl) (void)hipHostFree(h->p_burst_ctl);
     for (void* p : {(void*)h->d_rctl, (void*)h->d_flagged, (void*)h->d_list2, (void*)h->d_stage2, (void*)h->d_info_c, (void*)h->d_rows_c,
                     (void*)h->d_redec_ok, (void*)h->d_redec_bytes, (void*)h->d_st_c, (void*)h->d_overflow}) if (p) (void)hipFree(p);
     for (void* p : {(void*)h->p_rctl, (void*)h->p_flagged, (void*)h->p_info_c, (void*)h->p_rows_c, (void*)h->p_redec_ok,
@@ -733,7 +739,8 @@ int ria_gpu_decode_batch(ria_gpu_handle h, const float* llr_dev, int llr_stride,
 
 // ------------------------------------------------------------------------------------------------ demod
 static int demod_batch_slot(ria_gpu_handle h, const float* samples_dev, const uint64_t* frame_offsets_dev, const ria_frame_meta* meta_dev,
-                            int n_frames, float* llr_out_dev, ria_frame_status* status_dev, hipStream_t stream, int slot) {
+                            int n_frames, float* llr_out_dev, ria_frame_status* status_dev, hipStream_t stream, int slot,
+                            int llr_stride = 0 /* floats between the soft-bit rows of two frames; 0 = llrs_per_frame */) {
     DemodArgs A;
     A.k = static_cast<const DemodConst*>(h->d_demod_const);
     A.twiddle = static_cast<const float2*>(h->d_twiddle);
@@ -743,7 +750,7 @@ static int demod_batch_slot(ria_gpu_handle h, const float* samples_dev, const ui
     A.meta = meta_dev;
     A.n_frames = n_frames;
     A.llr_out = llr_out_dev;
-    A.llr_stride = h->geo.llrs_per_frame;
+    A.llr_stride = llr_stride ? llr_stride : h->geo.llrs_per_frame;
     A.status = status_dev;
     A.dbg = nullptr;
 #ifdef RIA_DEBUG_STAMPS
@@ -942,6 +949,29 @@ int ria_gpu_tx_batch(ria_gpu_handle h, const uint8_t* info_dev, int n_frames, fl
     launch_tx(static_cast<const TxConst*>(h->d_tx_const), static_cast<const float2*>(h->d_twiddle),
               static_cast<const float2*>(h->d_nco), info_dev, n_frames, peak_normalize, h->geo, samples_out_dev,
               static_cast<hipStream_t>(stream));
+    HIP_TRY(h, hipGetLastError());
+    return RIA_OK;
+}
+
+int ria_gpu_encode_frames_batch(ria_gpu_handle h, const uint8_t* info_dev, int n_frames, uint8_t* coded_out_dev, void* stream) {
+    if (!h || !info_dev || !coded_out_dev || n_frames < 0) return fail(h, RIA_ERR_INVALID, "ria_gpu_encode_frames_batch: bad argument");
+    if (n_frames == 0) return RIA_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    launch_tx_mode<1>(static_cast<const TxConst*>(h->d_tx_const), static_cast<const float2*>(h->d_twiddle),
+                      static_cast<const float2*>(h->d_nco), info_dev, n_frames, 0.0f, h->geo, nullptr, coded_out_dev,
+                      static_cast<hipStream_t>(stream));
+    HIP_TRY(h, hipGetLastError());
+    return RIA_OK;
+}
+
+int ria_gpu_tx_coded_batch(ria_gpu_handle h, const uint8_t* coded_dev, int n_frames, float peak_normalize,
+                           float* samples_out_dev, void* stream) {
+    if (!h || !coded_dev || !samples_out_dev || n_frames < 0) return fail(h, RIA_ERR_INVALID, "ria_gpu_tx_coded_batch: bad argument");
+    if (n_frames == 0) return RIA_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    launch_tx_mode<2>(static_cast<const TxConst*>(h->d_tx_const), static_cast<const float2*>(h->d_twiddle),
+                      static_cast<const float2*>(h->d_nco), coded_dev, n_frames, peak_normalize, h->geo, samples_out_dev, nullptr,
+                      static_cast<hipStream_t>(stream));
     HIP_TRY(h, hipGetLastError());
     return RIA_OK;
 }
@@ -1388,6 +1418,52 @@ static AcqList acq_list(unsigned char* base, size_t n) {   // the four arrays of
     return l;
 }
 
+// grows the acquisition workspace to n_windows; nothing of an earlier call is in flight: every call ends on a stream sync
+static int acq_ensure_ws(ria_gpu_handle h, int n_windows) {
+    if (n_windows > h->acq_windows) {
+        if (h->d_acq_ws) (void)hipFree(h->d_acq_ws);
+        h->d_acq_ws = nullptr; h->acq_windows = 0;
+        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&h->d_acq_ws), acq_layout(static_cast<size_t>(n_windows), static_cast<size_t>(h->geo.info_bytes_per_frame)).total));
+        h->acq_windows = n_windows;
+    }
+    if (!h->p_acq_ctl) HIP_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&h->p_acq_ctl), sizeof(AcqCtl), hipHostMallocDefault));
+    return RIA_OK;
+}
+
+// The rounds of ria_gpu_rx_acquire_batch on a planned round-0 list (lists[0] of the handle's workspace, its length in
+// A.ctl): round 0 runs every accepted window at its primary candidate, round r >= 1 the windows whose previous candidate
+// decoded nothing at their next candidate that fits; at most 8 recovery rounds (each advances every window it holds by at
+// least one of the 8 deltas).  A.acq / A.info_out / A.dst_out / A.fst_out take one row per window.
+static int acq_run_rounds(ria_gpu_handle h, const char* who, const float* samples_dev, AcqArgs A, const AcqLayout& L, int n_windows,
+                          uint32_t flags, hipStream_t s) {
+    unsigned char* W = h->d_acq_ws;
+    const size_t cap = static_cast<size_t>(h->acq_windows);
+    AcqList lists[2] = {acq_list(W + L.list[0], cap), acq_list(W + L.list[1], cap)};
+    A.info_c = W + L.info; A.dst_c = reinterpret_cast<const ria_decode_status*>(W + L.dst);
+    A.fst_c = reinterpret_cast<const ria_frame_status*>(W + L.fst);
+    const uint32_t dflags = flags & (RIA_DECODE_FULL | RIA_DECODE_NO_CHANNEL_DEINTERLEAVE);
+    for (int round = 0;; ++round) {
+        HIP_TRY(h, hipMemcpyAsync(h->p_acq_ctl, A.ctl, sizeof(AcqCtl), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        if (h->p_acq_ctl->fault) return fail(h, RIA_ERR_HIP, "decode work-queue fault in round %d: no window of this call was decoded", round - 1);
+        const int n_list = static_cast<int>(h->p_acq_ctl->n_list);
+        if (n_list == 0) break;
+        if (n_list > n_windows || round >= kAcqCandidates) return fail(h, RIA_ERR_HIP, "%s: work list of round %d broke its bound (%d)", who, round, n_list);
+        A.cur = lists[round & 1];
+        A.next = lists[(round + 1) & 1];
+        A.n_cur = n_list;
+        A.round = round;
+        A.retry = !(flags & RIA_ACQ_NO_TIMING_RETRY) && round + 1 < kAcqCandidates;
+        int rc = ria_gpu_rx_batch(h, samples_dev, A.cur.offset, A.cur.meta, n_list, dflags, W + L.info,
+                                  reinterpret_cast<ria_decode_status*>(W + L.dst), nullptr, reinterpret_cast<ria_frame_status*>(W + L.fst), s);
+        if (rc != RIA_OK) return rc;
+        hipLaunchKernelGGL(acq_scatter_kernel, dim3(std::min((n_list + 3) / 4, 4096)), dim3(256), 0, s, A);
+        hipLaunchKernelGGL(acq_next_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A);
+        HIP_TRY(h, hipGetLastError());
+    }
+    return RIA_OK;
+}
+
 int ria_gpu_rx_acquire_batch(ria_gpu_handle h, const float* samples_dev, int64_t stride, int search_len, int window_len,
                              int n_windows, const ria_acq_params* params_dev, uint32_t flags,
                              uint8_t* info_out_dev, ria_decode_status* decode_status_dev, ria_acq_result* acq_dev,
@@ -1403,13 +1479,7 @@ int ria_gpu_rx_acquire_batch(ria_gpu_handle h, const float* samples_dev, int64_t
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (int rc = lts_prepare(h)) return rc;
     const size_t n = static_cast<size_t>(n_windows), ib = static_cast<size_t>(h->geo.info_bytes_per_frame);
-    if (n_windows > h->acq_windows) {   // nothing of an earlier call is in flight: every call ends on a stream sync
-        if (h->d_acq_ws) (void)hipFree(h->d_acq_ws);
-        h->d_acq_ws = nullptr; h->acq_windows = 0;
-        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&h->d_acq_ws), acq_layout(n, ib).total));
-        h->acq_windows = n_windows;
-    }
-    if (!h->p_acq_ctl) HIP_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&h->p_acq_ctl), sizeof(AcqCtl), hipHostMallocDefault));
+    if (int rc = acq_ensure_ws(h, n_windows)) return rc;
     const size_t cap = static_cast<size_t>(h->acq_windows);
     const AcqLayout L = acq_layout(cap, ib);
     unsigned char* W = h->d_acq_ws;
@@ -1434,31 +1504,189 @@ int ria_gpu_rx_acquire_batch(ria_gpu_handle h, const float* samples_dev, int64_t
     A.next = lists[0];
     hipLaunchKernelGGL(acq_plan_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A);
     HIP_TRY(h, hipGetLastError());
-    A.info_c = W + L.info; A.dst_c = reinterpret_cast<const ria_decode_status*>(W + L.dst);
-    A.fst_c = reinterpret_cast<const ria_frame_status*>(W + L.fst);
     A.info_bytes = static_cast<int>(ib); A.info_out = info_out_dev; A.dst_out = decode_status_dev; A.fst_out = demod_status_dev;
-    const uint32_t dflags = flags & ~RIA_ACQ_NO_TIMING_RETRY;
-    // 3./4. rounds: round 0 runs every accepted window at its primary candidate, round r >= 1 the windows whose previous
-    // candidate decoded nothing at their next candidate that fits; at most 8 recovery rounds (each advances every window
-    // it holds by at least one of the 8 deltas)
-    for (int round = 0;; ++round) {
-        HIP_TRY(h, hipMemcpyAsync(h->p_acq_ctl, A.ctl, sizeof(AcqCtl), hipMemcpyDeviceToHost, s));
+    return acq_run_rounds(h, "ria_gpu_rx_acquire_batch", samples_dev, A, L, n_windows, flags, s);
+}
+
+// ------------------------------------------------------------------------------------------------ burst groups + continuation
+static_assert(sizeof(ria_burst_result) == 64, "ria_burst_result is 64 bytes (include/ria_gpu.h)");
+static_assert(offsetof(ria_burst_result, cfo_hz) == 20 && offsetof(ria_burst_result, delta) == 24 && offsetof(ria_burst_result, mode) == 28 &&
+              offsetof(ria_burst_result, stop) == 31 && offsetof(ria_burst_result, reserved) == 32, "ria_burst_result field offsets");
+
+// layout of the burst workspace for n windows and groups of N frames (offsets from d_burst_ws)
+struct BurstLayout {
+    size_t acq0, info0, dst0, fst0, cwin0, list[4], gfst, gpos, done, ctl, gllr, dec_in, dec_info, dec_dst, total;
+};
+static BurstLayout burst_layout(size_t n, size_t N, size_t info_bytes, size_t llrs) {
+    BurstLayout L{};
+    size_t o = 0;
+    L.acq0 = o; o = up256(o + n * sizeof(ria_acq_result));
+    L.info0 = o; o = up256(o + n * info_bytes);
+    L.dst0 = o; o = up256(o + n * sizeof(ria_decode_status));
+    L.fst0 = o; o = up256(o + n * sizeof(ria_frame_status));
+    L.cwin0 = o; o = up256(o + n * sizeof(uint32_t));
+    for (int q = 0; q < 4; ++q) { L.list[q] = o; o = up256(o + n * (sizeof(uint64_t) + sizeof(ria_frame_meta) + sizeof(uint32_t) + 1)); }
+    L.gfst = o; o = up256(o + n * sizeof(ria_frame_status));
+    L.gpos = o; o = up256(o + n * kBurstMaxGroup * sizeof(uint32_t));
+    L.done = o; o = up256(o + n * sizeof(uint32_t));
+    L.ctl = o; o = up256(o + sizeof(BurstCtl));
+    L.gllr = o; o = up256(o + n * N * llrs * sizeof(float));
+    L.dec_in = o; o = up256(o + n * N * kBurstFrameBits * sizeof(float));
+    L.dec_info = o; o = up256(o + n * N * info_bytes);
+    L.dec_dst = o; o = up256(o + n * N * sizeof(ria_decode_status));
+    L.total = o;
+    return L;
+}
+static BurstList burst_list(unsigned char* base, size_t n) {   // the four arrays of one list, widest first
+    BurstList l;
+    l.offset = reinterpret_cast<uint64_t*>(base);
+    l.meta = reinterpret_cast<ria_frame_meta*>(base + n * sizeof(uint64_t));
+    l.window = reinterpret_cast<uint32_t*>(base + n * (sizeof(uint64_t) + sizeof(ria_frame_meta)));
+    l.keep = base + n * (sizeof(uint64_t) + sizeof(ria_frame_meta) + sizeof(uint32_t));
+    return l;
+}
+
+int ria_gpu_rx_burst_batch(ria_gpu_handle h, const float* samples_dev, int64_t stride, int search_len, int window_len,
+                           int n_windows, int group_size, const ria_acq_params* params_dev, uint32_t flags,
+                           uint8_t* info_out_dev, ria_decode_status* decode_status_dev, ria_burst_result* burst_dev,
+                           ria_frame_status* demod_status_dev, float* cfo_used_dev, float* rms_dev, void* stream) {
+    if (!h) return RIA_ERR_INVALID;
+    const uint32_t known_flags = RIA_DECODE_FULL | RIA_DECODE_NO_CHANNEL_DEINTERLEAVE | RIA_ACQ_NO_TIMING_RETRY | RIA_BURST_INTERLEAVE | RIA_BURST_NO_CONTINUE;
+    if (n_windows < 0 || search_len < 0 || window_len < search_len || stride < window_len || (flags & ~known_flags) != 0 ||
+        group_size < 2 || group_size > kBurstMaxGroup)
+        return fail(h, RIA_ERR_INVALID, "ria_gpu_rx_burst_batch: bad argument (0 <= search_len <= window_len <= stride; group_size 2..8; flags: RIA_DECODE_*, RIA_ACQ_NO_TIMING_RETRY and RIA_BURST_* only)");
+    if (n_windows == 0) return RIA_OK;
+    if (!samples_dev || !params_dev || !info_out_dev || !decode_status_dev || !burst_dev)
+        return fail(h, RIA_ERR_INVALID, "ria_gpu_rx_burst_batch: null pointer");
+    if (static_cast<size_t>(n_windows) * ((flags & RIA_BURST_INTERLEAVE) ? static_cast<size_t>(group_size) : 1) > static_cast<size_t>(INT32_MAX / 8))
+        return fail(h, RIA_ERR_INVALID, "ria_gpu_rx_burst_batch: n_windows * group_size too large");   // before anything is sized or allocated
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = lts_prepare(h)) return rc;
+    const size_t n = static_cast<size_t>(n_windows), N = static_cast<size_t>(group_size), ib = static_cast<size_t>(h->geo.info_bytes_per_frame);
+    const size_t llrs = static_cast<size_t>(h->geo.llrs_per_frame);
+    const bool interleave = (flags & RIA_BURST_INTERLEAVE) != 0;
+    // every workspace grows here, before anything of this call is in flight (an earlier call has ended on a stream sync)
+    if (int rc = acq_ensure_ws(h, n_windows)) return rc;
+    const BurstLayout B = burst_layout(n, interleave ? N : 0, ib, llrs);
+    if (B.total > h->burst_bytes) {
+        if (h->d_burst_ws) (void)hipFree(h->d_burst_ws);
+        h->d_burst_ws = nullptr; h->burst_bytes = 0;
+        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&h->d_burst_ws), B.total));
+        h->burst_bytes = B.total;
+    }
+    if (!h->p_burst_ctl) HIP_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&h->p_burst_ctl), sizeof(BurstCtl), hipHostMallocDefault));
+    {
+        const int dec_frames = static_cast<int>(n * (interleave ? N : 1));
+        hipError_t e = ensure_decode_ws(h, dec_frames);
+        if (e == hipSuccess && (flags & RIA_DECODE_CRC_RECOVER)) e = ensure_recovery_ws(h, std::max(dec_frames, h->cfg.max_batch), false);
+        if (e != hipSuccess) return fail(h, RIA_ERR_HIP, "burst workspace: %s", hipGetErrorString(e));
+    }
+    const AcqLayout L = acq_layout(static_cast<size_t>(h->acq_windows), ib);
+    unsigned char* W = h->d_acq_ws;
+    unsigned char* V = h->d_burst_ws;
+    HIP_TRY(h, hipMemsetAsync(info_out_dev, 0, n * kBurstSlots * ib, s));
+    HIP_TRY(h, hipMemsetAsync(decode_status_dev, 0, n * kBurstSlots * sizeof(ria_decode_status), s));
+    if (demod_status_dev) HIP_TRY(h, hipMemsetAsync(demod_status_dev, 0, n * kBurstSlots * sizeof(ria_frame_status), s));
+    if (cfo_used_dev) HIP_TRY(h, hipMemsetAsync(cfo_used_dev, 0, n * kBurstSlots * sizeof(float), s));
+    if (rms_dev) HIP_TRY(h, hipMemsetAsync(rms_dev, 0, n * kBurstSlots * sizeof(float), s));
+    HIP_TRY(h, hipMemsetAsync(V + B.info0, 0, B.cwin0 - B.info0, s));   // frame-0 bytes, decode and demod status rows
+
+    // 1. LTS detection with each window's threshold and known CFO
+    LtsArgs S{};
+    S.samples = samples_dev; S.stride = stride; S.buf_len = search_len; S.n_buffers = n_windows;
+    S.known_cfo = &params_dev->known_cfo_hz; S.threshold_dev = &params_dev->detect_threshold;
+    S.param_stride = static_cast<int>(sizeof(ria_acq_params) / sizeof(float));
+    S.hilbert = static_cast<const float*>(h->d_hilbert65);
+    S.out = reinterpret_cast<ria_lts_result*>(W + L.lts);
+    hipLaunchKernelGGL(lts_sync_kernel, dim3(n_windows), dim3(kLtsThreads), lts_lds_bytes(), s, S);
+    // 2. acceptance, modes and the two round-0 lists
+    BurstArgs A{};
+    A.samples = samples_dev; A.stride = stride; A.n_windows = n_windows; A.window_len = window_len;
+    A.frame_samples = h->geo.frame_samples; A.group_size = group_size; A.flags = flags;
+    A.lts = S.out; A.params = params_dev; A.res = burst_dev;
+    A.ctl = reinterpret_cast<BurstCtl*>(V + B.ctl);
+    A.acq_ctl = reinterpret_cast<AcqCtl*>(W + L.ctl);
+    A.acq_first = acq_list(W + L.list[0], static_cast<size_t>(h->acq_windows));
+    A.acq0 = reinterpret_cast<ria_acq_result*>(V + B.acq0);
+    A.info0 = V + B.info0; A.dst0 = reinterpret_cast<const ria_decode_status*>(V + B.dst0);
+    A.fst0 = reinterpret_cast<const ria_frame_status*>(V + B.fst0);
+    A.c_win0 = reinterpret_cast<uint32_t*>(V + B.cwin0);
+    A.g_cur = burst_list(V + B.list[0], n); A.c_cur = burst_list(V + B.list[1], n);
+    A.g_stage = burst_list(V + B.list[2], n); A.c_stage = burst_list(V + B.list[3], n);
+    A.g_fst = reinterpret_cast<const ria_frame_status*>(V + B.gfst);
+    A.info_bytes = static_cast<int>(ib);
+    A.info_out = info_out_dev; A.dst_out = decode_status_dev; A.fst_out = demod_status_dev; A.cfo_used = cfo_used_dev; A.rms = rms_dev;
+    A.gpos = reinterpret_cast<uint32_t*>(V + B.gpos); A.done = reinterpret_cast<uint32_t*>(V + B.done);
+    A.gllr = reinterpret_cast<const float*>(V + B.gllr); A.llr_stride = static_cast<int>(llrs);
+    A.dec_in = reinterpret_cast<float*>(V + B.dec_in); A.dec_info = V + B.dec_info;
+    A.dec_dst = reinterpret_cast<const ria_decode_status*>(V + B.dec_dst);
+    hipLaunchKernelGGL(burst_plan_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A);
+    HIP_TRY(h, hipGetLastError());
+    const uint32_t dflags = flags & (RIA_DECODE_FULL | RIA_DECODE_NO_CHANNEL_DEINTERLEAVE);
+    float* gllr = reinterpret_cast<float*>(V + B.gllr);
+    auto read_ctl = [&]() -> int {
+        HIP_TRY(h, hipMemcpyAsync(h->p_burst_ctl, A.ctl, sizeof(BurstCtl), hipMemcpyDeviceToHost, s));
         HIP_TRY(h, hipStreamSynchronize(s));
-        if (h->p_acq_ctl->fault) return fail(h, RIA_ERR_HIP, "decode work-queue fault in round %d: no window of this call was decoded", round - 1);
-        const int n_list = static_cast<int>(h->p_acq_ctl->n_list);
-        if (n_list == 0) break;
-        if (n_list > n_windows || round >= kAcqCandidates) return fail(h, RIA_ERR_HIP, "ria_gpu_rx_acquire_batch: work list of round %d broke its bound (%d)", round, n_list);
-        A.cur = lists[round & 1];
-        A.next = lists[(round + 1) & 1];
-        A.n_cur = n_list;
-        A.round = round;
-        A.retry = !(flags & RIA_ACQ_NO_TIMING_RETRY) && round + 1 < kAcqCandidates;
-        int rc = ria_gpu_rx_batch(h, samples_dev, A.cur.offset, A.cur.meta, n_list, dflags, W + L.info,
-                                  reinterpret_cast<ria_decode_status*>(W + L.dst), nullptr, reinterpret_cast<ria_frame_status*>(W + L.fst), s);
-        if (rc != RIA_OK) return rc;
-        hipLaunchKernelGGL(acq_scatter_kernel, dim3(std::min((n_list + 3) / 4, 4096)), dim3(256), 0, s, A);
-        hipLaunchKernelGGL(acq_next_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A);
+        if (h->p_burst_ctl->fault) return fail(h, RIA_ERR_HIP, "ria_gpu_rx_burst_batch: decode work-queue fault: no window of this call was decoded");
+        return RIA_OK;
+    };
+    // demodulates the group list's frames as physical frame f: row i of the list writes soft-bit row i * N + f
+    auto demod_groups = [&](int n_g, int f) -> int {
+        return demod_batch_slot(h, samples_dev, A.g_cur.offset, A.g_cur.meta, n_g, gllr + static_cast<size_t>(f) * llrs,
+                                reinterpret_cast<ria_frame_status*>(V + B.gfst), s, 0, static_cast<int>(N * llrs));
+    };
+    if (int rc = read_ctl()) return rc;
+    int n_g = static_cast<int>(h->p_burst_ctl->n_group), n_c = static_cast<int>(h->p_burst_ctl->n_cont);
+    if (n_g + n_c > n_windows || (n_g && !interleave)) return fail(h, RIA_ERR_HIP, "ria_gpu_rx_burst_batch: round-0 lists broke their bound (%d, %d)", n_g, n_c);
+    // 3. frame 0: the groups' first frames are demodulated, the other windows go through ria_gpu_rx_acquire_batch's rounds
+    if (n_g) { if (int rc = demod_groups(n_g, 0)) return rc; }
+    if (n_c) {
+        AcqArgs Q{};
+        Q.lts = S.out; Q.params = params_dev; Q.n_windows = n_windows; Q.window_len = window_len;
+        Q.frame_samples = h->geo.frame_samples; Q.stride = stride; Q.acq = A.acq0; Q.ctl = A.acq_ctl;
+        Q.info_bytes = static_cast<int>(ib); Q.info_out = V + B.info0; Q.dst_out = reinterpret_cast<ria_decode_status*>(V + B.dst0);
+        Q.fst_out = reinterpret_cast<ria_frame_status*>(V + B.fst0);
+        if (int rc = acq_run_rounds(h, "ria_gpu_rx_burst_batch", samples_dev, Q, L, n_windows, flags, s)) return rc;
+    }
+    // 4. rounds: round f runs physical frame f of the windows still live; a group needs rounds 1 .. group_size - 1, a
+    // continuation at most rounds 1 .. 8, and the step after the last of them lists nothing
+    int n_done = 0;
+    for (int round = 1; n_g + n_c > 0; ++round) {
+        if (round > kBurstSlots) return fail(h, RIA_ERR_HIP, "ria_gpu_rx_burst_batch: round %d is past the bound (%d, %d)", round, n_g, n_c);
+        A.n_g = n_g; A.n_c = n_c; A.round = round; A.first = round == 1;
+        if (round == 1) { A.c_fst = A.fst0; A.c_dst = A.dst0; A.c_info = A.info0; }
+        else {
+            A.c_fst = reinterpret_cast<const ria_frame_status*>(W + L.fst); A.c_dst = reinterpret_cast<const ria_decode_status*>(W + L.dst);
+            A.c_info = W + L.info;
+        }
+        hipLaunchKernelGGL(burst_step_kernel, dim3((n_g + n_c + kBurstStepWaves - 1) / kBurstStepWaves), dim3(64 * kBurstStepWaves), 0, s, A);
+        hipLaunchKernelGGL(burst_list_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A);
         HIP_TRY(h, hipGetLastError());
+        if (int rc = read_ctl()) return rc;
+        const int ng2 = static_cast<int>(h->p_burst_ctl->n_group), nc2 = static_cast<int>(h->p_burst_ctl->n_cont);
+        n_done = static_cast<int>(h->p_burst_ctl->n_done);
+        if (ng2 > n_g || nc2 > n_c || n_done > n_windows || (ng2 && round >= group_size))
+            return fail(h, RIA_ERR_HIP, "ria_gpu_rx_burst_batch: lists of round %d broke their bound (%d, %d, %d)", round, ng2, nc2, n_done);
+        n_g = ng2; n_c = nc2;
+        if (n_g) { if (int rc = demod_groups(n_g, round)) return rc; }
+        if (n_c) {
+            int rc = ria_gpu_rx_batch(h, samples_dev, A.c_cur.offset, A.c_cur.meta, n_c, dflags, W + L.info,
+                                      reinterpret_cast<ria_decode_status*>(W + L.dst), nullptr, reinterpret_cast<ria_frame_status*>(W + L.fst), s);
+            if (rc != RIA_OK) return rc;
+        }
+    }
+    // 5. complete groups: de-interleave into one decode batch, decodeFixedFrame on every logical frame, scatter
+    if (n_done) {
+        A.n_done = n_done;
+        const long long items = static_cast<long long>(n_done) * group_size * 324;
+        hipLaunchKernelGGL(burst_gather_kernel, dim3(static_cast<unsigned>(std::min<long long>((items + 255) / 256, 16384))), dim3(256), 0, s, A);
+        int rc = launch_decode(h, A.dec_in, kBurstFrameBits, n_done * group_size, dflags, V + B.dec_info,
+                               reinterpret_cast<ria_decode_status*>(V + B.dec_dst), s);
+        if (rc != RIA_OK) return rc;
+        hipLaunchKernelGGL(burst_scatter_kernel, dim3(std::min((n_done * group_size + 3) / 4, 4096)), dim3(256), 0, s, A);
+        HIP_TRY(h, hipGetLastError());
+        if (int rc2 = read_ctl()) return rc2;
     }
     return RIA_OK;
 }

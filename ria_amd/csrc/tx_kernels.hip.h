@@ -198,11 +198,17 @@ __device__ __forceinline__ float2 map_bits(uint32_t bits, int mod) {  // modulat
     }
 }
 
+constexpr int kTxCodedBytes = 324;   // 4 codewords of 648 bits
+
 // One workgroup per frame.  LDS: 4 IFFT tiles + bit stream + differential state.
+// kMode 0: serialized frame -> samples.  The other two split it at the coded bytes (324 per frame, MSB first, channel
+// interleaved: what encodeFixedFrame returns), where the burst interleaver works (streaming_encoder.cpp:302-389):
+// kMode 1 stops there and writes them to coded_out, kMode 2 starts there (`info` holds coded bytes).
+template <int kMode>
 __global__ __launch_bounds__(256) void tx_frames_kernel(const TxConst* __restrict__ T, const float2* __restrict__ tw,
                                                         const float2* __restrict__ nco, const uint8_t* __restrict__ info,
                                                         int n_frames, float peak, int frame_samples,
-                                                        float* __restrict__ out) {
+                                                        float* __restrict__ out, uint8_t* __restrict__ coded_out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float2* tiles = reinterpret_cast<float2*>(smem);
     uint8_t* bits = reinterpret_cast<uint8_t*>(tiles + 4 * kFftBufFloats2);   // [2592] interleaved coded bits
@@ -211,7 +217,10 @@ __global__ __launch_bounds__(256) void tx_frames_kernel(const TxConst* __restric
     float* red = reinterpret_cast<float*>(dstate + 64 * 64);                  // [8] reduction scratch
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, frame = blockIdx.x;
     const int k = T->k, m = T->m, bpc = T->bytes_per_cw, mod = T->mod;
-    const uint8_t* fi = info + static_cast<size_t>(frame) * 4 * bpc;
+    const uint8_t* fi = info + static_cast<size_t>(frame) * (kMode == 2 ? kTxCodedBytes : 4 * bpc);
+    if constexpr (kMode == 2) {
+        for (int idx = tid; idx < 2592; idx += 256) bits[idx] = (fi[idx >> 3] >> (7 - (idx & 7))) & 1;
+    } else {
     // ---- LDPC encode: information bits, then parity[i] = XOR of the information bits in check i
     for (int idx = tid; idx < 4 * 648; idx += 256) {
         int cw = idx / 648, j = idx - cw * 648;
@@ -228,7 +237,16 @@ __global__ __launch_bounds__(256) void tx_frames_kernel(const TxConst* __restric
     }
     __syncthreads();
     for (int idx = tid; idx < 4 * 648; idx += 256) bits[T->scatter[idx]] = cwbits[idx];
+    }
     __syncthreads();
+    if constexpr (kMode == 1) {
+        for (int b = tid; b < kTxCodedBytes; b += 256) {
+            uint32_t v = 0;
+            for (int q = 0; q < 8; ++q) v = (v << 1) | bits[8 * b + q];
+            coded_out[static_cast<size_t>(frame) * kTxCodedBytes + b] = static_cast<uint8_t>(v);
+        }
+        return;
+    }
     // ---- differential pre-pass (sequential over symbols, parallel over carriers)
     const int n_sym = 2 + T->n_data_symbols, bps = T->bits_per_symbol, bcar = T->bits_per_carrier;
     const bool diff = (mod == RIA_MOD_DBPSK || mod == RIA_MOD_DQPSK || mod == RIA_MOD_D8PSK);
@@ -307,16 +325,21 @@ inline void launch_make_frames(const TxConst* T, const uint16_t* crc_bit, const 
     hipLaunchKernelGGL(make_frames_kernel, dim3(n_frames), dim3(64), 0, s, T, crc_bit, crc_init, seed, first_seq,
                        n_frames, out);
 }
-inline void launch_tx(const TxConst* T, const float2* tw, const float2* nco, const uint8_t* info, int n_frames,
-                      float peak, const ria_gpu_geometry& g, float* out, hipStream_t s) {
+template <int kMode>
+inline void launch_tx_mode(const TxConst* T, const float2* tw, const float2* nco, const uint8_t* in, int n_frames,
+                           float peak, const ria_gpu_geometry& g, float* out, uint8_t* coded_out, hipStream_t s) {
     static bool attr = false;
     if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(tx_frames_kernel),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(tx_frames_kernel<kMode>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, tx_lds_bytes());
         attr = true;
     }
-    hipLaunchKernelGGL(tx_frames_kernel, dim3(n_frames), dim3(256), tx_lds_bytes(), s, T, tw, nco, info, n_frames, peak,
-                       g.frame_samples, out);
+    hipLaunchKernelGGL(tx_frames_kernel<kMode>, dim3(n_frames), dim3(256), tx_lds_bytes(), s, T, tw, nco, in, n_frames, peak,
+                       g.frame_samples, out, coded_out);
+}
+inline void launch_tx(const TxConst* T, const float2* tw, const float2* nco, const uint8_t* info, int n_frames,
+                      float peak, const ria_gpu_geometry& g, float* out, hipStream_t s) {
+    launch_tx_mode<0>(T, tw, nco, info, n_frames, peak, g, out, nullptr, s);
 }
 
 // ---------------------------------------------------------------- channel

@@ -182,6 +182,22 @@ class RxEngine:
         self._check(self.lib.ria_gpu_tx_batch(self.h, _ptr(info), n, float(peak), _ptr(s), _stream_ptr()))
         return s
 
+    def encode_frames(self, info):
+        """encodeFixedFrame alone: info uint8 [n, info_bytes] -> coded uint8 [n, 324] (channel interleaved)."""
+        n = info.shape[0]
+        assert info.dtype == torch.uint8 and info.is_contiguous() and info.shape[1] == self.geo.info_bytes_per_frame
+        coded = torch.empty((n, 324), dtype=torch.uint8, device=self.device)
+        self._check(self.lib.ria_gpu_encode_frames_batch(self.h, _ptr(info), n, _ptr(coded), _stream_ptr()))
+        return coded
+
+    def tx_coded(self, coded, peak=0.8):
+        """The modulator on coded bytes (uint8 [n, 324], e.g. burst_interleave's output) -> samples [n, frame_samples]."""
+        n = coded.shape[0]
+        assert coded.dtype == torch.uint8 and coded.is_contiguous() and coded.shape[1] == 324
+        s = torch.empty((n, self.geo.frame_samples), dtype=torch.float32, device=self.device)
+        self._check(self.lib.ria_gpu_tx_coded_batch(self.h, _ptr(coded), n, float(peak), _ptr(s), _stream_ptr()))
+        return s
+
     def channel_(self, samples, kind, snr_db, seed, first_frame=0):
         n = samples.shape[0]
         assert samples.dtype == torch.float32 and samples.is_contiguous()
@@ -275,6 +291,52 @@ class RxEngine:
                                                       _ptr(info), _ptr(st), _ptr(acq), _ptr(fst), _stream_ptr()))
         res = self._status_array(acq, self.ACQ_RESULT)
         return (info, st, res, fst) if want_demod_status else (info, st, res)
+
+    BURST_RESULT = np.dtype([("detected", "<i4"), ("accepted", "<i4"), ("sync_start", "<i4"), ("frame_start", "<i4"),
+                             ("correlation", "<f4"), ("cfo_hz", "<f4"), ("delta", "<i2"), ("candidates", "u1"),
+                             ("burst_interleaved", "u1"), ("mode", "u1"), ("frames", "u1"), ("frames_decoded", "u1"),
+                             ("stop", "u1"), ("reserved", "<i4", 8)])
+
+    def rx_burst(self, windows, search_len, group_size=4, known_cfo=None, detect_threshold=0.15, min_confidence=None, abs_base=None,
+                 flags=capi.DECODE_FULL, interleave=True, continuation=True, retry=True, window_len=None, sync=True):
+        """Burst groups and burst continuation from capture windows (ria_gpu_rx_burst_batch): what rx_acquire does for the
+        first frame of each row of `windows` (float32 [n, stride] on the device; window_len <= stride samples of a row are
+        the window), then, with `interleave`, a marked window's group of group_size physical frames (energy gate, CFO chain,
+        burst de-interleave, decodeFixedFrame per logical frame) and, for every other accepted window, up to 8 continuation
+        blocks behind a successfully decoded data frame (`continuation`).  Parameters as rx_acquire.
+        Returns a dict: info uint8 [n, 9, info_bytes], decode_status / frame_status structured [n, 9], cfo_used / rms
+        float32 [n, 9], result structured [n] (BURST_RESULT).  sync=False leaves the arrays on the device (torch tensors,
+        raw bytes for the structured ones) and does not wait."""
+        from .acquire import lts_min_confidence
+        n, stride = windows.shape
+        window_len = stride if window_len is None else int(window_len)
+        assert windows.dtype == torch.float32 and windows.is_contiguous()
+        if min_confidence is None:
+            min_confidence = lts_min_confidence(self.modulation)
+        p = np.zeros(n, self.ACQ_PARAMS)
+        p["known_cfo_hz"] = 0.0 if known_cfo is None else known_cfo
+        p["detect_threshold"] = detect_threshold
+        p["min_confidence"] = min_confidence
+        p["abs_base"] = 0 if abs_base is None else abs_base
+        params = torch.from_numpy(p.view(np.uint8).reshape(n, 32)).to(self.device)
+        S = capi.BURST_MAX_FRAMES
+        info = torch.empty((n, S, self.geo.info_bytes_per_frame), dtype=torch.uint8, device=self.device)
+        st = torch.empty((n, S, 20), dtype=torch.uint8, device=self.device)
+        res = torch.empty((n, 64), dtype=torch.uint8, device=self.device)
+        fst = torch.empty((n, S, 32), dtype=torch.uint8, device=self.device)
+        cfo = torch.empty((n, S), dtype=torch.float32, device=self.device)
+        rms = torch.empty((n, S), dtype=torch.float32, device=self.device)
+        fl = int(flags) | (0 if retry else capi.ACQ_NO_TIMING_RETRY) | (capi.BURST_INTERLEAVE if interleave else 0) | \
+            (0 if continuation else capi.BURST_NO_CONTINUE)
+        self._check(self.lib.ria_gpu_rx_burst_batch(self.h, _ptr(windows), stride, int(search_len), window_len, n, int(group_size),
+                                                    _ptr(params), fl, _ptr(info), _ptr(st), _ptr(res), _ptr(fst), _ptr(cfo), _ptr(rms),
+                                                    _stream_ptr()))
+        if not sync:
+            return dict(info=info, decode_status=st, result=res, frame_status=fst, cfo_used=cfo, rms=rms)
+        torch.cuda.synchronize()
+        return dict(info=info.cpu().numpy(), decode_status=self._status_array(st, self.DECODE_STATUS).reshape(n, S),
+                    result=self._status_array(res, self.BURST_RESULT), frame_status=self._status_array(fst, self.FRAME_STATUS).reshape(n, S),
+                    cfo_used=cfo.cpu().numpy(), rms=rms.cpu().numpy())
 
     COX_RESULT = np.dtype([("found", "<i4"), ("start_sample", "<i4"), ("cfo_hz", "<f4"), ("noise_floor", "<f4"),
                            ("sts_position", "<i4"), ("reserved", "<i4", 3)])
