@@ -505,7 +505,7 @@ struct FastDecodeArgs {
     uint8_t* res_bytes;      // [4*n_frames][5][bytes_per_cw]
     CascadeWin* win;         // [4*n_frames]  result of the best successful cascade attempt so far, per entry
     float* staged;           // [4*n_frames][kStageFloats]  de-interleaved decoder input of list1 entry i, in register order
-    unsigned int* l1idx;     // [4*n_frames]  codeword -> its list1 index (valid for listed codewords only)
+    unsigned int* l1idx;     // [4*n_frames]  codeword -> its list1 index, kNotListed for the others (written by fast_mark_kernel when a retry flag is set)
     unsigned int* l1hash;    // [4*n_frames]  list1 entry -> hash of its first 16 soft bits (seed of the perturbation RNG)
     uint32_t* seed_ws;       // [cascade grid][kSeedWsWords]  seeded mt19937 states of the attempt group a cascade workgroup is on (this stream slot's)
 };
@@ -546,6 +546,19 @@ __device__ inline void fast_load_staged(FastState<S>& st, const float* __restric
     for (int r = 0; r < S::NR; ++r) st.lp[r] = src[(S::NC + r) * 64 + lane];
 }
 
+// Record the outcome of decoding codeword fc with factor index f (its bytes were stored by fast_pack).  The state is an
+// agent-scope atomic store because waves of the running fast_phase0_kernel read it (their skip test).  They read the
+// state ONLY: bytes and iteration counts are first read by later kernels, for which the kernel boundary orders every
+// store, so nothing orders the stores here.  A release fence in front of the state (a reader of state == 2 inside the
+// kernel could then read the result too) was measured: the write-back it forces per unit cost 4.6 % of the bench step
+// (DESIGN.md section 4 (27)).
+__device__ inline void fast_publish(CwResult* res, unsigned fc, int f, bool ok, int it, int lane) {
+    if (lane == 0) {
+        res[fc].iters[f] = static_cast<uint16_t>(it);
+        __hip_atomic_store(&res[fc].state[f], static_cast<uint8_t>(ok ? 2 : 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
 // decode codeword `fc` (= frame*4 + cw) with factor index f and record the result; staged != nullptr: the
 // codeword's de-interleaved input (fast_stage_kernel) instead of the gather from the frame
 template <class S, int NCV = S::kCv>
@@ -558,7 +571,7 @@ __device__ inline void fast_unit(FastState<S>& st, const FastDecodeArgs& A, unsi
     int it = fast_decode<S, NCV>(st, c, lds, kFactors[f], c.max_iter, lane, &ok);
     if (ok) fast_pack(st, c, lds, A.res_bytes + (static_cast<size_t>(fc) * kNumFactors + f) * c.bytes_per_cw,
                       c.bytes_per_cw, lane);
-    if (lane == 0) { A.res[fc].state[f] = ok ? 2 : 1; A.res[fc].iters[f] = static_cast<uint16_t>(it); }
+    fast_publish(A.res, fc, f, ok, it, lane);
 }
 
 // ------------------------------------------------------------------------------------------------ kernel P
@@ -585,6 +598,8 @@ __global__ __launch_bounds__(64) void fast_primary_kernel(FastDecodeArgs A) {
     fast_unit<S, RIA_PRIMARY_NCV>(st, A, smem, 4u * frame + cw, 0, lane);
 }
 
+constexpr unsigned int kNotListed = 0xFFFFFFFFu;
+
 // per frame: every codeword at or after the first one whose first decode failed may need the other
 // four factors (phase 0 itself, or a first decode that inherits factor 0.875 through the chain)
 __global__ void fast_mark_kernel(FastDecodeArgs A) {
@@ -599,6 +614,8 @@ __global__ void fast_mark_kernel(FastDecodeArgs A) {
             const unsigned i = atomicAdd(&A.ctl->n_list1, 1u);
             A.list1[i] = fc;
             A.l1idx[fc] = i;
+        } else {
+            A.l1idx[fc] = kNotListed;   // recovery_fill_kernel: no staged copy of this codeword
         }
     }
 }
@@ -651,12 +668,23 @@ __global__ __launch_bounds__(256) void fast_stage_kernel(FastDecodeArgs A) {
 
 // ------------------------------------------------------------------------------------------------ kernel Z
 // persistent single-wave workgroups pull (list1 entry, factor 1..4) units from an atomic queue (ctl->next_z): the
-// list length is only known on the device, so the grid is a fixed size; 80-iteration units and 5-iteration units mix
+// list length is only known on the device, so the grid is a fixed size; 80-iteration units and 5-iteration units mix.
+// The reference walks the factors 0.875, 0.75, 0.625, 0.5 of a codeword and stops at the first that converges
+// (frame_v2.cpp:1359-1470), so fast_chain_kernel reads state[1..t*] only, t* = the first converging factor.  The queue
+// is therefore factor-major (unit u: factor t = 1 + u / n_list1 of entry u % n_list1: every entry's 0.875 unit is
+// handed out before any 0.75 unit), and a unit for t > 1 does nothing once one of state[1..t-1] has been published as
+// converged.  As in the cascade (best[e]) no unit waits: where an earlier factor is still in flight the unit runs, and
+// its table entry is one nobody reads or one the fallback wants anyway.  A slot that was skipped stays 0 = "not
+// computed", which is what recovery_fill_kernel completes for the frames whose fallback stage reads it.
+// RIA_EAGER_FACTORS=1 (build-time) restores the entry-major queue that decodes all four factors of every entry.
+#ifndef RIA_EAGER_FACTORS
+#define RIA_EAGER_FACTORS 0
+#endif
 template <class S>
 __global__ __launch_bounds__(64) void fast_phase0_kernel(FastDecodeArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x;
-    const unsigned total = A.ctl->n_list1 * 4u;
+    const unsigned n_list1 = A.ctl->n_list1, total = n_list1 * 4u;
     if (blockIdx.x >= total) return;
     FastState<S> st;
     fast_load_tables(st, A.c, smem, lane);
@@ -666,7 +694,22 @@ __global__ __launch_bounds__(64) void fast_phase0_kernel(FastDecodeArgs A) {
         unsigned u = atomicAdd(&A.ctl->next_z, lane == 0 ? 1u : 0u);
         u = __builtin_amdgcn_readfirstlane(u);   // scalar: the loop control and every address derived from u stay uniform
         if (u >= total) break;
-        fast_unit<S>(st, A, smem, A.list1[u >> 2], 1 + static_cast<int>(u & 3u), lane, A.staged + static_cast<size_t>(u >> 2) * kStageFloats);
+#if RIA_EAGER_FACTORS
+        const unsigned entry = u >> 2;
+        const int t = 1 + static_cast<int>(u & 3u);
+        const unsigned fc = A.list1[entry];
+#else
+        const unsigned tq = u / n_list1, entry = u - tq * n_list1;
+        const int t = 1 + static_cast<int>(tq);
+        const unsigned fc = A.list1[entry];
+        bool done = false;   // wave-uniform: every lane reads the same bytes
+        for (int k = 1; k < t; ++k) {
+            const unsigned sk = __hip_atomic_load(&A.res[fc].state[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            done = done || __builtin_amdgcn_readfirstlane(sk) == 2u;
+        }
+        if (done) continue;
+#endif
+        fast_unit<S>(st, A, smem, fc, t, lane, A.staged + static_cast<size_t>(entry) * kStageFloats);
     }
 }
 
@@ -675,6 +718,12 @@ __global__ __launch_bounds__(64) void fast_phase0_kernel(FastDecodeArgs A) {
 // ONE decoder object serves the 4 codewords in order; its factor is restored to 0.9375 only after
 // phase 0 and left at 0.875 by phases 1-2 (frame_v2.cpp:1359-1361,1412,1447,1470), so a codeword that
 // follows one that needed phase >= 1 makes its FIRST decode at 0.875.
+// Slots read, against the slots fast_phase0_kernel may skip (slot t > 1 of a listed codeword, and only where one of
+// state[1..t-1] is 2): state[0] is the primary kernel's and always there.  state[f] with f == 1 is slot 1, which is
+// never skipped, and f == 1 only follows a codeword that failed, so this codeword is listed.  The phase-0 walk below
+// reads state[1], state[2], ... in ascending order and stops at the first that is 2 (t*): each slot t it reaches has
+// state[1..t-1] != 2, the very condition under which unit t runs.  The bytes and iteration count are read for the
+// accepted slot only (0, 1 or t*).  So no slot read here can have been skipped, whatever the interleaving of the units.
 __global__ void fast_chain_kernel(FastDecodeArgs A) {
     int frame = blockIdx.x * blockDim.x + threadIdx.x;
     if (frame >= A.n_frames) return;

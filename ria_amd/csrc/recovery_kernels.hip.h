@@ -538,11 +538,16 @@ __global__ __launch_bounds__(64) void recovery_fill_kernel(RecoveryArgs R) {
         if (!((e >> (f - 1)) & 1u)) continue;
         const FastCode& c = R.d.c;
         const int lane = threadIdx.x;
-        fast_gather_llr(st, c, R.d.llr + static_cast<size_t>(fc >> 2) * R.d.llr_stride, R.d.gather, fc & 3, lane);
+        // a listed codeword (one phase 0 left slots of) has its input staged in register order: 12 coalesced loads of the same
+        // values instead of the scattered gather from the frame
+        unsigned li = kNotListed;
+        if (R.d.flags & (RIA_DECODE_PHASE0 | RIA_DECODE_PERTURB)) li = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(R.d.l1idx[fc])));
+        if (li != kNotListed) fast_load_staged(st, R.d.staged + static_cast<size_t>(li) * kStageFloats, lane);
+        else fast_gather_llr(st, c, R.d.llr + static_cast<size_t>(fc >> 2) * R.d.llr_stride, R.d.gather, fc & 3, lane);
         bool ok;
         const int it = fast_decode<S>(st, c, smem, kFactors[f], c.max_iter, lane, &ok);
         if (ok) fast_pack(st, c, smem, R.d.res_bytes + (static_cast<size_t>(fc) * kNumFactors + f) * c.bytes_per_cw, c.bytes_per_cw, lane);
-        if (lane == 0) { R.d.res[fc].state[f] = ok ? 2 : 1; R.d.res[fc].iters[f] = static_cast<uint16_t>(it); }
+        fast_publish(R.d.res, fc, f, ok, it, lane);
     }
 }
 // one workgroup per flagged frame: compact copies of everything the host stage reads
