@@ -492,8 +492,10 @@ int ria_gpu_burst_interleave_batch(ria_gpu_handle h, const uint8_t* logical_byte
  * number of windows that fail: each round demodulates and decodes only the windows still failing, each at its own next
  * candidate.  Workspaces live on the handle and grow with n_windows.
  *
- * Not covered (the caller's side or other paths): control-frame hypotheses (R1/4 fast path, CW0 peek and salvage,
- * :1268-1335, :1505-1575, :2866-2990), the weak-accept and reject-streak state (fold them into min_confidence), the PING
+ * Not covered (the caller's side or other paths): decodeFrame's control-frame hypotheses on the soft bits (the R1/4 fast
+ * path, the raw CW0 probe, the 1-CW salvage and the legacy path, :2866-3058) are ria_gpu_decode_frame_batch's, which takes
+ * the soft bits this call can return; the control-first re-demodulation with the DQPSK R1/4 profile (:1268-1344), the
+ * 1-CW peek buffer and the pending_total_cw_ escalation (:1505-1597), the weak-accept and reject-streak state (fold them into min_confidence), the PING
  * energy check, burst groups and burst continuation (ria_gpu_rx_burst_batch), chase combining, Schmidl-Cox
  * acquisition, OFDM-COX, ring-buffer wrap-around, and the +-2 Hz clamp of the reported CFO the host applies before it
  * feeds it back (:1912-1918).  MC-DPSK frames (ZC and dual-chirp acquisition, the disconnected handshake fallbacks) are
@@ -704,6 +706,88 @@ int ria_gpu_mcdpsk_acquire_batch(ria_gpu_handle h, const ria_mcdpsk_config* cfg,
                                  const ria_mcdpsk_acq_params* params_dev, uint32_t flags,
                                  uint8_t* frame_out_dev, ria_mcdpsk_acq_result* acq_dev,
                                  float* llr_out_dev /* nullable */, int llr_stride, void* stream);
+
+/* ---- RX: decodeFrame, OFDM branch (StreamingDecoder::decodeFrame, src/gui/modem/streaming_decoder.cpp:2821-3059) ----
+ * The "try both" strategy every OFDM frame's soft bits go through, statement for statement, over a batch of rows.  Row f is
+ * n_llr_dev[f] soft bits (clamped to [0, llr_stride]; NULL: llr_stride each) at llr_dev + f*llr_stride.  `rate` is the
+ * handle's code rate (connected_ ? code_rate_ : R1_4: a disconnected receiver is a handle created at RIA_RATE_1_4), bps its
+ * bits_per_symbol, apply_channel_deinterleave is true unless RIA_DECODE_NO_CHANNEL_DEINTERLEAVE is set.  A "plain decode"
+ * is codec_->decode: LDPCDecoder::decodeSoft at getRecommendedIterations(rate of that decode), min-sum factor 0.75
+ * (ldpc_decoder.cpp:44, ldpc_codec.cpp:65-77); it returns ceil(ldpc_k/8) bytes and the frame layer truncates them to that
+ * rate's bytes per codeword (the R1/3 peculiarity of ria_gpu_geometry.ldpc_k applies unchanged).
+ *   0. n_llr < 648: the default DecodeResult (success 0, counts 0, frame_type 0x10, no bytes).              RIA_DFRAME_NONE
+ *   1. R1/4 fast path (:2867-2890), only if rate != R1_4: plain decode of [0, 648) at R1/4; ok, magic 55 4C and a valid
+ *      header (parseHeader, frame_v2.cpp:1195-1253) with total_cw 1: success, 1 codeword, those 20 bytes. RIA_DFRAME_CONTROL_R14
+ *   2. raw CW0 probe (:2892-2930): plain decode of [0, 648) at `rate`, no channel de-interleave.  ok with magic: truncate,
+ *      parse; a valid header sets frame_type; total_cw 1 is a success with the truncated CW0 (RIA_DFRAME_CONTROL_CW0);
+ *      total_cw 4 sets try_frame_interleave; any other count goes to the legacy path.  Magic with an invalid header: neither
+ *      (the row ends in step 4).  Not ok or no magic: try_frame_interleave.
+ *   3. fixed frame (:2932-3010), if try_frame_interleave and n_llr >= 2592: decodeFixedFrame of the first 2592 soft bits with
+ *      the call's RIA_DECODE_* bits (RIA_DECODE_FULL is the reference); codewords_ok / codewords_failed from its four flags.
+ *      All four ok: RIA_DFRAME_FIXED; success = ria_decode_status.frame_valid; frame_data = the reassembled frame
+ *      (CodewordStatus::reassemble: 17 + payload_len + 2 bytes, or 20), frame_type = its byte 2; with success 0 the result
+ *      keeps 4 / 0 and no bytes (under RIA_DECODE_FULL a frame that does not verify comes back with all four flags cleared,
+ *      so success 0 arises only without RIA_DECODE_CRC_RECOVER).  Not all ok: robustDecodeSingleCW (:1028-1058) of [0, 648)
+ *      at R1/4 and then, if rate != R1_4, at `rate`; the first with ok, magic and a valid header with total_cw 1 gives
+ *      success, 1 / 0 and the bytes truncated to that rate's codeword (RIA_DFRAME_SALVAGE_R14 / _RATE).  Neither: step 4
+ *      with the fixed attempt's counts.
+ *   4. legacy (:3012-3058), only if the step-2 probe was ok with magic: codewords_ok = 1 while codewords_failed is NOT
+ *      reset (a count left by step 3 stays and is added to, as in the reference).  Invalid header: return
+ *      (RIA_DFRAME_BAD_HEADER).  avail_cw = n_llr / 648 < total_cw: frame_data = CW0's bytes (RIA_DFRAME_PARTIAL).  Else CW
+ *      i = 1 .. total_cw-1: soft bits [648 i, 648 (i+1)) through ChannelInterleaver(bps, 648)::deinterleave when
+ *      apply_channel_deinterleave, plain decode at `rate`; all ok: success, frame_data = reassemble() (RIA_DFRAME_LEGACY;
+ *      success 0 when a codeword failed).  A data header with total_cw 0 is undefined behaviour in the reference
+ *      (decoded[0] of an empty vector); it is treated as an invalid header, as ria_gpu_mcdpsk_acquire_batch does.
+ *   5. anything else: the result as it stands: RIA_DFRAME_FIXED_FAILED when the fixed attempt ran, else RIA_DFRAME_NONE.
+ *
+ * Arguments: 648 <= llr_stride <= 32 * 648 and frame_row >= max(4, llr_stride / 648) * bytes_per_codeword, else
+ * RIA_ERR_INVALID.  The cap of 32 codewords per row is this library's: a legacy frame that does not fit the row is
+ * RIA_DFRAME_PARTIAL by the reference's own rule.  flags: the RIA_DECODE_* bits and RIA_DECODE_NO_CHANNEL_DEINTERLEAVE,
+ * anything else is RIA_ERR_INVALID.
+ * Outputs: every row of every output is written, zero where nothing applies: result_dev; frame_out_dev rows of frame_row
+ * bytes (frame_bytes of frame_data, then zeros); decode_status_dev (nullable) and info_out_dev (nullable, 4 *
+ * bytes_per_codeword per row): the fixed attempt's status and codeword bytes, zero where it did not run.  header_total_cw
+ * is the total_cw of the valid header behind the path: 1 for the control and salvage paths, the CW0 probe's count for
+ * LEGACY / PARTIAL, 4 or 0 (CW0 probe failed) for FIXED / FIXED_FAILED, 0 otherwise.
+ * Work: each stage runs on a compact, ascending list of the rows the stages before left open (stages, iters_* and tries_*
+ * show which ran for a row), so results do not depend on scheduling.  The call synchronises its stream exactly twice for
+ * one 32-byte device-to-host read each (the length of the fixed batch; the number of legacy codeword rows); no soft bits
+ * or payloads go to the host.  A decode work-queue fault in the fixed stage fails the whole call with RIA_ERR_HIP.  A handle
+ * whose rate is not R1/4 builds its R1/4 code at the first call; all workspace lives on the handle, is grown on demand
+ * (about 11 KB per row plus the size of the soft-bit rows behind the first codeword) and is allocated before anything of
+ * the call is in flight.  Not covered: see ria_gpu_rx_acquire_batch. */
+typedef struct ria_dframe_result {      /* 32 bytes, one per row */
+    uint8_t  success;          /* DecodeResult: success, codewords_ok, codewords_failed, frame_type */
+    uint8_t  codewords_ok;
+    uint8_t  codewords_failed;
+    uint8_t  frame_type;       /* 0x10 (DecodeResult's default) when no header was parsed */
+    uint8_t  path;             /* RIA_DFRAME_*: which statement produced the result */
+    uint8_t  header_total_cw;  /* total_cw of the valid header that decided the path, 0 if none */
+    uint8_t  stages;           /* bit0 R1/4 probe ran, bit1 rate probe, bit2 decodeFixedFrame, bit3 salvage R1/4, bit4 salvage rate, bit5 legacy CW1+ */
+    uint8_t  reserved0;
+    int32_t  frame_bytes;      /* length of frame_data in the row of frame_out_dev */
+    uint16_t iters_r14;        /* lastIterations() of the two plain probes (0 if the stage did not run) */
+    uint16_t iters_cw0;
+    uint8_t  tries_r14;        /* decodes made by the two salvage decoders, 0..5 */
+    uint8_t  tries_rate;
+    uint8_t  reserved1[2];
+    int32_t  reserved[3];
+} ria_dframe_result;
+enum { RIA_DFRAME_NONE = 0, RIA_DFRAME_CONTROL_R14 = 1, RIA_DFRAME_CONTROL_CW0 = 2, RIA_DFRAME_FIXED = 3,
+       RIA_DFRAME_SALVAGE_R14 = 4, RIA_DFRAME_SALVAGE_RATE = 5, RIA_DFRAME_FIXED_FAILED = 6,
+       RIA_DFRAME_LEGACY = 7, RIA_DFRAME_PARTIAL = 8, RIA_DFRAME_BAD_HEADER = 9 };
+
+int ria_gpu_decode_frame_batch(ria_gpu_handle h, const float* llr_dev, int llr_stride, const int32_t* n_llr_dev /* nullable: llr_stride each */,
+                               int n_frames, uint32_t flags, uint8_t* frame_out_dev, int frame_row,
+                               ria_dframe_result* result_dev,
+                               ria_decode_status* decode_status_dev /* nullable: the fixed attempt's, zero where it did not run */,
+                               uint8_t* info_out_dev /* nullable: the fixed attempt's 4 * bytes_per_codeword, zero where it did not run */,
+                               void* stream);
+/* One row from host memory, staged through the handle's pinned block and stream like ria_gpu_decode_frames_host.  Soft bits
+ * beyond 32 * 648 are ignored; max_bytes must be >= max(4, min(n_llr, 32 * 648) / 648) * bytes_per_codeword, of which
+ * result_out->frame_bytes hold frame_data and the rest is zeroed. */
+int ria_gpu_decode_frame_host(ria_gpu_handle h, const float* llr_host, int n_llr, uint32_t flags, uint8_t* frame_out_host, int max_bytes,
+                              ria_dframe_result* result_out, ria_decode_status* decode_status_out /* nullable */);
 
 /* ---- debug / test hooks ----------------------------------------------------------------------- */
 /* op: 0 sinf 1 cosf 2 logf 3 atan2f(a,b) 4 hypotf(a,b) 5 a/b 6 sqrtf(a); evaluates the device

@@ -164,6 +164,25 @@ def burst_tally(out, sent):
     return np.array([row[k] for k in BURST_COUNTERS], dtype=np.int64)
 
 
+DFRAME_PATHS = ("NONE", "CONTROL_R14", "CONTROL_CW0", "FIXED", "SALVAGE_R14", "SALVAGE_RATE", "FIXED_FAILED", "LEGACY", "PARTIAL",
+                "BAD_HEADER")                      # RIA_DFRAME_* by value
+DFRAME_COUNTERS = ("rows", "success") + tuple("path_" + p for p in DFRAME_PATHS) + \
+    ("stage_r14", "stage_rate", "stage_fixed", "stage_salvage_r14", "stage_salvage_rate", "stage_legacy", "probe_iterations")
+
+
+def dframe_tally(result):
+    """Counter row (DFRAME_COUNTERS) of decode_frame's result array: rows, successes, rows per RIA_DFRAME_* path, rows each
+    stage ran for, and the iterations the two plain CW0 probes spent."""
+    row = dict.fromkeys(DFRAME_COUNTERS, 0)
+    row.update(rows=len(result), success=int((result["success"] != 0).sum()))
+    for k, name in enumerate(DFRAME_PATHS):
+        row["path_" + name] = int((result["path"] == k).sum())
+    for bit, name in enumerate(("r14", "rate", "fixed", "salvage_r14", "salvage_rate", "legacy")):
+        row["stage_" + name] = int(((result["stages"] >> bit) & 1).sum())
+    row["probe_iterations"] = int(result["iters_r14"].astype(np.int64).sum() + result["iters_cw0"].astype(np.int64).sum())
+    return np.array([row[k] for k in DFRAME_COUNTERS], dtype=np.int64)
+
+
 def run_burst_point(engine, point, base_seed, point_index, start, n, n_frames, interleaved=True, search_len=SEARCH_LEN,
                     min_confidence=None, **kw):
     """One chunk of trials of one sweep point through ria_gpu_rx_burst_batch (group_size = n_frames for interleaved

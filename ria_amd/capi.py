@@ -22,6 +22,10 @@ MACQ_SYNC_CHIRP = 0x1
 MACQ_DISCONNECTED = 0x2
 MACQ_NO_RETRY = 0x4
 MACQ_CHANNEL_INTERLEAVE = 0x8
+# RIA_DFRAME_*: which statement of decodeFrame produced a row's result (ria_dframe_result.path)
+DFRAME_PATH = {"NONE": 0, "CONTROL_R14": 1, "CONTROL_CW0": 2, "FIXED": 3, "SALVAGE_R14": 4, "SALVAGE_RATE": 5, "FIXED_FAILED": 6,
+               "LEGACY": 7, "PARTIAL": 8, "BAD_HEADER": 9}
+DFRAME_MAX_CW = 32
 
 # every symbol include/ria_gpu.h declares
 EXPORTS = [
@@ -33,6 +37,7 @@ EXPORTS = [
     "ria_gpu_rx_acquire_batch", "ria_gpu_mcdpsk_acquire_batch", "ria_gpu_rx_burst_batch", "ria_gpu_encode_frames_batch", "ria_gpu_tx_coded_batch",
     "ria_gpu_sync_cox_batch", "ria_gpu_cox_preamble", "ria_gpu_channel_exact_cfo_batch", "ria_gpu_tx_cfo_batch",
     "ria_gpu_mcdpsk_demod_host", "ria_gpu_ldpc_decode_robust_host", "ria_gpu_mcdpsk_modulate_batch",
+    "ria_gpu_decode_frame_batch", "ria_gpu_decode_frame_host",
     "ria_link_recommend", "ria_link_data_mode", "ria_link_ofdm_code_rate", "ria_link_cap_initial_rate",
 ]
 
@@ -103,6 +108,13 @@ class McAcqResult(C.Structure):
                 ("modulation", C.c_uint8), ("candidates", C.c_uint8), ("success", C.c_uint8), ("codewords_ok", C.c_uint8),
                 ("codewords_failed", C.c_uint8), ("frame_type", C.c_uint8), ("header_total_cw", C.c_int32),
                 ("frame_bytes", C.c_int32), ("n_llr", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class DframeResult(C.Structure):
+    _fields_ = [("success", C.c_uint8), ("codewords_ok", C.c_uint8), ("codewords_failed", C.c_uint8), ("frame_type", C.c_uint8),
+                ("path", C.c_uint8), ("header_total_cw", C.c_uint8), ("stages", C.c_uint8), ("reserved0", C.c_uint8),
+                ("frame_bytes", C.c_int32), ("iters_r14", C.c_uint16), ("iters_cw0", C.c_uint16), ("tries_r14", C.c_uint8),
+                ("tries_rate", C.c_uint8), ("reserved1", C.c_uint8 * 2), ("reserved", C.c_int32 * 3)]
 
 
 def macq_frame_bytes(frame_cw):
@@ -180,6 +192,8 @@ def load(build_if_needed=True):
     L.ria_gpu_rx_acquire_batch.argtypes = [vp, vp, C.c_int64, i32, i32, i32, vp, u32, vp, vp, vp, vp, vp]
     L.ria_gpu_rx_burst_batch.argtypes = [vp, vp, C.c_int64, i32, i32, i32, i32, vp, u32, vp, vp, vp, vp, vp, vp, vp]
     L.ria_gpu_mcdpsk_acquire_batch.argtypes = [vp, vp, vp, C.c_int64, i32, i32, i32, i32, vp, u32, vp, vp, vp, i32, vp]
+    L.ria_gpu_decode_frame_batch.argtypes = [vp, vp, i32, vp, i32, u32, vp, i32, vp, vp, vp, vp]
+    L.ria_gpu_decode_frame_host.argtypes = [vp, vp, i32, u32, vp, i32, vp, vp]
     L.ria_link_recommend.argtypes = [f32, f32, C.POINTER(LinkRecommendation)]
     L.ria_link_recommend.restype = None
     L.ria_link_data_mode.argtypes = [f32, i32, f32, C.POINTER(LinkRecommendation)]

@@ -958,4 +958,13 @@ inline std::vector<uint16_t> build_rx_gather(int bps, bool use_channel) {
     return t;
 }
 
+// table[i] = position, inside one codeword's 648 soft bits, of decoder input i: ChannelInterleaver(bps, 648)::deinterleave
+// (ldpc_decoder.cpp:617-625) of a single codeword, as decodeFrame's legacy path applies it; the identity without it
+inline std::vector<uint16_t> build_cw_deinterleave(int bps, bool use_channel) {
+    std::vector<uint16_t> t(kCwBits);
+    const int step = use_channel ? channel_interleaver_step(bps, kCwBits) : 1;
+    for (int i = 0; i < kCwBits; ++i) t[i] = static_cast<uint16_t>((static_cast<long>(i) * step) % kCwBits);
+    return t;
+}
+
 }  // namespace ria

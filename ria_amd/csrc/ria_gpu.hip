@@ -35,6 +35,7 @@
 #include "acquire_kernels.hip.h"
 #include "mcdpsk_acquire_kernels.hip.h"
 #include "burst_kernels.hip.h"
+#include "decode_frame_kernels.hip.h"
 
 using namespace ria;
 
@@ -112,6 +113,11 @@ struct ria_gpu {
     // ria_gpu_rx_burst_batch: frame-0 rows of the acquire rounds, the round lists, the groups' soft bits and decode batch,
     // and the control block (device + pinned mirror), grown on demand
     unsigned char* d_burst_ws = nullptr; size_t burst_bytes = 0; BurstCtl* p_burst_ctl = nullptr;
+    // ria_gpu_decode_frame_batch: the R1/4 code of a handle of another rate (built at first use), the per-codeword channel
+    // de-interleave table and the identity, and the workspace with its control block (device + pinned mirror), grown on demand
+    FastCode fast14{}; void* d_f14[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; int wave_lds14 = 0; bool have14 = false;
+    void* d_cw_perm[2] = {nullptr, nullptr};
+    unsigned char* d_df_ws = nullptr; size_t df_bytes = 0; DfCtl* p_df_ctl = nullptr;
 };
 
 namespace {
@@ -192,7 +198,10 @@ static hipError_t ensure_decode_ws(ria_gpu_handle h, int n_frames) {
         if (p_) (void)hipFree(p_);
     h->d_entries = h->d_best = h->d_list1 = nullptr; h->d_res = nullptr; h->d_res_bytes = nullptr; h->d_win = nullptr; h->d_staged = nullptr; h->d_l1idx = nullptr; h->d_l1hash = nullptr;
     hipError_t e;
-    if (!h->d_ctl && (e = hipMalloc(reinterpret_cast<void**>(&h->d_ctl), kMaxParts * sizeof(DecodeCtl))) != hipSuccess) return e;   // one per stream slot
+    if (!h->d_ctl) {   // one per stream slot; zeroed here because ria_gpu_debug_queue_fault reads the slots no call has used yet as well
+        if ((e = hipMalloc(reinterpret_cast<void**>(&h->d_ctl), kMaxParts * sizeof(DecodeCtl))) != hipSuccess) return e;
+        if ((e = hipMemset(h->d_ctl, 0, kMaxParts * sizeof(DecodeCtl))) != hipSuccess) return e;
+    }
     // the cascade's seeded RNG states: one area per workgroup of its grid and per stream slot (the parts of a batch run concurrently)
     if (!h->d_seed_ws && (e = hipMalloc(reinterpret_cast<void**>(&h->d_seed_ws), static_cast<size_t>(kMaxParts) * persist_grid_size(false) * kSeedWsWords * sizeof(uint32_t))) != hipSuccess) return e;
     if ((e = hipMalloc(reinterpret_cast<void**>(&h->d_entries), static_cast<size_t>(n_frames) * 4 * sizeof(unsigned))) != hipSuccess) return e;
@@ -404,6 +413,25 @@ static int run_crc_recovery_host(ria_gpu_handle h, const FastDecodeArgs& D, hipS
     return RIA_OK;
 }
 
+// the lane/slot assignment against LDS bank conflicts (host_tables.hpp): the layout annealed offline and shipped with the
+// library (validated against this build's H), or - RIA_BANKOPT_MOVES set, or no valid shipped layout - annealed here, once
+// per rate and process
+static CoreTables core_tables_for(int rate, const LdpcCode& code) {
+    static std::mutex mu;
+    static std::map<std::pair<int, int>, CoreTables> cache;
+    const char* mv = getenv("RIA_BANKOPT_MOVES");
+    const int moves = mv ? atoi(mv) : -1;              // -1: shipped layout, annealing (1 M moves) as the fallback
+    std::lock_guard<std::mutex> lock(mu);
+    auto key = std::make_pair(rate, moves);
+    auto it = cache.find(key);
+    if (it == cache.end()) {
+        CoreTables t;
+        if (moves >= 0 || !load_saved_core_tables(code, t)) t = build_core_tables(code, moves >= 0 ? moves : 1000000);
+        it = cache.emplace(key, std::move(t)).first;
+    }
+    return it->second;
+}
+
 extern "C" {
 
 int ria_gpu_abi_version(void) { return RIA_GPU_ABI_VERSION; }
@@ -459,6 +487,10 @@ void ria_gpu_destroy(ria_gpu_handle h) {
     if (h->p_macq_ctl) (void)hipHostFree(h->p_macq_ctl);
     if (h->d_burst_ws) (void)hipFree(h->d_burst_ws);
     if (h->p_burst_ctl) (void)hipHostFree(h->p_burst_ctl);
+    for (void* p : h->d_f14) if (p) (void)hipFree(p);
+    for (void* p : h->d_cw_perm) if (p) (void)hipFree(p);
+    if (h->d_df_ws) (void)hipFree(h->d_df_ws);
+    if (h->p_df_ctl) (void)hipHostFree(h->p_df_ctl);
     for (void* p : {(void*)h->d_rctl, (void*)h->d_flagged, (void*)h->d_list2, (void*)h->d_stage2, (void*)h->d_info_c, (void*)h->d_rows_c,
                     (void*)h->d_redec_ok, (void*)h->d_redec_bytes, (void*)h->d_st_c, (void*)h->d_overflow}) if (p) (void)hipFree(p);
     for (void* p : {(void*)h->p_rctl, (void*)h->p_flagged, (void*)h->p_info_c, (void*)h->p_rows_c, (void*)h->p_redec_ok,
@@ -549,23 +581,7 @@ int ria_gpu_create(const ria_gpu_config* cfg, ria_gpu_handle* out) {
     CREATE_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_llr_ws),
                          static_cast<size_t>(h->cfg.max_batch) * g.llrs_per_frame * sizeof(float)));
 
-    {   // the lane/slot assignment against LDS bank conflicts (host_tables.hpp): the layout annealed offline and shipped
-        // with the library (validated against this build's H), or - RIA_BANKOPT_MOVES set, or no valid shipped layout -
-        // annealed here, once per rate and process
-        static std::mutex mu;
-        static std::map<std::pair<int, int>, CoreTables> cache;
-        const char* mv = getenv("RIA_BANKOPT_MOVES");
-        const int moves = mv ? atoi(mv) : -1;              // -1: shipped layout, annealing (1 M moves) as the fallback
-        std::lock_guard<std::mutex> lock(mu);
-        auto key = std::make_pair(static_cast<int>(cfg->code_rate), moves);
-        auto it = cache.find(key);
-        if (it == cache.end()) {
-            CoreTables t;
-            if (moves >= 0 || !load_saved_core_tables(h->code, t)) t = build_core_tables(h->code, moves >= 0 ? moves : 1000000);
-            it = cache.emplace(key, std::move(t)).first;
-        }
-        h->ftab = it->second;
-    }
+    h->ftab = core_tables_for(cfg->code_rate, h->code);
     CREATE_TRY(upload(&h->d_f_row_addr, h->ftab.row_addr));
     CREATE_TRY(upload(&h->d_f_col_addr, h->ftab.col_addr));
     CREATE_TRY(upload(&h->d_f_check_at, h->ftab.check_at));
@@ -2067,6 +2083,195 @@ int ria_gpu_mcdpsk_acquire_batch(ria_gpu_handle h, const ria_mcdpsk_config* cfg,
         hipLaunchKernelGGL(macq_next_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A);
         HIP_TRY(h, hipGetLastError());
     }
+    return RIA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ decodeFrame (OFDM branch)
+static_assert(sizeof(ria_dframe_result) == 32, "ria_dframe_result is 32 bytes (include/ria_gpu.h)");
+static_assert(offsetof(ria_dframe_result, frame_bytes) == 8 && offsetof(ria_dframe_result, iters_r14) == 12 &&
+              offsetof(ria_dframe_result, tries_r14) == 16 && offsetof(ria_dframe_result, reserved) == 20, "ria_dframe_result field offsets");
+static_assert(sizeof(DfProbe) == 80 && sizeof(DfRow) == 20, "decode_frame_kernels.hip.h record sizes");
+
+// the R1/4 code on a handle of another rate: H, the core layout of the per-rate cache, the tables on the device
+static int dframe_ensure_r14(ria_gpu_handle h) {
+    if (h->have14) return RIA_OK;
+    const LdpcCode code = build_ldpc(RIA_RATE_1_4);
+    const CoreTables t = core_tables_for(RIA_RATE_1_4, code);
+    if (!shape_fits(RIA_RATE_1_4, t, &h->wave_lds14)) return fail(h, RIA_ERR_UNSUPPORTED, "ria_gpu_decode_frame_batch: the R1/4 code does not fit its compiled shape");
+    for (void*& p : h->d_f14) { if (p) (void)hipFree(p); p = nullptr; }
+    HIP_TRY(h, upload(&h->d_f14[0], t.row_addr));
+    HIP_TRY(h, upload(&h->d_f14[1], t.col_addr));
+    HIP_TRY(h, upload(&h->d_f14[2], t.check_at));
+    HIP_TRY(h, upload(&h->d_f14[3], t.col_at));
+    HIP_TRY(h, upload(&h->d_f14[4], t.col_pos));
+    FastCode& f = h->fast14;
+    f.k = code.k; f.m = code.m; f.max_iter = recommended_iterations(RIA_RATE_1_4); f.bytes_per_cw = info_bits_for(RIA_RATE_1_4) / 8;
+    f.row_addr = static_cast<const uint16_t*>(h->d_f14[0]); f.col_addr = static_cast<const uint16_t*>(h->d_f14[1]);
+    f.check_at = static_cast<const uint16_t*>(h->d_f14[2]); f.col_at = static_cast<const uint16_t*>(h->d_f14[3]);
+    f.col_pos = static_cast<const uint16_t*>(h->d_f14[4]);
+    set_fast_attributes(RIA_RATE_1_4, h->wave_lds14);
+    h->have14 = true;
+    return RIA_OK;
+}
+
+struct DfLayout { size_t row, probe, list, fx_llr, fx_info, fx_st, lg_rows, lg_entry, lg_cw, lg_out, lg_ok, lg_it, ctl, total; };
+static DfLayout dframe_layout(size_t n, size_t max_cw, size_t bpc, size_t dec_bytes) {
+    DfLayout L{};
+    size_t o = 0;
+    const size_t nr = n * (max_cw - 1);   // legacy rows: CW1.. of every frame
+    L.ctl = o; o = up256(o + sizeof(DfCtl));
+    L.row = o; o = up256(o + n * sizeof(DfRow));
+    L.probe = o; o = up256(o + 4 * n * sizeof(DfProbe));
+    L.list = o; o = up256(o + kDfNumLists * n * sizeof(uint32_t));
+    L.fx_llr = o; o = up256(o + n * kDfFrameBits * sizeof(float));
+    L.fx_info = o; o = up256(o + n * 4 * bpc);
+    L.fx_st = o; o = up256(o + n * sizeof(ria_decode_status));
+    L.lg_rows = o; o = up256(o + nr * kDfBlock * sizeof(float));
+    L.lg_entry = o; o = up256(o + nr * sizeof(uint32_t));
+    L.lg_cw = o; o = up256(o + nr);
+    L.lg_out = o; o = up256(o + nr * dec_bytes);
+    L.lg_ok = o; o = up256(o + nr);
+    L.lg_it = o; o = up256(o + nr * sizeof(uint16_t));
+    L.total = o;
+    return L;
+}
+
+int ria_gpu_decode_frame_batch(ria_gpu_handle h, const float* llr_dev, int llr_stride, const int32_t* n_llr_dev, int n_frames,
+                               uint32_t flags, uint8_t* frame_out_dev, int frame_row, ria_dframe_result* result_dev,
+                               ria_decode_status* decode_status_dev, uint8_t* info_out_dev, void* stream) {
+    if (!h) return RIA_ERR_INVALID;
+    const int bpc = h->geo.bytes_per_codeword;
+    if (n_frames < 0 || llr_stride < kDfBlock || llr_stride > kDfMaxCw * kDfBlock || (flags & ~(RIA_DECODE_FULL | RIA_DECODE_NO_CHANNEL_DEINTERLEAVE)) != 0 ||
+        frame_row < std::max(4, llr_stride / kDfBlock) * bpc)
+        return fail(h, RIA_ERR_INVALID, "ria_gpu_decode_frame_batch: bad argument (648 <= llr_stride <= 32 * 648, frame_row >= max(4, llr_stride / 648) * "
+                                        "bytes_per_codeword, RIA_DECODE_* flags only)");
+    if (n_frames == 0) return RIA_OK;
+    if (!llr_dev || !frame_out_dev || !result_dev) return fail(h, RIA_ERR_INVALID, "ria_gpu_decode_frame_batch: null pointer");
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool r14 = h->cfg.code_rate == RIA_RATE_1_4;
+    const bool ch_deint = (flags & RIA_DECODE_NO_CHANNEL_DEINTERLEAVE) == 0;
+    // everything the call may need is allocated here, before any of it is in flight
+    if (!r14) { if (int rc = dframe_ensure_r14(h)) return rc; }
+    if (!h->d_cw_perm[ch_deint ? 1 : 0])
+        HIP_TRY(h, upload(&h->d_cw_perm[ch_deint ? 1 : 0], build_cw_deinterleave(h->geo.bits_per_symbol, ch_deint)));
+    const size_t n = static_cast<size_t>(n_frames), max_cw = static_cast<size_t>(llr_stride / kDfBlock);
+    const size_t dec_bytes = static_cast<size_t>((h->geo.ldpc_k + 7) / 8);
+    const DfLayout L = dframe_layout(n, max_cw, static_cast<size_t>(bpc), dec_bytes);
+    if (L.total > h->df_bytes) {   // nothing of an earlier call is in flight: every call ends on a stream sync
+        if (h->d_df_ws) (void)hipFree(h->d_df_ws);
+        h->d_df_ws = nullptr; h->df_bytes = 0;
+        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&h->d_df_ws), L.total));
+        h->df_bytes = L.total;
+    }
+    if (!h->p_df_ctl) HIP_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&h->p_df_ctl), sizeof(DfCtl), hipHostMallocDefault));
+    {
+        hipError_t e = ensure_decode_ws(h, n_frames);
+        if (e == hipSuccess && (flags & RIA_DECODE_CRC_RECOVER)) e = ensure_recovery_ws(h, std::max(n_frames, h->cfg.max_batch), false);
+        if (e != hipSuccess) return fail(h, RIA_ERR_HIP, "ria_gpu_decode_frame_batch workspace: %s", hipGetErrorString(e));
+    }
+    unsigned char* W = h->d_df_ws;
+    DfArgs A{};
+    A.llr = llr_dev; A.llr_stride = llr_stride; A.n_llr = n_llr_dev; A.n_frames = n_frames;
+    A.rate_is_r14 = r14 ? 1 : 0; A.bpc = bpc; A.bpc14 = info_bits_for(RIA_RATE_1_4) / 8;
+    A.row = reinterpret_cast<DfRow*>(W + L.row); A.probe = reinterpret_cast<DfProbe*>(W + L.probe);
+    A.list = reinterpret_cast<uint32_t*>(W + L.list); A.ctl = reinterpret_cast<DfCtl*>(W + L.ctl);
+    A.fx_llr = reinterpret_cast<float*>(W + L.fx_llr); A.fx_info = W + L.fx_info; A.fx_st = reinterpret_cast<ria_decode_status*>(W + L.fx_st);
+    A.perm = static_cast<const uint16_t*>(h->d_cw_perm[ch_deint ? 1 : 0]);
+    A.lg_rows = reinterpret_cast<float*>(W + L.lg_rows); A.lg_entry = reinterpret_cast<uint32_t*>(W + L.lg_entry); A.lg_cw = W + L.lg_cw;
+    A.lg_out = W + L.lg_out; A.lg_ok = W + L.lg_ok; A.dec_bytes = static_cast<int>(dec_bytes);
+    A.crc_bit = static_cast<const uint16_t*>(h->d_crc_bit); A.crc_init = static_cast<const uint16_t*>(h->d_crc_init);
+    A.frame_out = frame_out_dev; A.frame_row = frame_row; A.result = result_dev; A.st_out = decode_status_dev; A.info_out = info_out_dev;
+    // control block, row state, probe records and lists in one memset (they lie in front of the bulk areas)
+    HIP_TRY(h, hipMemsetAsync(W, 0, L.fx_llr, s));
+    const unsigned probe_grid = static_cast<unsigned>(std::min(n_frames, 16384));
+    auto list = [&](int stage) { hipLaunchKernelGGL(dframe_list_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A, stage); };
+    auto probe_rate = [&](bool robust, int which_list, int which_probe, unsigned grid) {
+        dispatch_shape(h->cfg.code_rate, [&](auto sh) {
+            using S = decltype(sh);
+            if (robust) hipLaunchKernelGGL((dframe_probe_kernel<S, true>), dim3(grid), dim3(64), ShapeInfo<S>::lds_bytes, s, h->fast, A, which_list, which_probe, bpc);
+            else hipLaunchKernelGGL((dframe_probe_kernel<S, false>), dim3(grid), dim3(64), ShapeInfo<S>::lds_bytes, s, h->fast, A, which_list, which_probe, bpc);
+        });
+    };
+    auto probe_r14 = [&](bool robust, int which_list, int which_probe, unsigned grid) {
+        if (robust) hipLaunchKernelGGL((dframe_probe_kernel<ShapeR14, true>), dim3(grid), dim3(64), ShapeInfo<ShapeR14>::lds_bytes, s, h->fast14, A, which_list, which_probe, A.bpc14);
+        else hipLaunchKernelGGL((dframe_probe_kernel<ShapeR14, false>), dim3(grid), dim3(64), ShapeInfo<ShapeR14>::lds_bytes, s, h->fast14, A, which_list, which_probe, A.bpc14);
+    };
+    // 1.-2. the two plain CW0 probes, each over the rows still open
+    list(kDfStageInit);
+    if (!r14) {
+        probe_r14(false, kDfListR14, kDfProbeR14, probe_grid);
+        list(kDfStageAfterR14);
+    }
+    probe_rate(false, kDfListRate, kDfProbeRate, probe_grid);
+    list(kDfStageAfterRate);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(h->p_df_ctl, A.ctl, sizeof(DfCtl), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));                                    // read 1 of 2: the length of the fixed batch
+    const int n_fixed = static_cast<int>(h->p_df_ctl->n[kDfListFixed]);
+    if (n_fixed < 0 || n_fixed > n_frames) return fail(h, RIA_ERR_HIP, "ria_gpu_decode_frame_batch: the fixed list broke its bound (%d)", n_fixed);
+    // 3.-4. decodeFixedFrame over the try_frame_interleave rows, then the two salvage decoders over what it left
+    if (n_fixed > 0) {
+        hipLaunchKernelGGL(dframe_fixed_gather_kernel, dim3(static_cast<unsigned>(std::min<size_t>((static_cast<size_t>(n_fixed) * kDfFrameBits + 255) / 256, 16384))),
+                           dim3(256), 0, s, A, n_fixed);
+        int rc = launch_decode(h, A.fx_llr, kDfFrameBits, n_fixed, flags, A.fx_info, A.fx_st, s);
+        if (rc != RIA_OK) return rc;
+        const unsigned sg = static_cast<unsigned>(std::min(n_fixed, 16384));
+        list(kDfStageAfterFixed);
+        if (r14) probe_rate(true, kDfListSalvR14, kDfSalvR14, sg); else probe_r14(true, kDfListSalvR14, kDfSalvR14, sg);
+        list(kDfStageAfterSalvR14);
+        if (!r14) probe_rate(true, kDfListSalvRate, kDfSalvRate, sg);
+    }
+    // 5. legacy: the rows of CW1.. of the non-interleaved multi-codeword frames
+    list(kDfStageLegacy);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(h->p_df_ctl, A.ctl, sizeof(DfCtl), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));                                    // read 2 of 2: the legacy rows (and the fault flag)
+    if (h->p_df_ctl->fault) return fail(h, RIA_ERR_HIP, "decode work-queue fault: no frame of this call was decoded");
+    const long long n_rows = static_cast<long long>(h->p_df_ctl->n_rows);
+    if (n_rows < 0 || static_cast<size_t>(n_rows) > n * (max_cw - 1)) return fail(h, RIA_ERR_HIP, "ria_gpu_decode_frame_batch: the legacy rows broke their bound (%lld)", n_rows);
+    if (n_rows > 0) {
+        const int nr = static_cast<int>(n_rows);
+        hipLaunchKernelGGL(dframe_legacy_rows_kernel, dim3(static_cast<unsigned>(std::min<size_t>((static_cast<size_t>(nr) * kDfBlock + 255) / 256, 16384))),
+                           dim3(256), 0, s, A, nr);
+        int rc = ria_gpu_ldpc_decode_batch(h, A.lg_rows, nr, h->geo.ldpc_max_iterations, 0.75f, W + L.lg_out, W + L.lg_ok,
+                                           reinterpret_cast<uint16_t*>(W + L.lg_it), s);
+        if (rc != RIA_OK) return rc;
+    }
+    // 6. results
+    hipLaunchKernelGGL(dframe_finish_kernel, dim3(static_cast<unsigned>(std::min((n_frames + 3) / 4, 4096))), dim3(256), 0, s, A);
+    HIP_TRY(h, hipGetLastError());
+    return RIA_OK;
+}
+
+int ria_gpu_decode_frame_host(ria_gpu_handle h, const float* llr_host, int n_llr, uint32_t flags, uint8_t* frame_out_host, int max_bytes,
+                              ria_dframe_result* result_out, ria_decode_status* decode_status_out) {
+    if (!h) return RIA_ERR_INVALID;
+    if (n_llr < 0 || (n_llr > 0 && !llr_host) || !frame_out_host || !result_out)
+        return fail(h, RIA_ERR_INVALID, "ria_gpu_decode_frame_host: bad argument");
+    const int n_use = std::min(n_llr, kDfMaxCw * kDfBlock);                 // the cap of 32 codewords per row
+    const int stride = std::max(kDfBlock, n_use);
+    const int frame_row = std::max(4, stride / kDfBlock) * h->geo.bytes_per_codeword;
+    if (max_bytes < frame_row) return fail(h, RIA_ERR_INVALID, "ria_gpu_decode_frame_host: max_bytes %d < %d (max(4, n_llr / 648) * bytes_per_codeword)", max_bytes, frame_row);
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t b_llr = static_cast<size_t>(stride) * sizeof(float), o_n = up256(b_llr), o_fr = up256(o_n + sizeof(int32_t));
+    const size_t o_res = up256(o_fr + frame_row), o_ds = up256(o_res + sizeof(ria_dframe_result)), total = up256(o_ds + sizeof(ria_decode_status));
+    int rc = ensure_host_stage(h, total);
+    if (rc != RIA_OK) return rc;
+    unsigned char *D = h->d_hstage, *P = h->p_hstage;
+    hipStream_t s = h->hstream;
+    std::memset(P, 0, b_llr);
+    if (n_use > 0) std::memcpy(P, llr_host, static_cast<size_t>(n_use) * sizeof(float));
+    *reinterpret_cast<int32_t*>(P + o_n) = n_use;
+    HIP_TRY(h, hipMemcpyAsync(D, P, o_n + sizeof(int32_t), hipMemcpyHostToDevice, s));
+    rc = ria_gpu_decode_frame_batch(h, reinterpret_cast<const float*>(D), stride, reinterpret_cast<const int32_t*>(D + o_n), 1, flags, D + o_fr,
+                                    frame_row, reinterpret_cast<ria_dframe_result*>(D + o_res), reinterpret_cast<ria_decode_status*>(D + o_ds), nullptr, s);
+    if (rc != RIA_OK) return rc;
+    HIP_TRY(h, hipMemcpyAsync(P + o_fr, D + o_fr, total - o_fr, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    std::memcpy(frame_out_host, P + o_fr, static_cast<size_t>(frame_row));
+    std::memcpy(result_out, P + o_res, sizeof(ria_dframe_result));
+    if (decode_status_out) std::memcpy(decode_status_out, P + o_ds, sizeof(ria_decode_status));
     return RIA_OK;
 }
 

@@ -120,6 +120,31 @@ class RxEngine:
                                                   _stream_ptr()))
         return info, st
 
+    DFRAME_RESULT = np.dtype([("success", "u1"), ("codewords_ok", "u1"), ("codewords_failed", "u1"), ("frame_type", "u1"),
+                              ("path", "u1"), ("header_total_cw", "u1"), ("stages", "u1"), ("reserved0", "u1"),
+                              ("frame_bytes", "<i4"), ("iters_r14", "<u2"), ("iters_cw0", "<u2"), ("tries_r14", "u1"),
+                              ("tries_rate", "u1"), ("reserved1", "u1", 2), ("reserved", "<i4", 3)])
+
+    def decode_frame(self, llr, n_llr=None, flags=capi.DECODE_FULL, want_info=False):
+        """StreamingDecoder::decodeFrame (OFDM branch) over rows of soft bits: llr float32 [n, 648 .. 32 * 648], n_llr the
+        soft bits of each row (None: the whole row).  Returns (frame bytes uint8 [n, max(4, cols // 648) * bytes_per_codeword],
+        result structured array (DFRAME_RESULT), decode status of the fixed attempt[, its codeword bytes])."""
+        n, stride = llr.shape
+        assert llr.dtype == torch.float32 and llr.is_contiguous()
+        row = max(4, stride // 648) * self.geo.bytes_per_codeword
+        frames = torch.empty((n, row), dtype=torch.uint8, device=self.device)
+        res = torch.empty((n, 32), dtype=torch.uint8, device=self.device)
+        st = torch.empty((n, 20), dtype=torch.uint8, device=self.device)
+        info = torch.empty((n, self.geo.info_bytes_per_frame), dtype=torch.uint8, device=self.device) if want_info else None
+        nl = None
+        if n_llr is not None:
+            nl = torch.as_tensor(np.ascontiguousarray(n_llr, np.int32)).to(self.device) if not torch.is_tensor(n_llr) else n_llr
+            assert nl.dtype == torch.int32 and nl.numel() == n and nl.is_contiguous()
+        self._check(self.lib.ria_gpu_decode_frame_batch(self.h, _ptr(llr), stride, _ptr(nl), n, flags, _ptr(frames), row,
+                                                        _ptr(res), _ptr(st), _ptr(info), _stream_ptr()))
+        out = (frames, self._status_array(res, self.DFRAME_RESULT), st)
+        return out + (info,) if want_info else out
+
     def rx(self, samples, flags=capi.DECODE_FULL, cfo_hz=None, abs_pos=None, meta_flags=None, want_llr=False,
            out=None, offsets=None):
         """Fused samples -> payload bytes. Returns (info, decode_status[, llr, frame_status])."""

@@ -415,4 +415,33 @@ inline CodewordStatus decodeFixedFrame(GpuOfdmChirpWaveform& wf, GpuHandle& gpu,
     return st;
 }
 
+// StreamingDecoder::decodeFrame(soft_bits, snr, cfo), OFDM branch (streaming_decoder.cpp:2821-3059): the R1/4 control fast
+// path, the raw CW0 probe, decodeFixedFrame, the 1-CW salvage and the legacy path in one library call
+// (ria_gpu_decode_frame_host).  `gpu` is the handle of the link's rate (connected_ ? code_rate_ : R1_4).  A failure of the
+// library is the reference's failure value: the default DecodeResult.
+struct DecodeFrameResult {            // the DecodeResult fields decodeFrame sets (streaming_decoder.hpp)
+    bool success = false;
+    int codewords_ok = 0, codewords_failed = 0;
+    uint8_t frame_type = 0x10;        // v2::FrameType::PROBE, DecodeResult's default
+    Bytes frame_data;
+    ria_dframe_result detail{};       // which path produced it (RIA_DFRAME_*) and what each stage spent
+};
+inline DecodeFrameResult decodeFrame(GpuHandle& gpu, const float* llr, size_t n_llr, bool use_channel_interleave = true) {
+    DecodeFrameResult r;
+    const size_t n_use = n_llr < size_t(32) * 648 ? n_llr : size_t(32) * 648;
+    const size_t cws = n_use / 648 > 4 ? n_use / 648 : 4;
+    Bytes buf(cws * static_cast<size_t>(gpu.geo().bytes_per_codeword));
+    ria_dframe_result d{};
+    const uint32_t flags = RIA_DECODE_FULL | (use_channel_interleave ? 0u : RIA_DECODE_NO_CHANNEL_DEINTERLEAVE);
+    if (ria_gpu_decode_frame_host(gpu.get(), llr, static_cast<int>(n_use), flags, buf.data(), static_cast<int>(buf.size()), &d, nullptr) != RIA_OK)
+        return r;
+    r.success = d.success != 0; r.codewords_ok = d.codewords_ok; r.codewords_failed = d.codewords_failed; r.frame_type = d.frame_type;
+    r.frame_data.assign(buf.begin(), buf.begin() + d.frame_bytes);
+    r.detail = d;
+    return r;
+}
+inline DecodeFrameResult decodeFrame(GpuHandle& gpu, const std::vector<float>& soft_bits, bool use_channel_interleave = true) {
+    return decodeFrame(gpu, soft_bits.data(), soft_bits.size(), use_channel_interleave);
+}
+
 }  // namespace ria_host
