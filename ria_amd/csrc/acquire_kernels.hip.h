@@ -24,11 +24,11 @@ struct AcqCtl {                  // written by the plan / next kernels, read bac
     unsigned int pad_[2];
 };
 
-struct AcqList {
+struct FrameList {               // a work list of the acquire and burst rounds
     uint64_t* offset;            // sample offset from samples_dev: window * stride + candidate start
     ria_frame_meta* meta;
     uint32_t* window;
-    uint8_t* cand;               // index into kAcqDelta
+    uint8_t* state;              // acquire rounds: index into kAcqDelta; burst stage lists: 0 dropped, 1 runs the next round, 2 group complete
 };
 
 struct AcqArgs {
@@ -39,7 +39,7 @@ struct AcqArgs {
     ria_acq_result* acq;
     AcqCtl* ctl;
     // round kernels
-    AcqList cur, next;
+    FrameList cur, next;
     int n_cur;
     int round;                   // 0: primary round (scatter every entry)
     int retry;                   // 0: RIA_ACQ_NO_TIMING_RETRY or the last round - list nothing
@@ -115,7 +115,7 @@ __global__ __launch_bounds__(kAcqScanThreads) void acq_plan_kernel(AcqArgs A) {
             m.abs_position = p.abs_base + static_cast<uint64_t>(start);
             A.next.meta[pos] = m;
             A.next.window[pos] = static_cast<uint32_t>(b);
-            A.next.cand[pos] = 0;
+            A.next.state[pos] = 0;
         }
         running += total;
     }
@@ -129,7 +129,7 @@ __global__ __launch_bounds__(256) void acq_scatter_kernel(AcqArgs A) {
     for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < A.n_cur; i += gridDim.x * 4) {
         const ria_decode_status st = A.dst_c[i];
         const uint32_t w = A.cur.window[i];
-        const int k = A.cur.cand[i];
+        const int k = A.cur.state[i];
         const bool any = st.cw_ok[0] | st.cw_ok[1] | st.cw_ok[2] | st.cw_ok[3];
         if (A.round == 0 || any) {
             const uint8_t* src = A.info_c + static_cast<size_t>(i) * A.info_bytes;
@@ -164,7 +164,7 @@ __global__ __launch_bounds__(kAcqScanThreads) void acq_next_kernel(AcqArgs A) {
             if (!(st.cw_ok[0] | st.cw_ok[1] | st.cw_ok[2] | st.cw_ok[3])) {
                 w = A.cur.window[i];
                 const int sync = A.acq[w].sync_start;
-                for (int k = A.cur.cand[i] + 1; k < kAcqCandidates; ++k) {
+                for (int k = A.cur.state[i] + 1; k < kAcqCandidates; ++k) {
                     if (acq_fits(sync + kAcqDelta[k], A.frame_samples, A.window_len)) { nk = k; s = sync + kAcqDelta[k]; break; }
                 }
             }
@@ -180,7 +180,7 @@ __global__ __launch_bounds__(kAcqScanThreads) void acq_next_kernel(AcqArgs A) {
             m.abs_position = p.abs_base + static_cast<uint64_t>(s);
             A.next.meta[pos] = m;
             A.next.window[pos] = w;
-            A.next.cand[pos] = static_cast<uint8_t>(nk);
+            A.next.state[pos] = static_cast<uint8_t>(nk);
         }
         running += total;
     }

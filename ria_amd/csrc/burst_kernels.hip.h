@@ -31,13 +31,6 @@ struct BurstCtl {                // read back by the host once per round
     unsigned int fault;          // a decode status carried the work-queue fault marker
 };
 
-struct BurstList {
-    uint64_t* offset;            // sample offset from samples_dev
-    ria_frame_meta* meta;
-    uint32_t* window;
-    uint8_t* keep;               // stage lists only: 0 dropped, 1 runs the next round, 2 group complete
-};
-
 struct BurstArgs {
     const float* samples;
     long long stride;
@@ -48,11 +41,11 @@ struct BurstArgs {
     ria_burst_result* res;
     BurstCtl* ctl;
     // frame 0 of continuation windows: the acquire rounds' own outputs, one row per window
-    AcqCtl* acq_ctl; AcqList acq_first; ria_acq_result* acq0;
+    AcqCtl* acq_ctl; FrameList acq_first; ria_acq_result* acq0;
     const uint8_t* info0; const ria_decode_status* dst0; const ria_frame_status* fst0;
     uint32_t* c_win0;            // the continuation windows in list order (the acquire rounds overwrite their lists)
     // round state
-    BurstList g_cur, c_cur, g_stage, c_stage;
+    FrameList g_cur, c_cur, g_stage, c_stage;
     int n_g, n_c, round;         // round = index of the physical frame the NEXT round would demodulate
     int first;                   // 1: the continuation entries are c_win0 and their frame-0 results are indexed by window
     const ria_frame_status* g_fst;                                                         // compact, group list order
@@ -129,7 +122,7 @@ __global__ __launch_bounds__(kAcqScanThreads) void burst_plan_kernel(BurstArgs A
                 A.gpos[static_cast<size_t>(b) * kBurstMaxGroup] = static_cast<uint32_t>(pg);
             } else {
                 A.acq_first.offset[pc] = off; A.acq_first.meta[pc] = m; A.acq_first.window[pc] = static_cast<uint32_t>(b);
-                A.acq_first.cand[pc] = 0;
+                A.acq_first.state[pc] = 0;
                 A.c_win0[pc] = static_cast<uint32_t>(b);
             }
             if (A.cfo_used) A.cfo_used[static_cast<size_t>(b) * kBurstSlots] = p.known_cfo_hz;
@@ -246,7 +239,7 @@ __global__ __launch_bounds__(64 * kBurstStepWaves) void burst_step_kernel(BurstA
         rp->frames_decoded = static_cast<uint8_t>(frames_decoded);
         rp->stop = static_cast<uint8_t>(stop);
         if (!group && f == 0) { rp->frame_start = frame_start; rp->delta = static_cast<int16_t>(delta); rp->candidates = static_cast<uint8_t>(candidates); }
-        (group ? A.g_stage.keep : A.c_stage.keep)[i] = go ? 1 : complete ? 2 : 0;
+        (group ? A.g_stage.state : A.c_stage.state)[i] = go ? 1 : complete ? 2 : 0;
         (group ? A.g_stage.window : A.c_stage.window)[i] = w;
         if (go) {
             (group ? A.g_stage.offset : A.c_stage.offset)[i] = static_cast<uint64_t>(w) * static_cast<uint64_t>(A.stride) + static_cast<uint64_t>(s);
@@ -265,7 +258,7 @@ __global__ __launch_bounds__(kAcqScanThreads) void burst_list_kernel(BurstArgs A
     int run_g = 0, run_d = 0, run_c = 0;
     for (int base = 0; base < A.n_g; base += kAcqScanThreads) {
         const int i = base + static_cast<int>(threadIdx.x);
-        const int k = i < A.n_g ? A.g_stage.keep[i] : 0;
+        const int k = i < A.n_g ? A.g_stage.state[i] : 0;
         int tot_g, tot_d;
         const int pg = run_g + acq_block_scan(k == 1, &tot_g);
         const int pd = run_d + acq_block_scan(k == 2, &tot_d);
@@ -279,7 +272,7 @@ __global__ __launch_bounds__(kAcqScanThreads) void burst_list_kernel(BurstArgs A
     }
     for (int base = 0; base < A.n_c; base += kAcqScanThreads) {
         const int i = base + static_cast<int>(threadIdx.x);
-        const int k = i < A.n_c ? A.c_stage.keep[i] : 0;
+        const int k = i < A.n_c ? A.c_stage.state[i] : 0;
         int tot_c;
         const int pc = run_c + acq_block_scan(k == 1, &tot_c);
         if (k == 1) { A.c_cur.offset[pc] = A.c_stage.offset[i]; A.c_cur.meta[pc] = A.c_stage.meta[i]; A.c_cur.window[pc] = A.c_stage.window[i]; }

@@ -20,6 +20,8 @@
 #include "host_tables.hpp"
 #include "../host/link_adaptation.hpp"
 #include "frame_recovery.hpp"
+#include "ws_carve.hpp"
+#include "device_buffers.hpp"
 #include "ldpc_kernels.hip.h"
 #include "ldpc_fast.hip.h"
 #ifdef RIA_WITH_DUAL_DECODER   // experiment record (two codewords per wave; measured slower): not in the default library
@@ -40,6 +42,7 @@
 using namespace ria;
 
 constexpr int kMaxParts = 4;   // ria_gpu_rx_batch overlaps up to this many parts of a batch on internal streams
+// Every device and pinned block of a handle is a DevBuf / PinBuf member: ria_gpu_destroy frees them by deleting the handle.
 struct ria_gpu {
     ria_gpu_config cfg{};
     ria_gpu_geometry geo{};
@@ -48,76 +51,60 @@ struct ria_gpu {
     std::string err;
     int device = 0;
     // device tables
-    void* d_row_deg = nullptr; void* d_row_var = nullptr; void* d_col_deg = nullptr; void* d_col_slot = nullptr;
-    void* d_gather = nullptr; void* d_gather_nochan = nullptr;
-    void* d_crc_bit = nullptr; void* d_crc_init = nullptr;
-    void* d_zc_ref = nullptr;
+    DevBuf d_gather, d_gather_nochan, d_crc_bit, d_crc_init, d_zc_ref;
     // dual-chirp acquisition: tables (built at first use) and the per-chunk workspace
-    void* d_ch_tw = nullptr; void* d_ch_tmpl = nullptr; void* d_ch_tmpl_fft = nullptr; float ch_energy[2] = {0, 0};
-    void* d_ch_w1 = nullptr; void* d_ch_w2 = nullptr; void* d_ch_mag = nullptr; void* d_ch_cum = nullptr; void* d_ch_st = nullptr;
-    int ch_chunk = 0, ch_outer = 0;
+    DevBuf d_ch_tw, d_ch_tmpl, d_ch_tmpl_fft; float ch_energy[2] = {0, 0};
+    DevBuf d_ch_w1, d_ch_w2, d_ch_mag, d_ch_cum, d_ch_st;
     hipStream_t ch_side = nullptr; hipEvent_t ch_ev[2] = {nullptr, nullptr};   // the time-domain fallback runs beside the FFT path
-    // transmitter-CFO impairment (cfo_kernels.hip.h): two complex arrays + the phase table, grown on demand
-    void* d_txcfo_ws = nullptr; size_t txcfo_ws_bytes = 0;
-    void* d_zc_ws = nullptr; size_t zc_ws_bytes = 0;   // baseband workspace of the long-buffer ZC search
-    float* d_chan_nstd = nullptr; int chan_nstd_frames = 0;   // per-frame noise sigma of the reference-identical channel
-    // MC-DPSK: mixer tables per carrier count, Hilbert taps, CFO workspace
-    std::map<int, void*> d_mc_carrier, d_mc_train;   // device modulator tables per carrier count
-    std::map<int, void*> d_mc_mixer; void* d_mc_hilbert = nullptr; void* d_hilbert65 = nullptr; void* d_sync_host = nullptr; size_t sync_host_bytes = 0; void* d_mc_ws = nullptr; size_t mc_ws_floats = 0;
-    void* d_twiddle = nullptr; void* d_nco = nullptr;
+    DevBuf d_txcfo_ws;    // transmitter-CFO impairment (cfo_kernels.hip.h): two complex arrays + the phase table, grown on demand
+    DevBuf d_zc_ws;       // baseband workspace of the long-buffer ZC search
+    DevBuf d_chan_nstd;   // per-frame noise sigma (float) of the reference-identical channel
+    // MC-DPSK: modulator and mixer tables per carrier count, Hilbert taps, CFO workspace
+    std::map<int, DevBuf> d_mc_carrier, d_mc_train, d_mc_mixer;
+    DevBuf d_mc_hilbert, d_hilbert65, d_sync_host, d_mc_ws;
+    DevBuf d_twiddle, d_nco;
     // Schmidl-Cox acquisition: LTS passband templates (built at first use) and the metric-table workspace
-    void* d_cox_tI = nullptr; void* d_cox_tQ = nullptr; float cox_energy_ref = 0.0f; void* d_cox_ws = nullptr; size_t cox_ws_floats = 0;
-    void* d_demod_const = nullptr;
-    void* d_demod_ws[kMaxParts] = {nullptr, nullptr, nullptr, nullptr};   // split demodulator: bins / CFO / phase markers of one chunk, per stream slot
-    void* d_tx_const = nullptr;
-    // workspace
-    float* d_llr_ws = nullptr;            // max_batch * llrs_per_frame (fused path)
+    DevBuf d_cox_tI, d_cox_tQ; float cox_energy_ref = 0.0f; DevBuf d_cox_ws;
+    DevBuf d_demod_const;
+    DevBuf d_demod_ws[kMaxParts];   // split demodulator: bins / CFO / phase markers of one chunk, per stream slot
+    DevBuf d_tx_const;
+    DevBuf d_llr_ws;                // float [max_batch * llrs_per_frame] (fused path)
     FastCode fast{};
     CoreTables ftab;
-    void* d_f_row_addr = nullptr; void* d_f_col_addr = nullptr; void* d_f_check_at = nullptr; void* d_f_col_at = nullptr; void* d_f_col_pos = nullptr;
+    DevBuf d_f[5];                  // row_addr, col_addr, check_at, col_at, col_pos of `fast`
     int wave_lds = 0;
     hipStream_t aux_stream[4] = {nullptr, nullptr, nullptr, nullptr};   // ria_gpu_rx_batch: the parts of a large batch overlap here
     hipEvent_t aux_event[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    DecodeCtl* d_ctl = nullptr;           // cascade work-list control block
-    unsigned int* d_entries = nullptr;    // [4 * ws_frames]
-    unsigned int* d_best = nullptr;       // [4 * ws_frames]
-    unsigned int* d_list1 = nullptr;      // [4 * ws_frames]
-    CwResult* d_res = nullptr;            // [4 * ws_frames]
-    uint8_t* d_res_bytes = nullptr;       // [4 * ws_frames][5][bytes_per_cw]
-    CascadeWin* d_win = nullptr;          // [4 * ws_frames]
-    float* d_staged = nullptr;            // [4 * ws_frames][kStageFloats]
-    unsigned int* d_l1idx = nullptr;      // [4 * ws_frames]
-    unsigned int* d_l1hash = nullptr;     // [4 * ws_frames]
-    uint32_t* d_seed_ws = nullptr;        // [kMaxParts][cascade grid][kSeedWsWords]: per stream slot, per persistent workgroup
+    DevBuf d_ctl;                   // DecodeCtl [kMaxParts]: cascade work-list control block per stream slot
+    DevBuf d_seed_ws;               // uint32_t [kMaxParts][cascade grid][kSeedWsWords]: per stream slot, per persistent workgroup
+    DevBuf d_decode_ws;             // the per-frame arrays of the decode (decode_ws_carve), for ws_frames frames
     int ws_frames = 0;
     int split_parts = 0;                  // RIA_OPT_SPLIT_PARTS (0 = library default)
     int dual_decoder = 0;                 // RIA_OPT_DUAL_DECODER: 0 = default (environment RIA_DUAL, else off), 1 = on, -1 = off
     // host-buffer entry points (the single-frame IWaveform adaptor path): one device + one pinned staging block and a
     // stream, kept for the life of the handle, grown on demand - no allocation and no device-wide sync per call
-    unsigned char* d_hstage = nullptr; unsigned char* p_hstage = nullptr; size_t hstage_bytes = 0; hipStream_t hstream = nullptr;
+    DevBuf d_hstage; PinBuf p_hstage; hipStream_t hstream = nullptr;
     int zc_lds_opted = 0, mc_lds_opted = 0, lts_lds_opted = 0;   // dynamic-LDS opt-ins made on this handle's device
-    // CRC-recovery staging (device + pinned host mirrors), sized for ws_frames
-    unsigned int* d_rctl = nullptr; unsigned int* d_flagged = nullptr; unsigned int* d_list2 = nullptr; unsigned int* d_stage2 = nullptr; unsigned int* d_overflow = nullptr;
-    uint8_t* d_info_c = nullptr; float* d_rows_c = nullptr; uint8_t* d_redec_ok = nullptr; uint8_t* d_redec_bytes = nullptr;
-    ria_decode_status* d_st_c = nullptr;
-    unsigned int* p_rctl = nullptr; unsigned int* p_flagged = nullptr; uint8_t* p_info_c = nullptr; float* p_rows_c = nullptr;
-    uint8_t* p_redec_ok = nullptr; uint8_t* p_redec_bytes = nullptr; ria_decode_status* p_st_c = nullptr;
+    // CRC recovery: the device lists (recovery_carve) for rec_frames frames; the host restatement's staging, device and
+    // pinned mirror (recovery_stage_carve), for rec_host_frames frames
+    DevBuf d_rec_ws, d_rec_stage; PinBuf p_rec_stage;
     int rec_frames = 0, rec_host_frames = 0;
     Crc16Tables crc;
     // ria_gpu_rx_acquire_batch: detector results, two work lists, the compact outputs of one round and the control block
-    // (device + pinned mirror), one block sized for acq_windows windows, grown on demand
-    unsigned char* d_acq_ws = nullptr; int acq_windows = 0; AcqCtl* p_acq_ctl = nullptr;
+    // (device + pinned mirror), one block (acq_carve) sized for acq_windows windows, grown on demand
+    DevBuf d_acq_ws; int acq_windows = 0; PinBuf p_acq_ctl;
     // ria_gpu_mcdpsk_acquire_batch: detector results, two work lists, one round's soft bits, codeword rows, decoder outputs and
-    // header state, and the control block (device + pinned mirror), grown on demand
-    unsigned char* d_macq_ws = nullptr; size_t macq_bytes = 0; MacqCtl* p_macq_ctl = nullptr;
+    // header state, and the control block (device + pinned mirror), grown on demand (macq_carve)
+    DevBuf d_macq_ws; PinBuf p_macq_ctl;
     // ria_gpu_rx_burst_batch: frame-0 rows of the acquire rounds, the round lists, the groups' soft bits and decode batch,
-    // and the control block (device + pinned mirror), grown on demand
-    unsigned char* d_burst_ws = nullptr; size_t burst_bytes = 0; BurstCtl* p_burst_ctl = nullptr;
+    // and the control block (device + pinned mirror), grown on demand (burst_carve)
+    DevBuf d_burst_ws; PinBuf p_burst_ctl;
     // ria_gpu_decode_frame_batch: the R1/4 code of a handle of another rate (built at first use), the per-codeword channel
-    // de-interleave table and the identity, and the workspace with its control block (device + pinned mirror), grown on demand
-    FastCode fast14{}; void* d_f14[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; int wave_lds14 = 0; bool have14 = false;
-    void* d_cw_perm[2] = {nullptr, nullptr};
-    unsigned char* d_df_ws = nullptr; size_t df_bytes = 0; DfCtl* p_df_ctl = nullptr;
+    // de-interleave table and the identity, and the workspace (dframe_carve) with its control block (device + pinned mirror),
+    // grown on demand
+    FastCode fast14{}; DevBuf d_f14[5]; int wave_lds14 = 0; bool have14 = false;
+    DevBuf d_cw_perm[2];
+    DevBuf d_df_ws; PinBuf p_df_ctl;
 };
 
 namespace {
@@ -141,13 +128,6 @@ int fail(ria_gpu_handle h, int code, const char* fmt, ...) {
         if (e_ != hipSuccess)                                                                \
             return fail(h, RIA_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
-
-template <typename T>
-hipError_t upload(void** dst, const std::vector<T>& v) {
-    hipError_t e = hipMalloc(dst, v.size() * sizeof(T) + 16);
-    if (e != hipSuccess) return e;
-    return hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-}
 
 uint16_t crc16_host(const uint8_t* d, int n, uint16_t init) {  // frame_v2.cpp:115-128
     uint16_t crc = init;
@@ -191,28 +171,41 @@ static int persist_grid_size(bool dual) {
     static const int grid_env = getenv("RIA_PERSIST_GRID") ? std::max(64, atoi(getenv("RIA_PERSIST_GRID"))) : 0;
     return grid_env ? grid_env : (dual ? 2048 : 3072);
 }
+// the per-frame arrays of the decode, 4 codewords per frame
+struct DecodeWs {
+    unsigned int *entries, *best, *list1;
+    CwResult* res;
+    uint8_t* res_bytes;           // [4 * n][kNumFactors][bytes_per_cw]
+    CascadeWin* win;
+    float* staged;                // [4 * n][kStageFloats]
+    unsigned int *l1idx, *l1hash;
+};
+static DecodeWs decode_ws_carve(Carver& c, size_t n_frames, size_t bytes_per_cw) {
+    const size_t n4 = 4 * n_frames;
+    DecodeWs w;
+    w.entries = c.take<unsigned int>(n4);
+    w.best = c.take<unsigned int>(n4);
+    w.list1 = c.take<unsigned int>(n4);
+    w.res = c.take<CwResult>(n4);
+    w.res_bytes = c.take<uint8_t>(n4 * kNumFactors * bytes_per_cw);
+    w.win = c.take<CascadeWin>(n4);
+    w.staged = c.take<float>(n4 * kStageFloats);
+    w.l1idx = c.take<unsigned int>(n4);
+    w.l1hash = c.take<unsigned int>(n4);
+    return w;
+}
 static hipError_t ensure_decode_ws(ria_gpu_handle h, int n_frames) {
-    if (n_frames <= h->ws_frames && h->d_ctl && h->d_l1hash && h->d_seed_ws) return hipSuccess;
+    if (n_frames <= h->ws_frames && h->d_ctl && h->d_seed_ws) return hipSuccess;
     h->ws_frames = 0;   // nothing is valid until every allocation below has succeeded
-    for (void* p_ : {(void*)h->d_entries, (void*)h->d_best, (void*)h->d_list1, (void*)h->d_res, (void*)h->d_res_bytes, (void*)h->d_win, (void*)h->d_staged, (void*)h->d_l1idx, (void*)h->d_l1hash})
-        if (p_) (void)hipFree(p_);
-    h->d_entries = h->d_best = h->d_list1 = nullptr; h->d_res = nullptr; h->d_res_bytes = nullptr; h->d_win = nullptr; h->d_staged = nullptr; h->d_l1idx = nullptr; h->d_l1hash = nullptr;
     hipError_t e;
     if (!h->d_ctl) {   // one per stream slot; zeroed here because ria_gpu_debug_queue_fault reads the slots no call has used yet as well
-        if ((e = hipMalloc(reinterpret_cast<void**>(&h->d_ctl), kMaxParts * sizeof(DecodeCtl))) != hipSuccess) return e;
-        if ((e = hipMemset(h->d_ctl, 0, kMaxParts * sizeof(DecodeCtl))) != hipSuccess) return e;
+        if ((e = h->d_ctl.reserve(kMaxParts * sizeof(DecodeCtl))) != hipSuccess) return e;
+        if ((e = hipMemset(h->d_ctl.as<>(), 0, kMaxParts * sizeof(DecodeCtl))) != hipSuccess) { h->d_ctl.release(); return e; }
     }
     // the cascade's seeded RNG states: one area per workgroup of its grid and per stream slot (the parts of a batch run concurrently)
-    if (!h->d_seed_ws && (e = hipMalloc(reinterpret_cast<void**>(&h->d_seed_ws), static_cast<size_t>(kMaxParts) * persist_grid_size(false) * kSeedWsWords * sizeof(uint32_t))) != hipSuccess) return e;
-    if ((e = hipMalloc(reinterpret_cast<void**>(&h->d_entries), static_cast<size_t>(n_frames) * 4 * sizeof(unsigned))) != hipSuccess) return e;
-    if ((e = hipMalloc(reinterpret_cast<void**>(&h->d_best), static_cast<size_t>(n_frames) * 4 * sizeof(unsigned))) != hipSuccess) return e;
-    if ((e = hipMalloc(reinterpret_cast<void**>(&h->d_list1), static_cast<size_t>(n_frames) * 4 * sizeof(unsigned))) != hipSuccess) return e;
-    if ((e = hipMalloc(reinterpret_cast<void**>(&h->d_res), static_cast<size_t>(n_frames) * 4 * sizeof(CwResult))) != hipSuccess) return e;
-    if ((e = hipMalloc(reinterpret_cast<void**>(&h->d_res_bytes), static_cast<size_t>(n_frames) * 4 * kNumFactors * h->geo.bytes_per_codeword)) != hipSuccess) return e;
-    if ((e = hipMalloc(reinterpret_cast<void**>(&h->d_win), static_cast<size_t>(n_frames) * 4 * sizeof(CascadeWin))) != hipSuccess) return e;
-    if ((e = hipMalloc(reinterpret_cast<void**>(&h->d_staged), static_cast<size_t>(n_frames) * 4 * kStageFloats * sizeof(float))) != hipSuccess) return e;
-    if ((e = hipMalloc(reinterpret_cast<void**>(&h->d_l1idx), static_cast<size_t>(n_frames) * 4 * sizeof(unsigned))) != hipSuccess) return e;
-    if ((e = hipMalloc(reinterpret_cast<void**>(&h->d_l1hash), static_cast<size_t>(n_frames) * 4 * sizeof(unsigned))) != hipSuccess) return e;
+    if ((e = h->d_seed_ws.reserve(static_cast<size_t>(kMaxParts) * persist_grid_size(false) * kSeedWsWords * sizeof(uint32_t))) != hipSuccess) return e;
+    const size_t bpc = h->geo.bytes_per_codeword;
+    if ((e = h->d_decode_ws.reserve(carved_size([&](Carver& c) { return decode_ws_carve(c, n_frames, bpc); }))) != hipSuccess) return e;
     h->ws_frames = n_frames;
     return hipSuccess;
 }
@@ -244,39 +237,52 @@ static void parallel_for(int n, F&& f) {
     for (auto& t : th) t.join();
 }
 
+struct RecoveryWs { unsigned int *rctl, *overflow, *flagged, *list2, *stage2; };
+static RecoveryWs recovery_carve(Carver& c, size_t n) {
+    RecoveryWs w;
+    w.rctl = c.take<unsigned int>(8 * kMaxParts);   // one 32-byte counter block per stream slot
+    w.overflow = c.take<unsigned int>(n);
+    w.flagged = c.take<unsigned int>(n);
+    w.list2 = c.take<unsigned int>(n * 16);
+    w.stage2 = c.take<unsigned int>(n);
+    return w;
+}
+// staging of the host restatement: the flagged frames' compact rows, on the device and in pinned memory
+struct RecoveryStage {
+    unsigned int *rctl, *flagged;   // pinned block only: the device's are in RecoveryWs
+    uint8_t* info_c; float* rows_c; uint8_t* redec_ok; uint8_t* redec_bytes; ria_decode_status* st_c;
+};
+static RecoveryStage recovery_stage_carve(Carver& c, size_t n, size_t info_bytes, size_t bytes_per_cw, bool pinned) {
+    RecoveryStage w{};
+    if (pinned) { w.rctl = c.take<unsigned int>(4); w.flagged = c.take<unsigned int>(n); }
+    w.info_c = c.take<uint8_t>(n * info_bytes);
+    w.rows_c = c.take<float>(n * 4 * 648);
+    w.redec_ok = c.take<uint8_t>(n * 16);
+    w.redec_bytes = c.take<uint8_t>(n * 16 * bytes_per_cw);
+    w.st_c = c.take<ria_decode_status>(n);
+    return w;
+}
+static RecoveryWs recovery_ws(ria_gpu_handle h) {
+    return carve_at(h->d_rec_ws.as<>(), [&](Carver& c) { return recovery_carve(c, h->rec_frames); });
+}
+static RecoveryStage recovery_stage(ria_gpu_handle h, bool pinned) {
+    return carve_at(pinned ? h->p_rec_stage.as<>() : h->d_rec_stage.as<>(), [&](Carver& c) {
+        return recovery_stage_carve(c, h->rec_host_frames, h->geo.info_bytes_per_frame, h->geo.bytes_per_codeword, pinned); });
+}
 static hipError_t ensure_recovery_ws(ria_gpu_handle h, int n_frames, bool host_staging) {
     const size_t n = static_cast<size_t>(n_frames), ib = h->geo.info_bytes_per_frame, bpc = h->geo.bytes_per_codeword;
     hipError_t e;
-#define A_TRY(expr) if ((e = (expr)) != hipSuccess) return e
     if (n_frames > h->rec_frames) {
-        for (void** p : {(void**)&h->d_rctl, (void**)&h->d_flagged, (void**)&h->d_list2, (void**)&h->d_stage2, (void**)&h->d_overflow}) { if (*p) (void)hipFree(*p); *p = nullptr; }
-        h->rec_frames = 0;
-        A_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_rctl), 32 * kMaxParts));   // one 32-byte counter block per stream slot
-        A_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_overflow), n * 4));
-        A_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_flagged), n * 4));
-        A_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_list2), n * 16 * 4));
-        A_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_stage2), n * 4));
+        h->rec_frames = 0;   // nothing is valid until the allocation has succeeded
+        if ((e = h->d_rec_ws.reserve(carved_size([&](Carver& c) { return recovery_carve(c, n); }))) != hipSuccess) return e;
         h->rec_frames = n_frames;
     }
     if (host_staging && n_frames > h->rec_host_frames) {
-        for (void** p : {(void**)&h->d_info_c, (void**)&h->d_rows_c, (void**)&h->d_redec_ok, (void**)&h->d_redec_bytes, (void**)&h->d_st_c}) { if (*p) (void)hipFree(*p); *p = nullptr; }
-        for (void** p : {(void**)&h->p_rctl, (void**)&h->p_flagged, (void**)&h->p_info_c, (void**)&h->p_rows_c, (void**)&h->p_redec_ok,
-                         (void**)&h->p_redec_bytes, (void**)&h->p_st_c}) { if (*p) (void)hipHostFree(*p); *p = nullptr; }
-        A_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_info_c), n * ib));
-        A_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_rows_c), n * 4 * 648 * 4));
-        A_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_redec_ok), n * 16));
-        A_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_redec_bytes), n * 16 * bpc));
-        A_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_st_c), n * sizeof(ria_decode_status)));
-        A_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->p_rctl), 16, hipHostMallocDefault));
-        A_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->p_flagged), n * 4, hipHostMallocDefault));
-        A_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->p_info_c), n * ib, hipHostMallocDefault));
-        A_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->p_rows_c), n * 4 * 648 * 4, hipHostMallocDefault));
-        A_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->p_redec_ok), n * 16, hipHostMallocDefault));
-        A_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->p_redec_bytes), n * 16 * bpc, hipHostMallocDefault));
-        A_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->p_st_c), n * sizeof(ria_decode_status), hipHostMallocDefault));
+        h->rec_host_frames = 0;
+        if ((e = h->d_rec_stage.reserve(carved_size([&](Carver& c) { return recovery_stage_carve(c, n, ib, bpc, false); }))) != hipSuccess) return e;
+        if ((e = h->p_rec_stage.reserve(carved_size([&](Carver& c) { return recovery_stage_carve(c, n, ib, bpc, true); }))) != hipSuccess) return e;
         h->rec_host_frames = n_frames;
     }
-#undef A_TRY
     return hipSuccess;
 }
 
@@ -312,10 +318,11 @@ static int run_crc_recovery(ria_gpu_handle h, const FastDecodeArgs& D, hipStream
     if (e0 != hipSuccess) return fail(h, RIA_ERR_HIP, "recovery workspace: %s", hipGetErrorString(e0));
     RecoveryArgs R{};
     R.d = D;
-    unsigned int* rctl = h->d_rctl + 8 * slot;
+    const RecoveryWs W = recovery_ws(h);
+    unsigned int* rctl = W.rctl + 8 * slot;
     R.n_flagged = rctl; R.n_list2 = rctl + 1; R.n_stage2 = rctl + 2; R.next_fill = rctl + 3; R.n_overflow = rctl + 4;
-    R.flagged = h->d_flagged + ws_off; R.list2 = h->d_list2 + static_cast<size_t>(ws_off) * 16; R.stage2 = h->d_stage2 + ws_off;
-    R.overflow = h->d_overflow + ws_off;
+    R.flagged = W.flagged + ws_off; R.list2 = W.list2 + static_cast<size_t>(ws_off) * 16; R.stage2 = W.stage2 + ws_off;
+    R.overflow = W.overflow + ws_off;
 #ifdef RIA_DEBUG_STAMPS   // diagnostic builds only (tools/build_variant.sh ... -DRIA_DEBUG_STAMPS): a raw device pointer from the environment
     if (const char* e = getenv("RIA_DEBUG_REC_STAMPS")) R.dbg = reinterpret_cast<unsigned long long*>(strtoull(e, nullptr, 0));
 #endif
@@ -346,11 +353,13 @@ static int run_crc_recovery_host(ria_gpu_handle h, const FastDecodeArgs& D, hipS
     const int bpc = h->geo.bytes_per_codeword, ib = h->geo.info_bytes_per_frame;
     RecoveryArgs R{};
     R.d = D;
-    R.n_flagged = h->d_rctl; R.n_list2 = h->d_rctl + 1; R.next_fill = h->d_rctl + 3;
-    R.flagged = h->d_flagged; R.list2 = h->d_list2; R.list_units_now = 1;
-    R.info_c = h->d_info_c; R.rows_c = h->d_rows_c; R.redec_ok = h->d_redec_ok; R.redec_bytes = h->d_redec_bytes;
+    const RecoveryWs W = recovery_ws(h);
+    const RecoveryStage Dv = recovery_stage(h, false), P = recovery_stage(h, true);
+    R.n_flagged = W.rctl; R.n_list2 = W.rctl + 1; R.next_fill = W.rctl + 3;
+    R.flagged = W.flagged; R.list2 = W.list2; R.list_units_now = 1;
+    R.info_c = Dv.info_c; R.rows_c = Dv.rows_c; R.redec_ok = Dv.redec_ok; R.redec_bytes = Dv.redec_bytes;
 #define R_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(h, RIA_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); } while (0)
-    R_TRY(hipMemsetAsync(h->d_rctl, 0, 16, s));
+    R_TRY(hipMemsetAsync(W.rctl, 0, 16, s));
     hipLaunchKernelGGL(recovery_list_kernel, dim3((n_frames + 255) / 256), dim3(256), 0, s, R);
     const int wb = h->wave_lds;
     dispatch_shape(h->cfg.code_rate, [&](auto sh) {
@@ -358,20 +367,20 @@ static int run_crc_recovery_host(ria_gpu_handle h, const FastDecodeArgs& D, hipS
         hipLaunchKernelGGL(recovery_fill_kernel<S>, dim3(std::min(n_frames * 16, 3072)), dim3(64), wb, s, R);
     });
     hipLaunchKernelGGL(recovery_gather_kernel, dim3(n_frames), dim3(256), 0, s, R);
-    hipLaunchKernelGGL(recovery_status_gather_kernel, dim3((n_frames + 255) / 256), dim3(256), 0, s, h->d_rctl, h->d_flagged,
-                       D.status, h->d_st_c);
+    hipLaunchKernelGGL(recovery_status_gather_kernel, dim3((n_frames + 255) / 256), dim3(256), 0, s, W.rctl, W.flagged,
+                       D.status, Dv.st_c);
     R_TRY(hipGetLastError());
-    R_TRY(hipMemcpyAsync(h->p_rctl, h->d_rctl, 16, hipMemcpyDeviceToHost, s));
+    R_TRY(hipMemcpyAsync(P.rctl, W.rctl, 16, hipMemcpyDeviceToHost, s));
     R_TRY(hipStreamSynchronize(s));
     double tB = now();
-    const int nf = static_cast<int>(h->p_rctl[0]);
+    const int nf = static_cast<int>(P.rctl[0]);
     if (nf == 0) return RIA_OK;
-    R_TRY(hipMemcpyAsync(h->p_flagged, h->d_flagged, static_cast<size_t>(nf) * 4, hipMemcpyDeviceToHost, s));
-    R_TRY(hipMemcpyAsync(h->p_info_c, h->d_info_c, static_cast<size_t>(nf) * ib, hipMemcpyDeviceToHost, s));
-    R_TRY(hipMemcpyAsync(h->p_rows_c, h->d_rows_c, static_cast<size_t>(nf) * 4 * 648 * 4, hipMemcpyDeviceToHost, s));
-    R_TRY(hipMemcpyAsync(h->p_redec_ok, h->d_redec_ok, static_cast<size_t>(nf) * 16, hipMemcpyDeviceToHost, s));
-    R_TRY(hipMemcpyAsync(h->p_redec_bytes, h->d_redec_bytes, static_cast<size_t>(nf) * 16 * bpc, hipMemcpyDeviceToHost, s));
-    R_TRY(hipMemcpyAsync(h->p_st_c, h->d_st_c, static_cast<size_t>(nf) * sizeof(ria_decode_status), hipMemcpyDeviceToHost, s));
+    R_TRY(hipMemcpyAsync(P.flagged, W.flagged, static_cast<size_t>(nf) * 4, hipMemcpyDeviceToHost, s));
+    R_TRY(hipMemcpyAsync(P.info_c, Dv.info_c, static_cast<size_t>(nf) * ib, hipMemcpyDeviceToHost, s));
+    R_TRY(hipMemcpyAsync(P.rows_c, Dv.rows_c, static_cast<size_t>(nf) * 4 * 648 * 4, hipMemcpyDeviceToHost, s));
+    R_TRY(hipMemcpyAsync(P.redec_ok, Dv.redec_ok, static_cast<size_t>(nf) * 16, hipMemcpyDeviceToHost, s));
+    R_TRY(hipMemcpyAsync(P.redec_bytes, Dv.redec_bytes, static_cast<size_t>(nf) * 16 * bpc, hipMemcpyDeviceToHost, s));
+    R_TRY(hipMemcpyAsync(P.st_c, Dv.st_c, static_cast<size_t>(nf) * sizeof(ria_decode_status), hipMemcpyDeviceToHost, s));
     R_TRY(hipStreamSynchronize(s));
     double tC = now();
     FrameRecovery rec(h->crc, bpc);
@@ -379,20 +388,20 @@ static int run_crc_recovery_host(ria_gpu_handle h, const FastDecodeArgs& D, hipS
     parallel_for(nf, [&](int i) {
         uint8_t cw[4][68];
         std::memset(cw, 0, sizeof(cw));
-        uint8_t* inf = h->p_info_c + static_cast<size_t>(i) * ib;
+        uint8_t* inf = P.info_c + static_cast<size_t>(i) * ib;
         for (int c = 0; c < 4; ++c) std::memcpy(cw[c], inf + c * bpc, bpc);
-        bool good = rec.recover_search(cw, h->p_rows_c + static_cast<size_t>(i) * 4 * 648);
+        bool good = rec.recover_search(cw, P.rows_c + static_cast<size_t>(i) * 4 * 648);
         if (!good) {
             n_stage2++;
             uint8_t rd[4][4][68], rok[4][4];
             for (int at = 0; at < 4; ++at)
                 for (int c = 0; c < 4; ++c) {
-                    rok[at][c] = h->p_redec_ok[static_cast<size_t>(i) * 16 + at * 4 + c];
-                    std::memcpy(rd[at][c], h->p_redec_bytes + (static_cast<size_t>(i) * 16 + at * 4 + c) * bpc, bpc);
+                    rok[at][c] = P.redec_ok[static_cast<size_t>(i) * 16 + at * 4 + c];
+                    std::memcpy(rd[at][c], P.redec_bytes + (static_cast<size_t>(i) * 16 + at * 4 + c) * bpc, bpc);
                 }
             good = rec.recover_fallback(cw, rok, rd);
         }
-        ria_decode_status& sn = h->p_st_c[i];
+        ria_decode_status& sn = P.st_c[i];
         sn.needs_recovery = 0;
         sn.frame_valid = good ? 1 : 0;
         for (int c = 0; c < 4; ++c) {
@@ -401,9 +410,9 @@ static int run_crc_recovery_host(ria_gpu_handle h, const FastDecodeArgs& D, hipS
         }
     });
     double tD = now();
-    R_TRY(hipMemcpyAsync(h->d_info_c, h->p_info_c, static_cast<size_t>(nf) * ib, hipMemcpyHostToDevice, s));
-    R_TRY(hipMemcpyAsync(h->d_st_c, h->p_st_c, static_cast<size_t>(nf) * sizeof(ria_decode_status), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(recovery_scatter_kernel, dim3(nf), dim3(64), 0, s, nf, h->d_flagged, h->d_info_c, h->d_st_c, ib, D.info_out,
+    R_TRY(hipMemcpyAsync(Dv.info_c, P.info_c, static_cast<size_t>(nf) * ib, hipMemcpyHostToDevice, s));
+    R_TRY(hipMemcpyAsync(Dv.st_c, P.st_c, static_cast<size_t>(nf) * sizeof(ria_decode_status), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(recovery_scatter_kernel, dim3(nf), dim3(64), 0, s, nf, W.flagged, Dv.info_c, Dv.st_c, ib, D.info_out,
                        D.status);
     R_TRY(hipGetLastError());
     R_TRY(hipStreamSynchronize(s));
@@ -411,6 +420,29 @@ static int run_crc_recovery_host(ria_gpu_handle h, const FastDecodeArgs& D, hipS
     if (tdbg) fprintf(stderr, "[ria_gpu] recovery: frames %d flagged %d stage2 %d | gpu(decode+prep) %.2f ms, D2H %.2f ms, host search %.2f ms, H2D+scatter %.2f ms\n",
                       n_frames, nf, n_stage2.load(), tB - tA, tC - tB, tD - tC, now() - tD);
     return RIA_OK;
+}
+
+// control block -> its pinned mirror (allocated by the caller), one stream sync; a set fault flag fails the call with fault_fmt,
+// which may print `arg`
+static unsigned int ctl_fault(const MacqCtl&) { return 0; }   // the robust decoder has no work queue
+template <class Ctl>
+static unsigned int ctl_fault(const Ctl& c) { return c.fault; }
+template <class Ctl>
+static int read_ctl(ria_gpu_handle h, PinBuf& mirror, const Ctl* ctl_dev, hipStream_t s, const char* fault_fmt = "", int arg = 0) {
+    HIP_TRY(h, hipMemcpyAsync(mirror.as<Ctl>(), ctl_dev, sizeof(Ctl), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    if (ctl_fault(*mirror.as<Ctl>())) return fail(h, RIA_ERR_HIP, fault_fmt, arg);
+    return RIA_OK;
+}
+
+// the decoder core's five tables on the device, and the pointers of the FastCode that reads them
+static hipError_t upload_core_tables(const CoreTables& t, DevBuf (&d)[5], FastCode& f) {
+    const std::vector<uint16_t>* src[5] = {&t.row_addr, &t.col_addr, &t.check_at, &t.col_at, &t.col_pos};
+    for (int i = 0; i < 5; ++i)
+        if (hipError_t e = upload(d[i], *src[i])) return e;
+    f.row_addr = d[0].as<const uint16_t>(); f.col_addr = d[1].as<const uint16_t>(); f.check_at = d[2].as<const uint16_t>();
+    f.col_at = d[3].as<const uint16_t>(); f.col_pos = d[4].as<const uint16_t>();
+    return hipSuccess;
 }
 
 // the lane/slot assignment against LDS bank conflicts (host_tables.hpp): the layout annealed offline and shipped with the
@@ -460,42 +492,10 @@ const char* ria_gpu_last_error(ria_gpu_handle h) { return h ? h->err.c_str() : "
 void ria_gpu_destroy(ria_gpu_handle h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
-    void* ptrs[] = {h->d_row_deg, h->d_row_var, h->d_col_deg, h->d_col_slot, h->d_gather, h->d_gather_nochan,
-                    h->d_crc_bit, h->d_crc_init, h->d_zc_ref, h->d_ch_tw, h->d_ch_tmpl, h->d_ch_tmpl_fft, h->d_ch_w1, h->d_ch_w2, h->d_ch_mag, h->d_ch_cum, h->d_ch_st, h->d_twiddle, h->d_nco, h->d_demod_const, h->d_tx_const, h->d_llr_ws,
-                    h->d_ctl, h->d_entries, h->d_best, h->d_list1, h->d_res, h->d_res_bytes, h->d_win, h->d_staged, h->d_l1idx, h->d_l1hash, h->d_seed_ws,
-                    h->d_f_row_addr, h->d_f_col_addr, h->d_f_check_at, h->d_f_col_at, h->d_f_col_pos};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    for (auto& st_ : h->aux_stream) if (st_) (void)hipStreamDestroy(st_);
-    if (h->hstream) (void)hipStreamDestroy(h->hstream);
-    if (h->ch_side) (void)hipStreamDestroy(h->ch_side);
+    for (hipStream_t st_ : {h->aux_stream[0], h->aux_stream[1], h->aux_stream[2], h->aux_stream[3], h->hstream, h->ch_side}) if (st_) (void)hipStreamDestroy(st_);
     for (auto& ev_ : h->ch_ev) if (ev_) (void)hipEventDestroy(ev_);
-    if (h->d_hstage) (void)hipFree(h->d_hstage);
-    if (h->p_hstage) (void)hipHostFree(h->p_hstage);
     for (auto& ev_ : h->aux_event) if (ev_) (void)hipEventDestroy(ev_);
-    for (auto& kv : h->d_mc_mixer) if (kv.second) (void)hipFree(kv.second);
-    for (auto& kv : h->d_mc_carrier) if (kv.second) (void)hipFree(kv.second);
-    for (auto& kv : h->d_mc_train) if (kv.second) (void)hipFree(kv.second);
-    if (h->d_mc_hilbert) (void)hipFree(h->d_mc_hilbert);
-    if (h->d_hilbert65) (void)hipFree(h->d_hilbert65);
-    if (h->d_sync_host) (void)hipFree(h->d_sync_host);
-    if (h->d_mc_ws) (void)hipFree(h->d_mc_ws);
-    for (void* p : {h->d_cox_tI, h->d_cox_tQ, h->d_cox_ws, h->d_txcfo_ws, h->d_zc_ws, static_cast<void*>(h->d_chan_nstd)}) if (p) (void)hipFree(p);
-    for (void* p : h->d_demod_ws) if (p) (void)hipFree(p);
-    if (h->d_acq_ws) (void)hipFree(h->d_acq_ws);
-    if (h->p_acq_ctl) (void)hipHostFree(h->p_acq_ctl);
-    if (h->d_macq_ws) (void)hipFree(h->d_macq_ws);
-    if (h->p_macq_ctl) (void)hipHostFree(h->p_macq_ctl);
-    if (h->d_burst_ws) (void)hipFree(h->d_burst_ws);
-    if (h->p_burst_ctl) (void)hipHostFree(h->p_burst_ctl);
-    for (void* p : h->d_f14) if (p) (void)hipFree(p);
-    for (void* p : h->d_cw_perm) if (p) (void)hipFree(p);
-    if (h->d_df_ws) (void)hipFree(h->d_df_ws);
-    if (h->p_df_ctl) (void)hipHostFree(h->p_df_ctl);
-    for (void* p : {(void*)h->d_rctl, (void*)h->d_flagged, (void*)h->d_list2, (void*)h->d_stage2, (void*)h->d_info_c, (void*)h->d_rows_c,
-                    (void*)h->d_redec_ok, (void*)h->d_redec_bytes, (void*)h->d_st_c, (void*)h->d_overflow}) if (p) (void)hipFree(p);
-    for (void* p : {(void*)h->p_rctl, (void*)h->p_flagged, (void*)h->p_info_c, (void*)h->p_rows_c, (void*)h->p_redec_ok,
-                    (void*)h->p_redec_bytes, (void*)h->p_st_c}) if (p) (void)hipHostFree(p);
-    delete h;
+    delete h;   // its DevBuf / PinBuf members free the memory
 }
 
 int ria_gpu_create(const ria_gpu_config* cfg, ria_gpu_handle* out) {
@@ -544,8 +544,8 @@ int ria_gpu_create(const ria_gpu_config* cfg, ria_gpu_handle* out) {
         }                                                                                             \
     } while (0)
 
-    CREATE_TRY(upload(&h->d_gather, build_rx_gather(g.bits_per_symbol, true)));
-    CREATE_TRY(upload(&h->d_gather_nochan, build_rx_gather(g.bits_per_symbol, false)));
+    CREATE_TRY(upload(h->d_gather, build_rx_gather(g.bits_per_symbol, true)));
+    CREATE_TRY(upload(h->d_gather_nochan, build_rx_gather(g.bits_per_symbol, false)));
     {
         // CRC-16 linear decomposition: crc(M) = crc_init[L] ^ XOR_{set bits} crc_bit[distance from end]
         std::vector<uint16_t> bit(4 * 68 * 8 + 16), init(4 * 68 + 2);
@@ -556,8 +556,8 @@ int ria_gpu_create(const ria_gpu_config* cfg, ria_gpu_handle* out) {
             bit[q] = crc16_host(msg.data(), static_cast<int>(msg.size()), 0);
         }
         for (size_t L = 0; L < init.size(); ++L) init[L] = crc16_host(z.data(), static_cast<int>(L), 0xFFFF);
-        CREATE_TRY(upload(&h->d_crc_bit, bit));
-        CREATE_TRY(upload(&h->d_crc_init, init));
+        CREATE_TRY(upload(h->d_crc_bit, bit));
+        CREATE_TRY(upload(h->d_crc_init, init));
     }
     h->crc.build(4 * 68);
     {
@@ -566,33 +566,23 @@ int ria_gpu_create(const ria_gpu_config* cfg, ria_gpu_handle* out) {
             build_zc_reference(2 * r + 1, re, im);
             for (int i = 0; i < kZcRepSamples; ++i) { zc[(static_cast<size_t>(r) * kZcRepSamples + i) * 2] = re[i]; zc[(static_cast<size_t>(r) * kZcRepSamples + i) * 2 + 1] = im[i]; }
         }
-        CREATE_TRY(upload(&h->d_zc_ref, zc));
+        CREATE_TRY(upload(h->d_zc_ref, zc));
     }
-    CREATE_TRY(upload(&h->d_twiddle, build_twiddles()));
-    CREATE_TRY(upload(&h->d_nco, build_nco_table(g.frame_samples)));
+    CREATE_TRY(upload(h->d_twiddle, build_twiddles()));
+    CREATE_TRY(upload(h->d_nco, build_nco_table(g.frame_samples)));
     {
         DemodConst dc = build_demod_const(h->plan, cfg->modulation, g);
         std::vector<DemodConst> v(1, dc);
-        CREATE_TRY(upload(&h->d_demod_const, v));
+        CREATE_TRY(upload(h->d_demod_const, v));
         TxConst tc = build_tx_const(h->plan, h->code, cfg->modulation, g);
         std::vector<TxConst> tv(1, tc);
-        CREATE_TRY(upload(&h->d_tx_const, tv));
+        CREATE_TRY(upload(h->d_tx_const, tv));
     }
-    CREATE_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_llr_ws),
-                         static_cast<size_t>(h->cfg.max_batch) * g.llrs_per_frame * sizeof(float)));
+    CREATE_TRY(h->d_llr_ws.reserve(static_cast<size_t>(h->cfg.max_batch) * g.llrs_per_frame * sizeof(float)));
 
     h->ftab = core_tables_for(cfg->code_rate, h->code);
-    CREATE_TRY(upload(&h->d_f_row_addr, h->ftab.row_addr));
-    CREATE_TRY(upload(&h->d_f_col_addr, h->ftab.col_addr));
-    CREATE_TRY(upload(&h->d_f_check_at, h->ftab.check_at));
-    CREATE_TRY(upload(&h->d_f_col_at, h->ftab.col_at));
-    CREATE_TRY(upload(&h->d_f_col_pos, h->ftab.col_pos));
+    CREATE_TRY(upload_core_tables(h->ftab, h->d_f, h->fast));
     h->fast.k = h->code.k; h->fast.m = h->code.m; h->fast.max_iter = g.ldpc_max_iterations; h->fast.bytes_per_cw = g.bytes_per_codeword;
-    h->fast.row_addr = static_cast<const uint16_t*>(h->d_f_row_addr);
-    h->fast.col_addr = static_cast<const uint16_t*>(h->d_f_col_addr);
-    h->fast.check_at = static_cast<const uint16_t*>(h->d_f_check_at);
-    h->fast.col_at = static_cast<const uint16_t*>(h->d_f_col_at);
-    h->fast.col_pos = static_cast<const uint16_t*>(h->d_f_col_pos);
     if (!shape_fits(cfg->code_rate, h->ftab, &h->wave_lds)) { ria_gpu_destroy(h); return RIA_ERR_UNSUPPORTED; }
     set_fast_attributes(cfg->code_rate, h->wave_lds);
     CREATE_TRY(ensure_decode_ws(h, h->cfg.max_batch));
@@ -660,30 +650,31 @@ static int launch_decode(ria_gpu_handle h, const float* llr_dev, int llr_stride,
     hipError_t e = ensure_decode_ws(h, ws_off + n_frames);
     if (e != hipSuccess) return fail(h, RIA_ERR_HIP, "decode workspace: %s", hipGetErrorString(e));
     FastDecodeArgs A;
-    const size_t o4 = static_cast<size_t>(ws_off) * 4;
-    if ((e = hipMemsetAsync(h->d_res + o4, 0, static_cast<size_t>(n_frames) * 4 * sizeof(CwResult), s)) != hipSuccess)
+    const size_t o4 = static_cast<size_t>(ws_off) * 4, bpc = h->geo.bytes_per_codeword;
+    const DecodeWs W = carve_at(h->d_decode_ws.as<>(), [&](Carver& c) { return decode_ws_carve(c, h->ws_frames, bpc); });
+    if ((e = hipMemsetAsync(W.res + o4, 0, static_cast<size_t>(n_frames) * 4 * sizeof(CwResult), s)) != hipSuccess)
         return fail(h, RIA_ERR_HIP, "hipMemsetAsync: %s", hipGetErrorString(e));
     A.c = h->fast;
-    A.gather = static_cast<const uint16_t*>((flags & RIA_DECODE_NO_CHANNEL_DEINTERLEAVE) ? h->d_gather_nochan : h->d_gather);
+    A.gather = ((flags & RIA_DECODE_NO_CHANNEL_DEINTERLEAVE) ? h->d_gather_nochan : h->d_gather).as<const uint16_t>();
     A.llr = llr_dev;
     A.llr_stride = llr_stride;
     A.n_frames = n_frames;
     A.flags = flags;
     A.info_out = info_out_dev;
     A.status = status_dev;
-    A.crc_bit = static_cast<const uint16_t*>(h->d_crc_bit);
-    A.crc_init = static_cast<const uint16_t*>(h->d_crc_init);
-    A.ctl = h->d_ctl + slot;
-    A.entries = h->d_entries + o4;
-    A.best = h->d_best + o4;
-    A.list1 = h->d_list1 + o4;
-    A.res = h->d_res + o4;
-    A.res_bytes = h->d_res_bytes + o4 * kNumFactors * h->geo.bytes_per_codeword;
-    A.win = h->d_win + o4;
-    A.staged = h->d_staged + o4 * kStageFloats;
-    A.l1idx = h->d_l1idx + o4;
-    A.l1hash = h->d_l1hash + o4;
-    A.seed_ws = h->d_seed_ws + static_cast<size_t>(slot) * persist_grid_size(false) * kSeedWsWords;
+    A.crc_bit = h->d_crc_bit.as<const uint16_t>();
+    A.crc_init = h->d_crc_init.as<const uint16_t>();
+    A.ctl = h->d_ctl.as<DecodeCtl>() + slot;
+    A.entries = W.entries + o4;
+    A.best = W.best + o4;
+    A.list1 = W.list1 + o4;
+    A.res = W.res + o4;
+    A.res_bytes = W.res_bytes + o4 * kNumFactors * bpc;
+    A.win = W.win + o4;
+    A.staged = W.staged + o4 * kStageFloats;
+    A.l1idx = W.l1idx + o4;
+    A.l1hash = W.l1hash + o4;
+    A.seed_ws = h->d_seed_ws.as<uint32_t>() + static_cast<size_t>(slot) * persist_grid_size(false) * kSeedWsWords;
     if ((e = hipMemsetAsync(A.ctl, 0, sizeof(DecodeCtl), s)) != hipSuccess)
         return fail(h, RIA_ERR_HIP, "hipMemsetAsync: %s", hipGetErrorString(e));
     const int wb = h->wave_lds;
@@ -758,9 +749,9 @@ static int demod_batch_slot(ria_gpu_handle h, const float* samples_dev, const ui
                             int n_frames, float* llr_out_dev, ria_frame_status* status_dev, hipStream_t stream, int slot,
                             int llr_stride = 0 /* floats between the soft-bit rows of two frames; 0 = llrs_per_frame */) {
     DemodArgs A;
-    A.k = static_cast<const DemodConst*>(h->d_demod_const);
-    A.twiddle = static_cast<const float2*>(h->d_twiddle);
-    A.nco = static_cast<const float2*>(h->d_nco);
+    A.k = h->d_demod_const.as<const DemodConst>();
+    A.twiddle = h->d_twiddle.as<const float2>();
+    A.nco = h->d_nco.as<const float2>();
     A.samples = samples_dev;
     A.offsets = frame_offsets_dev;
     A.meta = meta_dev;
@@ -774,8 +765,8 @@ static int demod_batch_slot(ria_gpu_handle h, const float* samples_dev, const ui
 #endif
     if (demod_fused_selected()) launch_demod_fused(A, stream);
     else {
-        if (!h->d_demod_ws[slot]) HIP_TRY(h, hipMalloc(&h->d_demod_ws[slot], demod_ws_bytes(2 + h->geo.n_data_symbols)));
-        launch_demod(A, h->geo, h->cfg.modulation, h->d_demod_ws[slot], stream);
+        HIP_TRY(h, h->d_demod_ws[slot].reserve(demod_ws_bytes(2 + h->geo.n_data_symbols)));   // at the slot's first use
+        launch_demod(A, h->geo, h->cfg.modulation, h->d_demod_ws[slot].as<>(), stream);
     }
     HIP_TRY(h, hipGetLastError());
     return RIA_OK;
@@ -815,7 +806,7 @@ int ria_gpu_rx_batch(ria_gpu_handle h, const float* samples_dev, const uint64_t*
     for (int done = 0; done < n_frames;) {
         int nb = n_frames - done;
         if (!llr_out_dev && nb > h->cfg.max_batch) nb = h->cfg.max_batch;
-        float* llr = llr_out_dev ? llr_out_dev + static_cast<size_t>(done) * h->geo.llrs_per_frame : h->d_llr_ws;
+        float* llr = llr_out_dev ? llr_out_dev + static_cast<size_t>(done) * h->geo.llrs_per_frame : h->d_llr_ws.as<float>();
         const int n_parts = (nb >= 4096) ? want_parts : 1;
         {   // grow the workspaces BEFORE anything is in flight: the parts share them
             hipError_t e = ensure_decode_ws(h, nb);
@@ -860,18 +851,13 @@ int ria_gpu_rx_batch(ria_gpu_handle h, const float* samples_dev, const uint64_t*
 // staging block of the host-buffer entry points: `bytes` of device memory and as many of pinned host memory
 static int ensure_host_stage(ria_gpu_handle h, size_t bytes) {
     if (!h->hstream) HIP_TRY(h, hipStreamCreateWithFlags(&h->hstream, hipStreamNonBlocking));
-    if (bytes <= h->hstage_bytes) return RIA_OK;
-    HIP_TRY(h, hipStreamSynchronize(h->hstream));
-    if (h->d_hstage) (void)hipFree(h->d_hstage);
-    if (h->p_hstage) (void)hipHostFree(h->p_hstage);
-    h->d_hstage = nullptr; h->p_hstage = nullptr; h->hstage_bytes = 0;
     bytes = (bytes + (size_t(1) << 20) - 1) & ~((size_t(1) << 20) - 1);
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&h->d_hstage), bytes));
-    HIP_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&h->p_hstage), bytes, hipHostMallocDefault));
-    h->hstage_bytes = bytes;
+    if (bytes <= h->d_hstage.bytes() && bytes <= h->p_hstage.bytes()) return RIA_OK;
+    HIP_TRY(h, hipStreamSynchronize(h->hstream));   // one drain of the handle's stream for both blocks
+    HIP_TRY(h, h->d_hstage.reserve(bytes));
+    HIP_TRY(h, h->p_hstage.reserve(bytes));
     return RIA_OK;
 }
-static inline size_t up256(size_t v) { return (v + 255) & ~size_t(255); }
 
 int ria_gpu_rx_frames_host(ria_gpu_handle h, const float* samples_host, const ria_frame_meta* meta_host, int n_frames,
                            uint32_t flags, uint8_t* info_out_host, ria_decode_status* decode_status_host,
@@ -892,7 +878,7 @@ int ria_gpu_rx_frames_host(ria_gpu_handle h, const float* samples_host, const ri
     const size_t total = up256(o_fs + b_fs);
     int rc = ensure_host_stage(h, total);
     if (rc != RIA_OK) return rc;
-    unsigned char *D = h->d_hstage, *P = h->p_hstage;
+    unsigned char *D = h->d_hstage.as<unsigned char>(), *P = h->p_hstage.as<unsigned char>();
     hipStream_t s = h->hstream;
     std::memcpy(P + o_s, samples_host, b_s);
     if (meta_host) std::memcpy(P + o_m, meta_host, b_m);
@@ -929,7 +915,7 @@ int ria_gpu_decode_frames_host(ria_gpu_handle h, const float* llr_host, int llr_
     const size_t o_ds = up256(o_info + b_info), b_ds = n * sizeof(ria_decode_status), total = up256(o_ds + b_ds);
     int rc = ensure_host_stage(h, total);
     if (rc != RIA_OK) return rc;
-    unsigned char *D = h->d_hstage, *P = h->p_hstage;
+    unsigned char *D = h->d_hstage.as<unsigned char>(), *P = h->p_hstage.as<unsigned char>();
     hipStream_t s = h->hstream;
     std::memcpy(P, llr_host, b_llr);
     HIP_TRY(h, hipMemcpyAsync(D, P, b_llr, hipMemcpyHostToDevice, s));
@@ -950,8 +936,8 @@ int ria_gpu_make_frames(ria_gpu_handle h, uint64_t seed, int first_seq, int n_fr
     if (!h || !info_out_dev || n_frames < 0) return fail(h, RIA_ERR_INVALID, "ria_gpu_make_frames: bad argument");
     if (n_frames == 0) return RIA_OK;
     HIP_TRY(h, hipSetDevice(h->device));
-    launch_make_frames(static_cast<const TxConst*>(h->d_tx_const), static_cast<const uint16_t*>(h->d_crc_bit),
-                       static_cast<const uint16_t*>(h->d_crc_init), seed, first_seq, n_frames, h->geo, info_out_dev,
+    launch_make_frames(h->d_tx_const.as<const TxConst>(), h->d_crc_bit.as<const uint16_t>(),
+                       h->d_crc_init.as<const uint16_t>(), seed, first_seq, n_frames, h->geo, info_out_dev,
                        static_cast<hipStream_t>(stream));
     HIP_TRY(h, hipGetLastError());
     return RIA_OK;
@@ -962,8 +948,8 @@ int ria_gpu_tx_batch(ria_gpu_handle h, const uint8_t* info_dev, int n_frames, fl
     if (!h || !info_dev || !samples_out_dev || n_frames < 0) return fail(h, RIA_ERR_INVALID, "ria_gpu_tx_batch: bad argument");
     if (n_frames == 0) return RIA_OK;
     HIP_TRY(h, hipSetDevice(h->device));
-    launch_tx(static_cast<const TxConst*>(h->d_tx_const), static_cast<const float2*>(h->d_twiddle),
-              static_cast<const float2*>(h->d_nco), info_dev, n_frames, peak_normalize, h->geo, samples_out_dev,
+    launch_tx(h->d_tx_const.as<const TxConst>(), h->d_twiddle.as<const float2>(),
+              h->d_nco.as<const float2>(), info_dev, n_frames, peak_normalize, h->geo, samples_out_dev,
               static_cast<hipStream_t>(stream));
     HIP_TRY(h, hipGetLastError());
     return RIA_OK;
@@ -973,8 +959,8 @@ int ria_gpu_encode_frames_batch(ria_gpu_handle h, const uint8_t* info_dev, int n
     if (!h || !info_dev || !coded_out_dev || n_frames < 0) return fail(h, RIA_ERR_INVALID, "ria_gpu_encode_frames_batch: bad argument");
     if (n_frames == 0) return RIA_OK;
     HIP_TRY(h, hipSetDevice(h->device));
-    launch_tx_mode<1>(static_cast<const TxConst*>(h->d_tx_const), static_cast<const float2*>(h->d_twiddle),
-                      static_cast<const float2*>(h->d_nco), info_dev, n_frames, 0.0f, h->geo, nullptr, coded_out_dev,
+    launch_tx_mode<1>(h->d_tx_const.as<const TxConst>(), h->d_twiddle.as<const float2>(),
+                      h->d_nco.as<const float2>(), info_dev, n_frames, 0.0f, h->geo, nullptr, coded_out_dev,
                       static_cast<hipStream_t>(stream));
     HIP_TRY(h, hipGetLastError());
     return RIA_OK;
@@ -985,8 +971,8 @@ int ria_gpu_tx_coded_batch(ria_gpu_handle h, const uint8_t* coded_dev, int n_fra
     if (!h || !coded_dev || !samples_out_dev || n_frames < 0) return fail(h, RIA_ERR_INVALID, "ria_gpu_tx_coded_batch: bad argument");
     if (n_frames == 0) return RIA_OK;
     HIP_TRY(h, hipSetDevice(h->device));
-    launch_tx_mode<2>(static_cast<const TxConst*>(h->d_tx_const), static_cast<const float2*>(h->d_twiddle),
-                      static_cast<const float2*>(h->d_nco), coded_dev, n_frames, peak_normalize, h->geo, samples_out_dev, nullptr,
+    launch_tx_mode<2>(h->d_tx_const.as<const TxConst>(), h->d_twiddle.as<const float2>(),
+                      h->d_nco.as<const float2>(), coded_dev, n_frames, peak_normalize, h->geo, samples_out_dev, nullptr,
                       static_cast<hipStream_t>(stream));
     HIP_TRY(h, hipGetLastError());
     return RIA_OK;
@@ -1006,12 +992,7 @@ int ria_gpu_channel_batch(ria_gpu_handle h, int kind, float snr_db, uint64_t see
 
 // per-frame workspace of channel_power_kernel, grown on demand (a growth waits for the stream's earlier users of the old block)
 static int chan_ws(ria_gpu_handle h, int n_frames, hipStream_t s) {
-    if (n_frames <= h->chan_nstd_frames) return RIA_OK;
-    if (h->d_chan_nstd) { HIP_TRY(h, hipStreamSynchronize(s)); (void)hipFree(h->d_chan_nstd); }
-    h->d_chan_nstd = nullptr; h->chan_nstd_frames = 0;
-    const int cap = std::max(n_frames, 4096);
-    HIP_TRY(h, hipMalloc(&h->d_chan_nstd, static_cast<size_t>(cap) * sizeof(float)));
-    h->chan_nstd_frames = cap;
+    HIP_TRY(h, h->d_chan_nstd.reserve(static_cast<size_t>(std::max(n_frames, 4096)) * sizeof(float), &s));
     return RIA_OK;
 }
 
@@ -1023,7 +1004,7 @@ int ria_gpu_channel_exact_batch(ria_gpu_handle h, int kind, float snr_db, uint32
     if (!samples_dev) return fail(h, RIA_ERR_INVALID, "ria_gpu_channel_exact_batch: null samples");
     HIP_TRY(h, hipSetDevice(h->device));
     if (int rc = chan_ws(h, n_frames, static_cast<hipStream_t>(stream))) return rc;
-    launch_channel_exact(kind, snr_db, seed, first_frame, samples_dev, stride, frame_samples, n_frames, static_cast<hipStream_t>(stream), h->d_chan_nstd);
+    launch_channel_exact(kind, snr_db, seed, first_frame, samples_dev, stride, frame_samples, n_frames, static_cast<hipStream_t>(stream), h->d_chan_nstd.as<float>());
     HIP_TRY(h, hipGetLastError());
     return RIA_OK;
 }
@@ -1036,7 +1017,7 @@ int ria_gpu_channel_exact_seeded_batch(ria_gpu_handle h, int kind, float snr_db,
     if (!samples_dev || !seeds_dev) return fail(h, RIA_ERR_INVALID, "ria_gpu_channel_exact_seeded_batch: null pointer");
     HIP_TRY(h, hipSetDevice(h->device));
     if (int rc = chan_ws(h, n_frames, static_cast<hipStream_t>(stream))) return rc;
-    launch_channel_exact(kind, snr_db, 0u, 0u, samples_dev, stride, frame_samples, n_frames, static_cast<hipStream_t>(stream), h->d_chan_nstd, seeds_dev);
+    launch_channel_exact(kind, snr_db, 0u, 0u, samples_dev, stride, frame_samples, n_frames, static_cast<hipStream_t>(stream), h->d_chan_nstd.as<float>(), seeds_dev);
     HIP_TRY(h, hipGetLastError());
     return RIA_OK;
 }
@@ -1050,7 +1031,7 @@ int ria_gpu_channel_exact_cfo_batch(ria_gpu_handle h, int kind, float snr_db, co
     if (!samples_dev || !seeds_dev) return fail(h, RIA_ERR_INVALID, "ria_gpu_channel_exact_cfo_batch: null pointer");
     HIP_TRY(h, hipSetDevice(h->device));
     if (int rc = chan_ws(h, n_frames, static_cast<hipStream_t>(stream))) return rc;
-    launch_channel_exact(kind, snr_db, 0u, 0u, samples_dev, stride, frame_samples, n_frames, static_cast<hipStream_t>(stream), h->d_chan_nstd, seeds_dev,
+    launch_channel_exact(kind, snr_db, 0u, 0u, samples_dev, stride, frame_samples, n_frames, static_cast<hipStream_t>(stream), h->d_chan_nstd.as<float>(), seeds_dev,
                          cfo_hz_dev, 0.0f, random_cfo_max_hz, actual_cfo_out_dev);
     HIP_TRY(h, hipGetLastError());
     return RIA_OK;
@@ -1083,7 +1064,7 @@ static int sync_zc_impl(ria_gpu_handle h, const float* samples_dev, int64_t stri
         return fail(h, RIA_ERR_INVALID, "ria_gpu_sync_zc_batch: bad arguments");
     ZcArgs A{};
     A.samples = samples_dev; A.stride = stride; A.buf_len = buf_len; A.n_buffers = n_buffers; A.threshold = threshold;
-    A.root_mask = root_mask & 15u; A.known_cfo = known_cfo_dev; A.ref = static_cast<const float2*>(h->d_zc_ref); A.out = out_dev;
+    A.root_mask = root_mask & 15u; A.known_cfo = known_cfo_dev; A.ref = h->d_zc_ref.as<const float2>(); A.out = out_dev;
     A.threshold_dev = threshold_dev; A.param_stride = param_stride;
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1097,13 +1078,8 @@ static int sync_zc_impl(ria_gpu_handle h, const float* samples_dev, int64_t stri
     } else {                      // long search windows: baseband in a global workspace, chunks of buffers under 256 MiB
         const size_t per = static_cast<size_t>(buf_len) * sizeof(float2);
         const int chunk = static_cast<int>(std::min<size_t>(n_buffers, std::max<size_t>(1, (size_t(256) << 20) / per)));
-        if (per * chunk > h->zc_ws_bytes) {
-            if (h->d_zc_ws) { HIP_TRY(h, hipStreamSynchronize(s)); (void)hipFree(h->d_zc_ws); }
-            h->d_zc_ws = nullptr; h->zc_ws_bytes = 0;
-            HIP_TRY(h, hipMalloc(&h->d_zc_ws, per * chunk));
-            h->zc_ws_bytes = per * chunk;
-        }
-        A.bb_ws = static_cast<float2*>(h->d_zc_ws);
+        HIP_TRY(h, h->d_zc_ws.reserve(per * chunk, &s));   // a growth waits for the stream's earlier users of the old block
+        A.bb_ws = h->d_zc_ws.as<float2>();
         for (int first = 0; first < n_buffers; first += chunk) {
             A.samples = samples_dev + static_cast<int64_t>(first) * stride; A.n_buffers = std::min(chunk, n_buffers - first);
             A.known_cfo = known_cfo_dev ? known_cfo_dev + static_cast<int64_t>(first) * param_stride : nullptr; A.out = out_dev + first;
@@ -1162,35 +1138,27 @@ __global__ void chirp_template_conj_kernel(const float2* src, float2* dst) {
 static int chirp_prepare(ria_gpu_handle h, int chunk, int outer, hipStream_t s) {
     hipError_t e;
 #define C_TRY(expr) if ((e = (expr)) != hipSuccess) return fail(h, RIA_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e))
-    if (chunk > h->ch_chunk) {
-        for (void** p : {&h->d_ch_w1, &h->d_ch_w2, &h->d_ch_mag}) { if (*p) (void)hipFree(*p); *p = nullptr; }
-        const size_t c = static_cast<size_t>(chunk);
-        C_TRY(hipMalloc(&h->d_ch_w1, c * kChFft * sizeof(float2)));
-        C_TRY(hipMalloc(&h->d_ch_w2, c * kChFft * sizeof(float2)));
-        C_TRY(hipMalloc(&h->d_ch_mag, c * sizeof(unsigned long long)));   // packed first-maximum keys
-        h->ch_chunk = chunk;
-    }
-    if (outer > h->ch_outer) {
-        for (void** p : {&h->d_ch_cum, &h->d_ch_st}) { if (*p) (void)hipFree(*p); *p = nullptr; }
-        C_TRY(hipMalloc(&h->d_ch_cum, static_cast<size_t>(outer) * (kChFft + 1) * sizeof(float)));
-        C_TRY(hipMalloc(&h->d_ch_st, static_cast<size_t>(outer) * sizeof(ChirpBufState)));
-        h->ch_outer = outer;
-    }
+    const size_t c = static_cast<size_t>(chunk);
+    C_TRY(h->d_ch_w1.reserve(c * kChFft * sizeof(float2)));
+    C_TRY(h->d_ch_w2.reserve(c * kChFft * sizeof(float2)));
+    C_TRY(h->d_ch_mag.reserve(c * sizeof(unsigned long long)));   // packed first-maximum keys
+    C_TRY(h->d_ch_cum.reserve(static_cast<size_t>(outer) * (kChFft + 1) * sizeof(float)));
+    C_TRY(h->d_ch_st.reserve(static_cast<size_t>(outer) * sizeof(ChirpBufState)));
     if (!h->d_ch_tmpl_fft) {
         ChirpTables t = build_chirp_tables();
-        if (!h->d_ch_tw) C_TRY(upload(&h->d_ch_tw, t.tw));
-        C_TRY(upload(&h->d_ch_tmpl, t.tmpl));
+        if (!h->d_ch_tw) C_TRY(upload(h->d_ch_tw, t.tw));
+        C_TRY(upload(h->d_ch_tmpl, t.tmpl));
         h->ch_energy[0] = t.energy[0]; h->ch_energy[1] = t.energy[1];
-        C_TRY(hipMalloc(&h->d_ch_tmpl_fft, static_cast<size_t>(2) * kChFft * sizeof(float2)));
+        C_TRY(h->d_ch_tmpl_fft.reserve(static_cast<size_t>(2) * kChFft * sizeof(float2)));
         // conj(FFT(template)) with the same butterflies the signal goes through (chirp_sync.hpp:573-623)
         ChirpArgs A{};
-        A.n_buffers = 1; A.tw = static_cast<const float2*>(h->d_ch_tw); A.w1 = static_cast<float2*>(h->d_ch_w1);
-        A.w2 = static_cast<float2*>(h->d_ch_w2); A.st = static_cast<ChirpBufState*>(h->d_ch_st);
+        A.n_buffers = 1; A.tw = h->d_ch_tw.as<const float2>(); A.w1 = h->d_ch_w1.as<float2>();
+        A.w2 = h->d_ch_w2.as<float2>(); A.st = h->d_ch_st.as<ChirpBufState>();
         for (int d = 0; d < 2; ++d) {
-            hipLaunchKernelGGL(chirp_template_stage_kernel, dim3(kChFft / 256), dim3(256), 0, s, static_cast<const float*>(h->d_ch_tmpl), d, A.w2, A.st);
+            hipLaunchKernelGGL(chirp_template_stage_kernel, dim3(kChFft / 256), dim3(256), 0, s, h->d_ch_tmpl.as<const float>(), d, A.w2, A.st);
             chirp_fft_forward(A, 1, s, false, false);
             hipLaunchKernelGGL(chirp_template_conj_kernel, dim3(kChFft / 256), dim3(256), 0, s, static_cast<const float2*>(A.w1),
-                               static_cast<float2*>(h->d_ch_tmpl_fft) + static_cast<size_t>(d) * kChFft);
+                               h->d_ch_tmpl_fft.as<float2>() + static_cast<size_t>(d) * kChFft);
         }
         C_TRY(hipGetLastError());
     }
@@ -1226,10 +1194,10 @@ static int sync_chirp_impl(ria_gpu_handle h, const float* samples_dev, int64_t s
     }
     ChirpArgs A{};
     A.samples = samples_dev; A.stride = stride; A.buf_len = buf_len; A.threshold = threshold;
-    A.tw = static_cast<const float2*>(h->d_ch_tw); A.tmpl_fft = static_cast<const float2*>(h->d_ch_tmpl_fft);
-    A.tmpl = static_cast<const float*>(h->d_ch_tmpl); A.tmpl_energy[0] = h->ch_energy[0]; A.tmpl_energy[1] = h->ch_energy[1];
-    A.w1 = static_cast<float2*>(h->d_ch_w1); A.w2 = static_cast<float2*>(h->d_ch_w2); A.best = static_cast<unsigned long long*>(h->d_ch_mag);
-    A.cum = static_cast<float*>(h->d_ch_cum); A.st = static_cast<ChirpBufState*>(h->d_ch_st); A.out = out_dev;
+    A.tw = h->d_ch_tw.as<const float2>(); A.tmpl_fft = h->d_ch_tmpl_fft.as<const float2>();
+    A.tmpl = h->d_ch_tmpl.as<const float>(); A.tmpl_energy[0] = h->ch_energy[0]; A.tmpl_energy[1] = h->ch_energy[1];
+    A.w1 = h->d_ch_w1.as<float2>(); A.w2 = h->d_ch_w2.as<float2>(); A.best = h->d_ch_mag.as<unsigned long long>();
+    A.cum = h->d_ch_cum.as<float>(); A.st = h->d_ch_st.as<ChirpBufState>(); A.out = out_dev;
     A.threshold_dev = threshold_dev; A.param_stride = param_stride;
     for (int first = 0; first < n_buffers; first += outer) {
         const int nb = std::min(outer, n_buffers - first);
@@ -1271,27 +1239,21 @@ int ria_gpu_tx_cfo_batch(ria_gpu_handle h, const float* samples_dev, int64_t str
     if (n_samples > (1 << kTxCfoMaxLog)) return fail(h, RIA_ERR_UNSUPPORTED, "ria_gpu_tx_cfo_batch: at most 131072 samples per transmission");
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (!h->d_ch_tw) { ChirpTables t = build_chirp_tables(); HIP_TRY(h, upload(&h->d_ch_tw, t.tw)); }
+    if (!h->d_ch_tw) { ChirpTables t = build_chirp_tables(); HIP_TRY(h, upload(h->d_ch_tw, t.tw)); }
     int L = 0;
     while ((1 << L) < n_samples) ++L;
     const size_t N = size_t(1) << L, per = 2 * N * sizeof(float2) + static_cast<size_t>(n_samples) * sizeof(float);
     // buffers per pass: the workspace of one pass stays under 256 MiB (and the grid's y extent under 65536)
     const int chunk = static_cast<int>(std::min<size_t>(std::min(n_buffers, 32768), std::max<size_t>(1, (size_t(256) << 20) / per)));
-    const size_t need = per * static_cast<size_t>(chunk);
-    if (need > h->txcfo_ws_bytes) {
-        if (h->d_txcfo_ws) { HIP_TRY(h, hipStreamSynchronize(s)); (void)hipFree(h->d_txcfo_ws); }
-        h->d_txcfo_ws = nullptr; h->txcfo_ws_bytes = 0;
-        HIP_TRY(h, hipMalloc(&h->d_txcfo_ws, need));
-        h->txcfo_ws_bytes = need;
-    }
+    HIP_TRY(h, h->d_txcfo_ws.reserve(per * static_cast<size_t>(chunk), &s));   // a growth waits for the stream's earlier users of the old block
     for (int first = 0; first < n_buffers; first += chunk) {
         const int nb = std::min(chunk, n_buffers - first);
         TxCfoArgs A{};
         A.in = samples_dev + static_cast<int64_t>(first) * stride; A.in_stride = stride;
         A.out = out_dev + static_cast<int64_t>(first) * out_stride; A.out_stride = out_stride;
         A.n = n_samples; A.log2n = L; A.n_buffers = nb; A.cfo_hz = cfo_hz_dev + first; A.phase = phase_inout_dev ? phase_inout_dev + first : nullptr;
-        A.tw = static_cast<const float2*>(h->d_ch_tw);
-        A.w1 = static_cast<float2*>(h->d_txcfo_ws); A.w2 = A.w1 + static_cast<size_t>(nb) * N; A.ph = reinterpret_cast<float*>(A.w2 + static_cast<size_t>(nb) * N);
+        A.tw = h->d_ch_tw.as<const float2>();
+        A.w1 = h->d_txcfo_ws.as<float2>(); A.w2 = A.w1 + static_cast<size_t>(nb) * N; A.ph = reinterpret_cast<float*>(A.w2 + static_cast<size_t>(nb) * N);
         hipLaunchKernelGGL(txcfo_phase_kernel, dim3((nb + 63) / 64), dim3(64), 0, s, A);
         for (int inv = 0; inv < 2; ++inv) {
             float2* dst = inv ? A.w2 : A.w1;
@@ -1327,7 +1289,7 @@ int ria_gpu_chirp_preamble(ria_gpu_handle h, float* out_host, int max_n) {
 
 // the LTS detector's tables and LDS opt-in, made once per handle
 static int lts_prepare(ria_gpu_handle h) {
-    if (!h->d_hilbert65) { std::vector<float> hc = build_hilbert(65); HIP_TRY(h, upload(&h->d_hilbert65, hc)); }
+    if (!h->d_hilbert65) HIP_TRY(h, upload(h->d_hilbert65, build_hilbert(65)));
     if (!h->lts_lds_opted) {
         HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(lts_sync_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lts_lds_bytes()));
         h->lts_lds_opted = 1;
@@ -1345,7 +1307,7 @@ int ria_gpu_sync_lts_batch(ria_gpu_handle h, const float* samples_dev, int64_t s
     if (int rc = lts_prepare(h)) return rc;
     LtsArgs A{};
     A.samples = samples_dev; A.stride = stride; A.buf_len = buf_len; A.n_buffers = n_buffers; A.known_cfo = known_cfo_dev;
-    A.threshold = threshold; A.hilbert = static_cast<const float*>(h->d_hilbert65); A.out = out_dev;
+    A.threshold = threshold; A.hilbert = h->d_hilbert65.as<const float>(); A.out = out_dev;
     hipLaunchKernelGGL(lts_sync_kernel, dim3(n_buffers), dim3(kLtsThreads), lts_lds_bytes(), static_cast<hipStream_t>(stream), A);
     HIP_TRY(h, hipGetLastError());
     return RIA_OK;
@@ -1359,10 +1321,10 @@ int ria_gpu_sync_cox_batch(ria_gpu_handle h, const float* samples_dev, int64_t s
         return fail(h, RIA_ERR_INVALID, "ria_gpu_sync_cox_batch: bad arguments");
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (!h->d_cox_tI) {
+    if (!h->d_cox_tI || !h->d_cox_tQ) {
         const CoxTemplate t = build_cox_template(h->plan);
-        HIP_TRY(h, upload(&h->d_cox_tI, t.tI));
-        HIP_TRY(h, upload(&h->d_cox_tQ, t.tQ));
+        HIP_TRY(h, upload(h->d_cox_tI, t.tI));
+        HIP_TRY(h, upload(h->d_cox_tQ, t.tQ));
         h->cox_energy_ref = t.energy_ref;
     }
     const bool searched = buf_len >= kCoxMinSearch && buf_len >= kCoxTotal + kCoxWindow;
@@ -1372,21 +1334,15 @@ int ria_gpu_sync_cox_batch(ria_gpu_handle h, const float* samples_dev, int64_t s
     int chunk = n_buffers;
     if (per) chunk = static_cast<int>(std::min<size_t>(chunk, std::max<size_t>(1, (size_t(64) << 20) / per)));
     chunk = std::min(chunk, 32768);
-    const size_t need = per * static_cast<size_t>(chunk) + 16;
-    if (need > h->cox_ws_floats) {
-        if (h->d_cox_ws) { HIP_TRY(h, hipStreamSynchronize(s)); (void)hipFree(h->d_cox_ws); }
-        h->d_cox_ws = nullptr; h->cox_ws_floats = 0;
-        HIP_TRY(h, hipMalloc(&h->d_cox_ws, need * sizeof(float)));
-        h->cox_ws_floats = need;
-    }
+    HIP_TRY(h, h->d_cox_ws.reserve((per * static_cast<size_t>(chunk) + 16) * sizeof(float), &s));   // a growth waits for the stream's earlier users of the old block
     for (int first = 0; first < n_buffers; first += chunk) {
         const int nb = std::min(chunk, n_buffers - first);
         CoxArgs A{};
         A.samples = samples_dev + static_cast<int64_t>(first) * stride; A.stride = stride; A.buf_len = buf_len; A.n_buffers = nb;
         A.threshold = threshold; A.noise_in = noise_floor_dev ? noise_floor_dev + first : nullptr;
-        A.twiddle = static_cast<const float2*>(h->d_twiddle);
-        A.tI = static_cast<const float*>(h->d_cox_tI); A.tQ = static_cast<const float*>(h->d_cox_tQ); A.energy_ref = h->cox_energy_ref;
-        float* ws = static_cast<float*>(h->d_cox_ws);
+        A.twiddle = h->d_twiddle.as<const float2>();
+        A.tI = h->d_cox_tI.as<const float>(); A.tQ = h->d_cox_tQ.as<const float>(); A.energy_ref = h->cox_energy_ref;
+        float* ws = h->d_cox_ws.as<float>();
         A.dc = ws; A.metric = ws + static_cast<size_t>(nM) * nb; A.energy = ws + 2 * static_cast<size_t>(nM) * nb;
         A.nM = nM; A.nE = nE; A.out = out_dev + first;
         if (nM > 0) {
@@ -1409,69 +1365,71 @@ int ria_gpu_cox_preamble(ria_gpu_handle h, float* out_host, int max_n) {
 }
 
 // ------------------------------------------------------------------------------------------------ acquire + decode
-// layout of the acquisition workspace for n windows (offsets from d_acq_ws)
-struct AcqLayout {
-    size_t lts, list[2], info, dst, fst, ctl, total;
+// one work list of n rows: its four arrays back to back in one area, widest first
+static void take_frame_list(Carver& c, FrameList& l, size_t n) { c.take_list(n, l.offset, l.meta, l.window, l.state); }
+
+// the acquisition workspace for n windows
+struct AcqWs {
+    ria_lts_result* lts;
+    FrameList list[2];
+    uint8_t* info; ria_decode_status* dst; ria_frame_status* fst;   // compact outputs of one round
+    AcqCtl* ctl;
 };
-static AcqLayout acq_layout(size_t n, size_t info_bytes) {
-    AcqLayout L{};
-    size_t o = 0;
-    L.lts = o; o = up256(o + n * sizeof(ria_lts_result));
-    for (int q = 0; q < 2; ++q) { L.list[q] = o; o = up256(o + n * (sizeof(uint64_t) + sizeof(ria_frame_meta) + sizeof(uint32_t) + 1)); }
-    L.info = o; o = up256(o + n * info_bytes);
-    L.dst = o; o = up256(o + n * sizeof(ria_decode_status));
-    L.fst = o; o = up256(o + n * sizeof(ria_frame_status));
-    L.ctl = o; o = up256(o + sizeof(AcqCtl));
-    L.total = o;
-    return L;
-}
-static AcqList acq_list(unsigned char* base, size_t n) {   // the four arrays of one list, widest first
-    AcqList l;
-    l.offset = reinterpret_cast<uint64_t*>(base);
-    l.meta = reinterpret_cast<ria_frame_meta*>(base + n * sizeof(uint64_t));
-    l.window = reinterpret_cast<uint32_t*>(base + n * (sizeof(uint64_t) + sizeof(ria_frame_meta)));
-    l.cand = base + n * (sizeof(uint64_t) + sizeof(ria_frame_meta) + sizeof(uint32_t));
-    return l;
+static AcqWs acq_carve(Carver& c, size_t n, size_t info_bytes) {
+    AcqWs w;
+    w.lts = c.take<ria_lts_result>(n);
+    for (FrameList& l : w.list) take_frame_list(c, l, n);
+    w.info = c.take<uint8_t>(n * info_bytes);
+    w.dst = c.take<ria_decode_status>(n);
+    w.fst = c.take<ria_frame_status>(n);
+    w.ctl = c.take<AcqCtl>(1);
+    return w;
 }
 
 // grows the acquisition workspace to n_windows; nothing of an earlier call is in flight: every call ends on a stream sync
-static int acq_ensure_ws(ria_gpu_handle h, int n_windows) {
+static int acq_ensure_ws(ria_gpu_handle h, int n_windows, AcqWs* out) {
+    const size_t ib = static_cast<size_t>(h->geo.info_bytes_per_frame);
     if (n_windows > h->acq_windows) {
-        if (h->d_acq_ws) (void)hipFree(h->d_acq_ws);
-        h->d_acq_ws = nullptr; h->acq_windows = 0;
-        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&h->d_acq_ws), acq_layout(static_cast<size_t>(n_windows), static_cast<size_t>(h->geo.info_bytes_per_frame)).total));
+        h->acq_windows = 0;
+        HIP_TRY(h, h->d_acq_ws.reserve(carved_size([&](Carver& c) { return acq_carve(c, n_windows, ib); })));
         h->acq_windows = n_windows;
     }
-    if (!h->p_acq_ctl) HIP_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&h->p_acq_ctl), sizeof(AcqCtl), hipHostMallocDefault));
+    HIP_TRY(h, h->p_acq_ctl.reserve(sizeof(AcqCtl)));
+    *out = carve_at(h->d_acq_ws.as<>(), [&](Carver& c) { return acq_carve(c, h->acq_windows, ib); });
     return RIA_OK;
+}
+
+// LTS detection of every window with its own threshold and known CFO (ria_acq_params); lts_prepare has run
+static void launch_lts_acquire(ria_gpu_handle h, const float* samples_dev, int64_t stride, int search_len, int n_windows,
+                               const ria_acq_params* params_dev, ria_lts_result* out, hipStream_t s) {
+    LtsArgs S{};
+    S.samples = samples_dev; S.stride = stride; S.buf_len = search_len; S.n_buffers = n_windows;
+    S.known_cfo = &params_dev->known_cfo_hz; S.threshold_dev = &params_dev->detect_threshold;
+    S.param_stride = static_cast<int>(sizeof(ria_acq_params) / sizeof(float));
+    S.hilbert = h->d_hilbert65.as<const float>();
+    S.out = out;
+    hipLaunchKernelGGL(lts_sync_kernel, dim3(n_windows), dim3(kLtsThreads), lts_lds_bytes(), s, S);
 }
 
 // The rounds of ria_gpu_rx_acquire_batch on a planned round-0 list (lists[0] of the handle's workspace, its length in
 // A.ctl): round 0 runs every accepted window at its primary candidate, round r >= 1 the windows whose previous candidate
 // decoded nothing at their next candidate that fits; at most 8 recovery rounds (each advances every window it holds by at
 // least one of the 8 deltas).  A.acq / A.info_out / A.dst_out / A.fst_out take one row per window.
-static int acq_run_rounds(ria_gpu_handle h, const char* who, const float* samples_dev, AcqArgs A, const AcqLayout& L, int n_windows,
+static int acq_run_rounds(ria_gpu_handle h, const char* who, const float* samples_dev, AcqArgs A, const AcqWs& W, int n_windows,
                           uint32_t flags, hipStream_t s) {
-    unsigned char* W = h->d_acq_ws;
-    const size_t cap = static_cast<size_t>(h->acq_windows);
-    AcqList lists[2] = {acq_list(W + L.list[0], cap), acq_list(W + L.list[1], cap)};
-    A.info_c = W + L.info; A.dst_c = reinterpret_cast<const ria_decode_status*>(W + L.dst);
-    A.fst_c = reinterpret_cast<const ria_frame_status*>(W + L.fst);
+    A.info_c = W.info; A.dst_c = W.dst; A.fst_c = W.fst;
     const uint32_t dflags = flags & (RIA_DECODE_FULL | RIA_DECODE_NO_CHANNEL_DEINTERLEAVE);
     for (int round = 0;; ++round) {
-        HIP_TRY(h, hipMemcpyAsync(h->p_acq_ctl, A.ctl, sizeof(AcqCtl), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipStreamSynchronize(s));
-        if (h->p_acq_ctl->fault) return fail(h, RIA_ERR_HIP, "decode work-queue fault in round %d: no window of this call was decoded", round - 1);
-        const int n_list = static_cast<int>(h->p_acq_ctl->n_list);
+        if (int rc = read_ctl(h, h->p_acq_ctl, A.ctl, s, "decode work-queue fault in round %d: no window of this call was decoded", round - 1)) return rc;
+        const int n_list = static_cast<int>(h->p_acq_ctl.as<AcqCtl>()->n_list);
         if (n_list == 0) break;
         if (n_list > n_windows || round >= kAcqCandidates) return fail(h, RIA_ERR_HIP, "%s: work list of round %d broke its bound (%d)", who, round, n_list);
-        A.cur = lists[round & 1];
-        A.next = lists[(round + 1) & 1];
+        A.cur = W.list[round & 1];
+        A.next = W.list[(round + 1) & 1];
         A.n_cur = n_list;
         A.round = round;
         A.retry = !(flags & RIA_ACQ_NO_TIMING_RETRY) && round + 1 < kAcqCandidates;
-        int rc = ria_gpu_rx_batch(h, samples_dev, A.cur.offset, A.cur.meta, n_list, dflags, W + L.info,
-                                  reinterpret_cast<ria_decode_status*>(W + L.dst), nullptr, reinterpret_cast<ria_frame_status*>(W + L.fst), s);
+        int rc = ria_gpu_rx_batch(h, samples_dev, A.cur.offset, A.cur.meta, n_list, dflags, W.info, W.dst, nullptr, W.fst, s);
         if (rc != RIA_OK) return rc;
         hipLaunchKernelGGL(acq_scatter_kernel, dim3(std::min((n_list + 3) / 4, 4096)), dim3(256), 0, s, A);
         hipLaunchKernelGGL(acq_next_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A);
@@ -1495,33 +1453,24 @@ int ria_gpu_rx_acquire_batch(ria_gpu_handle h, const float* samples_dev, int64_t
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (int rc = lts_prepare(h)) return rc;
     const size_t n = static_cast<size_t>(n_windows), ib = static_cast<size_t>(h->geo.info_bytes_per_frame);
-    if (int rc = acq_ensure_ws(h, n_windows)) return rc;
-    const size_t cap = static_cast<size_t>(h->acq_windows);
-    const AcqLayout L = acq_layout(cap, ib);
-    unsigned char* W = h->d_acq_ws;
+    AcqWs W;
+    if (int rc = acq_ensure_ws(h, n_windows, &W)) return rc;
     HIP_TRY(h, hipMemsetAsync(info_out_dev, 0, n * ib, s));
     HIP_TRY(h, hipMemsetAsync(decode_status_dev, 0, n * sizeof(ria_decode_status), s));
     if (demod_status_dev) HIP_TRY(h, hipMemsetAsync(demod_status_dev, 0, n * sizeof(ria_frame_status), s));
 
     // 1. LTS detection with each window's threshold and known CFO
-    LtsArgs S{};
-    S.samples = samples_dev; S.stride = stride; S.buf_len = search_len; S.n_buffers = n_windows;
-    S.known_cfo = &params_dev->known_cfo_hz; S.threshold_dev = &params_dev->detect_threshold;
-    S.param_stride = static_cast<int>(sizeof(ria_acq_params) / sizeof(float));
-    S.hilbert = static_cast<const float*>(h->d_hilbert65);
-    S.out = reinterpret_cast<ria_lts_result*>(W + L.lts);
-    hipLaunchKernelGGL(lts_sync_kernel, dim3(n_windows), dim3(kLtsThreads), lts_lds_bytes(), s, S);
+    launch_lts_acquire(h, samples_dev, stride, search_len, n_windows, params_dev, W.lts, s);
     // 2. acceptance + the round-0 list
     AcqArgs A{};
-    A.lts = S.out; A.params = params_dev; A.n_windows = n_windows; A.window_len = window_len;
+    A.lts = W.lts; A.params = params_dev; A.n_windows = n_windows; A.window_len = window_len;
     A.frame_samples = h->geo.frame_samples; A.stride = stride; A.acq = acq_dev;
-    A.ctl = reinterpret_cast<AcqCtl*>(W + L.ctl);
-    AcqList lists[2] = {acq_list(W + L.list[0], cap), acq_list(W + L.list[1], cap)};
-    A.next = lists[0];
+    A.ctl = W.ctl;
+    A.next = W.list[0];
     hipLaunchKernelGGL(acq_plan_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A);
     HIP_TRY(h, hipGetLastError());
     A.info_bytes = static_cast<int>(ib); A.info_out = info_out_dev; A.dst_out = decode_status_dev; A.fst_out = demod_status_dev;
-    return acq_run_rounds(h, "ria_gpu_rx_acquire_batch", samples_dev, A, L, n_windows, flags, s);
+    return acq_run_rounds(h, "ria_gpu_rx_acquire_batch", samples_dev, A, W, n_windows, flags, s);
 }
 
 // ------------------------------------------------------------------------------------------------ burst groups + continuation
@@ -1529,37 +1478,31 @@ static_assert(sizeof(ria_burst_result) == 64, "ria_burst_result is 64 bytes (inc
 static_assert(offsetof(ria_burst_result, cfo_hz) == 20 && offsetof(ria_burst_result, delta) == 24 && offsetof(ria_burst_result, mode) == 28 &&
               offsetof(ria_burst_result, stop) == 31 && offsetof(ria_burst_result, reserved) == 32, "ria_burst_result field offsets");
 
-// layout of the burst workspace for n windows and groups of N frames (offsets from d_burst_ws)
-struct BurstLayout {
-    size_t acq0, info0, dst0, fst0, cwin0, list[4], gfst, gpos, done, ctl, gllr, dec_in, dec_info, dec_dst, total;
+// the burst workspace for n windows and groups of N frames
+struct BurstWs {
+    ria_acq_result* acq0; uint8_t* info0; ria_decode_status* dst0; ria_frame_status* fst0; uint32_t* cwin0;
+    FrameList list[4];            // group / continuation lists of the round, then their stage lists
+    ria_frame_status* gfst; uint32_t* gpos; uint32_t* done;
+    BurstCtl* ctl;
+    float* gllr; float* dec_in; uint8_t* dec_info; ria_decode_status* dec_dst;
 };
-static BurstLayout burst_layout(size_t n, size_t N, size_t info_bytes, size_t llrs) {
-    BurstLayout L{};
-    size_t o = 0;
-    L.acq0 = o; o = up256(o + n * sizeof(ria_acq_result));
-    L.info0 = o; o = up256(o + n * info_bytes);
-    L.dst0 = o; o = up256(o + n * sizeof(ria_decode_status));
-    L.fst0 = o; o = up256(o + n * sizeof(ria_frame_status));
-    L.cwin0 = o; o = up256(o + n * sizeof(uint32_t));
-    for (int q = 0; q < 4; ++q) { L.list[q] = o; o = up256(o + n * (sizeof(uint64_t) + sizeof(ria_frame_meta) + sizeof(uint32_t) + 1)); }
-    L.gfst = o; o = up256(o + n * sizeof(ria_frame_status));
-    L.gpos = o; o = up256(o + n * kBurstMaxGroup * sizeof(uint32_t));
-    L.done = o; o = up256(o + n * sizeof(uint32_t));
-    L.ctl = o; o = up256(o + sizeof(BurstCtl));
-    L.gllr = o; o = up256(o + n * N * llrs * sizeof(float));
-    L.dec_in = o; o = up256(o + n * N * kBurstFrameBits * sizeof(float));
-    L.dec_info = o; o = up256(o + n * N * info_bytes);
-    L.dec_dst = o; o = up256(o + n * N * sizeof(ria_decode_status));
-    L.total = o;
-    return L;
-}
-static BurstList burst_list(unsigned char* base, size_t n) {   // the four arrays of one list, widest first
-    BurstList l;
-    l.offset = reinterpret_cast<uint64_t*>(base);
-    l.meta = reinterpret_cast<ria_frame_meta*>(base + n * sizeof(uint64_t));
-    l.window = reinterpret_cast<uint32_t*>(base + n * (sizeof(uint64_t) + sizeof(ria_frame_meta)));
-    l.keep = base + n * (sizeof(uint64_t) + sizeof(ria_frame_meta) + sizeof(uint32_t));
-    return l;
+static BurstWs burst_carve(Carver& c, size_t n, size_t N, size_t info_bytes, size_t llrs) {
+    BurstWs w;
+    w.acq0 = c.take<ria_acq_result>(n);
+    w.info0 = c.take<uint8_t>(n * info_bytes);
+    w.dst0 = c.take<ria_decode_status>(n);
+    w.fst0 = c.take<ria_frame_status>(n);
+    w.cwin0 = c.take<uint32_t>(n);
+    for (FrameList& l : w.list) take_frame_list(c, l, n);
+    w.gfst = c.take<ria_frame_status>(n);
+    w.gpos = c.take<uint32_t>(n * kBurstMaxGroup);
+    w.done = c.take<uint32_t>(n);
+    w.ctl = c.take<BurstCtl>(1);
+    w.gllr = c.take<float>(n * N * llrs);
+    w.dec_in = c.take<float>(n * N * kBurstFrameBits);
+    w.dec_info = c.take<uint8_t>(n * N * info_bytes);
+    w.dec_dst = c.take<ria_decode_status>(n * N);
+    return w;
 }
 
 int ria_gpu_rx_burst_batch(ria_gpu_handle h, const float* samples_dev, int64_t stride, int search_len, int window_len,
@@ -1583,87 +1526,68 @@ int ria_gpu_rx_burst_batch(ria_gpu_handle h, const float* samples_dev, int64_t s
     const size_t llrs = static_cast<size_t>(h->geo.llrs_per_frame);
     const bool interleave = (flags & RIA_BURST_INTERLEAVE) != 0;
     // every workspace grows here, before anything of this call is in flight (an earlier call has ended on a stream sync)
-    if (int rc = acq_ensure_ws(h, n_windows)) return rc;
-    const BurstLayout B = burst_layout(n, interleave ? N : 0, ib, llrs);
-    if (B.total > h->burst_bytes) {
-        if (h->d_burst_ws) (void)hipFree(h->d_burst_ws);
-        h->d_burst_ws = nullptr; h->burst_bytes = 0;
-        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&h->d_burst_ws), B.total));
-        h->burst_bytes = B.total;
-    }
-    if (!h->p_burst_ctl) HIP_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&h->p_burst_ctl), sizeof(BurstCtl), hipHostMallocDefault));
+    AcqWs W;
+    if (int rc = acq_ensure_ws(h, n_windows, &W)) return rc;
+    auto carve = [&](Carver& c) { return burst_carve(c, n, interleave ? N : 0, ib, llrs); };
+    HIP_TRY(h, h->d_burst_ws.reserve(carved_size(carve)));
+    HIP_TRY(h, h->p_burst_ctl.reserve(sizeof(BurstCtl)));
+    const BurstWs B = carve_at(h->d_burst_ws.as<>(), carve);
     {
         const int dec_frames = static_cast<int>(n * (interleave ? N : 1));
         hipError_t e = ensure_decode_ws(h, dec_frames);
         if (e == hipSuccess && (flags & RIA_DECODE_CRC_RECOVER)) e = ensure_recovery_ws(h, std::max(dec_frames, h->cfg.max_batch), false);
         if (e != hipSuccess) return fail(h, RIA_ERR_HIP, "burst workspace: %s", hipGetErrorString(e));
     }
-    const AcqLayout L = acq_layout(static_cast<size_t>(h->acq_windows), ib);
-    unsigned char* W = h->d_acq_ws;
-    unsigned char* V = h->d_burst_ws;
     HIP_TRY(h, hipMemsetAsync(info_out_dev, 0, n * kBurstSlots * ib, s));
     HIP_TRY(h, hipMemsetAsync(decode_status_dev, 0, n * kBurstSlots * sizeof(ria_decode_status), s));
     if (demod_status_dev) HIP_TRY(h, hipMemsetAsync(demod_status_dev, 0, n * kBurstSlots * sizeof(ria_frame_status), s));
     if (cfo_used_dev) HIP_TRY(h, hipMemsetAsync(cfo_used_dev, 0, n * kBurstSlots * sizeof(float), s));
     if (rms_dev) HIP_TRY(h, hipMemsetAsync(rms_dev, 0, n * kBurstSlots * sizeof(float), s));
-    HIP_TRY(h, hipMemsetAsync(V + B.info0, 0, B.cwin0 - B.info0, s));   // frame-0 bytes, decode and demod status rows
+    HIP_TRY(h, hipMemsetAsync(B.info0, 0, span_bytes(B.info0, B.cwin0), s));   // frame-0 bytes, decode and demod status rows
 
     // 1. LTS detection with each window's threshold and known CFO
-    LtsArgs S{};
-    S.samples = samples_dev; S.stride = stride; S.buf_len = search_len; S.n_buffers = n_windows;
-    S.known_cfo = &params_dev->known_cfo_hz; S.threshold_dev = &params_dev->detect_threshold;
-    S.param_stride = static_cast<int>(sizeof(ria_acq_params) / sizeof(float));
-    S.hilbert = static_cast<const float*>(h->d_hilbert65);
-    S.out = reinterpret_cast<ria_lts_result*>(W + L.lts);
-    hipLaunchKernelGGL(lts_sync_kernel, dim3(n_windows), dim3(kLtsThreads), lts_lds_bytes(), s, S);
+    launch_lts_acquire(h, samples_dev, stride, search_len, n_windows, params_dev, W.lts, s);
     // 2. acceptance, modes and the two round-0 lists
     BurstArgs A{};
     A.samples = samples_dev; A.stride = stride; A.n_windows = n_windows; A.window_len = window_len;
     A.frame_samples = h->geo.frame_samples; A.group_size = group_size; A.flags = flags;
-    A.lts = S.out; A.params = params_dev; A.res = burst_dev;
-    A.ctl = reinterpret_cast<BurstCtl*>(V + B.ctl);
-    A.acq_ctl = reinterpret_cast<AcqCtl*>(W + L.ctl);
-    A.acq_first = acq_list(W + L.list[0], static_cast<size_t>(h->acq_windows));
-    A.acq0 = reinterpret_cast<ria_acq_result*>(V + B.acq0);
-    A.info0 = V + B.info0; A.dst0 = reinterpret_cast<const ria_decode_status*>(V + B.dst0);
-    A.fst0 = reinterpret_cast<const ria_frame_status*>(V + B.fst0);
-    A.c_win0 = reinterpret_cast<uint32_t*>(V + B.cwin0);
-    A.g_cur = burst_list(V + B.list[0], n); A.c_cur = burst_list(V + B.list[1], n);
-    A.g_stage = burst_list(V + B.list[2], n); A.c_stage = burst_list(V + B.list[3], n);
-    A.g_fst = reinterpret_cast<const ria_frame_status*>(V + B.gfst);
+    A.lts = W.lts; A.params = params_dev; A.res = burst_dev;
+    A.ctl = B.ctl;
+    A.acq_ctl = W.ctl;
+    A.acq_first = W.list[0];
+    A.acq0 = B.acq0;
+    A.info0 = B.info0; A.dst0 = B.dst0; A.fst0 = B.fst0;
+    A.c_win0 = B.cwin0;
+    A.g_cur = B.list[0]; A.c_cur = B.list[1];
+    A.g_stage = B.list[2]; A.c_stage = B.list[3];
+    A.g_fst = B.gfst;
     A.info_bytes = static_cast<int>(ib);
     A.info_out = info_out_dev; A.dst_out = decode_status_dev; A.fst_out = demod_status_dev; A.cfo_used = cfo_used_dev; A.rms = rms_dev;
-    A.gpos = reinterpret_cast<uint32_t*>(V + B.gpos); A.done = reinterpret_cast<uint32_t*>(V + B.done);
-    A.gllr = reinterpret_cast<const float*>(V + B.gllr); A.llr_stride = static_cast<int>(llrs);
-    A.dec_in = reinterpret_cast<float*>(V + B.dec_in); A.dec_info = V + B.dec_info;
-    A.dec_dst = reinterpret_cast<const ria_decode_status*>(V + B.dec_dst);
+    A.gpos = B.gpos; A.done = B.done;
+    A.gllr = B.gllr; A.llr_stride = static_cast<int>(llrs);
+    A.dec_in = B.dec_in; A.dec_info = B.dec_info;
+    A.dec_dst = B.dec_dst;
     hipLaunchKernelGGL(burst_plan_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A);
     HIP_TRY(h, hipGetLastError());
     const uint32_t dflags = flags & (RIA_DECODE_FULL | RIA_DECODE_NO_CHANNEL_DEINTERLEAVE);
-    float* gllr = reinterpret_cast<float*>(V + B.gllr);
-    auto read_ctl = [&]() -> int {
-        HIP_TRY(h, hipMemcpyAsync(h->p_burst_ctl, A.ctl, sizeof(BurstCtl), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipStreamSynchronize(s));
-        if (h->p_burst_ctl->fault) return fail(h, RIA_ERR_HIP, "ria_gpu_rx_burst_batch: decode work-queue fault: no window of this call was decoded");
-        return RIA_OK;
-    };
+    const BurstCtl& ctl = *h->p_burst_ctl.as<BurstCtl>();
+    auto read_burst_ctl = [&]() { return read_ctl(h, h->p_burst_ctl, A.ctl, s, "ria_gpu_rx_burst_batch: decode work-queue fault: no window of this call was decoded"); };
     // demodulates the group list's frames as physical frame f: row i of the list writes soft-bit row i * N + f
     auto demod_groups = [&](int n_g, int f) -> int {
-        return demod_batch_slot(h, samples_dev, A.g_cur.offset, A.g_cur.meta, n_g, gllr + static_cast<size_t>(f) * llrs,
-                                reinterpret_cast<ria_frame_status*>(V + B.gfst), s, 0, static_cast<int>(N * llrs));
+        return demod_batch_slot(h, samples_dev, A.g_cur.offset, A.g_cur.meta, n_g, B.gllr + static_cast<size_t>(f) * llrs, B.gfst, s, 0,
+                                static_cast<int>(N * llrs));
     };
-    if (int rc = read_ctl()) return rc;
-    int n_g = static_cast<int>(h->p_burst_ctl->n_group), n_c = static_cast<int>(h->p_burst_ctl->n_cont);
+    if (int rc = read_burst_ctl()) return rc;
+    int n_g = static_cast<int>(ctl.n_group), n_c = static_cast<int>(ctl.n_cont);
     if (n_g + n_c > n_windows || (n_g && !interleave)) return fail(h, RIA_ERR_HIP, "ria_gpu_rx_burst_batch: round-0 lists broke their bound (%d, %d)", n_g, n_c);
     // 3. frame 0: the groups' first frames are demodulated, the other windows go through ria_gpu_rx_acquire_batch's rounds
     if (n_g) { if (int rc = demod_groups(n_g, 0)) return rc; }
     if (n_c) {
         AcqArgs Q{};
-        Q.lts = S.out; Q.params = params_dev; Q.n_windows = n_windows; Q.window_len = window_len;
+        Q.lts = W.lts; Q.params = params_dev; Q.n_windows = n_windows; Q.window_len = window_len;
         Q.frame_samples = h->geo.frame_samples; Q.stride = stride; Q.acq = A.acq0; Q.ctl = A.acq_ctl;
-        Q.info_bytes = static_cast<int>(ib); Q.info_out = V + B.info0; Q.dst_out = reinterpret_cast<ria_decode_status*>(V + B.dst0);
-        Q.fst_out = reinterpret_cast<ria_frame_status*>(V + B.fst0);
-        if (int rc = acq_run_rounds(h, "ria_gpu_rx_burst_batch", samples_dev, Q, L, n_windows, flags, s)) return rc;
+        Q.info_bytes = static_cast<int>(ib); Q.info_out = B.info0; Q.dst_out = B.dst0; Q.fst_out = B.fst0;
+        if (int rc = acq_run_rounds(h, "ria_gpu_rx_burst_batch", samples_dev, Q, W, n_windows, flags, s)) return rc;
     }
     // 4. rounds: round f runs physical frame f of the windows still live; a group needs rounds 1 .. group_size - 1, a
     // continuation at most rounds 1 .. 8, and the step after the last of them lists nothing
@@ -1672,23 +1596,19 @@ int ria_gpu_rx_burst_batch(ria_gpu_handle h, const float* samples_dev, int64_t s
         if (round > kBurstSlots) return fail(h, RIA_ERR_HIP, "ria_gpu_rx_burst_batch: round %d is past the bound (%d, %d)", round, n_g, n_c);
         A.n_g = n_g; A.n_c = n_c; A.round = round; A.first = round == 1;
         if (round == 1) { A.c_fst = A.fst0; A.c_dst = A.dst0; A.c_info = A.info0; }
-        else {
-            A.c_fst = reinterpret_cast<const ria_frame_status*>(W + L.fst); A.c_dst = reinterpret_cast<const ria_decode_status*>(W + L.dst);
-            A.c_info = W + L.info;
-        }
+        else { A.c_fst = W.fst; A.c_dst = W.dst; A.c_info = W.info; }
         hipLaunchKernelGGL(burst_step_kernel, dim3((n_g + n_c + kBurstStepWaves - 1) / kBurstStepWaves), dim3(64 * kBurstStepWaves), 0, s, A);
         hipLaunchKernelGGL(burst_list_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A);
         HIP_TRY(h, hipGetLastError());
-        if (int rc = read_ctl()) return rc;
-        const int ng2 = static_cast<int>(h->p_burst_ctl->n_group), nc2 = static_cast<int>(h->p_burst_ctl->n_cont);
-        n_done = static_cast<int>(h->p_burst_ctl->n_done);
+        if (int rc = read_burst_ctl()) return rc;
+        const int ng2 = static_cast<int>(ctl.n_group), nc2 = static_cast<int>(ctl.n_cont);
+        n_done = static_cast<int>(ctl.n_done);
         if (ng2 > n_g || nc2 > n_c || n_done > n_windows || (ng2 && round >= group_size))
             return fail(h, RIA_ERR_HIP, "ria_gpu_rx_burst_batch: lists of round %d broke their bound (%d, %d, %d)", round, ng2, nc2, n_done);
         n_g = ng2; n_c = nc2;
         if (n_g) { if (int rc = demod_groups(n_g, round)) return rc; }
         if (n_c) {
-            int rc = ria_gpu_rx_batch(h, samples_dev, A.c_cur.offset, A.c_cur.meta, n_c, dflags, W + L.info,
-                                      reinterpret_cast<ria_decode_status*>(W + L.dst), nullptr, reinterpret_cast<ria_frame_status*>(W + L.fst), s);
+            int rc = ria_gpu_rx_batch(h, samples_dev, A.c_cur.offset, A.c_cur.meta, n_c, dflags, W.info, W.dst, nullptr, W.fst, s);
             if (rc != RIA_OK) return rc;
         }
     }
@@ -1697,12 +1617,11 @@ int ria_gpu_rx_burst_batch(ria_gpu_handle h, const float* samples_dev, int64_t s
         A.n_done = n_done;
         const long long items = static_cast<long long>(n_done) * group_size * 324;
         hipLaunchKernelGGL(burst_gather_kernel, dim3(static_cast<unsigned>(std::min<long long>((items + 255) / 256, 16384))), dim3(256), 0, s, A);
-        int rc = launch_decode(h, A.dec_in, kBurstFrameBits, n_done * group_size, dflags, V + B.dec_info,
-                               reinterpret_cast<ria_decode_status*>(V + B.dec_dst), s);
+        int rc = launch_decode(h, A.dec_in, kBurstFrameBits, n_done * group_size, dflags, B.dec_info, B.dec_dst, s);
         if (rc != RIA_OK) return rc;
         hipLaunchKernelGGL(burst_scatter_kernel, dim3(std::min((n_done * group_size + 3) / 4, 4096)), dim3(256), 0, s, A);
         HIP_TRY(h, hipGetLastError());
-        if (int rc2 = read_ctl()) return rc2;
+        if (int rc2 = read_burst_ctl()) return rc2;
     }
     return RIA_OK;
 }
@@ -1711,14 +1630,8 @@ int ria_gpu_sync_host(ria_gpu_handle h, int kind, const float* samples_host, int
                       uint32_t root_mask, void* result_out) {
     if (!h || !samples_host || !result_out || n_samples < 0 || kind < 0 || kind > 3) return RIA_ERR_INVALID;
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t need = static_cast<size_t>(n_samples) * sizeof(float) + 64;
-    if (need > h->sync_host_bytes) {
-        if (h->d_sync_host) (void)hipFree(h->d_sync_host);
-        h->d_sync_host = nullptr; h->sync_host_bytes = 0;
-        HIP_TRY(h, hipMalloc(&h->d_sync_host, need));
-        h->sync_host_bytes = need;
-    }
-    unsigned char* base = static_cast<unsigned char*>(h->d_sync_host);
+    HIP_TRY(h, h->d_sync_host.reserve(static_cast<size_t>(n_samples) * sizeof(float) + 64));   // no drain: every call ends on a device sync
+    unsigned char* base = h->d_sync_host.as<unsigned char>();
     float* d_param = reinterpret_cast<float*>(base);
     void* d_res = base + 16;
     float* d_x = reinterpret_cast<float*>(base + 64);
@@ -1770,13 +1683,9 @@ static int mcdpsk_demod_impl(ria_gpu_handle h, const ria_mcdpsk_config* cfg, con
     const int nds = std::max(1, num_rx / cfg->spreading);
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (!h->d_mc_mixer.count(nc)) {
-        void* p = nullptr;
-        std::vector<float> m = build_mcdpsk_mixer(nc);
-        HIP_TRY(h, upload(&p, m));
-        h->d_mc_mixer[nc] = p;
-    }
-    if (!h->d_mc_hilbert) { std::vector<float> hc = build_hilbert127(); HIP_TRY(h, upload(&h->d_mc_hilbert, hc)); }
+    DevBuf& mixer = h->d_mc_mixer[nc];
+    if (!mixer) HIP_TRY(h, upload(mixer, build_mcdpsk_mixer(nc)));
+    if (!h->d_mc_hilbert) HIP_TRY(h, upload(h->d_mc_hilbert, build_hilbert127()));
     const int lds = mcdpsk_lds_bytes(nc, frame_samples);
     if (lds > 160 * 1024) return fail(h, RIA_ERR_UNSUPPORTED, "ria_gpu_mcdpsk_demod_batch: frame too long for one workgroup's LDS");
     if (lds > h->mc_lds_opted) {
@@ -1787,26 +1696,18 @@ static int mcdpsk_demod_impl(ria_gpu_handle h, const ria_mcdpsk_config* cfg, con
     // workspace; a batch is walked in chunks of frames that fit it
     const size_t per_frame = mcdpsk_ws_floats_per_frame(nc, frame_samples, cfg->spreading, cfo_hz_dev != nullptr);
     const int chunk = static_cast<int>(std::min<size_t>(static_cast<size_t>(n_frames), std::max<size_t>(1, (size_t(256) << 20) / (per_frame * sizeof(float)))));
-    {
-        const size_t need = static_cast<size_t>(chunk) * per_frame + 64;
-        if (need > h->mc_ws_floats) {
-            if (h->d_mc_ws) { HIP_TRY(h, hipStreamSynchronize(s)); (void)hipFree(h->d_mc_ws); }
-            h->d_mc_ws = nullptr; h->mc_ws_floats = 0;
-            HIP_TRY(h, hipMalloc(&h->d_mc_ws, need * sizeof(float)));
-            h->mc_ws_floats = need;
-        }
-    }
+    HIP_TRY(h, h->d_mc_ws.reserve((static_cast<size_t>(chunk) * per_frame + 64) * sizeof(float), &s));   // a growth waits for the stream's earlier users of the old block
     McArgs A{};
     A.samples = samples_dev; A.stride = stride; A.frame_samples = frame_samples; A.nc = nc; A.bps = cfg->bits_per_symbol;
-    A.spreading = cfg->spreading; A.cfo = cfo_hz_dev; A.phase0 = phase0_dev; A.mixer = static_cast<const float2*>(h->d_mc_mixer[nc]);
-    A.hilbert = static_cast<const float*>(h->d_mc_hilbert); A.llr = llr_out_dev;
+    A.spreading = cfg->spreading; A.cfo = cfo_hz_dev; A.phase0 = phase0_dev; A.mixer = mixer.as<const float2>();
+    A.hilbert = h->d_mc_hilbert.as<const float>(); A.llr = llr_out_dev;
     A.llr_stride = llr_stride; A.status = status_dev; A.chunk = mcdpsk_corr_chunk(nc, frame_samples);
     A.offset = offsets_dev; A.bps_list = bps_dev;
     const size_t n_sym = static_cast<size_t>(3 + num_rx);
     for (int first = 0; first < n_frames; first += chunk) {
         A.first = first; A.n_frames = std::min(chunk, n_frames - first);
         const size_t F = static_cast<size_t>(A.n_frames);
-        float* p = static_cast<float*>(h->d_mc_ws);
+        float* p = h->d_mc_ws.as<float>();
         A.ws = p; if (cfo_hz_dev) p += F * 2 * frame_samples;
         p = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(p) + 15) & ~uintptr_t(15));
         A.Yg = reinterpret_cast<float2*>(p); p += 2 * n_sym * nc * F;
@@ -1838,7 +1739,7 @@ int ria_gpu_mcdpsk_demod_host(ria_gpu_handle h, const ria_mcdpsk_config* cfg, co
     const size_t o_st = up256(o_llr + static_cast<size_t>(n_llr) * sizeof(float)), total = up256(o_st + sizeof(ria_mcdpsk_status));
     int rc = ensure_host_stage(h, total);
     if (rc != RIA_OK) return rc;
-    unsigned char *D = h->d_hstage, *P = h->p_hstage;
+    unsigned char *D = h->d_hstage.as<unsigned char>(), *P = h->p_hstage.as<unsigned char>();
     hipStream_t s = h->hstream;
     std::memcpy(P, samples_host, b_s);
     const float par[2] = {cfo_hz, phase0};
@@ -1864,7 +1765,7 @@ int ria_gpu_ldpc_decode_robust_host(ria_gpu_handle h, const float* llr_host, int
     const size_t total = up256(o_tr + n);
     int rc = ensure_host_stage(h, total);
     if (rc != RIA_OK) return rc;
-    unsigned char *D = h->d_hstage, *P = h->p_hstage;
+    unsigned char *D = h->d_hstage.as<unsigned char>(), *P = h->p_hstage.as<unsigned char>();
     hipStream_t s = h->hstream;
     std::memcpy(P, llr_host, b_llr);
     HIP_TRY(h, hipMemcpyAsync(D, P, b_llr, hipMemcpyHostToDevice, s));
@@ -1892,17 +1793,16 @@ int ria_gpu_mcdpsk_modulate_batch(ria_gpu_handle h, const ria_mcdpsk_config* cfg
     const int lds = n_data_sym * nc * static_cast<int>(sizeof(float2)) + 16;
     if (lds > 64 * 1024) return fail(h, RIA_ERR_UNSUPPORTED, "ria_gpu_mcdpsk_modulate_batch: too many data symbols for one workgroup");
     HIP_TRY(h, hipSetDevice(h->device));
-    if (!h->d_mc_carrier.count(nc)) {
+    DevBuf &carrier = h->d_mc_carrier[nc], &train = h->d_mc_train[nc];
+    if (!carrier || !train) {
         std::vector<float> car, tr;
         build_mcdpsk_mod_tables(nc, car, tr);
-        void *pc = nullptr, *pt = nullptr;
-        HIP_TRY(h, upload(&pc, car));
-        HIP_TRY(h, upload(&pt, tr));
-        h->d_mc_carrier[nc] = pc; h->d_mc_train[nc] = pt;
+        HIP_TRY(h, upload(carrier, car));
+        HIP_TRY(h, upload(train, tr));
     }
     McModArgs A{};
     A.data = data_dev; A.n_bytes = n_bytes; A.n_frames = n_frames; A.nc = nc; A.bps = cfg->bits_per_symbol; A.spreading = cfg->spreading;
-    A.n_data_sym = n_data_sym; A.carrier = static_cast<const float2*>(h->d_mc_carrier[nc]); A.train = static_cast<const float2*>(h->d_mc_train[nc]);
+    A.n_data_sym = n_data_sym; A.carrier = carrier.as<const float2>(); A.train = train.as<const float2>();
     A.out = out_dev; A.stride = out_stride;
     hipLaunchKernelGGL(mcdpsk_modulate_kernel, dim3(n_frames), dim3(256), lds, static_cast<hipStream_t>(stream), A);
     HIP_TRY(h, hipGetLastError());
@@ -1923,43 +1823,39 @@ static_assert(sizeof(ria_mcdpsk_acq_params) == 32, "ria_mcdpsk_acq_params is 32 
 static_assert(sizeof(ria_mcdpsk_acq_result) == 64, "ria_mcdpsk_acq_result is 64 bytes (include/ria_gpu.h)");
 static_assert(offsetof(ria_mcdpsk_acq_params, abs_base) == 16 && offsetof(ria_mcdpsk_acq_result, delta) == 28 &&
               offsetof(ria_mcdpsk_acq_result, header_total_cw) == 36, "ria_mcdpsk_acq_* field offsets");
-// layout of the MC-DPSK acquisition workspace for n windows, llr_ws soft bits and max_cw codewords per candidate
-struct MacqLayout {
-    size_t det, list[2], mst, llr, rows, row_entry, row_cw, out_a, ok_a, it_a, out_b, ok_b, it_b, hdr, need, base, done, ctl, total;
+static_assert(sizeof(ria_chirp_result) == 32 && sizeof(ria_zc_result) == 32, "one detector area serves either detector");
+// the MC-DPSK acquisition workspace for n windows, llr_ws soft bits and max_cw codewords per candidate
+struct MacqWs {
+    uint8_t* det;                 // [n] ria_chirp_result or ria_zc_result
+    MacqList list[2];
+    ria_mcdpsk_status* mst; float* llr; float* rows; uint32_t* row_entry; uint8_t* row_cw;
+    uint8_t *out_a, *ok_a; uint16_t* it_a;   // round A: n rows
+    uint8_t *out_b, *ok_b; uint16_t* it_b;   // round B: n * (max_cw - 1) rows
+    int *hdr, *need; uint32_t* base; uint8_t* done;
+    MacqCtl* ctl;
 };
-static MacqLayout macq_layout(size_t n, size_t llr_ws, size_t max_cw, size_t dec_bytes) {
-    MacqLayout L{};
-    size_t o = 0;
+static MacqWs macq_carve(Carver& c, size_t n, size_t llr_ws, size_t max_cw, size_t dec_bytes) {
     const size_t nr = n * max_cw;   // rows of round A (n) and round B (n * (max_cw - 1))
-    L.det = o; o = up256(o + n * 32);
-    for (int q = 0; q < 2; ++q) { L.list[q] = o; o = up256(o + n * (sizeof(uint64_t) + sizeof(float) + sizeof(uint32_t) + 2)); }
-    L.mst = o; o = up256(o + n * sizeof(ria_mcdpsk_status));
-    L.llr = o; o = up256(o + n * llr_ws * sizeof(float));
-    L.rows = o; o = up256(o + nr * kMacqLdpcBlock * sizeof(float));
-    L.row_entry = o; o = up256(o + nr * sizeof(uint32_t));
-    L.row_cw = o; o = up256(o + nr);
-    L.out_a = o; o = up256(o + n * dec_bytes);
-    L.ok_a = o; o = up256(o + n);
-    L.it_a = o; o = up256(o + n * sizeof(uint16_t));
-    L.out_b = o; o = up256(o + nr * dec_bytes);
-    L.ok_b = o; o = up256(o + nr);
-    L.it_b = o; o = up256(o + nr * sizeof(uint16_t));
-    L.hdr = o; o = up256(o + n * sizeof(int));
-    L.need = o; o = up256(o + n * sizeof(int));
-    L.base = o; o = up256(o + n * sizeof(uint32_t));
-    L.done = o; o = up256(o + n);
-    L.ctl = o; o = up256(o + sizeof(MacqCtl));
-    L.total = o;
-    return L;
-}
-static MacqList macq_list(unsigned char* base, size_t n) {   // the five arrays of one list, widest first
-    MacqList l;
-    l.offset = reinterpret_cast<uint64_t*>(base);
-    l.cfo = reinterpret_cast<float*>(base + n * sizeof(uint64_t));
-    l.window = reinterpret_cast<uint32_t*>(base + n * (sizeof(uint64_t) + sizeof(float)));
-    l.cand = base + n * (sizeof(uint64_t) + sizeof(float) + sizeof(uint32_t));
-    l.bps = l.cand + n;
-    return l;
+    MacqWs w;
+    w.det = c.take<uint8_t>(n * 32);
+    for (MacqList& l : w.list) c.take_list(n, l.offset, l.cfo, l.window, l.cand, l.bps);   // the five arrays of one list, widest first
+    w.mst = c.take<ria_mcdpsk_status>(n);
+    w.llr = c.take<float>(n * llr_ws);
+    w.rows = c.take<float>(nr * kMacqLdpcBlock);
+    w.row_entry = c.take<uint32_t>(nr);
+    w.row_cw = c.take<uint8_t>(nr);
+    w.out_a = c.take<uint8_t>(n * dec_bytes);
+    w.ok_a = c.take<uint8_t>(n);
+    w.it_a = c.take<uint16_t>(n);
+    w.out_b = c.take<uint8_t>(nr * dec_bytes);
+    w.ok_b = c.take<uint8_t>(nr);
+    w.it_b = c.take<uint16_t>(nr);
+    w.hdr = c.take<int>(n);
+    w.need = c.take<int>(n);
+    w.base = c.take<uint32_t>(n);
+    w.done = c.take<uint8_t>(n);
+    w.ctl = c.take<MacqCtl>(1);
+    return w;
 }
 
 int ria_gpu_mcdpsk_acquire_batch(ria_gpu_handle h, const ria_mcdpsk_config* cfg, const float* samples_dev, int64_t stride,
@@ -1995,15 +1891,11 @@ int ria_gpu_mcdpsk_acquire_batch(ria_gpu_handle h, const ria_mcdpsk_config* cfg,
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t n = static_cast<size_t>(n_windows), dec_bytes = static_cast<size_t>((h->geo.ldpc_k + 7) / 8);
-    const MacqLayout L = macq_layout(n, static_cast<size_t>(llr_ws), static_cast<size_t>(max_cw), dec_bytes);
-    if (L.total > h->macq_bytes) {   // nothing of an earlier call is in flight: every call ends on a stream sync
-        if (h->d_macq_ws) (void)hipFree(h->d_macq_ws);
-        h->d_macq_ws = nullptr; h->macq_bytes = 0;
-        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&h->d_macq_ws), L.total));
-        h->macq_bytes = L.total;
-    }
-    if (!h->p_macq_ctl) HIP_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&h->p_macq_ctl), sizeof(MacqCtl), hipHostMallocDefault));
-    unsigned char* W = h->d_macq_ws;
+    auto carve = [&](Carver& c) { return macq_carve(c, n, static_cast<size_t>(llr_ws), static_cast<size_t>(max_cw), dec_bytes); };
+    HIP_TRY(h, h->d_macq_ws.reserve(carved_size(carve)));   // nothing of an earlier call is in flight: every call ends on a stream sync
+    HIP_TRY(h, h->p_macq_ctl.reserve(sizeof(MacqCtl)));
+    const MacqWs W = carve_at(h->d_macq_ws.as<>(), carve);
+    const MacqCtl& ctl = *h->p_macq_ctl.as<MacqCtl>();
     const int frame_row = RIA_MACQ_FRAME_BYTES(frame_cw);
     HIP_TRY(h, hipMemsetAsync(frame_out_dev, 0, n * frame_row, s));
     if (llr_out_dev) HIP_TRY(h, hipMemsetAsync(llr_out_dev, 0, n * static_cast<size_t>(llr_stride) * sizeof(float), s));
@@ -2012,71 +1904,68 @@ int ria_gpu_mcdpsk_acquire_batch(ria_gpu_handle h, const ria_mcdpsk_config* cfg,
     const int pstride = static_cast<int>(sizeof(ria_mcdpsk_acq_params) / sizeof(float));
     MacqArgs A{};
     if (chirp) {
-        A.chirp = reinterpret_cast<const ria_chirp_result*>(W + L.det);
-        int rc = sync_chirp_impl(h, samples_dev, stride, search_len, n_windows, 0.15f, reinterpret_cast<ria_chirp_result*>(W + L.det), s,
-                                 &params_dev->detect_threshold, pstride);
+        ria_chirp_result* det = reinterpret_cast<ria_chirp_result*>(W.det);
+        A.chirp = det;
+        int rc = sync_chirp_impl(h, samples_dev, stride, search_len, n_windows, 0.15f, det, s, &params_dev->detect_threshold, pstride);
         if (rc != RIA_OK) return rc;
     } else {
-        A.zc = reinterpret_cast<const ria_zc_result*>(W + L.det);
+        ria_zc_result* det = reinterpret_cast<ria_zc_result*>(W.det);
+        A.zc = det;
         int rc = sync_zc_impl(h, samples_dev, stride, search_len, n_windows, 0.2f, 12u /* DATA | CONTROL */, &params_dev->known_cfo_hz,
-                              reinterpret_cast<ria_zc_result*>(W + L.det), s, &params_dev->detect_threshold, pstride);
+                              det, s, &params_dev->detect_threshold, pstride);
         if (rc != RIA_OK) return rc;
     }
     // 2. acceptance + the round-0 list
     A.params = params_dev; A.n_windows = n_windows; A.window_len = window_len; A.frame_len = frame_len; A.stride = stride;
     A.connected = !disconnected; A.retry = retry; A.bps = bps; A.acq = acq_dev;
-    A.ctl = reinterpret_cast<MacqCtl*>(W + L.ctl);
-    MacqList lists[2] = {macq_list(W + L.list[0], n), macq_list(W + L.list[1], n)};
-    A.next = lists[0];
+    A.ctl = W.ctl;
+    A.next = W.list[0];
     hipLaunchKernelGGL(macq_plan_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A);
     HIP_TRY(h, hipGetLastError());
-    A.mst = reinterpret_cast<const ria_mcdpsk_status*>(W + L.mst);
-    A.llr = reinterpret_cast<const float*>(W + L.llr); A.llr_ws = llr_ws;
-    A.rows = reinterpret_cast<float*>(W + L.rows);
-    A.row_entry = reinterpret_cast<uint32_t*>(W + L.row_entry); A.row_cw = W + L.row_cw;
-    A.out_a = W + L.out_a; A.ok_a = W + L.ok_a; A.out_b = W + L.out_b; A.ok_b = W + L.ok_b;
+    A.mst = W.mst;
+    A.llr = W.llr; A.llr_ws = llr_ws;
+    A.rows = W.rows;
+    A.row_entry = W.row_entry; A.row_cw = W.row_cw;
+    A.out_a = W.out_a; A.ok_a = W.ok_a; A.out_b = W.out_b; A.ok_b = W.ok_b;
     A.dec_bytes = static_cast<int>(dec_bytes);
-    A.hdr_total = reinterpret_cast<int*>(W + L.hdr); A.need_rows = reinterpret_cast<int*>(W + L.need);
-    A.row_base = reinterpret_cast<uint32_t*>(W + L.base); A.done = W + L.done;
-    A.crc_bit = static_cast<const uint16_t*>(h->d_crc_bit); A.crc_init = static_cast<const uint16_t*>(h->d_crc_init);
+    A.hdr_total = W.hdr; A.need_rows = W.need;
+    A.row_base = W.base; A.done = W.done;
+    A.crc_bit = h->d_crc_bit.as<const uint16_t>(); A.crc_init = h->d_crc_init.as<const uint16_t>();
     A.frame_out = frame_out_dev; A.frame_row = frame_row; A.llr_out = llr_out_dev; A.llr_stride = llr_stride;
     const ria_mcdpsk_config c = *cfg;
     // 3.-5. rounds: round 0 runs every accepted window at its primary candidate, round r >= 1 the windows still searching at
     // their next candidate that fits (at most 25 more rounds: each advances every window it holds by at least one candidate)
     for (int round = 0;; ++round) {
-        HIP_TRY(h, hipMemcpyAsync(h->p_macq_ctl, A.ctl, sizeof(MacqCtl), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipStreamSynchronize(s));
-        const int n_list = static_cast<int>(h->p_macq_ctl->n_list);
+        if (int rc = read_ctl(h, h->p_macq_ctl, A.ctl, s)) return rc;
+        const int n_list = static_cast<int>(ctl.n_list);
         if (n_list == 0) break;
         if (n_list > n_windows || round >= kMacqCandidates)
             return fail(h, RIA_ERR_HIP, "ria_gpu_mcdpsk_acquire_batch: work list of round %d broke its bound (%d)", round, n_list);
-        A.cur = lists[round & 1];
-        A.next = lists[(round + 1) & 1];
+        A.cur = W.list[round & 1];
+        A.next = W.list[(round + 1) & 1];
         A.n_cur = n_list;
-        int rc = mcdpsk_demod_impl(h, &c, samples_dev, stride, A.cur.offset, A.cur.bps, frame_len, n_list, A.cur.cfo, nullptr,
-                                   const_cast<float*>(A.llr), llr_ws, const_cast<ria_mcdpsk_status*>(A.mst), s);
+        int rc = mcdpsk_demod_impl(h, &c, samples_dev, stride, A.cur.offset, A.cur.bps, frame_len, n_list, A.cur.cfo, nullptr, W.llr, llr_ws, W.mst, s);
         if (rc != RIA_OK) return rc;
         // round A: CW0 of every entry, then the headers and the round-B row list
         MacqArgs G = A;
         G.row_entry = nullptr;
         hipLaunchKernelGGL(macq_gather_kernel, dim3(static_cast<unsigned>(std::min<size_t>((static_cast<size_t>(n_list) * kMacqLdpcBlock + 255) / 256, 16384))),
                            dim3(256), 0, s, G, n_list);
-        rc = ria_gpu_ldpc_decode_robust_batch(h, A.rows, n_list, W + L.out_a, W + L.ok_a, reinterpret_cast<uint16_t*>(W + L.it_a), nullptr, s);
+        rc = ria_gpu_ldpc_decode_robust_batch(h, A.rows, n_list, W.out_a, W.ok_a, W.it_a, nullptr, s);
         if (rc != RIA_OK) return rc;
         const unsigned waves = static_cast<unsigned>(std::min((n_list + 3) / 4, 4096));
         hipLaunchKernelGGL(macq_header_kernel, dim3(waves), dim3(256), 0, s, A);
         hipLaunchKernelGGL(macq_rows_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A);
         HIP_TRY(h, hipGetLastError());
-        HIP_TRY(h, hipMemcpyAsync(h->p_macq_ctl, A.ctl, sizeof(MacqCtl), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipStreamSynchronize(s));
-        const int n_rows = static_cast<int>(h->p_macq_ctl->n_rows);
+        if ((rc = read_ctl(h, h->p_macq_ctl, A.ctl, s)) != RIA_OK) return rc;
+        const int n_rows = static_cast<int>(ctl.n_rows);
         if (n_rows < 0 || n_rows > n_list * (max_cw - 1))
             return fail(h, RIA_ERR_HIP, "ria_gpu_mcdpsk_acquire_batch: codeword rows of round %d broke their bound (%d)", round, n_rows);
         // round B: CW1..total_cw-1 of the entries whose header asks for them
         if (n_rows > 0) {
             hipLaunchKernelGGL(macq_gather_kernel, dim3(static_cast<unsigned>(std::min<size_t>((static_cast<size_t>(n_rows) * kMacqLdpcBlock + 255) / 256, 16384))),
                                dim3(256), 0, s, A, n_rows);
-            rc = ria_gpu_ldpc_decode_robust_batch(h, A.rows, n_rows, W + L.out_b, W + L.ok_b, reinterpret_cast<uint16_t*>(W + L.it_b), nullptr, s);
+            rc = ria_gpu_ldpc_decode_robust_batch(h, A.rows, n_rows, W.out_b, W.ok_b, W.it_b, nullptr, s);
             if (rc != RIA_OK) return rc;
         }
         hipLaunchKernelGGL(macq_finish_kernel, dim3(waves), dim3(256), 0, s, A);
@@ -2098,42 +1987,38 @@ static int dframe_ensure_r14(ria_gpu_handle h) {
     const LdpcCode code = build_ldpc(RIA_RATE_1_4);
     const CoreTables t = core_tables_for(RIA_RATE_1_4, code);
     if (!shape_fits(RIA_RATE_1_4, t, &h->wave_lds14)) return fail(h, RIA_ERR_UNSUPPORTED, "ria_gpu_decode_frame_batch: the R1/4 code does not fit its compiled shape");
-    for (void*& p : h->d_f14) { if (p) (void)hipFree(p); p = nullptr; }
-    HIP_TRY(h, upload(&h->d_f14[0], t.row_addr));
-    HIP_TRY(h, upload(&h->d_f14[1], t.col_addr));
-    HIP_TRY(h, upload(&h->d_f14[2], t.check_at));
-    HIP_TRY(h, upload(&h->d_f14[3], t.col_at));
-    HIP_TRY(h, upload(&h->d_f14[4], t.col_pos));
     FastCode& f = h->fast14;
+    HIP_TRY(h, upload_core_tables(t, h->d_f14, f));
     f.k = code.k; f.m = code.m; f.max_iter = recommended_iterations(RIA_RATE_1_4); f.bytes_per_cw = info_bits_for(RIA_RATE_1_4) / 8;
-    f.row_addr = static_cast<const uint16_t*>(h->d_f14[0]); f.col_addr = static_cast<const uint16_t*>(h->d_f14[1]);
-    f.check_at = static_cast<const uint16_t*>(h->d_f14[2]); f.col_at = static_cast<const uint16_t*>(h->d_f14[3]);
-    f.col_pos = static_cast<const uint16_t*>(h->d_f14[4]);
     set_fast_attributes(RIA_RATE_1_4, h->wave_lds14);
     h->have14 = true;
     return RIA_OK;
 }
 
-struct DfLayout { size_t row, probe, list, fx_llr, fx_info, fx_st, lg_rows, lg_entry, lg_cw, lg_out, lg_ok, lg_it, ctl, total; };
-static DfLayout dframe_layout(size_t n, size_t max_cw, size_t bpc, size_t dec_bytes) {
-    DfLayout L{};
-    size_t o = 0;
-    const size_t nr = n * (max_cw - 1);   // legacy rows: CW1.. of every frame
-    L.ctl = o; o = up256(o + sizeof(DfCtl));
-    L.row = o; o = up256(o + n * sizeof(DfRow));
-    L.probe = o; o = up256(o + 4 * n * sizeof(DfProbe));
-    L.list = o; o = up256(o + kDfNumLists * n * sizeof(uint32_t));
-    L.fx_llr = o; o = up256(o + n * kDfFrameBits * sizeof(float));
-    L.fx_info = o; o = up256(o + n * 4 * bpc);
-    L.fx_st = o; o = up256(o + n * sizeof(ria_decode_status));
-    L.lg_rows = o; o = up256(o + nr * kDfBlock * sizeof(float));
-    L.lg_entry = o; o = up256(o + nr * sizeof(uint32_t));
-    L.lg_cw = o; o = up256(o + nr);
-    L.lg_out = o; o = up256(o + nr * dec_bytes);
-    L.lg_ok = o; o = up256(o + nr);
-    L.lg_it = o; o = up256(o + nr * sizeof(uint16_t));
-    L.total = o;
-    return L;
+// the decodeFrame workspace for n rows of up to max_cw codewords.  The control block, row state, probe records and lists lie
+// in front of the bulk areas: one memset clears them.
+struct DfWs {
+    DfCtl* ctl; DfRow* row; DfProbe* probe; uint32_t* list;
+    float* fx_llr; uint8_t* fx_info; ria_decode_status* fx_st;                                             // the fixed batch
+    float* lg_rows; uint32_t* lg_entry; uint8_t* lg_cw; uint8_t* lg_out; uint8_t* lg_ok; uint16_t* lg_it;   // legacy rows: CW1.. of every frame
+};
+static DfWs dframe_carve(Carver& c, size_t n, size_t max_cw, size_t bpc, size_t dec_bytes) {
+    const size_t nr = n * (max_cw - 1);
+    DfWs w;
+    w.ctl = c.take<DfCtl>(1);
+    w.row = c.take<DfRow>(n);
+    w.probe = c.take<DfProbe>(4 * n);
+    w.list = c.take<uint32_t>(kDfNumLists * n);
+    w.fx_llr = c.take<float>(n * kDfFrameBits);
+    w.fx_info = c.take<uint8_t>(n * 4 * bpc);
+    w.fx_st = c.take<ria_decode_status>(n);
+    w.lg_rows = c.take<float>(nr * kDfBlock);
+    w.lg_entry = c.take<uint32_t>(nr);
+    w.lg_cw = c.take<uint8_t>(nr);
+    w.lg_out = c.take<uint8_t>(nr * dec_bytes);
+    w.lg_ok = c.take<uint8_t>(nr);
+    w.lg_it = c.take<uint16_t>(nr);
+    return w;
 }
 
 int ria_gpu_decode_frame_batch(ria_gpu_handle h, const float* llr_dev, int llr_stride, const int32_t* n_llr_dev, int n_frames,
@@ -2153,37 +2038,32 @@ int ria_gpu_decode_frame_batch(ria_gpu_handle h, const float* llr_dev, int llr_s
     const bool ch_deint = (flags & RIA_DECODE_NO_CHANNEL_DEINTERLEAVE) == 0;
     // everything the call may need is allocated here, before any of it is in flight
     if (!r14) { if (int rc = dframe_ensure_r14(h)) return rc; }
-    if (!h->d_cw_perm[ch_deint ? 1 : 0])
-        HIP_TRY(h, upload(&h->d_cw_perm[ch_deint ? 1 : 0], build_cw_deinterleave(h->geo.bits_per_symbol, ch_deint)));
+    DevBuf& perm = h->d_cw_perm[ch_deint ? 1 : 0];
+    if (!perm) HIP_TRY(h, upload(perm, build_cw_deinterleave(h->geo.bits_per_symbol, ch_deint)));
     const size_t n = static_cast<size_t>(n_frames), max_cw = static_cast<size_t>(llr_stride / kDfBlock);
     const size_t dec_bytes = static_cast<size_t>((h->geo.ldpc_k + 7) / 8);
-    const DfLayout L = dframe_layout(n, max_cw, static_cast<size_t>(bpc), dec_bytes);
-    if (L.total > h->df_bytes) {   // nothing of an earlier call is in flight: every call ends on a stream sync
-        if (h->d_df_ws) (void)hipFree(h->d_df_ws);
-        h->d_df_ws = nullptr; h->df_bytes = 0;
-        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&h->d_df_ws), L.total));
-        h->df_bytes = L.total;
-    }
-    if (!h->p_df_ctl) HIP_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&h->p_df_ctl), sizeof(DfCtl), hipHostMallocDefault));
+    auto carve = [&](Carver& c) { return dframe_carve(c, n, max_cw, static_cast<size_t>(bpc), dec_bytes); };
+    HIP_TRY(h, h->d_df_ws.reserve(carved_size(carve)));   // nothing of an earlier call is in flight: every call ends on a stream sync
+    HIP_TRY(h, h->p_df_ctl.reserve(sizeof(DfCtl)));
+    const DfWs W = carve_at(h->d_df_ws.as<>(), carve);
+    const DfCtl& ctl = *h->p_df_ctl.as<DfCtl>();
     {
         hipError_t e = ensure_decode_ws(h, n_frames);
         if (e == hipSuccess && (flags & RIA_DECODE_CRC_RECOVER)) e = ensure_recovery_ws(h, std::max(n_frames, h->cfg.max_batch), false);
         if (e != hipSuccess) return fail(h, RIA_ERR_HIP, "ria_gpu_decode_frame_batch workspace: %s", hipGetErrorString(e));
     }
-    unsigned char* W = h->d_df_ws;
     DfArgs A{};
     A.llr = llr_dev; A.llr_stride = llr_stride; A.n_llr = n_llr_dev; A.n_frames = n_frames;
     A.rate_is_r14 = r14 ? 1 : 0; A.bpc = bpc; A.bpc14 = info_bits_for(RIA_RATE_1_4) / 8;
-    A.row = reinterpret_cast<DfRow*>(W + L.row); A.probe = reinterpret_cast<DfProbe*>(W + L.probe);
-    A.list = reinterpret_cast<uint32_t*>(W + L.list); A.ctl = reinterpret_cast<DfCtl*>(W + L.ctl);
-    A.fx_llr = reinterpret_cast<float*>(W + L.fx_llr); A.fx_info = W + L.fx_info; A.fx_st = reinterpret_cast<ria_decode_status*>(W + L.fx_st);
-    A.perm = static_cast<const uint16_t*>(h->d_cw_perm[ch_deint ? 1 : 0]);
-    A.lg_rows = reinterpret_cast<float*>(W + L.lg_rows); A.lg_entry = reinterpret_cast<uint32_t*>(W + L.lg_entry); A.lg_cw = W + L.lg_cw;
-    A.lg_out = W + L.lg_out; A.lg_ok = W + L.lg_ok; A.dec_bytes = static_cast<int>(dec_bytes);
-    A.crc_bit = static_cast<const uint16_t*>(h->d_crc_bit); A.crc_init = static_cast<const uint16_t*>(h->d_crc_init);
+    A.row = W.row; A.probe = W.probe; A.list = W.list; A.ctl = W.ctl;
+    A.fx_llr = W.fx_llr; A.fx_info = W.fx_info; A.fx_st = W.fx_st;
+    A.perm = perm.as<const uint16_t>();
+    A.lg_rows = W.lg_rows; A.lg_entry = W.lg_entry; A.lg_cw = W.lg_cw;
+    A.lg_out = W.lg_out; A.lg_ok = W.lg_ok; A.dec_bytes = static_cast<int>(dec_bytes);
+    A.crc_bit = h->d_crc_bit.as<const uint16_t>(); A.crc_init = h->d_crc_init.as<const uint16_t>();
     A.frame_out = frame_out_dev; A.frame_row = frame_row; A.result = result_dev; A.st_out = decode_status_dev; A.info_out = info_out_dev;
     // control block, row state, probe records and lists in one memset (they lie in front of the bulk areas)
-    HIP_TRY(h, hipMemsetAsync(W, 0, L.fx_llr, s));
+    HIP_TRY(h, hipMemsetAsync(W.ctl, 0, span_bytes(W.ctl, W.fx_llr), s));
     const unsigned probe_grid = static_cast<unsigned>(std::min(n_frames, 16384));
     auto list = [&](int stage) { hipLaunchKernelGGL(dframe_list_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A, stage); };
     auto probe_rate = [&](bool robust, int which_list, int which_probe, unsigned grid) {
@@ -2206,9 +2086,8 @@ int ria_gpu_decode_frame_batch(ria_gpu_handle h, const float* llr_dev, int llr_s
     probe_rate(false, kDfListRate, kDfProbeRate, probe_grid);
     list(kDfStageAfterRate);
     HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(h->p_df_ctl, A.ctl, sizeof(DfCtl), hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));                                    // read 1 of 2: the length of the fixed batch
-    const int n_fixed = static_cast<int>(h->p_df_ctl->n[kDfListFixed]);
+    if (int rc = read_ctl(h, h->p_df_ctl, A.ctl, s, "decode work-queue fault: no frame of this call was decoded")) return rc;   // read 1 of 2: the length of the fixed batch
+    const int n_fixed = static_cast<int>(ctl.n[kDfListFixed]);
     if (n_fixed < 0 || n_fixed > n_frames) return fail(h, RIA_ERR_HIP, "ria_gpu_decode_frame_batch: the fixed list broke its bound (%d)", n_fixed);
     // 3.-4. decodeFixedFrame over the try_frame_interleave rows, then the two salvage decoders over what it left
     if (n_fixed > 0) {
@@ -2225,17 +2104,14 @@ int ria_gpu_decode_frame_batch(ria_gpu_handle h, const float* llr_dev, int llr_s
     // 5. legacy: the rows of CW1.. of the non-interleaved multi-codeword frames
     list(kDfStageLegacy);
     HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(h->p_df_ctl, A.ctl, sizeof(DfCtl), hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));                                    // read 2 of 2: the legacy rows (and the fault flag)
-    if (h->p_df_ctl->fault) return fail(h, RIA_ERR_HIP, "decode work-queue fault: no frame of this call was decoded");
-    const long long n_rows = static_cast<long long>(h->p_df_ctl->n_rows);
+    if (int rc = read_ctl(h, h->p_df_ctl, A.ctl, s, "decode work-queue fault: no frame of this call was decoded")) return rc;   // read 2 of 2: the legacy rows (and the fault flag)
+    const long long n_rows = static_cast<long long>(ctl.n_rows);
     if (n_rows < 0 || static_cast<size_t>(n_rows) > n * (max_cw - 1)) return fail(h, RIA_ERR_HIP, "ria_gpu_decode_frame_batch: the legacy rows broke their bound (%lld)", n_rows);
     if (n_rows > 0) {
         const int nr = static_cast<int>(n_rows);
         hipLaunchKernelGGL(dframe_legacy_rows_kernel, dim3(static_cast<unsigned>(std::min<size_t>((static_cast<size_t>(nr) * kDfBlock + 255) / 256, 16384))),
                            dim3(256), 0, s, A, nr);
-        int rc = ria_gpu_ldpc_decode_batch(h, A.lg_rows, nr, h->geo.ldpc_max_iterations, 0.75f, W + L.lg_out, W + L.lg_ok,
-                                           reinterpret_cast<uint16_t*>(W + L.lg_it), s);
+        int rc = ria_gpu_ldpc_decode_batch(h, A.lg_rows, nr, h->geo.ldpc_max_iterations, 0.75f, W.lg_out, W.lg_ok, W.lg_it, s);
         if (rc != RIA_OK) return rc;
     }
     // 6. results
@@ -2258,7 +2134,7 @@ int ria_gpu_decode_frame_host(ria_gpu_handle h, const float* llr_host, int n_llr
     const size_t o_res = up256(o_fr + frame_row), o_ds = up256(o_res + sizeof(ria_dframe_result)), total = up256(o_ds + sizeof(ria_decode_status));
     int rc = ensure_host_stage(h, total);
     if (rc != RIA_OK) return rc;
-    unsigned char *D = h->d_hstage, *P = h->p_hstage;
+    unsigned char *D = h->d_hstage.as<unsigned char>(), *P = h->p_hstage.as<unsigned char>();
     hipStream_t s = h->hstream;
     std::memset(P, 0, b_llr);
     if (n_use > 0) std::memcpy(P, llr_host, static_cast<size_t>(n_use) * sizeof(float));
@@ -2350,7 +2226,7 @@ int ria_gpu_debug_queue_fault(ria_gpu_handle h) {
     HIP_TRY(h, hipSetDevice(h->device));
     DecodeCtl c[kMaxParts];
     HIP_TRY(h, hipDeviceSynchronize());
-    HIP_TRY(h, hipMemcpy(c, h->d_ctl, sizeof(c), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(c, h->d_ctl.as<>(), sizeof(c), hipMemcpyDeviceToHost));
     int bad = 0;
     for (const DecodeCtl& q : c) bad |= q.queue_fault ? 1 : 0;
     return bad;

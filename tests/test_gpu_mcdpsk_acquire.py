@@ -254,3 +254,20 @@ def test_argument_rejections_on_a_real_handle(eng):
         assert call(e2.h, n=0) == -1                                         # MC-DPSK is R1/4 only
     finally:
         e2.close()
+
+
+def test_workspace_growth_leaves_results_alone():
+    """A call on 2 windows, then one on the handshake set, on a fresh R1/4 handle: every array of the second equals the same
+    call on another fresh handle that never ran the first, and the first equals that call's first two rows."""
+    from ria_amd.engine import RxEngine
+    x, sl = build(handshake_set(), True, 3)
+    a, b = RxEngine("DQPSK", "R1_4", max_batch=64), RxEngine("DQPSK", "R1_4", max_batch=64)
+    small = run(a, x[:2], sl, 3)
+    big = run(a, x, sl, 3)
+    ref = run(b, x, sl, 3)
+    assert ref[1]["success"].sum() >= 3 and ref[1]["candidates"].max() > 2   # decodes and fallback rounds ran
+    for k, (s, g, r) in enumerate(zip(small, big, ref)):
+        assert g.tobytes() == r.tobytes(), k
+        assert s.tobytes() == r[:2].tobytes(), k
+    a.close()
+    b.close()

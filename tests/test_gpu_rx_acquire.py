@@ -128,10 +128,17 @@ def run_gpu(e, X, abs_base, **kw):
 _cache = {}
 
 
+def _windows(oracle):
+    """the parity set's windows without the restatement: (windows, sent infos, kinds, abs_base)"""
+    if "windows" not in _cache:
+        X, infos, kinds = parity_set(oracle)
+        _cache["windows"] = (X, infos, kinds, 1_000_000 + 40_000 * np.arange(len(X), dtype=np.uint64))
+    return _cache["windows"]
+
+
 def _set(oracle):
     if "set" not in _cache:
-        X, infos, kinds = parity_set(oracle)
-        abs_base = 1_000_000 + 40_000 * np.arange(len(X), dtype=np.uint64)
+        X, infos, kinds, abs_base = _windows(oracle)
         _cache["set"] = (X, infos, kinds, abs_base, restate(X, abs_base))
     return _cache["set"]
 
@@ -280,3 +287,20 @@ def test_acquire_sweep_counters_do_not_depend_on_the_chunk():
     assert c["windows"] == n and c["recovered"] <= c["accepted"] <= c["detected"] <= c["windows"]
     assert c["primary_ok"] + c["recovered"] <= c["accepted"] and c["decodes"] >= c["accepted"]
     assert c["recovered"] > 0 and c["frame_err"] <= n
+
+
+def test_workspace_growth_leaves_results_alone(oracle):
+    """A call on 2 windows, then one on the whole parity set, on a fresh handle: every array of the second equals the same
+    call on another fresh handle that never ran the first, and the first equals that call's first two rows."""
+    from ria_amd.engine import RxEngine
+    X, _, _, abs_base = _windows(oracle)
+    a, b = RxEngine("QAM16", "R1_2", max_batch=64), RxEngine("QAM16", "R1_2", max_batch=64)
+    small = run_gpu(a, X[:2], abs_base[:2])
+    big = run_gpu(a, X, abs_base)
+    ref = run_gpu(b, X, abs_base)
+    assert ref[2]["accepted"].sum() > 2 and (ref[2]["delta"] != 0).any()     # rounds ran, recoveries among them
+    for k, (s, g, r) in enumerate(zip(small, big, ref)):
+        assert g.tobytes() == r.tobytes(), k
+        assert s.tobytes() == r[:2].tobytes(), k
+    a.close()
+    b.close()
