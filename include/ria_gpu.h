@@ -162,6 +162,12 @@ int  ria_gpu_get_geometry(ria_gpu_handle h, ria_gpu_geometry* out);
  *                        image (ldpc_dual.hip.h): 1 = on, -1 = off, 0 = library default (off).  An experiment record that
  *                        measured slower: only in builds made with -DRIA_WITH_DUAL_DECODER; elsewhere 1 is RIA_ERR_UNSUPPORTED. */
 #define RIA_OPT_DUAL_DECODER 2
+/*   RIA_OPT_FALLBACK_QUEUE_ALL  the CRC recovery's fallback stage re-decodes each codeword of an unrepaired frame at four
+ *                        factors and substitutes one result at a time.  0 (default): only the re-decodes of codewords
+ *                        through which a substitution can make the frame verify are run - codeword 0 always, codeword
+ *                        c >= 1 only if the header in codeword 0 parses and the frame's bytes reach into c.  1: every missing
+ *                        re-decode is run, the others for nothing (the behaviour before the rule; kept to measure it). */
+#define RIA_OPT_FALLBACK_QUEUE_ALL 3
 int  ria_gpu_set_option(ria_gpu_handle h, int option, int value);
 
 /* ---- RX: demodulate  (IWaveform::process + getSoftBits, waveform_interface.hpp:124,135;
@@ -798,6 +804,11 @@ int ria_gpu_debug_math(ria_gpu_handle h, int op, const float* a_dev, const float
  * instead of the queue's end (a broken queue loop terminates and is reported, it does not hang the GPU); 0 if not;
  * negative = error.  Synchronises the device. */
 int ria_gpu_debug_queue_fault(ria_gpu_handle h);
+/* Counters of the CRC recovery (device path) of the last call that ran it on stream slot `slot` (0 for every call but the
+ * parts 1.. of a split ria_gpu_rx_batch): out[0] frames flagged (four converged codewords, frame check fails), out[1]
+ * frames stage 1 could not repair (they reach the fallback stage), out[2] codewords with re-decodes queued for it,
+ * out[3] (codeword, factor) re-decodes queued.  All zero before the first such call.  Synchronises the device. */
+int ria_gpu_debug_recovery_counts(ria_gpu_handle h, int slot, uint32_t out[4]);
 
 #ifdef __cplusplus
 }

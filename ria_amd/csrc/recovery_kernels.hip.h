@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fallback_relevance.hpp"
 #include "ldpc_fast.hip.h"
 #include "sort_exact.hpp"
 
@@ -60,19 +61,11 @@ __device__ inline bool rec_parse_header(const RecCtx& x, const uint8_t* d, int l
 // already parsed (control: 20 bytes, data: 17 + payload + 2); one wave, returns the length
 template <class CwAt>
 __device__ inline int rec_reassemble_cws(bool ctl, int plen, CwAt cw_at, int n_cw, int bpc, int lane, uint8_t* out) {
-    const int expected = ctl ? 20 : 17 + plen + 2;
-    int n = 0;
-    for (int i = 0; i < n_cw; ++i) {
-        const int remaining = expected - n;
-        if (remaining == 0) break;
-        const uint8_t* src = cw_at(i);
-        int avail = bpc;
-        if (i != 0 && src[0] == 0xD5) { src += 2; avail -= 2; }
-        const int c = remaining < avail ? remaining : avail;
-        for (int b = lane; b < c; b += 64) out[n + b] = src[b];
-        n += c;
-    }
-    return n;
+    return cws_walk(frame_expected_bytes(ctl, plen), n_cw, bpc, [&](int i) { return cw_at(i)[0]; },
+                    [&](int i, int skip, int at, int c) {
+                        const uint8_t* src = cw_at(i) + skip;
+                        for (int b = lane; b < c; b += 64) out[at + b] = src[b];
+                    });
 }
 // CodewordStatus::reassemble + reassembleCodewords (frame_v2.cpp:1030-1063, :959-989), all CWs decoded
 __device__ inline int rec_reassemble(const RecCtx& x, uint8_t* out) {
@@ -497,6 +490,8 @@ struct RecoveryArgs {
     unsigned int* n_overflow;    // counter
     unsigned int* overflow;      // [n_frames] frames with more suspects than the small stage-1 instance holds
     int list_units_now;          // recovery_list_kernel also lists the missing re-decodes (host-search path)
+    unsigned int* n_queued;      // counter: (codeword, factor) decodes recovery_stage1_kernel queued for the fill
+    int queue_all;               // RIA_OPT_FALLBACK_QUEUE_ALL: queue every missing re-decode, relevant or not
     // host-search staging (RIA_RECOVERY_HOST=1 only)
     uint8_t* info_c;             // [n_flagged][4*bpc]
     float* rows_c;               // [n_flagged][4][648] decoder-order LLRs
@@ -629,10 +624,20 @@ __global__ __launch_bounds__(64) void recovery_stage1_kernel(RecoveryArgs R) {
     if (good) { rec_publish(x, R, frame, info, true, lane); return; }
     // queue the decodes the fallback still misses, one entry per codeword (mask of its missing factors): lanes 0..15 =
     // (codeword, factor) pairs, ONE reservation per frame on the shared counter (a counter bumped once per entry by
-    // thousands of waves serialises)
+    // thousands of waves serialises).  Only of the codewords the fallback can repair the frame through
+    // (fallback_relevance.hpp): every failed trial of the search was reverted, so x.cw holds the original bytes.  A
+    // codeword left out keeps its slots at state 0, which recovery_stage2_kernel skips; where phase 0 had computed such a
+    // slot anyway (state 2) stage 2 still tries it and its rec_try fails, as the substitution does in the reference.
+    unsigned relevant = 15u;
+    if (!R.queue_all) {
+        bool ctl = false; int plen = 0;
+        wave_sync();
+        const bool hdr = rec_parse_header(x, x.cw, x.bpc, &ctl, &plen);
+        relevant = fallback_relevant_cws(x.cw, 68, x.bpc, hdr, ctl, plen);
+    }
     const unsigned fc = frame * 4u + static_cast<unsigned>((lane >> 2) & 3);
     const int f = 1 + (lane & 3);
-    const bool need = lane < 16 && R.d.res[fc].state[f] == 0;
+    const bool need = lane < 16 && ((relevant >> ((lane >> 2) & 3)) & 1u) != 0u && R.d.res[fc].state[f] == 0;
     const unsigned long long mk = __ballot(need);
     const unsigned mine = static_cast<unsigned>(mk >> (lane & 12)) & 15u;          // the four factor bits of this lane's codeword
     const bool writer = lane < 16 && (lane & 3) == 0 && mine != 0u;
@@ -640,14 +645,20 @@ __global__ __launch_bounds__(64) void recovery_stage1_kernel(RecoveryArgs R) {
     unsigned base = 0;
     if (lane == 0) {
         R.stage2[atomicAdd(R.n_stage2, 1u)] = frame;
-        if (wk) base = atomicAdd(R.n_list2, static_cast<unsigned>(__popcll(wk)));
+        if (wk) {
+            base = atomicAdd(R.n_list2, static_cast<unsigned>(__popcll(wk)));
+            atomicAdd(R.n_queued, static_cast<unsigned>(__popcll(mk)));
+        }
     }
     base = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(base)));
     if (writer) R.list2[base + __popcll(wk & ((1ull << lane) - 1ull))] = (fc << 4) | mine;
 }
 
 // Stage 2 (frame_v2.cpp:1836-1866): factors 0.75, 0.625, 0.5, 0.875 = kFactors[2, 3, 4, 1]; stage 1 left the
-// codeword bytes untouched (every failed trial is reverted), so they are re-read from the output buffer
+// codeword bytes untouched (every failed trial is reverted), so they are re-read from the output buffer.  A slot is tried
+// iff its state is 2: the slots recovery_stage1_kernel did not queue because no substitution of their codeword can make the
+// frame verify (fallback_relevance.hpp) stay at 0 and are passed over; one that phase 0 had filled anyway is tried and fails
+// its rec_try here, as it does in the reference.
 __global__ __launch_bounds__(64) void recovery_stage2_kernel(RecoveryArgs R) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const unsigned q = blockIdx.x;

@@ -81,6 +81,7 @@ struct ria_gpu {
     int ws_frames = 0;
     int split_parts = 0;                  // RIA_OPT_SPLIT_PARTS (0 = library default)
     int dual_decoder = 0;                 // RIA_OPT_DUAL_DECODER: 0 = default (environment RIA_DUAL, else off), 1 = on, -1 = off
+    int fallback_queue_all = 0;           // RIA_OPT_FALLBACK_QUEUE_ALL: 1 = the recovery fill also runs the re-decodes no trial can read
     // host-buffer entry points (the single-frame IWaveform adaptor path): one device + one pinned staging block and a
     // stream, kept for the life of the handle, grown on demand - no allocation and no device-wide sync per call
     DevBuf d_hstage; PinBuf p_hstage; hipStream_t hstream = nullptr;
@@ -275,6 +276,8 @@ static hipError_t ensure_recovery_ws(ria_gpu_handle h, int n_frames, bool host_s
     if (n_frames > h->rec_frames) {
         h->rec_frames = 0;   // nothing is valid until the allocation has succeeded
         if ((e = h->d_rec_ws.reserve(carved_size([&](Carver& c) { return recovery_carve(c, n); }))) != hipSuccess) return e;
+        // the counter blocks of every stream slot: ria_gpu_debug_recovery_counts reads the slots no call has used yet as well
+        if ((e = hipMemset(h->d_rec_ws.as<>(), 0, 8 * kMaxParts * sizeof(unsigned int))) != hipSuccess) { h->d_rec_ws.release(); return e; }
         h->rec_frames = n_frames;
     }
     if (host_staging && n_frames > h->rec_host_frames) {
@@ -321,6 +324,7 @@ static int run_crc_recovery(ria_gpu_handle h, const FastDecodeArgs& D, hipStream
     const RecoveryWs W = recovery_ws(h);
     unsigned int* rctl = W.rctl + 8 * slot;
     R.n_flagged = rctl; R.n_list2 = rctl + 1; R.n_stage2 = rctl + 2; R.next_fill = rctl + 3; R.n_overflow = rctl + 4;
+    R.n_queued = rctl + 5; R.queue_all = h->fallback_queue_all;
     R.flagged = W.flagged + ws_off; R.list2 = W.list2 + static_cast<size_t>(ws_off) * 16; R.stage2 = W.stage2 + ws_off;
     R.overflow = W.overflow + ws_off;
 #ifdef RIA_DEBUG_STAMPS   // diagnostic builds only (tools/build_variant.sh ... -DRIA_DEBUG_STAMPS): a raw device pointer from the environment
@@ -607,6 +611,7 @@ int ria_gpu_set_option(ria_gpu_handle h, int option, int value) {
 #endif
         h->dual_decoder = value; return RIA_OK;
     }
+    if (option == RIA_OPT_FALLBACK_QUEUE_ALL && value >= 0 && value <= 1) { h->fallback_queue_all = value; return RIA_OK; }
     return fail(h, RIA_ERR_INVALID, "ria_gpu_set_option: unknown option %d or value %d out of range", option, value);
 }
 
@@ -2230,6 +2235,18 @@ int ria_gpu_debug_queue_fault(ria_gpu_handle h) {
     int bad = 0;
     for (const DecodeCtl& q : c) bad |= q.queue_fault ? 1 : 0;
     return bad;
+}
+
+int ria_gpu_debug_recovery_counts(ria_gpu_handle h, int slot, uint32_t out[4]) {
+    if (!h || !out || slot < 0 || slot >= kMaxParts) return fail(h, RIA_ERR_INVALID, "ria_gpu_debug_recovery_counts: bad argument");
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (h->rec_frames == 0) return RIA_OK;   // no call has run the recovery yet
+    HIP_TRY(h, hipSetDevice(h->device));
+    unsigned int c[8];
+    HIP_TRY(h, hipDeviceSynchronize());
+    HIP_TRY(h, hipMemcpy(c, recovery_ws(h).rctl + 8 * slot, sizeof(c), hipMemcpyDeviceToHost));
+    out[0] = c[0]; out[1] = c[2]; out[2] = c[1]; out[3] = c[5];   // n_flagged, n_stage2, n_list2, n_queued
+    return RIA_OK;
 }
 
 int ria_gpu_debug_math(ria_gpu_handle h, int op, const float* a_dev, const float* b_dev, int n, float* out_dev,

@@ -65,6 +65,17 @@ class RxEngine:
         """1: two codewords per wave in the retry kernels, -1: one, 0: library default"""
         self._check(self.lib.ria_gpu_set_option(self.h, capi.OPT_DUAL_DECODER, int(mode)))
 
+    def set_fallback_queue_all(self, on):
+        """1: the recovery fill also runs the fallback re-decodes no trial can read (as before the relevance rule); 0: default"""
+        self._check(self.lib.ria_gpu_set_option(self.h, capi.OPT_FALLBACK_QUEUE_ALL, int(on)))
+
+    def recovery_counts(self, slot=0):
+        """Counters of the last CRC recovery on stream slot `slot`: frames flagged, frames reaching the fallback stage,
+        codewords with re-decodes queued, (codeword, factor) re-decodes queued.  Synchronises the device."""
+        out = (C.c_uint32 * 4)()
+        self._check(self.lib.ria_gpu_debug_recovery_counts(self.h, int(slot), out))
+        return {"flagged": int(out[0]), "fallback": int(out[1]), "list2": int(out[2]), "queued": int(out[3])}
+
     # ---- helpers
     def _meta(self, n, cfo_hz, abs_pos, flags):
         if cfo_hz is None and abs_pos is None and flags is None:
