@@ -168,6 +168,16 @@ int  ria_gpu_get_geometry(ria_gpu_handle h, ria_gpu_geometry* out);
  *                        c >= 1 only if the header in codeword 0 parses and the frame's bytes reach into c.  1: every missing
  *                        re-decode is run, the others for nothing (the behaviour before the rule; kept to measure it). */
 #define RIA_OPT_FALLBACK_QUEUE_ALL 3
+/*   RIA_OPT_STATE_EXIT   the retry kernels whose failed decodes leave no bits behind (phase 0, cascade, recovery fill) end
+ *                        a decode that has not converged once its complete message state equals, bit for bit, the state
+ *                        24 iterations earlier (compared at iterations 46 and 70): it can only repeat itself, so it is
+ *                        reported as the 80-iteration failure it would become.  0 (default) = off: every failing decode
+ *                        runs to its last iteration, in kernels without the exit.  1 = on at R1/2 and R1/3, the shapes
+ *                        with room for the state copy (a second instance of the three kernels; no effect at other
+ *                        rates).  Measured slower on the bench workload: the exit saves 3 % of
+ *                        the step, the kernels that contain it lose 6 %.  The environment variable RIA_STATE_EXIT=1 / 0
+ *                        sets the default of handles created after it.  ria_gpu_debug_state_exits counts the exits. */
+#define RIA_OPT_STATE_EXIT 4
 int  ria_gpu_set_option(ria_gpu_handle h, int option, int value);
 
 /* ---- RX: demodulate  (IWaveform::process + getSoftBits, waveform_interface.hpp:124,135;
@@ -809,6 +819,11 @@ int ria_gpu_debug_queue_fault(ria_gpu_handle h);
  * frames stage 1 could not repair (they reach the fallback stage), out[2] codewords with re-decodes queued for it,
  * out[3] (codeword, factor) re-decodes queued.  All zero before the first such call.  Synchronises the device. */
 int ria_gpu_debug_recovery_counts(ria_gpu_handle h, int slot, uint32_t out[4]);
+/* Decodes that the repeated-state exit (RIA_OPT_STATE_EXIT) ended in the last decode call on stream slot `slot`: out[0] all,
+ * out[1] in phase 0, out[2] in the cascade, out[3] in the recovery fill.  Attempts behind a codeword's winner and factor
+ * decodes behind its first converging one run or not depending on timing, so the counts vary a little from call to call.
+ * All zero before the first call, with the option off and at a rate without the exit.  Synchronises the device. */
+int ria_gpu_debug_state_exits(ria_gpu_handle h, int slot, uint32_t out[4]);
 
 #ifdef __cplusplus
 }

@@ -40,6 +40,7 @@ struct ShapeR12 {   // R1/2: m = 324, k = 324
     static constexpr int NR = 6, NC = 6;
     static constexpr int kCascadeWaves = 3;   // waves/SIMD the cascade kernel is held to (its register budget)
     static constexpr int kCv = 24;   // the row's own c2v words of slot groups < kCv stay in VGPRs between iterations (their LDS re-reads saved) as the register budget allows
+    static constexpr bool kStateExit = true;   // repeated-state exit of the retry kernels (fast_decode, EX): 15 copy words per lane fit beside three waves per SIMD
     static constexpr int ne(int r) { constexpr int t[NR] = {6, 6, 5, 4, 2, 1}; return t[r]; }
     static constexpr int nm(int r) { constexpr int t[NR] = {6, 5, 4, 2, 1, 1}; return t[r]; }
     static constexpr int dv(int r) { constexpr int t[NC] = {5, 4, 4, 4, 4, 4}; return t[r]; }
@@ -48,6 +49,7 @@ struct ShapeR13 {   // R1/3 entry of the rate table: same (324,324) parameters, 
     static constexpr int NR = 6, NC = 6;
     static constexpr int kCascadeWaves = 3;   // waves/SIMD the cascade kernel is held to (its register budget)
     static constexpr int kCv = 24;   // the row's own c2v words of slot groups < kCv stay in VGPRs between iterations (their LDS re-reads saved) as the register budget allows
+    static constexpr bool kStateExit = true;   // repeated-state exit of the retry kernels (fast_decode, EX): 15 copy words per lane fit beside three waves per SIMD
     static constexpr int ne(int r) { constexpr int t[NR] = {6, 6, 5, 3, 3, 1}; return t[r]; }
     static constexpr int nm(int r) { constexpr int t[NR] = {6, 5, 3, 3, 1, 1}; return t[r]; }
     static constexpr int dv(int r) { constexpr int t[NC] = {6, 4, 4, 4, 4, 4}; return t[r]; }
@@ -56,6 +58,7 @@ struct ShapeR14 {   // m = 486, k = 162
     static constexpr int NR = 8, NC = 3;
     static constexpr int kCascadeWaves = 3;   // waves/SIMD the cascade kernel is held to (its register budget)
     static constexpr int kCv = 0;   // the row's own c2v words of slot groups < kCv stay in VGPRs between iterations (their LDS re-reads saved) as the register budget allows
+    static constexpr bool kStateExit = false;   // 8 rounds: 20 copy words per lane, twelve waves' regions (15 KB each) would not fit the CU's LDS
     static constexpr int ne(int r) { constexpr int t[NR] = {6, 6, 5, 5, 4, 3, 2, 2}; return t[r]; }
     static constexpr int nm(int r) { constexpr int t[NR] = {6, 6, 5, 4, 3, 2, 2, 1}; return t[r]; }
     static constexpr int dv(int r) { constexpr int t[NC] = {13, 12, 12}; return t[r]; }
@@ -64,6 +67,7 @@ struct ShapeR23 {   // m = 216, k = 432
     static constexpr int NR = 4, NC = 7;
     static constexpr int kCascadeWaves = 3;   // waves/SIMD the cascade kernel is held to (its register budget)
     static constexpr int kCv = 24;   // the row's own c2v words of slot groups < kCv stay in VGPRs between iterations (their LDS re-reads saved) as the register budget allows
+    static constexpr bool kStateExit = false;   // not a bench shape: never measured
     static constexpr int ne(int r) { constexpr int t[NR] = {6, 6, 6, 6}; return t[r]; }
     static constexpr int nm(int r) { constexpr int t[NR] = {6, 6, 6, 4}; return t[r]; }
     static constexpr int dv(int r) { constexpr int t[NC] = {3, 3, 3, 3, 3, 3, 3}; return t[r]; }
@@ -72,6 +76,7 @@ struct ShapeR34 {   // m = 162, k = 486 (161 information columns have no edge at
     static constexpr int NR = 3, NC = 8;
     static constexpr int kCascadeWaves = 4;   // waves/SIMD the cascade kernel is held to (its register budget)
     static constexpr int kCv = 0;   // the row's own c2v words of slot groups < kCv stay in VGPRs between iterations (their LDS re-reads saved) as the register budget allows
+    static constexpr bool kStateExit = false;   // not a bench shape: never measured
     static constexpr int ne(int r) { constexpr int t[NR] = {6, 6, 6}; return t[r]; }
     static constexpr int nm(int r) { constexpr int t[NR] = {6, 6, 6}; return t[r]; }
     static constexpr int dv(int r) { constexpr int t[NC] = {3, 3, 3, 3, 3, 3, 0, 0}; return t[r]; }
@@ -80,6 +85,7 @@ struct ShapeR56 {   // m = 108, k = 540
     static constexpr int NR = 2, NC = 9;
     static constexpr int kCascadeWaves = 5;   // waves/SIMD the cascade kernel is held to (its register budget)
     static constexpr int kCv = 0;   // the row's own c2v words of slot groups < kCv stay in VGPRs between iterations (their LDS re-reads saved) as the register budget allows
+    static constexpr bool kStateExit = false;   // not a bench shape: never measured
     static constexpr int ne(int r) { constexpr int t[NR] = {6, 6}; return t[r]; }
     static constexpr int nm(int r) { constexpr int t[NR] = {6, 6}; return t[r]; }
     static constexpr int dv(int r) { constexpr int t[NC] = {3, 3, 3, 3, 0, 0, 0, 0, 0}; return t[r]; }
@@ -106,6 +112,10 @@ struct ShapeInfo {
     static constexpr int words = big_word + 64;
     // the same region doubles as mt19937 state + 648 normals during the retry cascade (>= 1296 words)
     static constexpr int lds_bytes = ((words < 1296 ? 1296 : words) * 4 + 15) & ~15;
+    // repeated-state exit (fast_decode, EX): the compressed copy of the check-to-variable state sits behind the wave's
+    // region, per lane two magnitude words per row round and one word of sign / minimum-edge bits per two rounds
+    static constexpr int copy_words = 2 * S::NR + (S::NR + 1) / 2;
+    static constexpr int exit_lds_bytes = lds_bytes + (S::kStateExit ? 256 * copy_words : 0);
 };
 
 template <int B, int E, class F>
@@ -278,10 +288,28 @@ __device__ __forceinline__ float llr_canon(float x) {
 #ifndef RIA_SINGLE_PREFETCH
 #define RIA_SINGLE_PREFETCH 2
 #endif
-template <class S, int NCV = (kCvRegs ? 1024 : S::kCv), int PF = RIA_SINGLE_PREFETCH>
+//
+// EX (repeated-state exit, off by default): the decoder is a deterministic map on its check-to-
+// variable messages, so a decode that has not converged and whose complete message state after the check pass of
+// iteration t equals, bit for bit, the state after iteration t - kExitStride (both >= 1: iteration 0 runs without the
+// clamp) repeats those iterations for ever.  Every state of the cycle has had its syndrome tested non-zero, so the result
+// is known: not converged, max_iter.  The state (the row's own c2v words and the c2v of its identity edge) is compared
+// through a copy taken at iterations kExitFirst, + kExitStride, ...: a row's messages have two magnitudes only,
+// |min1 * factor| (every edge but the row's minimum) and |min2 * factor| (the minimum edge), so the copy is those two words
+// per row plus a sign bit and a which-magnitude bit per edge, an injective image of the state.  It lives behind the wave's
+// LDS region (ShapeInfo::exit_lds_bytes), lane-private.  A copy iteration is a second instance of the iteration body
+// (SNAP) that runs between two runs of the ordinary loop.  `exits` == nullptr switches the exit off at run time; otherwise
+// it is the counter an exit bumps.  ONLY for callers that never read the bits of a failed decode: the exit leaves the
+// column totals of iteration t - 1 in LDS, not those of iteration max_iter - 1.
+// Measured: the exit removes the iterations the count predicts, but a kernel that contains the
+// copy instance runs its ORDINARY iterations 6 % slower (the register allocation and schedule of the whole function
+// change), more than the exit saves: the retry kernels are therefore built twice and the exit is off by default.
+constexpr int kExitFirst = 22, kExitStride = 24;
+template <class S, int NCV = (kCvRegs ? 1024 : S::kCv), int PF = RIA_SINGLE_PREFETCH, bool EX = false>
 __device__ inline int fast_decode(FastState<S>& st, const FastCode& c, unsigned char* __restrict__ lds,
-                                  float factor, int max_iter, int lane, bool* ok) {
+                                  float factor, int max_iter, int lane, bool* ok, unsigned int* exits = nullptr) {
     using I = ShapeInfo<S>;
+    static_assert(!EX || S::kStateExit, "the shape has no room for the state copy");
     const uint32_t lane4 = lds_addr(lds) + static_cast<uint32_t>(lane) * 4u;
     const uint32_t kAbs = 0x7fffffffu;
     const uint32_t m0base = lds_addr(lds);
@@ -306,8 +334,11 @@ __device__ inline int fast_decode(FastState<S>& st, const FastCode& c, unsigned 
     float hi = __builtin_inff();
     int it = 0;
     bool success = false;
-    for (; it < max_iter; ++it) {
+    // one iteration; 0: go on, 1: converged, 2 (SNAP only): the state equals the copy.  SNAP = a copy iteration.
+    auto iteration = [&](auto SNAP_) __attribute__((always_inline)) -> int {
+        constexpr bool SNAP = decltype(SNAP_)::value;
         uint32_t syn = 0;
+        uint32_t sb = 0, sd = 0;              // SNAP: bits of the round pair, difference words of this lane
         // the total gathers of round r + PF are issued before round r is computed (LDS operations keep their program
         // order: without this every round starts by waiting out an LDS round trip)
         float tt[I::TS];
@@ -379,9 +410,31 @@ __device__ inline int fast_decode(FastState<S>& st, const FastCode& c, unsigned 
                 const float tot = st.lp[r] + c2v;
                 st.pv[r] = tot - c2v;                    // clamped where it is used (see above)
                 st.pt[r] = tot;
+                if constexpr (SNAP) {
+                    // every message of the row has magnitude |min1 * factor| or |min2 * factor| (the product's magnitude does
+                    // not depend on the signs): two words, and per edge its sign and whether its magnitude is not the first
+                    static_assert(NE + 1 <= 8, "16 bits per round");
+                    const uint32_t ma = f2u(min1 * factor) & kAbs, mb = f2u(min2 * factor) & kAbs;
+                    uint32_t bits = (f2u(c2v) >> 31) | (((f2u(c2v) & kAbs) != ma) ? 2u : 0u);
+#pragma unroll
+                    for (int s = 0; s < NE; ++s) bits = (bits << 2) | (f2u(o[s]) >> 31) | (((f2u(o[s]) & kAbs) != ma) ? 2u : 0u);
+                    const uint32_t ca = lane4 + static_cast<uint32_t>(I::lds_bytes) + 256u * (2 * r);
+                    sd |= (f2u(lds_f(ca)) ^ ma) | (f2u(lds_f(ca + 256u)) ^ mb);
+                    lds_sf(ca, u2f(ma));
+                    lds_sf(ca + 256u, u2f(mb));
+                    sb = (r & 1) ? (sb | (bits << 16)) : bits;
+                    if constexpr ((r & 1) || r == S::NR - 1) {
+                        const uint32_t cb = lane4 + static_cast<uint32_t>(I::lds_bytes) + 256u * (2 * S::NR + r / 2);
+                        sd |= f2u(lds_f(cb)) ^ sb;
+                        lds_sf(cb, u2f(sb));
+                    }
+                }
             }
         });
-        if (it > 0 && __ballot(static_cast<int>(syn) < 0) == 0ull) { success = true; --it; break; }
+        if (it > 0 && __ballot(static_cast<int>(syn) < 0) == 0ull) return 1;
+        if constexpr (SNAP) {   // the first copy has nothing to be compared with (what the area held is a past decode's)
+            if (it != kExitFirst && __ballot(sd != 0u) == 0ull) return 2;
+        }
         hi = 50.0f;
         wave_sync();
         // information columns: tot = llr + sum of c2v in ascending check order
@@ -410,6 +463,34 @@ __device__ inline int fast_decode(FastState<S>& st, const FastCode& c, unsigned 
             lds_store_tid_n<gn, 4 * (I::tot_word + 64 * g0), 256>(m0base, tv);
         });
         wave_sync();
+        return 0;
+    };
+    // The ordinary iterations run in a loop of their own, up to the next copy iteration (or the end); a copy iteration is a
+    // second instance of the body between two such runs.
+    int snap_at = (EX && exits != nullptr) ? kExitFirst : 0x7fffffff;   // wave-uniform
+    int status = 0;
+    for (;;) {
+        const int stop = snap_at < max_iter ? snap_at : max_iter;
+        for (; it < stop; ++it) {
+            status = iteration(std::false_type{});
+            if (status != 0) break;
+        }
+        if (status != 0 || it >= max_iter) break;
+        if constexpr (!EX) break;
+        else {
+            status = iteration(std::true_type{});
+            if (status != 0) break;
+            ++it;
+            snap_at += kExitStride;
+        }
+    }
+    if (status == 1) { success = true; --it; }
+    if constexpr (EX) {
+        if (status == 2) {   // a cycle of states whose syndromes were all tested non-zero: the decode fails at max_iter
+            if (lane == 0) atomicAdd(exits, 1u);
+            *ok = false;
+            return max_iter;
+        }
     }
     if (!success) {   // syndrome of the final iteration
         uint32_t syn = 0;
@@ -461,8 +542,10 @@ struct DecodeCtl {          // zeroed by hipMemsetAsync before every decode call
     unsigned int n_list1;   // codewords that need the other four min-sum factors
     unsigned int next_z;    // phase-0 work queue head
     unsigned int queue_fault;  // set by a persistent wave whose queue loop ran past its bound (see kQueueGuard)
-    unsigned int pad_[3];
+    unsigned int exits[3];     // decodes ended by the repeated-state exit (fast_decode, EX): phase 0, cascade, recovery fill
 };
+static_assert(sizeof(DecodeCtl) == 32, "control block layout");
+enum { kExitsPhase0 = 0, kExitsCascade = 1, kExitsFill = 2 };
 // Queue pops are written in the all-lane form (lane 0 adds 1, the others 0, then readfirstlane).  The round-1 hang had this
 // cause, read off the ISA of tools/probes/queue_pop_probe.hip: with the pop written `u = 0; if (lane == 0) u = atomicAdd(..);
 // u = readfirstlane(u)` (or __shfl(u, 0)), hipcc 7.2 threads the lane != 0 edge of that branch THROUGH the convergent
@@ -508,6 +591,9 @@ struct FastDecodeArgs {
     unsigned int* l1idx;     // [4*n_frames]  codeword -> its list1 index, kNotListed for the others (written by fast_mark_kernel when a retry flag is set)
     unsigned int* l1hash;    // [4*n_frames]  list1 entry -> hash of its first 16 soft bits (seed of the perturbation RNG)
     uint32_t* seed_ws;       // [cascade grid][kSeedWsWords]  seeded mt19937 states of the attempt group a cascade workgroup is on (this stream slot's)
+    int state_exit;          // RIA_OPT_STATE_EXIT: the retry kernels end a failing decode whose message state repeats (fast_decode, EX)
+    // the counter of kernel `which` (kExits*), or nullptr = exit off: wave-uniform, fast_decode's run-time switch
+    __device__ unsigned int* exit_counter(int which) const { return state_exit ? &ctl->exits[which] : nullptr; }
 };
 
 // A codeword that needs more than its first decode is decoded up to 4 + 34 more times.  Its soft bits are gathered
@@ -561,14 +647,14 @@ __device__ inline void fast_publish(CwResult* res, unsigned fc, int f, bool ok, 
 
 // decode codeword `fc` (= frame*4 + cw) with factor index f and record the result; staged != nullptr: the
 // codeword's de-interleaved input (fast_stage_kernel) instead of the gather from the frame
-template <class S, int NCV = S::kCv>
+template <class S, int NCV = S::kCv, bool EX = false>
 __device__ inline void fast_unit(FastState<S>& st, const FastDecodeArgs& A, unsigned char* lds, unsigned fc, int f, int lane,
-                                 const float* staged = nullptr) {
+                                 const float* staged = nullptr, unsigned int* exits = nullptr) {
     const FastCode& c = A.c;
     if (staged) fast_load_staged(st, staged, lane);
     else fast_gather_llr(st, c, A.llr + static_cast<size_t>(fc >> 2) * A.llr_stride, A.gather, fc & 3, lane);
     bool ok;
-    int it = fast_decode<S, NCV>(st, c, lds, kFactors[f], c.max_iter, lane, &ok);
+    int it = fast_decode<S, NCV, RIA_SINGLE_PREFETCH, EX>(st, c, lds, kFactors[f], c.max_iter, lane, &ok, exits);
     if (ok) fast_pack(st, c, lds, A.res_bytes + (static_cast<size_t>(fc) * kNumFactors + f) * c.bytes_per_cw,
                       c.bytes_per_cw, lane);
     fast_publish(A.res, fc, f, ok, it, lane);
@@ -680,7 +766,7 @@ __global__ __launch_bounds__(256) void fast_stage_kernel(FastDecodeArgs A) {
 #ifndef RIA_EAGER_FACTORS
 #define RIA_EAGER_FACTORS 0
 #endif
-template <class S>
+template <class S, bool EX = false>   // EX: with the repeated-state exit (RIA_OPT_STATE_EXIT; launched with ShapeInfo::exit_lds_bytes)
 __global__ __launch_bounds__(64) void fast_phase0_kernel(FastDecodeArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x;
@@ -709,7 +795,9 @@ __global__ __launch_bounds__(64) void fast_phase0_kernel(FastDecodeArgs A) {
         }
         if (done) continue;
 #endif
-        fast_unit<S>(st, A, smem, fc, t, lane, A.staged + static_cast<size_t>(entry) * kStageFloats);
+        // a failed unit publishes its state and iteration count only: the repeated-state exit applies (fast_decode, EX)
+        fast_unit<S, S::kCv, EX>(st, A, smem, fc, t, lane, A.staged + static_cast<size_t>(entry) * kStageFloats,
+                                 A.exit_counter(kExitsPhase0));
     }
 }
 
@@ -816,7 +904,7 @@ __device__ inline float fast_perturb(FastState<S>& st, const FastCode& c, const 
 // wave touches.  best[e] is still the smallest successful attempt: an attempt runs unless a smaller one has been
 // published, a success ends the group (its later attempts can never win), and the result slot is written under the
 // lock by the current best only.  No wave waits for another.
-template <class S>
+template <class S, bool EX = false>   // EX: with the repeated-state exit (RIA_OPT_STATE_EXIT; launched with ShapeInfo::exit_lds_bytes)
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(S::kCascadeWaves))) void fast_cascade_kernel(FastDecodeArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const FastCode& c = A.c;
@@ -859,7 +947,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(S::kCascadeW
             for (int r = 0; r < S::NR; ++r) bp[r] = st.lp[r];
             float factor = fast_perturb(st, c, bi, bp, reinterpret_cast<uint32_t*>(msg), msg + 640, ws, j, static_cast<int>(a), lane);
             bool ok;
-            const int it = fast_decode<S>(st, c, smem, factor, c.max_iter, lane, &ok);
+            // a failed attempt leaves nothing behind: the repeated-state exit applies (fast_decode, EX)
+            const int it = fast_decode<S, (kCvRegs ? 1024 : S::kCv), RIA_SINGLE_PREFETCH, EX>(st, c, smem, factor, c.max_iter, lane, &ok,
+                                                                                     A.exit_counter(kExitsCascade));
             if (!ok) continue;
             // all-lane forms here too (no lane-0-only atomic inside the loop): only lane 0's operand can change the word
             unsigned int prev = atomicMin(&A.best[e], lane == 0 ? a : 0xFFFFFFFFu);

@@ -82,6 +82,7 @@ struct ria_gpu {
     int split_parts = 0;                  // RIA_OPT_SPLIT_PARTS (0 = library default)
     int dual_decoder = 0;                 // RIA_OPT_DUAL_DECODER: 0 = default (environment RIA_DUAL, else off), 1 = on, -1 = off
     int fallback_queue_all = 0;           // RIA_OPT_FALLBACK_QUEUE_ALL: 1 = the recovery fill also runs the re-decodes no trial can read
+    int state_exit = 0;                   // RIA_OPT_STATE_EXIT: 1 = the retry kernels end a failing decode whose message state repeats (measured slower: off)
     // host-buffer entry points (the single-frame IWaveform adaptor path): one device + one pinned staging block and a
     // stream, kept for the life of the handle, grown on demand - no allocation and no device-wide sync per call
     DevBuf d_hstage; PinBuf p_hstage; hipStream_t hstream = nullptr;
@@ -210,12 +211,27 @@ static hipError_t ensure_decode_ws(ria_gpu_handle h, int n_frames) {
     h->ws_frames = n_frames;
     return hipSuccess;
 }
+// Phase 0, the cascade and the recovery fill exist twice: as they are without the repeated-state exit, and (shapes with
+// room for the state copy) with it and the copy behind the wave's LDS region.  RIA_OPT_STATE_EXIT picks per call.
+template <class S, class F>
+static void with_state_exit(ria_gpu_handle h, F&& f) {
+    if constexpr (S::kStateExit) {
+        if (h->state_exit) { f(std::true_type{}, ShapeInfo<S>::exit_lds_bytes); return; }
+    }
+    f(std::false_type{}, ShapeInfo<S>::lds_bytes);
+}
 static void set_fast_attributes(int rate, int wb) {
     dispatch_shape(rate, [&](auto s) {
         using S = decltype(s);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fast_primary_kernel<S>), hipFuncAttributeMaxDynamicSharedMemorySize, wb);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fast_phase0_kernel<S>), hipFuncAttributeMaxDynamicSharedMemorySize, wb);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fast_cascade_kernel<S>), hipFuncAttributeMaxDynamicSharedMemorySize, wb);
+        if constexpr (S::kStateExit) {   // the instances with the repeated-state exit: the state copy behind the wave's region
+            const int wbx = ShapeInfo<S>::exit_lds_bytes;
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fast_phase0_kernel<S, true>), hipFuncAttributeMaxDynamicSharedMemorySize, wbx);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fast_cascade_kernel<S, true>), hipFuncAttributeMaxDynamicSharedMemorySize, wbx);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(recovery_fill_kernel<S, true>), hipFuncAttributeMaxDynamicSharedMemorySize, wbx);
+        }
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fast_rows_kernel<S>), hipFuncAttributeMaxDynamicSharedMemorySize, wb);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fast_robust_kernel<S>), hipFuncAttributeMaxDynamicSharedMemorySize, wb);
 #ifdef RIA_WITH_DUAL_DECODER
@@ -337,7 +353,9 @@ static int run_crc_recovery(ria_gpu_handle h, const FastDecodeArgs& D, hipStream
     hipLaunchKernelGGL(recovery_stage1_kernel, dim3(n_frames), dim3(64), rl, s, R);
     dispatch_shape(h->cfg.code_rate, [&](auto sh) {
         using S = decltype(sh);
-        hipLaunchKernelGGL(recovery_fill_kernel<S>, dim3(std::min(n_frames * 16, 3072)), dim3(64), h->wave_lds, s, R);
+        with_state_exit<S>(h, [&](auto ex, int lds) {
+            hipLaunchKernelGGL((recovery_fill_kernel<S, decltype(ex)::value>), dim3(std::min(n_frames * 16, 3072)), dim3(64), lds, s, R);
+        });
     });
     hipLaunchKernelGGL(recovery_stage2_kernel, dim3(n_frames), dim3(64), rl, s, R);
     // a work-queue fault recorded anywhere in this call (cascade, phase 0, recovery fill) turns every frame into a failure
@@ -514,6 +532,7 @@ int ria_gpu_create(const ria_gpu_config* cfg, ria_gpu_handle* out) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= cfg->device) return RIA_ERR_NO_DEVICE;
     ria_gpu_handle h = new ria_gpu();
+    if (const char* se = getenv("RIA_STATE_EXIT")) h->state_exit = se[0] != '0';   // the default of RIA_OPT_STATE_EXIT, for A/B runs of programs that never set it
     h->cfg = *cfg;
     h->device = cfg->device;
     if (h->cfg.max_batch <= 0) h->cfg.max_batch = 4096;
@@ -612,6 +631,7 @@ int ria_gpu_set_option(ria_gpu_handle h, int option, int value) {
         h->dual_decoder = value; return RIA_OK;
     }
     if (option == RIA_OPT_FALLBACK_QUEUE_ALL && value >= 0 && value <= 1) { h->fallback_queue_all = value; return RIA_OK; }
+    if (option == RIA_OPT_STATE_EXIT && value >= 0 && value <= 1) { h->state_exit = value; return RIA_OK; }
     return fail(h, RIA_ERR_INVALID, "ria_gpu_set_option: unknown option %d or value %d out of range", option, value);
 }
 
@@ -680,6 +700,7 @@ static int launch_decode(ria_gpu_handle h, const float* llr_dev, int llr_stride,
     A.l1idx = W.l1idx + o4;
     A.l1hash = W.l1hash + o4;
     A.seed_ws = h->d_seed_ws.as<uint32_t>() + static_cast<size_t>(slot) * persist_grid_size(false) * kSeedWsWords;
+    dispatch_shape(h->cfg.code_rate, [&](auto sh) { A.state_exit = decltype(sh)::kStateExit ? h->state_exit : 0; });
     if ((e = hipMemsetAsync(A.ctl, 0, sizeof(DecodeCtl), s)) != hipSuccess)
         return fail(h, RIA_ERR_HIP, "hipMemsetAsync: %s", hipGetErrorString(e));
     const int wb = h->wave_lds;
@@ -715,7 +736,9 @@ static int launch_decode(ria_gpu_handle h, const float* llr_dev, int llr_stride,
             if (dual) hipLaunchKernelGGL(dual_phase0_kernel<S>, dim3(std::min(n_frames * 8, persist_grid)), dim3(64), DualInfo<S>::lds_bytes, s, A);
             else
 #endif
-            hipLaunchKernelGGL(fast_phase0_kernel<S>, dim3(std::min(n_frames * 16, persist_grid)), dim3(64), wb, s, A);
+            with_state_exit<S>(h, [&](auto ex, int lds) {
+                hipLaunchKernelGGL((fast_phase0_kernel<S, decltype(ex)::value>), dim3(std::min(n_frames * 16, persist_grid)), dim3(64), lds, s, A);
+            });
         }
         stage("phase0");
         hipLaunchKernelGGL(fast_chain_kernel, dim3((n_frames + 255) / 256), dim3(256), 0, s, A);
@@ -726,7 +749,9 @@ static int launch_decode(ria_gpu_handle h, const float* llr_dev, int llr_stride,
             if (dual) hipLaunchKernelGGL(dual_cascade_kernel<S>, dim3(persist_grid), dim3(64), DualInfo<S>::lds_bytes, s, A);
             else
 #endif
-            hipLaunchKernelGGL(fast_cascade_kernel<S>, dim3(persist_grid), dim3(64), wb, s, A);
+            with_state_exit<S>(h, [&](auto ex, int lds) {
+                hipLaunchKernelGGL((fast_cascade_kernel<S, decltype(ex)::value>), dim3(persist_grid), dim3(64), lds, s, A);
+            });
             stage("cascade");
             hipLaunchKernelGGL(fast_finalize_kernel, dim3(std::min((4 * n_frames + 255) / 256, 1024)), dim3(256), 0, s, A);
             stage("finalize");
@@ -2246,6 +2271,19 @@ int ria_gpu_debug_recovery_counts(ria_gpu_handle h, int slot, uint32_t out[4]) {
     HIP_TRY(h, hipDeviceSynchronize());
     HIP_TRY(h, hipMemcpy(c, recovery_ws(h).rctl + 8 * slot, sizeof(c), hipMemcpyDeviceToHost));
     out[0] = c[0]; out[1] = c[2]; out[2] = c[1]; out[3] = c[5];   // n_flagged, n_stage2, n_list2, n_queued
+    return RIA_OK;
+}
+
+int ria_gpu_debug_state_exits(ria_gpu_handle h, int slot, uint32_t out[4]) {
+    if (!h || !out || slot < 0 || slot >= kMaxParts) return fail(h, RIA_ERR_INVALID, "ria_gpu_debug_state_exits: bad argument");
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (!h->d_ctl) return RIA_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    DecodeCtl c;
+    HIP_TRY(h, hipDeviceSynchronize());
+    HIP_TRY(h, hipMemcpy(&c, h->d_ctl.as<DecodeCtl>() + slot, sizeof(c), hipMemcpyDeviceToHost));
+    out[1] = c.exits[kExitsPhase0]; out[2] = c.exits[kExitsCascade]; out[3] = c.exits[kExitsFill];
+    out[0] = out[1] + out[2] + out[3];
     return RIA_OK;
 }
 

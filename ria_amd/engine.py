@@ -76,6 +76,18 @@ class RxEngine:
         self._check(self.lib.ria_gpu_debug_recovery_counts(self.h, int(slot), out))
         return {"flagged": int(out[0]), "fallback": int(out[1]), "list2": int(out[2]), "queued": int(out[3])}
 
+    def set_state_exit(self, on):
+        """1: the retry kernels end a failing decode whose message state repeats (R1/2, R1/3); 0 (default): every failing decode
+        runs to its end"""
+        self._check(self.lib.ria_gpu_set_option(self.h, capi.OPT_STATE_EXIT, int(on)))
+
+    def state_exits(self, slot=0):
+        """Decodes the repeated-state exit ended in the last decode call on stream slot `slot` (parts 1.. of a split rx call use
+        slots 1..): all, phase 0, cascade, recovery fill.  Synchronises the device."""
+        out = (C.c_uint32 * 4)()
+        self._check(self.lib.ria_gpu_debug_state_exits(self.h, int(slot), out))
+        return {"all": int(out[0]), "phase0": int(out[1]), "cascade": int(out[2]), "fill": int(out[3])}
+
     # ---- helpers
     def _meta(self, n, cfo_hz, abs_pos, flags):
         if cfo_hz is None and abs_pos is None and flags is None:
