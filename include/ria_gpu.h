@@ -674,7 +674,8 @@ int ria_gpu_rx_burst_batch(ria_gpu_handle h, const float* samples_dev, int64_t s
  * DQPSK alternate over a DBPSK frame length carries up to 2 * frame_cw codewords) holding the DecodeResult's frame_data
  * (frame_bytes of them), zero elsewhere; llr_out_dev (nullable) rows of llr_stride floats with the reported candidate's
  * soft bits (n_llr of them, the rest zero; llr_stride must hold every candidate that can run), e.g. for
- * ria_gpu_chase_combine_batch.  The chase cache itself, channel interleaving (RIA_MACQ_CHANNEL_INTERLEAVE is
+ * ria_gpu_chase_combine_batch.  This call leaves out the chase cache (:2729-2731, :2766-2789, :2796-2799, :2808-2811):
+ * ria_gpu_mcdpsk_acquire_harq_batch below is the same call with it.  Channel interleaving (RIA_MACQ_CHANNEL_INTERLEAVE is
  * RIA_ERR_UNSUPPORTED), PING/PONG classification and the CW0-peek escalation stay with the caller.
  *
  * Work: round r demodulates and decodes the list of windows still searching, each at its own next candidate that fits,
@@ -722,6 +723,131 @@ int ria_gpu_mcdpsk_acquire_batch(ria_gpu_handle h, const ria_mcdpsk_config* cfg,
                                  const ria_mcdpsk_acq_params* params_dev, uint32_t flags,
                                  uint8_t* frame_out_dev, ria_mcdpsk_acq_result* acq_dev,
                                  float* llr_out_dev /* nullable */, int llr_stride, void* stream);
+
+/* ---- HARQ chase combining: fec::ChaseCache on the device (src/fec/chase_cache.{hpp,cpp}) ----------------------------
+ * A pool holds n_caches independent caches, one per link or Monte-Carlo trial, as one StreamingDecoder owns one ChaseCache.
+ * A cache holds up to max_entries entries keyed by the header's (seq, src_hash, dst_hash); an entry keeps total_cw,
+ * frame_type, last_access and, per codeword (up to the reference's sanity limit of 16), a 648-float sum, combine_count and
+ * decoded.  The policy is the reference's statement for statement (ria_amd/csrc/chase_policy.hpp, one host/device header):
+ *   store         argument checks in the reference's order (cw_index in [0, total_cw), total_cw in 1..16), then stores++,
+ *                 pruneExpired, and for a new key evictIfNeeded and a fresh entry holding this codeword (count 1); for an
+ *                 existing entry: last_access = now, then refuse cw_index >= entry.total_cw, a decoded codeword, a count of
+ *                 MAX_COMBINES = 4; copy on the codeword's first reception, else one float += per element and combines++.
+ *   getCombined   a hit iff the entry exists, the index is in range, the codeword has a sum and is not decoded; else a miss.
+ *   markDecoded   acts on an existing entry only: sets decoded, drops the sum, erases the entry when all are decoded.
+ *   removeEntry, clear (entries go, counters stay), Stats (seven counters; recoveries is counted by the decode path).
+ * Time is the caller's: one now_ms per row or window, used by every cache operation of that row in the call.  An entry is
+ * expired iff (int64)(now - last_access) > ttl_ms, so a `now` earlier than last_access does not expire it.
+ * Eviction takes the smallest last_access as the reference does.  The reference's clock advances strictly, so it never sees
+ * two entries with one last_access; here one now_ms may serve several stores, and entries are ordered by (last_access_ms,
+ * the cache's store sequence number at the moment last_access was set): among equal times the one touched first goes.
+ * Memory: n_caches * max_entries * 16 * 648 * 4 bytes of sums (41 472 bytes per entry, 663 552 per cache at 16 entries)
+ * plus 1 344 bytes of metadata and 4 bytes of owner word per cache, all allocated by ria_gpu_chase_create and owned by the
+ * handle (ria_gpu_destroy frees the pools still alive; a pool must not be used after its handle is destroyed). */
+#define RIA_CHASE_MAX_CW       16
+#define RIA_CHASE_MAX_ENTRIES  16
+#define RIA_CHASE_MAX_COMBINES 4
+typedef struct ria_chase_config {        /* 32 bytes */
+    int32_t n_caches;                    /* >= 1 */
+    int32_t max_entries;                 /* 1..16, reference default 16 */
+    int64_t ttl_ms;                      /* >= 0, reference default 30000 */
+    int32_t reserved[4];
+} ria_chase_config;
+typedef struct ria_chase_stats {         /* ChaseCache::Stats, 56 bytes */
+    uint64_t cache_hits, cache_misses, stores, combines, entries_evicted, entries_expired, recoveries;
+} ria_chase_stats;
+typedef struct ria_chase_entry {         /* 80 bytes */
+    uint64_t last_access_ms;
+    uint64_t order;                      /* the cache's store sequence number when last_access was set (eviction tie-break) */
+    uint32_t src_hash, dst_hash;
+    uint16_t seq;
+    uint8_t  used;                       /* always 1 in what ria_gpu_chase_export returns */
+    uint8_t  total_cw, frame_type;
+    uint8_t  reserved[3];
+    uint8_t  combine_count[RIA_CHASE_MAX_CW];
+    uint8_t  decoded[RIA_CHASE_MAX_CW];
+    uint8_t  has_sum[RIA_CHASE_MAX_CW];  /* cw_soft_bits[i] is not empty */
+} ria_chase_entry;
+typedef struct ria_chase_pool_s* ria_chase_pool;
+
+void ria_gpu_chase_default_config(ria_chase_config* cfg);   /* 1 cache, 16 entries, 30000 ms */
+int  ria_gpu_chase_create(ria_gpu_handle h, const ria_chase_config* cfg, ria_chase_pool* out);
+void ria_gpu_chase_destroy(ria_chase_pool pool);
+/* ChaseCache::clear (what setMode does at streaming_decoder.cpp:2206) for the n caches listed in cache_ids_dev (device,
+ * int32; ids out of range are skipped) or, with NULL, for every cache of the pool (n ignored).  Counters stay. */
+int  ria_gpu_chase_clear(ria_chase_pool pool, const int32_t* cache_ids_dev /* nullable = all */, int n, void* stream);
+/* getStats of one cache into host memory.  Synchronises the device. */
+int  ria_gpu_chase_stats(ria_chase_pool pool, int cache_id, ria_chase_stats* out_host);
+/* The live entries of one cache in slot order: returns their number (size(), >= 0) or a negative ria_status.
+ * entries_out_host (nullable) takes max_entries records, sums_out_host (nullable) max_entries * 16 * 648 floats: entry e's
+ * codeword c at (e * 16 + c) * 648, zero where has_sum is 0.  Synchronises the device. */
+int  ria_gpu_chase_export(ria_chase_pool pool, int cache_id, ria_chase_entry* entries_out_host, float* sums_out_host);
+
+/* ---- RX: decodeMCDPSKFrame on soft bits, with the chase cache (streaming_decoder.cpp:2595-2819) -----------------------
+ * ria_gpu_mcdpsk_decode_frame_batch is step 3 of ria_gpu_mcdpsk_acquire_batch on rows of soft bits, taken like
+ * ria_gpu_decode_frame_batch: row f is n_llr_dev[f] soft bits (clamped to [0, llr_stride]; NULL: llr_stride each) at
+ * llr_dev + f * llr_stride, 648 <= llr_stride <= 16 * 648, frame_row >= 20 * (llr_stride / 648).  The handle's rate must be
+ * RIA_RATE_1_4.  With a pool, row f uses cache cache_id_dev[f] of it (-1: chase off for the row, the result is that of
+ * the plain decode) at time now_ms_dev[f]; pool NULL turns chase off for the call (cache_id_dev, now_ms_dev unused).
+ * Stages, each over a compact ascending list, so that no result depends on scheduling:
+ *   1. CW0 robust decode   2. header + CONNECT guard   3. CW1.. robust decode
+ *   4. chase store: one wave per row with a cache, i = 1 .. total_cw-1 ascending with both outcomes in hand: a codeword that
+ *      decoded -> markDecoded (:2796-2799; a no-op while the key has no entry, which is why "store all failures, then mark
+ *      all successes" would be wrong: it would refuse a later store of a codeword that decoded before the entry existed);
+ *      a codeword that failed -> store, getCombined, getCombineCount (:2766-2776); count > 1 lists (row, i) for stage 5
+ *   5. the listed sums gathered from the pool and robustly decoded
+ *   6. chase resolve: ok_chase (:2779) -> markDecoded, recoveries++, the codeword's bytes and flag replaced
+ *   7. reassembly (the finish of the acquire call), removeEntry on full success (:2808-2811)
+ * A sum decode touches only its own codeword's state, so running 5-6 after all of 4 gives the reference's result.
+ * cw_decoded[0] is never set on this path (CW0 is not handed to the cache), so markDecoded's "all decoded -> erase" never
+ * fires here; it is implemented all the same.
+ * Two rows of one call with the same cache id >= 0 (or an id >= n_caches) are RIA_ERR_INVALID: they would need an order
+ * between them.  This is found on the device (an owner word per cache, atomicCAS) and read with the call's first control
+ * read, before any cache is touched.  Retransmissions of one link go into successive calls.
+ * The call synchronises its stream once for the codeword-row count and, with a pool and at least one such row, once more
+ * for the length of the list of sums; stage 5 is skipped when that list is empty.  Every row of every output is written. */
+typedef struct ria_mcdpsk_dframe_result {   /* 16 bytes: the DecodeResult */
+    uint8_t success, codewords_ok, codewords_failed;
+    uint8_t frame_type;                  /* 0x10 when no header was parsed */
+    int32_t header_total_cw;             /* total_cw of a valid CW0 header, 0 if none */
+    int32_t frame_bytes;                 /* frame_data length in the row of frame_out_dev */
+    int32_t reserved;
+} ria_mcdpsk_dframe_result;
+enum { RIA_HARQ_ENTRY_NONE = 0,          /* the key has no entry after the row */
+       RIA_HARQ_ENTRY_KEPT = 1,          /* it has one */
+       RIA_HARQ_ENTRY_REMOVED = 2 };     /* it had one and the frame's full success removed it */
+typedef struct ria_mcdpsk_harq_result {  /* 32 bytes, one per row / window; all zero unless a valid header met a cache id >= 0 */
+    uint16_t seq;                        /* the key (:2730) */
+    uint8_t  valid;                      /* 1: the key and cache_id below hold */
+    uint8_t  entry;                      /* RIA_HARQ_ENTRY_*; NONE also when no CW1+ was walked (total_cw 1, or too few soft bits) */
+    uint32_t src_hash, dst_hash;
+    uint16_t stored_mask;                /* bit i: store() of codeword i returned true */
+    uint16_t sum_mask;                   /* bit i: the combined sum of codeword i was decoded (count > 1) */
+    uint16_t recovered_mask;             /* bit i: that decode recovered it */
+    uint8_t  max_combine;                /* largest getCombineCount after the store, over the codewords that failed */
+    uint8_t  reserved0;
+    int32_t  cache_id;
+    int32_t  reserved[2];
+} ria_mcdpsk_harq_result;
+int ria_gpu_mcdpsk_decode_frame_batch(ria_gpu_handle h, const float* llr_dev, int llr_stride, const int32_t* n_llr_dev /* nullable */,
+                                      int n_frames, ria_chase_pool pool /* nullable */, const int32_t* cache_id_dev,
+                                      const uint64_t* now_ms_dev, uint8_t* frame_out_dev, int frame_row,
+                                      ria_mcdpsk_dframe_result* result_dev, ria_mcdpsk_harq_result* harq_dev /* nullable */,
+                                      void* stream);
+/* ria_gpu_mcdpsk_acquire_batch with decodeMCDPSKFrame's chase statements: window b uses cache cache_id_dev[b] (-1: off) at
+ * now_ms_dev[b].  The reference calls decodeMCDPSKFrame for every candidate, so in disconnected mode a candidate that
+ * decodes a header but not the frame stores into the cache too and the window's next candidate sees it; rounds run one
+ * after the other on one stream, which gives that order.  harq_dev[b] (nullable) describes the window's last candidate in
+ * which a valid header met the cache.  pool NULL: every output is that of ria_gpu_mcdpsk_acquire_batch and no extra read
+ * is made.  Duplicate ids among the windows are RIA_ERR_INVALID as above, read with the first control read.  With a pool,
+ * each round that has codeword rows makes one more small device-to-host read (the length of its list of sums). */
+int ria_gpu_mcdpsk_acquire_harq_batch(ria_gpu_handle h, const ria_mcdpsk_config* cfg, const float* samples_dev, int64_t stride,
+                                      int search_len, int window_len, int n_windows, int frame_cw,
+                                      const ria_mcdpsk_acq_params* params_dev, uint32_t flags,
+                                      uint8_t* frame_out_dev, ria_mcdpsk_acq_result* acq_dev,
+                                      float* llr_out_dev /* nullable */, int llr_stride,
+                                      ria_chase_pool pool /* nullable */, const int32_t* cache_id_dev, const uint64_t* now_ms_dev,
+                                      ria_mcdpsk_harq_result* harq_dev /* nullable */, void* stream);
 
 /* ---- RX: decodeFrame, OFDM branch (StreamingDecoder::decodeFrame, src/gui/modem/streaming_decoder.cpp:2821-3059) ----
  * The "try both" strategy every OFDM frame's soft bits go through, statement for statement, over a batch of rows.  Row f is

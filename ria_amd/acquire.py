@@ -240,3 +240,33 @@ def make_mcdpsk_windows(engine, coded, preamble, n, frame_cw, kind, snr_db, seed
     win[:, lead:lead + m] = tx[torch.arange(n, device=engine.device) % tx.shape[0], :m]
     engine.channel_exact_seeded_(win, kind, snr_db, np.ascontiguousarray(seeds, np.uint32))
     return win, search_len
+
+
+# ---- HARQ chase combining (ria_gpu_mcdpsk_acquire_harq_batch, ria_gpu_mcdpsk_decode_frame_batch)
+HARQ_COUNTERS = ("rows", "keyed", "stored_rows", "stores", "stored", "combines", "sum_decodes", "recoveries", "delivered_by_combining",
+                 "entries_kept", "entries_removed")
+
+
+def _popcount16(v):
+    v = np.asarray(v, np.uint16)
+    return sum(((v >> b) & 1).astype(np.int64) for b in range(16))
+
+
+def harq_tally(result, harq):
+    """Counter row (HARQ_COUNTERS) of one call from its result array (MCACQ_RESULT or MCDFRAME_RESULT) and its harq array
+    (HARQ_RESULT): rows; rows whose valid header met a cache; rows that stored; store() calls (every codeword that failed
+    its own decode: those still failed plus those recovered; ChaseCache::Stats.stores); stores that returned true; combines
+    (a store onto an existing sum: stored and its sum decoded; Stats.combines); combined sums decoded; codewords recovered
+    (Stats.recoveries); frames delivered through combining (a success with a recovered codeword); entries kept; entries
+    removed on success.  Summed over the calls of a connected link the three Stats columns equal the cache's counters.  For
+    a disconnected acquire call the harq array describes each window's last candidate that met the cache, so what earlier
+    candidates of a window stored shows in the caches' own statistics only."""
+    keyed = harq["valid"] != 0
+    row = dict(rows=len(harq), keyed=int(keyed.sum()), stored_rows=int((harq["stored_mask"] != 0).sum()),
+               stores=int((result["codewords_failed"].astype(np.int64) + _popcount16(harq["recovered_mask"]))[keyed].sum()),
+               stored=int(_popcount16(harq["stored_mask"]).sum()), combines=int(_popcount16(harq["stored_mask"] & harq["sum_mask"]).sum()),
+               sum_decodes=int(_popcount16(harq["sum_mask"]).sum()), recoveries=int(_popcount16(harq["recovered_mask"]).sum()),
+               delivered_by_combining=int(((result["success"] != 0) & (harq["recovered_mask"] != 0)).sum()),
+               entries_kept=int((harq["entry"] == capi.HARQ_ENTRY["KEPT"]).sum()),
+               entries_removed=int((harq["entry"] == capi.HARQ_ENTRY["REMOVED"]).sum()))
+    return np.array([row[k] for k in HARQ_COUNTERS], dtype=np.int64)

@@ -28,6 +28,8 @@ MACQ_CHANNEL_INTERLEAVE = 0x8
 DFRAME_PATH = {"NONE": 0, "CONTROL_R14": 1, "CONTROL_CW0": 2, "FIXED": 3, "SALVAGE_R14": 4, "SALVAGE_RATE": 5, "FIXED_FAILED": 6,
                "LEGACY": 7, "PARTIAL": 8, "BAD_HEADER": 9}
 DFRAME_MAX_CW = 32
+CHASE_MAX_CW, CHASE_MAX_ENTRIES, CHASE_MAX_COMBINES = 16, 16, 4
+HARQ_ENTRY = {"NONE": 0, "KEPT": 1, "REMOVED": 2}
 
 # every symbol include/ria_gpu.h declares
 EXPORTS = [
@@ -40,6 +42,8 @@ EXPORTS = [
     "ria_gpu_sync_cox_batch", "ria_gpu_cox_preamble", "ria_gpu_channel_exact_cfo_batch", "ria_gpu_tx_cfo_batch",
     "ria_gpu_mcdpsk_demod_host", "ria_gpu_ldpc_decode_robust_host", "ria_gpu_mcdpsk_modulate_batch",
     "ria_gpu_decode_frame_batch", "ria_gpu_decode_frame_host",
+    "ria_gpu_chase_default_config", "ria_gpu_chase_create", "ria_gpu_chase_destroy", "ria_gpu_chase_clear", "ria_gpu_chase_stats", "ria_gpu_chase_export",
+    "ria_gpu_mcdpsk_decode_frame_batch", "ria_gpu_mcdpsk_acquire_harq_batch",
     "ria_link_recommend", "ria_link_data_mode", "ria_link_ofdm_code_rate", "ria_link_cap_initial_rate",
 ]
 
@@ -117,6 +121,32 @@ class DframeResult(C.Structure):
                 ("path", C.c_uint8), ("header_total_cw", C.c_uint8), ("stages", C.c_uint8), ("reserved0", C.c_uint8),
                 ("frame_bytes", C.c_int32), ("iters_r14", C.c_uint16), ("iters_cw0", C.c_uint16), ("tries_r14", C.c_uint8),
                 ("tries_rate", C.c_uint8), ("reserved1", C.c_uint8 * 2), ("reserved", C.c_int32 * 3)]
+
+
+class ChaseConfig(C.Structure):
+    _fields_ = [("n_caches", C.c_int32), ("max_entries", C.c_int32), ("ttl_ms", C.c_int64), ("reserved", C.c_int32 * 4)]
+
+
+class ChaseStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("cache_hits", "cache_misses", "stores", "combines", "entries_evicted", "entries_expired",
+                                          "recoveries")]
+
+
+class ChaseEntry(C.Structure):
+    _fields_ = [("last_access_ms", C.c_uint64), ("order", C.c_uint64), ("src_hash", C.c_uint32), ("dst_hash", C.c_uint32),
+                ("seq", C.c_uint16), ("used", C.c_uint8), ("total_cw", C.c_uint8), ("frame_type", C.c_uint8), ("reserved", C.c_uint8 * 3),
+                ("combine_count", C.c_uint8 * 16), ("decoded", C.c_uint8 * 16), ("has_sum", C.c_uint8 * 16)]
+
+
+class McDframeResult(C.Structure):
+    _fields_ = [("success", C.c_uint8), ("codewords_ok", C.c_uint8), ("codewords_failed", C.c_uint8), ("frame_type", C.c_uint8),
+                ("header_total_cw", C.c_int32), ("frame_bytes", C.c_int32), ("reserved", C.c_int32)]
+
+
+class McHarqResult(C.Structure):
+    _fields_ = [("seq", C.c_uint16), ("valid", C.c_uint8), ("entry", C.c_uint8), ("src_hash", C.c_uint32), ("dst_hash", C.c_uint32),
+                ("stored_mask", C.c_uint16), ("sum_mask", C.c_uint16), ("recovered_mask", C.c_uint16), ("max_combine", C.c_uint8),
+                ("reserved0", C.c_uint8), ("cache_id", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
 def macq_frame_bytes(frame_cw):
@@ -198,6 +228,16 @@ def load(build_if_needed=True):
     L.ria_gpu_mcdpsk_acquire_batch.argtypes = [vp, vp, vp, C.c_int64, i32, i32, i32, i32, vp, u32, vp, vp, vp, i32, vp]
     L.ria_gpu_decode_frame_batch.argtypes = [vp, vp, i32, vp, i32, u32, vp, i32, vp, vp, vp, vp]
     L.ria_gpu_decode_frame_host.argtypes = [vp, vp, i32, u32, vp, i32, vp, vp]
+    L.ria_gpu_chase_default_config.argtypes = [C.POINTER(ChaseConfig)]
+    L.ria_gpu_chase_default_config.restype = None
+    L.ria_gpu_chase_create.argtypes = [vp, C.POINTER(ChaseConfig), C.POINTER(vp)]
+    L.ria_gpu_chase_destroy.argtypes = [vp]
+    L.ria_gpu_chase_destroy.restype = None
+    L.ria_gpu_chase_clear.argtypes = [vp, vp, i32, vp]
+    L.ria_gpu_chase_stats.argtypes = [vp, i32, C.POINTER(ChaseStats)]
+    L.ria_gpu_chase_export.argtypes = [vp, i32, vp, vp]
+    L.ria_gpu_mcdpsk_decode_frame_batch.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp]
+    L.ria_gpu_mcdpsk_acquire_harq_batch.argtypes = [vp, vp, vp, C.c_int64, i32, i32, i32, i32, vp, u32, vp, vp, vp, i32, vp, vp, vp, vp, vp]
     L.ria_link_recommend.argtypes = [f32, f32, C.POINTER(LinkRecommendation)]
     L.ria_link_recommend.restype = None
     L.ria_link_data_mode.argtypes = [f32, i32, f32, C.POINTER(LinkRecommendation)]
@@ -205,7 +245,7 @@ def load(build_if_needed=True):
     L.ria_link_ofdm_code_rate.argtypes = [f32, f32]
     L.ria_link_cap_initial_rate.argtypes = [f32, f32, i32]
     for name in EXPORTS:
-        if name not in ("ria_gpu_default_config", "ria_gpu_destroy", "ria_gpu_last_error", "ria_link_recommend", "ria_link_data_mode"):
+        if name not in ("ria_gpu_chase_default_config", "ria_gpu_chase_destroy", "ria_gpu_default_config", "ria_gpu_destroy", "ria_gpu_last_error", "ria_link_recommend", "ria_link_data_mode"):
             getattr(L, name).restype = i32
     _lib = L
     return L

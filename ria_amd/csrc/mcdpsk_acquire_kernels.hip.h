@@ -28,7 +28,8 @@ __device__ __forceinline__ bool macq_alt(int k) { return k == 1 || (k >= 2 && ((
 struct MacqCtl {                 // read back by the host twice per round
     unsigned int n_list;         // entries of the list the next round runs
     unsigned int n_rows;         // codeword rows of this round's round B
-    unsigned int pad_[2];
+    unsigned int dup;            // HARQ calls: two windows claimed one cache, or a cache id the pool does not have
+    unsigned int n_sums;         // HARQ calls: combined sums this round decodes
 };
 
 struct MacqList {

@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <atomic>
 #include <chrono>
@@ -38,8 +39,16 @@
 #include "mcdpsk_acquire_kernels.hip.h"
 #include "burst_kernels.hip.h"
 #include "decode_frame_kernels.hip.h"
+#include "mcdpsk_harq_kernels.hip.h"
 
 using namespace ria;
+
+// A pool of chase caches (include/ria_gpu.h): metadata, sums and owner words, allocated once at create.  The handle owns it.
+struct ria_chase_pool_s {
+    ria_gpu* h = nullptr;
+    ria_chase_config cfg{};
+    DevBuf d_meta, d_sums, d_owner;   // ChaseCache [n_caches]; float [n_caches][max_entries][16][648]; int32 [n_caches]
+};
 
 constexpr int kMaxParts = 4;   // ria_gpu_rx_batch overlaps up to this many parts of a batch on internal streams
 // Every device and pinned block of a handle is a DevBuf / PinBuf member: ria_gpu_destroy frees them by deleting the handle.
@@ -107,6 +116,10 @@ struct ria_gpu {
     FastCode fast14{}; DevBuf d_f14[5]; int wave_lds14 = 0; bool have14 = false;
     DevBuf d_cw_perm[2];
     DevBuf d_df_ws; PinBuf p_df_ctl;
+    // HARQ: the chase pools created on this handle; the per-row arrays of the chase stages (harq_carve) and, for
+    // ria_gpu_mcdpsk_decode_frame_batch, the round's arrays (macq_carve without soft bits) with their control block
+    std::vector<std::unique_ptr<ria_chase_pool_s>> chase_pools;
+    DevBuf d_harq_ws, d_mdf_ws; PinBuf p_mdf_ctl;
 };
 
 namespace {
@@ -1888,36 +1901,110 @@ static MacqWs macq_carve(Carver& c, size_t n, size_t llr_ws, size_t max_cw, size
     return w;
 }
 
-int ria_gpu_mcdpsk_acquire_batch(ria_gpu_handle h, const ria_mcdpsk_config* cfg, const float* samples_dev, int64_t stride,
-                                 int search_len, int window_len, int n_windows, int frame_cw,
-                                 const ria_mcdpsk_acq_params* params_dev, uint32_t flags,
-                                 uint8_t* frame_out_dev, ria_mcdpsk_acq_result* acq_dev,
-                                 float* llr_out_dev, int llr_stride, void* stream) {
+// ---- the chase stages of decodeMCDPSKFrame (mcdpsk_harq_kernels.hip.h), shared by the two HARQ calls
+struct HarqWs {
+    ria_mcdpsk_harq_result* harq;                                   // [n] when the caller passes none
+    uint8_t* sum_flag; uint32_t* sum_src; int32_t* sum_pos; uint32_t* sum_list;   // [rows]
+    uint8_t *out_c, *ok_c; uint16_t* it_c;                          // [rows] the decodes of the sums
+};
+static HarqWs harq_carve(Carver& c, size_t n, size_t rows, size_t dec_bytes) {
+    HarqWs w;
+    w.harq = c.take<ria_mcdpsk_harq_result>(n);
+    w.sum_flag = c.take<uint8_t>(rows);
+    w.sum_src = c.take<uint32_t>(rows);
+    w.sum_pos = c.take<int32_t>(rows);
+    w.sum_list = c.take<uint32_t>(rows);
+    w.out_c = c.take<uint8_t>(rows * dec_bytes);
+    w.ok_c = c.take<uint8_t>(rows);
+    w.it_c = c.take<uint16_t>(rows);
+    return w;
+}
+static bool chase_pool_alive(ria_gpu_handle h, ria_chase_pool pool) {
+    for (const auto& p : h->chase_pools) if (p.get() == pool) return true;
+    return false;
+}
+// Allocates the stages' arrays (before anything of the call is in flight), clears the owner words and the control block's
+// flags and claims every window's cache.  The caller reads ctl.dup with its first control read.
+static int harq_begin(ria_gpu_handle h, const char* who, ria_chase_pool pool, const int32_t* cache_id_dev, const uint64_t* now_ms_dev,
+                      ria_mcdpsk_harq_result* harq_dev, int n, size_t rows, size_t dec_bytes, MacqCtl* ctl_dev, hipStream_t s,
+                      HarqArgs* H, HarqWs* HW) {
+    if (!chase_pool_alive(h, pool)) return fail(h, RIA_ERR_INVALID, "%s: the pool does not belong to this handle", who);
+    if (!cache_id_dev || !now_ms_dev) return fail(h, RIA_ERR_INVALID, "%s: a pool needs cache_id_dev and now_ms_dev", who);
+    auto carve = [&](Carver& c) { return harq_carve(c, static_cast<size_t>(n), rows, dec_bytes); };
+    HIP_TRY(h, h->d_harq_ws.reserve(carved_size(carve), &s));
+    *HW = carve_at(h->d_harq_ws.as<>(), carve);
+    H->caches = pool->d_meta.as<ChaseCache>();
+    H->sums = pool->d_sums.as<float>();
+    H->owner = pool->d_owner.as<int32_t>();
+    H->n_caches = pool->cfg.n_caches;
+    H->cfg.max_entries = pool->cfg.max_entries;
+    H->cfg.ttl_ms = pool->cfg.ttl_ms;
+    H->cache_id = cache_id_dev; H->now_ms = now_ms_dev;
+    H->harq = harq_dev ? harq_dev : HW->harq;
+    H->sum_flag = HW->sum_flag; H->sum_src = HW->sum_src; H->sum_pos = HW->sum_pos; H->sum_list = HW->sum_list;
+    H->out_c = HW->out_c; H->ok_c = HW->ok_c;
+    HIP_TRY(h, hipMemsetAsync(H->owner, 0xFF, static_cast<size_t>(pool->cfg.n_caches) * sizeof(int32_t), s));
+    HIP_TRY(h, hipMemsetAsync(ctl_dev, 0, sizeof(MacqCtl), s));
+    hipLaunchKernelGGL(harq_claim_kernel, dim3(static_cast<unsigned>(std::min((n + 255) / 256, 1024))), dim3(256), 0, s, *H, n, ctl_dev);
+    HIP_TRY(h, hipGetLastError());
+    return RIA_OK;
+}
+// Stages 4-6 of a round with n_rows round-B rows, between round B's decode and the finish.  One control read (the length
+// of the list of sums) when the round has rows.
+static int harq_stages(ria_gpu_handle h, const char* who, const MacqArgs& A, HarqArgs H, const HarqWs& HW, PinBuf& mirror, int n_rows,
+                       unsigned waves, hipStream_t s) {
+    H.out_b = const_cast<uint8_t*>(A.out_b); H.ok_b = const_cast<uint8_t*>(A.ok_b);
+    hipLaunchKernelGGL(harq_store_kernel, dim3(waves), dim3(256), 0, s, A, H);
+    int n_sums = 0;
+    if (n_rows > 0) {
+        hipLaunchKernelGGL(harq_sum_list_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, H, n_rows, A.ctl);
+        HIP_TRY(h, hipGetLastError());
+        if (int rc = read_ctl(h, mirror, A.ctl, s)) return rc;
+        n_sums = static_cast<int>(mirror.as<MacqCtl>()->n_sums);
+        if (n_sums < 0 || n_sums > n_rows) return fail(h, RIA_ERR_HIP, "%s: the list of sums broke its bound (%d)", who, n_sums);
+    }
+    if (n_sums > 0) {
+        hipLaunchKernelGGL(harq_sum_gather_kernel, dim3(static_cast<unsigned>(std::min<size_t>((static_cast<size_t>(n_sums) * kMacqLdpcBlock + 255) / 256, 16384))),
+                           dim3(256), 0, s, H, A.rows, n_sums);
+        int rc = ria_gpu_ldpc_decode_robust_batch(h, A.rows, n_sums, HW.out_c, HW.ok_c, HW.it_c, nullptr, s);
+        if (rc != RIA_OK) return rc;
+    }
+    hipLaunchKernelGGL(harq_resolve_kernel, dim3(waves), dim3(256), 0, s, A, H, n_sums > 0 ? 1 : 0);
+    HIP_TRY(h, hipGetLastError());
+    return RIA_OK;
+}
+
+static int macq_impl(ria_gpu_handle h, const char* who, const ria_mcdpsk_config* cfg, const float* samples_dev, int64_t stride,
+                     int search_len, int window_len, int n_windows, int frame_cw,
+                     const ria_mcdpsk_acq_params* params_dev, uint32_t flags,
+                     uint8_t* frame_out_dev, ria_mcdpsk_acq_result* acq_dev,
+                     float* llr_out_dev, int llr_stride, ria_chase_pool pool, const int32_t* cache_id_dev, const uint64_t* now_ms_dev,
+                     ria_mcdpsk_harq_result* harq_dev, void* stream) {
     if (!h) return RIA_ERR_INVALID;
     const uint32_t known_flags = RIA_MACQ_SYNC_CHIRP | RIA_MACQ_DISCONNECTED | RIA_MACQ_NO_RETRY | RIA_MACQ_CHANNEL_INTERLEAVE;
     const bool chirp = (flags & RIA_MACQ_SYNC_CHIRP) != 0, disconnected = (flags & RIA_MACQ_DISCONNECTED) != 0;
     if (!mcdpsk_config_ok(cfg) || n_windows < 0 || search_len < 0 || window_len < search_len || stride < window_len ||
         frame_cw < 1 || frame_cw > 8 || (flags & ~known_flags) != 0 || (disconnected && !chirp) || (!chirp && search_len > kZcMaxBuf))
-        return fail(h, RIA_ERR_INVALID, "ria_gpu_mcdpsk_acquire_batch: bad argument (config, 0 <= search_len <= window_len <= stride, "
-                                        "frame_cw 1..8, known flags, ZC only when connected)");
-    if (h->cfg.code_rate != RIA_RATE_1_4) return fail(h, RIA_ERR_INVALID, "ria_gpu_mcdpsk_acquire_batch: MC-DPSK frames are R1/4: the handle's rate must be RIA_RATE_1_4");
-    if (flags & RIA_MACQ_CHANNEL_INTERLEAVE) return fail(h, RIA_ERR_UNSUPPORTED, "ria_gpu_mcdpsk_acquire_batch: MC-DPSK channel interleaving is not implemented");
+        return fail(h, RIA_ERR_INVALID, "%s: bad argument (config, 0 <= search_len <= window_len <= stride, "
+                                        "frame_cw 1..8, known flags, ZC only when connected)", who);
+    if (h->cfg.code_rate != RIA_RATE_1_4) return fail(h, RIA_ERR_INVALID, "%s: MC-DPSK frames are R1/4: the handle's rate must be RIA_RATE_1_4", who);
+    if (flags & RIA_MACQ_CHANNEL_INTERLEAVE) return fail(h, RIA_ERR_UNSUPPORTED, "%s: MC-DPSK channel interleaving is not implemented", who);
     const int nc = cfg->num_carriers, bps = cfg->bits_per_symbol, sp = cfg->spreading;
     const bool retry = disconnected && !(flags & RIA_MACQ_NO_RETRY);
     const int sym_per_cw = (kMacqLdpcBlock + nc * bps - 1) / (nc * bps);
     const int frame_len = (kMcTrain + 1) * kMcSps + frame_cw * sym_per_cw * kMcSps * sp;      // getMinSamplesForCWCount
     if (mcdpsk_lds_bytes(nc, frame_len) > 160 * 1024)
-        return fail(h, RIA_ERR_UNSUPPORTED, "ria_gpu_mcdpsk_acquire_batch: frame of %d samples too long for the MC-DPSK demodulator", frame_len);
+        return fail(h, RIA_ERR_UNSUPPORTED, "%s: frame of %d samples too long for the MC-DPSK demodulator", who, frame_len);
     const int nds = frame_cw * sym_per_cw;
     const int llr_ws = nds * nc * 2;                                   // either modulation
     const int llr_need = nds * nc * (retry ? 2 : bps);                 // candidates that can run
     const int max_cw = llr_ws / kMacqLdpcBlock;                        // <= 2 * frame_cw
     if (llr_out_dev && llr_stride < llr_need)
-        return fail(h, RIA_ERR_INVALID, "ria_gpu_mcdpsk_acquire_batch: llr_stride %d < %d soft bits", llr_stride, llr_need);
-    if (max_cw > 2 * frame_cw) return fail(h, RIA_ERR_UNSUPPORTED, "ria_gpu_mcdpsk_acquire_batch: codeword bound broken");
+        return fail(h, RIA_ERR_INVALID, "%s: llr_stride %d < %d soft bits", who, llr_stride, llr_need);
+    if (max_cw > 2 * frame_cw) return fail(h, RIA_ERR_UNSUPPORTED, "%s: codeword bound broken", who);
     if (n_windows == 0) return RIA_OK;
     if (!samples_dev || !params_dev || !frame_out_dev || !acq_dev)
-        return fail(h, RIA_ERR_INVALID, "ria_gpu_mcdpsk_acquire_batch: null pointer");
+        return fail(h, RIA_ERR_INVALID, "%s: null pointer", who);
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t n = static_cast<size_t>(n_windows), dec_bytes = static_cast<size_t>((h->geo.ldpc_k + 7) / 8);
@@ -1929,6 +2016,13 @@ int ria_gpu_mcdpsk_acquire_batch(ria_gpu_handle h, const ria_mcdpsk_config* cfg,
     const int frame_row = RIA_MACQ_FRAME_BYTES(frame_cw);
     HIP_TRY(h, hipMemsetAsync(frame_out_dev, 0, n * frame_row, s));
     if (llr_out_dev) HIP_TRY(h, hipMemsetAsync(llr_out_dev, 0, n * static_cast<size_t>(llr_stride) * sizeof(float), s));
+    HarqArgs H{};
+    HarqWs HW{};
+    if (pool) {
+        if (int rc = harq_begin(h, who, pool, cache_id_dev, now_ms_dev, harq_dev, n_windows, n * static_cast<size_t>(max_cw), dec_bytes, W.ctl, s, &H, &HW)) return rc;
+    } else if (harq_dev) {
+        HIP_TRY(h, hipMemsetAsync(harq_dev, 0, n * sizeof(ria_mcdpsk_harq_result), s));
+    }
 
     // 1. detection with each window's threshold (and known CFO for ZC)
     const int pstride = static_cast<int>(sizeof(ria_mcdpsk_acq_params) / sizeof(float));
@@ -1967,10 +2061,12 @@ int ria_gpu_mcdpsk_acquire_batch(ria_gpu_handle h, const ria_mcdpsk_config* cfg,
     // their next candidate that fits (at most 25 more rounds: each advances every window it holds by at least one candidate)
     for (int round = 0;; ++round) {
         if (int rc = read_ctl(h, h->p_macq_ctl, A.ctl, s)) return rc;
+        if (pool && round == 0 && ctl.dup)
+            return fail(h, RIA_ERR_INVALID, "%s: two windows of one call use one cache id, or an id is not below n_caches; no cache was touched", who);
         const int n_list = static_cast<int>(ctl.n_list);
         if (n_list == 0) break;
         if (n_list > n_windows || round >= kMacqCandidates)
-            return fail(h, RIA_ERR_HIP, "ria_gpu_mcdpsk_acquire_batch: work list of round %d broke its bound (%d)", round, n_list);
+            return fail(h, RIA_ERR_HIP, "%s: work list of round %d broke its bound (%d)", who, round, n_list);
         A.cur = W.list[round & 1];
         A.next = W.list[(round + 1) & 1];
         A.n_cur = n_list;
@@ -1990,7 +2086,7 @@ int ria_gpu_mcdpsk_acquire_batch(ria_gpu_handle h, const ria_mcdpsk_config* cfg,
         if ((rc = read_ctl(h, h->p_macq_ctl, A.ctl, s)) != RIA_OK) return rc;
         const int n_rows = static_cast<int>(ctl.n_rows);
         if (n_rows < 0 || n_rows > n_list * (max_cw - 1))
-            return fail(h, RIA_ERR_HIP, "ria_gpu_mcdpsk_acquire_batch: codeword rows of round %d broke their bound (%d)", round, n_rows);
+            return fail(h, RIA_ERR_HIP, "%s: codeword rows of round %d broke their bound (%d)", who, round, n_rows);
         // round B: CW1..total_cw-1 of the entries whose header asks for them
         if (n_rows > 0) {
             hipLaunchKernelGGL(macq_gather_kernel, dim3(static_cast<unsigned>(std::min<size_t>((static_cast<size_t>(n_rows) * kMacqLdpcBlock + 255) / 256, 16384))),
@@ -1998,10 +2094,188 @@ int ria_gpu_mcdpsk_acquire_batch(ria_gpu_handle h, const ria_mcdpsk_config* cfg,
             rc = ria_gpu_ldpc_decode_robust_batch(h, A.rows, n_rows, W.out_b, W.ok_b, W.it_b, nullptr, s);
             if (rc != RIA_OK) return rc;
         }
+        if (pool && (rc = harq_stages(h, who, A, H, HW, h->p_macq_ctl, n_rows, waves, s)) != RIA_OK) return rc;
         hipLaunchKernelGGL(macq_finish_kernel, dim3(waves), dim3(256), 0, s, A);
         hipLaunchKernelGGL(macq_next_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A);
         HIP_TRY(h, hipGetLastError());
     }
+    return RIA_OK;
+}
+
+int ria_gpu_mcdpsk_acquire_batch(ria_gpu_handle h, const ria_mcdpsk_config* cfg, const float* samples_dev, int64_t stride,
+                                 int search_len, int window_len, int n_windows, int frame_cw,
+                                 const ria_mcdpsk_acq_params* params_dev, uint32_t flags,
+                                 uint8_t* frame_out_dev, ria_mcdpsk_acq_result* acq_dev,
+                                 float* llr_out_dev, int llr_stride, void* stream) {
+    return macq_impl(h, "ria_gpu_mcdpsk_acquire_batch", cfg, samples_dev, stride, search_len, window_len, n_windows, frame_cw, params_dev, flags,
+                     frame_out_dev, acq_dev, llr_out_dev, llr_stride, nullptr, nullptr, nullptr, nullptr, stream);
+}
+int ria_gpu_mcdpsk_acquire_harq_batch(ria_gpu_handle h, const ria_mcdpsk_config* cfg, const float* samples_dev, int64_t stride,
+                                      int search_len, int window_len, int n_windows, int frame_cw,
+                                      const ria_mcdpsk_acq_params* params_dev, uint32_t flags,
+                                      uint8_t* frame_out_dev, ria_mcdpsk_acq_result* acq_dev,
+                                      float* llr_out_dev, int llr_stride,
+                                      ria_chase_pool pool, const int32_t* cache_id_dev, const uint64_t* now_ms_dev,
+                                      ria_mcdpsk_harq_result* harq_dev, void* stream) {
+    return macq_impl(h, "ria_gpu_mcdpsk_acquire_harq_batch", cfg, samples_dev, stride, search_len, window_len, n_windows, frame_cw, params_dev, flags,
+                     frame_out_dev, acq_dev, llr_out_dev, llr_stride, pool, cache_id_dev, now_ms_dev, harq_dev, stream);
+}
+
+// ------------------------------------------------------------------------------------------------ the chase pool
+static_assert(sizeof(ria_chase_config) == 32 && sizeof(ria_chase_stats) == 56 && sizeof(ria_chase_entry) == 80 && sizeof(ChaseCache) == 1344 &&
+              sizeof(ria_mcdpsk_harq_result) == 32 && sizeof(ria_mcdpsk_dframe_result) == 16, "HARQ record sizes (include/ria_gpu.h)");
+
+void ria_gpu_chase_default_config(ria_chase_config* cfg) {
+    if (!cfg) return;
+    std::memset(cfg, 0, sizeof(*cfg));
+    cfg->n_caches = 1; cfg->max_entries = RIA_CHASE_MAX_ENTRIES; cfg->ttl_ms = 30000;
+}
+int ria_gpu_chase_create(ria_gpu_handle h, const ria_chase_config* cfg, ria_chase_pool* out) {
+    if (!h) return RIA_ERR_INVALID;
+    if (!cfg || !out || cfg->n_caches < 1 || cfg->max_entries < 1 || cfg->max_entries > RIA_CHASE_MAX_ENTRIES || cfg->ttl_ms < 0)
+        return fail(h, RIA_ERR_INVALID, "ria_gpu_chase_create: bad argument (n_caches >= 1, max_entries 1..16, ttl_ms >= 0)");
+    *out = nullptr;
+    HIP_TRY(h, hipSetDevice(h->device));
+    auto p = std::make_unique<ria_chase_pool_s>();
+    p->h = h; p->cfg = *cfg;
+    const size_t nc = static_cast<size_t>(cfg->n_caches);
+    HIP_TRY(h, p->d_meta.reserve(nc * sizeof(ChaseCache)));
+    HIP_TRY(h, p->d_sums.reserve(nc * static_cast<size_t>(cfg->max_entries) * RIA_CHASE_MAX_CW * kMacqLdpcBlock * sizeof(float)));
+    HIP_TRY(h, p->d_owner.reserve(nc * sizeof(int32_t)));
+    HIP_TRY(h, hipMemset(p->d_meta.as<>(), 0, nc * sizeof(ChaseCache)));
+    HIP_TRY(h, hipMemset(p->d_sums.as<>(), 0, p->d_sums.bytes()));
+    *out = p.get();
+    h->chase_pools.push_back(std::move(p));
+    return RIA_OK;
+}
+void ria_gpu_chase_destroy(ria_chase_pool pool) {
+    if (!pool || !pool->h) return;
+    ria_gpu_handle h = pool->h;
+    (void)hipSetDevice(h->device);
+    (void)hipDeviceSynchronize();      // work that reads the pool may still be in flight
+    auto& v = h->chase_pools;
+    v.erase(std::remove_if(v.begin(), v.end(), [&](const std::unique_ptr<ria_chase_pool_s>& p) { return p.get() == pool; }), v.end());
+}
+int ria_gpu_chase_clear(ria_chase_pool pool, const int32_t* cache_ids_dev, int n, void* stream) {
+    if (!pool || !pool->h) return RIA_ERR_INVALID;
+    ria_gpu_handle h = pool->h;
+    if (cache_ids_dev && n < 0) return fail(h, RIA_ERR_INVALID, "ria_gpu_chase_clear: n < 0");
+    const int count = cache_ids_dev ? n : pool->cfg.n_caches;
+    if (count == 0) return RIA_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipLaunchKernelGGL(harq_clear_kernel, dim3(static_cast<unsigned>(std::min((count + 255) / 256, 1024))), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       pool->d_meta.as<ChaseCache>(), pool->cfg.n_caches, cache_ids_dev, count);
+    HIP_TRY(h, hipGetLastError());
+    return RIA_OK;
+}
+static int chase_read_cache(ria_chase_pool pool, const char* who, int cache_id, ChaseCache* out) {
+    ria_gpu_handle h = pool->h;
+    if (cache_id < 0 || cache_id >= pool->cfg.n_caches) return fail(h, RIA_ERR_INVALID, "%s: cache_id %d outside the pool", who, cache_id);
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipDeviceSynchronize());
+    HIP_TRY(h, hipMemcpy(out, pool->d_meta.as<ChaseCache>() + cache_id, sizeof(ChaseCache), hipMemcpyDeviceToHost));
+    return RIA_OK;
+}
+int ria_gpu_chase_stats(ria_chase_pool pool, int cache_id, ria_chase_stats* out_host) {
+    if (!pool || !pool->h) return RIA_ERR_INVALID;
+    if (!out_host) return fail(pool->h, RIA_ERR_INVALID, "ria_gpu_chase_stats: null pointer");
+    ChaseCache c;
+    if (int rc = chase_read_cache(pool, "ria_gpu_chase_stats", cache_id, &c)) return rc;
+    *out_host = c.stats;
+    return RIA_OK;
+}
+int ria_gpu_chase_export(ria_chase_pool pool, int cache_id, ria_chase_entry* entries_out_host, float* sums_out_host) {
+    if (!pool || !pool->h) return RIA_ERR_INVALID;
+    ria_gpu_handle h = pool->h;
+    ChaseCache c;
+    if (int rc = chase_read_cache(pool, "ria_gpu_chase_export", cache_id, &c)) return rc;
+    const int me = pool->cfg.max_entries;
+    const size_t per_entry = static_cast<size_t>(RIA_CHASE_MAX_CW) * kMacqLdpcBlock;
+    if (entries_out_host) std::memset(entries_out_host, 0, static_cast<size_t>(me) * sizeof(ria_chase_entry));
+    if (sums_out_host) std::memset(sums_out_host, 0, static_cast<size_t>(me) * per_entry * sizeof(float));
+    int n = 0;
+    for (int s = 0; s < me; ++s) {
+        if (!c.e[s].used) continue;
+        if (entries_out_host) entries_out_host[n] = c.e[s];
+        if (sums_out_host) {
+            const float* src = pool->d_sums.as<float>() + (static_cast<size_t>(cache_id) * me + s) * per_entry;
+            for (int cw = 0; cw < RIA_CHASE_MAX_CW; ++cw)
+                if (c.e[s].has_sum[cw])
+                    HIP_TRY(h, hipMemcpy(sums_out_host + (static_cast<size_t>(n) * RIA_CHASE_MAX_CW + cw) * kMacqLdpcBlock, src + static_cast<size_t>(cw) * kMacqLdpcBlock,
+                                         kMacqLdpcBlock * sizeof(float), hipMemcpyDeviceToHost));
+        }
+        ++n;
+    }
+    return n;
+}
+
+// ------------------------------------------------------------------------------------------------ decodeMCDPSKFrame on soft bits
+struct MdfWs { MacqWs m; ria_mcdpsk_acq_result* acq; };
+int ria_gpu_mcdpsk_decode_frame_batch(ria_gpu_handle h, const float* llr_dev, int llr_stride, const int32_t* n_llr_dev, int n_frames,
+                                      ria_chase_pool pool, const int32_t* cache_id_dev, const uint64_t* now_ms_dev,
+                                      uint8_t* frame_out_dev, int frame_row, ria_mcdpsk_dframe_result* result_dev,
+                                      ria_mcdpsk_harq_result* harq_dev, void* stream) {
+    if (!h) return RIA_ERR_INVALID;
+    const char* who = "ria_gpu_mcdpsk_decode_frame_batch";
+    if (n_frames < 0 || llr_stride < kMacqLdpcBlock || llr_stride > RIA_CHASE_MAX_CW * kMacqLdpcBlock || frame_row < kMacqCwBytes * (llr_stride / kMacqLdpcBlock))
+        return fail(h, RIA_ERR_INVALID, "%s: bad argument (648 <= llr_stride <= 16 * 648, frame_row >= 20 * (llr_stride / 648))", who);
+    if (h->cfg.code_rate != RIA_RATE_1_4) return fail(h, RIA_ERR_INVALID, "%s: MC-DPSK frames are R1/4: the handle's rate must be RIA_RATE_1_4", who);
+    if (n_frames == 0) return RIA_OK;
+    if (!llr_dev || !frame_out_dev || !result_dev) return fail(h, RIA_ERR_INVALID, "%s: null pointer", who);
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t n = static_cast<size_t>(n_frames), max_cw = static_cast<size_t>(llr_stride / kMacqLdpcBlock);
+    const size_t dec_bytes = static_cast<size_t>((h->geo.ldpc_k + 7) / 8);
+    auto carve = [&](Carver& c) { MdfWs w; w.m = macq_carve(c, n, 0, max_cw, dec_bytes); w.acq = c.take<ria_mcdpsk_acq_result>(n); return w; };
+    HIP_TRY(h, h->d_mdf_ws.reserve(carved_size(carve), &s));
+    HIP_TRY(h, h->p_mdf_ctl.reserve(sizeof(MacqCtl)));
+    const MdfWs MW = carve_at(h->d_mdf_ws.as<>(), carve);
+    const MacqWs& W = MW.m;
+    const MacqCtl& ctl = *h->p_mdf_ctl.as<MacqCtl>();
+    HarqArgs H{};
+    HarqWs HW{};
+    if (pool) {
+        if (int rc = harq_begin(h, who, pool, cache_id_dev, now_ms_dev, harq_dev, n_frames, n * max_cw, dec_bytes, W.ctl, s, &H, &HW)) return rc;
+    } else if (harq_dev) {
+        HIP_TRY(h, hipMemsetAsync(harq_dev, 0, n * sizeof(ria_mcdpsk_harq_result), s));
+    }
+    MacqArgs A{};
+    A.n_windows = n_frames; A.retry = 0; A.bps = 1; A.acq = MW.acq; A.ctl = W.ctl;
+    A.cur = W.list[0]; A.next = W.list[1]; A.n_cur = n_frames;
+    A.mst = W.mst; A.llr = llr_dev; A.llr_ws = llr_stride;
+    A.rows = W.rows; A.row_entry = W.row_entry; A.row_cw = W.row_cw;
+    A.out_a = W.out_a; A.ok_a = W.ok_a; A.out_b = W.out_b; A.ok_b = W.ok_b;
+    A.dec_bytes = static_cast<int>(dec_bytes);
+    A.hdr_total = W.hdr; A.need_rows = W.need; A.row_base = W.base; A.done = W.done;
+    A.crc_bit = h->d_crc_bit.as<const uint16_t>(); A.crc_init = h->d_crc_init.as<const uint16_t>();
+    A.frame_out = frame_out_dev; A.frame_row = frame_row;
+    // the rows as one round's list (every row, in order), then that round's stages
+    const unsigned tgrid = static_cast<unsigned>(std::min((n_frames + 255) / 256, 1024));
+    hipLaunchKernelGGL(mdf_list_kernel, dim3(tgrid), dim3(256), 0, s, A, n_llr_dev, W.mst);
+    MacqArgs G = A;
+    G.row_entry = nullptr;
+    hipLaunchKernelGGL(macq_gather_kernel, dim3(static_cast<unsigned>(std::min<size_t>((n * kMacqLdpcBlock + 255) / 256, 16384))), dim3(256), 0, s, G, n_frames);
+    int rc = ria_gpu_ldpc_decode_robust_batch(h, A.rows, n_frames, W.out_a, W.ok_a, W.it_a, nullptr, s);
+    if (rc != RIA_OK) return rc;
+    const unsigned waves = static_cast<unsigned>(std::min((n_frames + 3) / 4, 4096));
+    hipLaunchKernelGGL(macq_header_kernel, dim3(waves), dim3(256), 0, s, A);
+    hipLaunchKernelGGL(macq_rows_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A);
+    HIP_TRY(h, hipGetLastError());
+    if ((rc = read_ctl(h, h->p_mdf_ctl, A.ctl, s)) != RIA_OK) return rc;
+    if (pool && ctl.dup)
+        return fail(h, RIA_ERR_INVALID, "%s: two rows of one call use one cache id, or an id is not below n_caches; no cache was touched", who);
+    const int n_rows = static_cast<int>(ctl.n_rows);
+    if (n_rows < 0 || static_cast<size_t>(n_rows) > n * (max_cw - 1)) return fail(h, RIA_ERR_HIP, "%s: the codeword rows broke their bound (%d)", who, n_rows);
+    if (n_rows > 0) {
+        hipLaunchKernelGGL(macq_gather_kernel, dim3(static_cast<unsigned>(std::min<size_t>((static_cast<size_t>(n_rows) * kMacqLdpcBlock + 255) / 256, 16384))),
+                           dim3(256), 0, s, A, n_rows);
+        rc = ria_gpu_ldpc_decode_robust_batch(h, A.rows, n_rows, W.out_b, W.ok_b, W.it_b, nullptr, s);
+        if (rc != RIA_OK) return rc;
+    }
+    if (pool && (rc = harq_stages(h, who, A, H, HW, h->p_mdf_ctl, n_rows, waves, s)) != RIA_OK) return rc;
+    hipLaunchKernelGGL(macq_finish_kernel, dim3(waves), dim3(256), 0, s, A);
+    hipLaunchKernelGGL(mdf_result_kernel, dim3(tgrid), dim3(256), 0, s, MW.acq, n_frames, result_dev);
+    HIP_TRY(h, hipGetLastError());
     return RIA_OK;
 }
 

@@ -20,6 +20,51 @@ def _stream_ptr():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+class ChasePool:
+    """A pool of device-resident HARQ chase caches (ria_gpu_chase_create): one fec::ChaseCache per link or trial.  Owned by
+    the engine's handle: close it before the engine, or let the engine's close free it."""
+    ENTRY = np.dtype([("last_access_ms", "<u8"), ("order", "<u8"), ("src_hash", "<u4"), ("dst_hash", "<u4"), ("seq", "<u2"),
+                      ("used", "u1"), ("total_cw", "u1"), ("frame_type", "u1"), ("reserved", "u1", 3), ("combine_count", "u1", 16),
+                      ("decoded", "u1", 16), ("has_sum", "u1", 16)])
+    STATS = ("cache_hits", "cache_misses", "stores", "combines", "entries_evicted", "entries_expired", "recoveries")
+
+    def __init__(self, engine, n_caches, max_entries=16, ttl_ms=30000):
+        self.engine, self.lib = engine, engine.lib
+        self.n_caches, self.max_entries, self.ttl_ms = int(n_caches), int(max_entries), int(ttl_ms)
+        cfg = capi.ChaseConfig()
+        self.lib.ria_gpu_chase_default_config(C.byref(cfg))
+        cfg.n_caches, cfg.max_entries, cfg.ttl_ms = self.n_caches, self.max_entries, self.ttl_ms
+        p = C.c_void_p()
+        engine._check(self.lib.ria_gpu_chase_create(engine.h, C.byref(cfg), C.byref(p)))
+        self.p = p
+
+    def close(self):
+        if getattr(self, "p", None) and getattr(self.engine, "h", None):
+            self.lib.ria_gpu_chase_destroy(self.p)
+        self.p = None
+
+    def clear(self, cache_ids=None):
+        """ChaseCache::clear for the listed caches (None: all); counters stay"""
+        ids = None
+        if cache_ids is not None:
+            ids = torch.as_tensor(np.ascontiguousarray(cache_ids, np.int32)).to(self.engine.device)
+        self.engine._check(self.lib.ria_gpu_chase_clear(self.p, _ptr(ids), 0 if ids is None else ids.numel(), _stream_ptr()))
+
+    def stats(self, cache_id):
+        st = capi.ChaseStats()
+        self.engine._check(self.lib.ria_gpu_chase_stats(self.p, int(cache_id), C.byref(st)))
+        return {k: int(getattr(st, k)) for k in self.STATS}
+
+    def export(self, cache_id):
+        """(entries structured array [size()], sums float32 [size(), 16, 648], zero where has_sum is 0)"""
+        ent = np.zeros(self.max_entries, self.ENTRY)
+        sums = np.zeros((self.max_entries, 16, 648), np.float32)
+        n = self.lib.ria_gpu_chase_export(self.p, int(cache_id), ent.ctypes.data, sums.ctypes.data)
+        if n < 0:
+            self.engine._check(n)
+        return ent[:n], sums[:n]
+
+
 class RxEngine:
     def __init__(self, modulation="QAM16", code_rate="R1_2", device=0, max_batch=4096):
         if not torch.cuda.is_available():
@@ -431,13 +476,17 @@ class RxEngine:
 
     def mcdpsk_acquire(self, windows, search_len, frame_cw, carriers=10, modulation="DBPSK", spreading=1, sync="chirp",
                        disconnected=None, known_cfo=None, detect_threshold=None, min_confidence=None, abs_base=None, retry=True,
-                       want_llr=False):
+                       want_llr=False, chase=None, cache_id=None, now_ms=None, harq_entry=False):
         """MC-DPSK frames from capture windows (ria_gpu_mcdpsk_acquire_batch): ZC ("zc") or dual-chirp ("chirp") detection
         on the first search_len samples of each row of `windows` (float32 [n, window_len] on the device), the acceptance
         test, demodulation + decodeMCDPSKFrame at R1/4 and, when `disconnected` (default: chirp), the handshake fallbacks.
         The handle must be R1/4.  known_cfo / detect_threshold / min_confidence / abs_base: scalars or one value per window
         (defaults: 0, the reference's 0.2 ZC / 0.15 chirp, acquire.zc_min_confidence(0) for ZC and 0 for chirp).
-        Returns (frames uint8 [n, 40 * frame_cw], acq_result structured array (MCACQ_RESULT)[, llr float32 [n, stride]])."""
+        chase: a ChasePool routes the call to ria_gpu_mcdpsk_acquire_harq_batch; window b then uses cache cache_id[b] (default
+        b, -1 = off) at time now_ms (scalar or one per window, default 0).  harq_entry: use that entry point without a pool too
+        (the same outputs as the plain call, plus an all-zero harq array).
+        Returns (frames uint8 [n, 40 * frame_cw], acq_result structured array (MCACQ_RESULT)[, llr float32 [n, stride]]
+        [, harq result structured array (HARQ_RESULT) when chase is given])."""
         from .acquire import zc_min_confidence
         n, window_len = windows.shape
         assert windows.dtype == torch.float32 and windows.is_contiguous()
@@ -459,11 +508,54 @@ class RxEngine:
             stride = frame_cw * -(-648 // (carriers * bps)) * carriers * 2        # room for either modulation
             llr = torch.empty((n, stride), dtype=torch.float32, device=self.device)
         cfg = capi.McdpskConfig(carriers, bps, spreading, 0)
-        self._check(self.lib.ria_gpu_mcdpsk_acquire_batch(self.h, C.byref(cfg), _ptr(windows), window_len, int(search_len), window_len, n,
-                                                          int(frame_cw), _ptr(params), fl, _ptr(frames), _ptr(acq), _ptr(llr), stride,
-                                                          _stream_ptr()))
+        if chase is None and not harq_entry:
+            self._check(self.lib.ria_gpu_mcdpsk_acquire_batch(self.h, C.byref(cfg), _ptr(windows), window_len, int(search_len), window_len, n,
+                                                              int(frame_cw), _ptr(params), fl, _ptr(frames), _ptr(acq), _ptr(llr), stride,
+                                                              _stream_ptr()))
+            res = self._status_array(acq, self.MCACQ_RESULT)
+            return (frames, res, llr) if want_llr else (frames, res)
+        ids, now, harq = self._harq_in(n, cache_id, now_ms)
+        self._check(self.lib.ria_gpu_mcdpsk_acquire_harq_batch(self.h, C.byref(cfg), _ptr(windows), window_len, int(search_len), window_len, n,
+                                                               int(frame_cw), _ptr(params), fl, _ptr(frames), _ptr(acq), _ptr(llr), stride,
+                                                               chase.p if chase is not None else None, _ptr(ids), _ptr(now), _ptr(harq),
+                                                               _stream_ptr()))
         res = self._status_array(acq, self.MCACQ_RESULT)
-        return (frames, res, llr) if want_llr else (frames, res)
+        hq = self._status_array(harq, self.HARQ_RESULT)
+        return (frames, res, llr, hq) if want_llr else (frames, res, hq)
+
+    MCDFRAME_RESULT = np.dtype([("success", "u1"), ("codewords_ok", "u1"), ("codewords_failed", "u1"), ("frame_type", "u1"),
+                                ("header_total_cw", "<i4"), ("frame_bytes", "<i4"), ("reserved", "<i4")])
+    HARQ_RESULT = np.dtype([("seq", "<u2"), ("valid", "u1"), ("entry", "u1"), ("src_hash", "<u4"), ("dst_hash", "<u4"),
+                            ("stored_mask", "<u2"), ("sum_mask", "<u2"), ("recovered_mask", "<u2"), ("max_combine", "u1"),
+                            ("reserved0", "u1"), ("cache_id", "<i4"), ("reserved", "<i4", 2)])
+
+    def chase_pool(self, n_caches, max_entries=16, ttl_ms=30000):
+        return ChasePool(self, n_caches, max_entries, ttl_ms)
+
+    def _harq_in(self, n, cache_id, now_ms):
+        ids = np.arange(n, dtype=np.int32) if cache_id is None else np.ascontiguousarray(np.broadcast_to(np.asarray(cache_id, np.int32), (n,)))
+        now = np.ascontiguousarray(np.broadcast_to(np.asarray(0 if now_ms is None else now_ms, np.uint64), (n,)))
+        return (torch.from_numpy(ids.copy()).to(self.device), torch.from_numpy(now.view(np.int64).copy()).to(self.device),
+                torch.empty((n, 32), dtype=torch.uint8, device=self.device))
+
+    def mcdpsk_decode_frame(self, llr, n_llr=None, chase=None, cache_id=None, now_ms=None):
+        """StreamingDecoder::decodeMCDPSKFrame at R1/4 over rows of soft bits (ria_gpu_mcdpsk_decode_frame_batch): llr float32
+        [n, 648 .. 16 * 648], n_llr the soft bits of each row (None: the whole row).  chase: a ChasePool; row f then uses cache
+        cache_id[f] (default f, -1 = off) at time now_ms (scalar or per row, default 0).
+        Returns (frame bytes uint8 [n, 20 * (cols // 648)], result (MCDFRAME_RESULT), harq result (HARQ_RESULT))."""
+        n, stride = llr.shape
+        assert llr.dtype == torch.float32 and llr.is_contiguous()
+        row = 20 * (stride // 648)
+        frames = torch.empty((n, row), dtype=torch.uint8, device=self.device)
+        res = torch.empty((n, 16), dtype=torch.uint8, device=self.device)
+        nl = None
+        if n_llr is not None:
+            nl = torch.as_tensor(np.ascontiguousarray(n_llr, np.int32)).to(self.device) if not torch.is_tensor(n_llr) else n_llr
+            assert nl.dtype == torch.int32 and nl.numel() == n and nl.is_contiguous()
+        ids, now, harq = self._harq_in(n, cache_id, now_ms)
+        self._check(self.lib.ria_gpu_mcdpsk_decode_frame_batch(self.h, _ptr(llr), stride, _ptr(nl), n, chase.p if chase is not None else None,
+                                                               _ptr(ids), _ptr(now), _ptr(frames), row, _ptr(res), _ptr(harq), _stream_ptr()))
+        return frames, self._status_array(res, self.MCDFRAME_RESULT), self._status_array(harq, self.HARQ_RESULT)
 
     def mcdpsk_modulate(self, data, carriers=10, bits_per_symbol=1, spreading=1):
         data = np.ascontiguousarray(data, np.uint8)

@@ -6,6 +6,12 @@ Workloads (all windows built and channelled on the device, ria_amd.acquire.make_
   zc_connected: connected ZC windows of a 1-CW control frame
   host_chain: the connect_awgn windows through the separate calls driven from the host, primary candidate only, with
               the time of each stage (sync_chirp, mcdpsk_demod, ldpc_decode_robust of every codeword)
+
+--harq N: instead, the cost of the HARQ chase cache (ria_gpu_mcdpsk_acquire_harq_batch).  The connect_moderate windows at
+  --harq-snr are N transmissions of the same links (window i = link i = cache i of one pool, a new channel seed per
+  transmission).  Times the plain call and the HARQ entry without a pool on transmission 0, then the N transmissions into
+  the pool (cleared before each repetition), with the HARQ counters of every transmission (ria_amd.acquire.harq_tally: the
+  windows' last candidates) and what the transmission added to the caches' own statistics, summed over the pool.  --harq-call-only: one pass of the pool calls alone, for a kernel trace.
 """
 import argparse
 import json
@@ -31,8 +37,75 @@ def timed(fn, reps):
     return (time.perf_counter() - t) / reps, out
 
 
+def harq_mode(e, a):
+    from mcdpsk_acquire_restatement import CONNECT, data_frame, encode_frame
+    from ria_amd.acquire import HARQ_COUNTERS, harq_tally, make_mcdpsk_windows
+    from ria_amd.engine import ChasePool
+    from ria_amd.srchash import csrc_sha256
+    n, N = a.windows, a.harq
+    connect = encode_frame(data_frame(CONNECT, 7, np.arange(25, dtype=np.uint8)))[None, :]
+    chirp = e.chirp_preamble()
+    base = np.arange(1, n + 1, dtype=np.uint32) * np.uint32(2654435761)
+    wins = []
+    for t in range(N):
+        w, sl = make_mcdpsk_windows(e, connect, chirp, n, 3, 2, a.harq_snr, base + np.uint32(7919 * t))
+        wins.append(w)
+    pool = e.chase_pool(n, max_entries=a.harq_entries)
+    out = {"metric": "mcdpsk_acquire_harq_ms", "windows": n, "transmissions": N, "snr_db": a.harq_snr, "channel": "moderate",
+           "pool_entries": a.harq_entries, "pool_bytes": n * a.harq_entries * 16 * 648 * 4, "source_hash": csrc_sha256()}
+
+    def pass_(record):
+        pool.clear()
+        torch.cuda.synchronize()
+        rows = []
+        for t in range(N):
+            t0 = time.perf_counter()
+            frames, res, hq = e.mcdpsk_acquire(wins[t], sl, 3, chase=pool, now_ms=1000 * t)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            if record:
+                rows.append((dt, res, hq))
+        return rows
+    pass_(False)
+    if a.harq_call_only:
+        print(json.dumps(out))
+        return
+    reps = [pass_(True) for _ in range(a.reps)]
+    dt, (_, res0) = timed(lambda: e.mcdpsk_acquire(wins[0], sl, 3), a.reps)
+    out["plain_call"] = {"ms": dt * 1e3, "success": int(res0["success"].sum()), "candidates": int(res0["candidates"].sum())}
+    dt, (_, res1, _) = timed(lambda: e.mcdpsk_acquire(wins[0], sl, 3, harq_entry=True), a.reps)
+    out["harq_entry_no_pool"] = {"ms": dt * 1e3, "equal_to_plain": bool(res0.tobytes() == res1.tobytes())}
+    out["with_pool"] = []
+    for t in range(N):
+        _, res, hq = reps[-1][t]
+        row = {"transmission": t, "ms": float(np.mean([r[t][0] for r in reps])) * 1e3, "success": int(res["success"].sum()),
+               "candidates": int(res["candidates"].sum())}
+        row.update({k: int(v) for k, v in zip(HARQ_COUNTERS, harq_tally(res, hq))})
+        out["with_pool"].append(row)
+    # the caches' own counters per transmission, from one more pass (the counters run on through clear(): differences)
+    def totals():
+        tot = dict.fromkeys(ChasePool.STATS, 0)
+        for c in range(n):
+            for k, v in pool.stats(c).items():
+                tot[k] += v
+        return tot
+    pool.clear()
+    before = totals()
+    for t in range(N):
+        e.mcdpsk_acquire(wins[t], sl, 3, chase=pool, now_ms=1000 * t)
+        after = totals()
+        out["with_pool"][t]["cache_stats"] = {k: after[k] - before[k] for k in ChasePool.STATS}
+        before = after
+    out["live_entries"] = sum(len(pool.export(c)[0]) for c in range(n))
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--harq", type=int, default=0, help="N > 0: time N transmissions of the same links into one chase pool instead")
+    ap.add_argument("--harq-snr", type=float, default=-8.0)
+    ap.add_argument("--harq-entries", type=int, default=2)
+    ap.add_argument("--harq-call-only", action="store_true")
     ap.add_argument("--windows", type=int, default=1024)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--snr", type=float, default=0.0)
@@ -43,6 +116,8 @@ def main():
     from ria_amd.engine import RxEngine
     from ria_amd.srchash import csrc_sha256
     e = RxEngine("DQPSK", "R1_4", max_batch=64)
+    if a.harq > 0:
+        return harq_mode(e, a)
     n = a.windows
     seeds = np.arange(1, n + 1, dtype=np.uint32) * np.uint32(2654435761)
     connect = encode_frame(data_frame(CONNECT, 7, np.arange(25, dtype=np.uint8)))[None, :]
