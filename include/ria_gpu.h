@@ -170,13 +170,15 @@ int  ria_gpu_get_geometry(ria_gpu_handle h, ria_gpu_geometry* out);
 #define RIA_OPT_FALLBACK_QUEUE_ALL 3
 /*   RIA_OPT_STATE_EXIT   the retry kernels whose failed decodes leave no bits behind (phase 0, cascade, recovery fill) end
  *                        a decode that has not converged once its complete message state equals, bit for bit, the state
- *                        24 iterations earlier (compared at iterations 46 and 70): it can only repeat itself, so it is
- *                        reported as the 80-iteration failure it would become.  0 (default) = off: every failing decode
- *                        runs to its last iteration, in kernels without the exit.  1 = on at R1/2 and R1/3, the shapes
- *                        with room for the state copy (a second instance of the three kernels; no effect at other
- *                        rates).  Measured slower on the bench workload: the exit saves 3 % of
- *                        the step, the kernels that contain it lose 6 %.  The environment variable RIA_STATE_EXIT=1 / 0
- *                        sets the default of handles created after it.  ria_gpu_debug_state_exits counts the exits. */
+ *                        24 iterations earlier (compared after iterations 46 and 70): it can only repeat itself, so it is
+ *                        reported as the 80-iteration failure it would become.  The state is the 36 words a lane carries
+ *                        from one iteration into the next; its copy lives in an area of device memory per persistent
+ *                        workgroup and stream slot (113 MB at the default grid, reserved at R1/2 and R1/3 only).
+ *                        1 (default) = on at R1/2 and R1/3, the shapes that keep every such word in registers (no effect
+ *                        at other rates).  0 = off: every failing decode runs to its last iteration, the same kernels
+ *                        make no copy.  Outputs are identical either way.  The
+ *                        environment variable RIA_STATE_EXIT=1 / 0 sets the default of handles created after it.
+ *                        ria_gpu_debug_state_exits counts the exits. */
 #define RIA_OPT_STATE_EXIT 4
 int  ria_gpu_set_option(ria_gpu_handle h, int option, int value);
 

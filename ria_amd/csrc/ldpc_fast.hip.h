@@ -40,7 +40,7 @@ struct ShapeR12 {   // R1/2: m = 324, k = 324
     static constexpr int NR = 6, NC = 6;
     static constexpr int kCascadeWaves = 3;   // waves/SIMD the cascade kernel is held to (its register budget)
     static constexpr int kCv = 24;   // the row's own c2v words of slot groups < kCv stay in VGPRs between iterations (their LDS re-reads saved) as the register budget allows
-    static constexpr bool kStateExit = true;   // repeated-state exit of the retry kernels (fast_decode, EX): 15 copy words per lane fit beside three waves per SIMD
+    static constexpr bool kStateExit = true;   // repeated-state exit of the retry kernels (fast_decode, EX): every word carried between iterations is in a register (kCv == TS)
     static constexpr int ne(int r) { constexpr int t[NR] = {6, 6, 5, 4, 2, 1}; return t[r]; }
     static constexpr int nm(int r) { constexpr int t[NR] = {6, 5, 4, 2, 1, 1}; return t[r]; }
     static constexpr int dv(int r) { constexpr int t[NC] = {5, 4, 4, 4, 4, 4}; return t[r]; }
@@ -49,7 +49,7 @@ struct ShapeR13 {   // R1/3 entry of the rate table: same (324,324) parameters, 
     static constexpr int NR = 6, NC = 6;
     static constexpr int kCascadeWaves = 3;   // waves/SIMD the cascade kernel is held to (its register budget)
     static constexpr int kCv = 24;   // the row's own c2v words of slot groups < kCv stay in VGPRs between iterations (their LDS re-reads saved) as the register budget allows
-    static constexpr bool kStateExit = true;   // repeated-state exit of the retry kernels (fast_decode, EX): 15 copy words per lane fit beside three waves per SIMD
+    static constexpr bool kStateExit = true;   // repeated-state exit of the retry kernels (fast_decode, EX): every word carried between iterations is in a register (kCv == TS)
     static constexpr int ne(int r) { constexpr int t[NR] = {6, 6, 5, 3, 3, 1}; return t[r]; }
     static constexpr int nm(int r) { constexpr int t[NR] = {6, 5, 3, 3, 1, 1}; return t[r]; }
     static constexpr int dv(int r) { constexpr int t[NC] = {6, 4, 4, 4, 4, 4}; return t[r]; }
@@ -58,7 +58,7 @@ struct ShapeR14 {   // m = 486, k = 162
     static constexpr int NR = 8, NC = 3;
     static constexpr int kCascadeWaves = 3;   // waves/SIMD the cascade kernel is held to (its register budget)
     static constexpr int kCv = 0;   // the row's own c2v words of slot groups < kCv stay in VGPRs between iterations (their LDS re-reads saved) as the register budget allows
-    static constexpr bool kStateExit = false;   // 8 rounds: 20 copy words per lane, twelve waves' regions (15 KB each) would not fit the CU's LDS
+    static constexpr bool kStateExit = false;   // kCv == 0: the row's own words live in LDS, there is no register-resident state to copy
     static constexpr int ne(int r) { constexpr int t[NR] = {6, 6, 5, 5, 4, 3, 2, 2}; return t[r]; }
     static constexpr int nm(int r) { constexpr int t[NR] = {6, 6, 5, 4, 3, 2, 2, 1}; return t[r]; }
     static constexpr int dv(int r) { constexpr int t[NC] = {13, 12, 12}; return t[r]; }
@@ -112,10 +112,8 @@ struct ShapeInfo {
     static constexpr int words = big_word + 64;
     // the same region doubles as mt19937 state + 648 normals during the retry cascade (>= 1296 words)
     static constexpr int lds_bytes = ((words < 1296 ? 1296 : words) * 4 + 15) & ~15;
-    // repeated-state exit (fast_decode, EX): the compressed copy of the check-to-variable state sits behind the wave's
-    // region, per lane two magnitude words per row round and one word of sign / minimum-edge bits per two rounds
-    static constexpr int copy_words = 2 * S::NR + (S::NR + 1) / 2;
-    static constexpr int exit_lds_bytes = lds_bytes + (S::kStateExit ? 256 * copy_words : 0);
+    // repeated-state exit (fast_decode, EX): the words a lane carries from one iteration into the next (cv, pv, pt)
+    static constexpr int state_words = TS + 2 * S::NR;
 };
 
 template <int B, int E, class F>
@@ -289,27 +287,72 @@ __device__ __forceinline__ float llr_canon(float x) {
 #define RIA_SINGLE_PREFETCH 2
 #endif
 //
-// EX (repeated-state exit, off by default): the decoder is a deterministic map on its check-to-
-// variable messages, so a decode that has not converged and whose complete message state after the check pass of
-// iteration t equals, bit for bit, the state after iteration t - kExitStride (both >= 1: iteration 0 runs without the
-// clamp) repeats those iterations for ever.  Every state of the cycle has had its syndrome tested non-zero, so the result
-// is known: not converged, max_iter.  The state (the row's own c2v words and the c2v of its identity edge) is compared
-// through a copy taken at iterations kExitFirst, + kExitStride, ...: a row's messages have two magnitudes only,
-// |min1 * factor| (every edge but the row's minimum) and |min2 * factor| (the minimum edge), so the copy is those two words
-// per row plus a sign bit and a which-magnitude bit per edge, an injective image of the state.  It lives behind the wave's
-// LDS region (ShapeInfo::exit_lds_bytes), lane-private.  A copy iteration is a second instance of the iteration body
-// (SNAP) that runs between two runs of the ordinary loop.  `exits` == nullptr switches the exit off at run time; otherwise
-// it is the counter an exit bumps.  ONLY for callers that never read the bits of a failed decode: the exit leaves the
-// column totals of iteration t - 1 in LDS, not those of iteration max_iter - 1.
-// Measured: the exit removes the iterations the count predicts, but a kernel that contains the
-// copy instance runs its ORDINARY iterations 6 % slower (the register allocation and schedule of the whole function
-// change), more than the exit saves: the retry kernels are therefore built twice and the exit is off by default.
+// EX (repeated-state exit): the decoder is a deterministic map on its check-to-variable
+// messages, so a decode that has not converged and whose complete message state after iteration t equals, bit for bit, the
+// state after iteration t - kExitStride (both >= 1: iteration 0 runs without the clamp) repeats those iterations for ever.
+// Every state of the cycle has had its syndrome tested non-zero, so the result is known: not converged, max_iter.
+// What is compared are the words a lane carries from one complete iteration into the next: st.cv (the row's own c2v words,
+// all of them: NCV >= TS), st.pv and st.pt.  The column totals in LDS are a function of every lane's cv and of the constant
+// li, hi is 50 from iteration 1 on, so equality of these words in every lane IS equality of the decoder's state.  They are
+// live registers between two iterations anyway: the copy is plain stores of them, after iterations kExitFirst,
+// + kExitStride, ..., into `state_ws`, an area of global memory that this workgroup owns ([state_words][64] words,
+// lane-linear), and the comparison loads them back.  Nothing of it is inside the iteration body: the ordinary loop runs up
+// to and including a copy iteration and the copy block sits between two runs of it.  The accesses are inline assembly in
+// the scalar-base form (one VGPR of lane * 4, the area in SGPRs, the word's position as the immediate offset): written in
+// C++ they cost 64-bit address pairs in VGPRs, which the function that holds the hot loop does not have.
+// `exits` == nullptr switches the exit off at run time (no copy traffic, no counter); otherwise it is the counter an exit
+// bumps.  ONLY for callers that never read the bits of a failed decode: the exit leaves the column totals of iteration t
+// in LDS, not those of iteration max_iter - 1.
+constexpr int kStateChunk = 12;                  // words behind one SGPR base: 12 x 256 B stays inside the 13-bit immediate offset
+constexpr int kStateWsWords = 36 * 64;           // per workgroup: state_words of the shapes with the exit (R1/2, R1/3) x 64 lanes
+#ifndef RIA_EXIT_FLIGHT
+#define RIA_EXIT_FLIGHT 3                        // chunks of a comparison loaded behind one wait (3: the whole state in one round trip)
+#endif
+// stores words w[12 C .. 12 C + 11] of this lane: no wait (fast_decode waits once, after its loop)
+template <int C, int N>
+__device__ __forceinline__ void state_store_chunk(const uint32_t* area, uint32_t lane4, const uint32_t (&w)[N]) {
+    static_assert(kStateChunk == 12 && 12 * C + 12 <= N && 256 * 11 < 4096, "twelve immediate offsets");
+    const uint32_t* base = area + 64 * kStateChunk * C;
+    asm volatile("global_store_dword %0, %1, %13\n\tglobal_store_dword %0, %2, %13 offset:256\n\t"
+                 "global_store_dword %0, %3, %13 offset:512\n\tglobal_store_dword %0, %4, %13 offset:768\n\t"
+                 "global_store_dword %0, %5, %13 offset:1024\n\tglobal_store_dword %0, %6, %13 offset:1280\n\t"
+                 "global_store_dword %0, %7, %13 offset:1536\n\tglobal_store_dword %0, %8, %13 offset:1792\n\t"
+                 "global_store_dword %0, %9, %13 offset:2048\n\tglobal_store_dword %0, %10, %13 offset:2304\n\t"
+                 "global_store_dword %0, %11, %13 offset:2560\n\tglobal_store_dword %0, %12, %13 offset:2816"
+                 : : "v"(lane4), "v"(w[12 * C]), "v"(w[12 * C + 1]), "v"(w[12 * C + 2]), "v"(w[12 * C + 3]), "v"(w[12 * C + 4]),
+                     "v"(w[12 * C + 5]), "v"(w[12 * C + 6]), "v"(w[12 * C + 7]), "v"(w[12 * C + 8]), "v"(w[12 * C + 9]),
+                     "v"(w[12 * C + 10]), "v"(w[12 * C + 11]), "s"(base) : "memory");
+}
+// issues the loads of words 12 C .. 12 C + 11 of this lane's copy; t is valid after state_wait_chunk only
+template <int C>
+__device__ __forceinline__ void state_load_chunk(const uint32_t* area, uint32_t lane4, uint32_t (&t)[kStateChunk]) {
+    const uint32_t* base = area + 64 * kStateChunk * C;
+    asm volatile("global_load_dword %0, %12, %13\n\tglobal_load_dword %1, %12, %13 offset:256\n\t"
+                 "global_load_dword %2, %12, %13 offset:512\n\tglobal_load_dword %3, %12, %13 offset:768\n\t"
+                 "global_load_dword %4, %12, %13 offset:1024\n\tglobal_load_dword %5, %12, %13 offset:1280\n\t"
+                 "global_load_dword %6, %12, %13 offset:1536\n\tglobal_load_dword %7, %12, %13 offset:1792\n\t"
+                 "global_load_dword %8, %12, %13 offset:2048\n\tglobal_load_dword %9, %12, %13 offset:2304\n\t"
+                 "global_load_dword %10, %12, %13 offset:2560\n\tglobal_load_dword %11, %12, %13 offset:2816"
+                 : "=&v"(t[0]), "=&v"(t[1]), "=&v"(t[2]), "=&v"(t[3]), "=&v"(t[4]), "=&v"(t[5]), "=&v"(t[6]), "=&v"(t[7]),
+                   "=&v"(t[8]), "=&v"(t[9]), "=&v"(t[10]), "=&v"(t[11])
+                 : "v"(lane4), "s"(base) : "memory");
+}
+// the compiler does not count the loads of an asm statement: the wait is ours, and the words pass through it as operands
+// so that no use of them can be scheduled in front of it
+__device__ __forceinline__ void state_wait_chunk(uint32_t (&t)[kStateChunk]) {
+    asm volatile("s_waitcnt vmcnt(0)"
+                 : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4]), "+v"(t[5]), "+v"(t[6]), "+v"(t[7]),
+                   "+v"(t[8]), "+v"(t[9]), "+v"(t[10]), "+v"(t[11]) : : "memory");
+}
 constexpr int kExitFirst = 22, kExitStride = 24;
 template <class S, int NCV = (kCvRegs ? 1024 : S::kCv), int PF = RIA_SINGLE_PREFETCH, bool EX = false>
 __device__ inline int fast_decode(FastState<S>& st, const FastCode& c, unsigned char* __restrict__ lds,
-                                  float factor, int max_iter, int lane, bool* ok, unsigned int* exits = nullptr) {
+                                  float factor, int max_iter, int lane, bool* ok, unsigned int* exits = nullptr,
+                                  uint32_t* state_ws = nullptr) {
     using I = ShapeInfo<S>;
-    static_assert(!EX || S::kStateExit, "the shape has no room for the state copy");
+    static_assert(!EX || S::kStateExit, "the shape has no repeated-state exit");
+    static_assert(!EX || (NCV >= I::TS && I::state_words % kStateChunk == 0 && I::state_words * 64 <= kStateWsWords),
+                  "the exit compares registers: every own c2v word must be in st.cv, in whole chunks, inside the workgroup's area");
     const uint32_t lane4 = lds_addr(lds) + static_cast<uint32_t>(lane) * 4u;
     const uint32_t kAbs = 0x7fffffffu;
     const uint32_t m0base = lds_addr(lds);
@@ -334,11 +377,9 @@ __device__ inline int fast_decode(FastState<S>& st, const FastCode& c, unsigned 
     float hi = __builtin_inff();
     int it = 0;
     bool success = false;
-    // one iteration; 0: go on, 1: converged, 2 (SNAP only): the state equals the copy.  SNAP = a copy iteration.
-    auto iteration = [&](auto SNAP_) __attribute__((always_inline)) -> int {
-        constexpr bool SNAP = decltype(SNAP_)::value;
+    // one iteration; 0: go on, 1: converged
+    auto iteration = [&]() __attribute__((always_inline)) -> int {
         uint32_t syn = 0;
-        uint32_t sb = 0, sd = 0;              // SNAP: bits of the round pair, difference words of this lane
         // the total gathers of round r + PF are issued before round r is computed (LDS operations keep their program
         // order: without this every round starts by waiting out an LDS round trip)
         float tt[I::TS];
@@ -410,31 +451,9 @@ __device__ inline int fast_decode(FastState<S>& st, const FastCode& c, unsigned 
                 const float tot = st.lp[r] + c2v;
                 st.pv[r] = tot - c2v;                    // clamped where it is used (see above)
                 st.pt[r] = tot;
-                if constexpr (SNAP) {
-                    // every message of the row has magnitude |min1 * factor| or |min2 * factor| (the product's magnitude does
-                    // not depend on the signs): two words, and per edge its sign and whether its magnitude is not the first
-                    static_assert(NE + 1 <= 8, "16 bits per round");
-                    const uint32_t ma = f2u(min1 * factor) & kAbs, mb = f2u(min2 * factor) & kAbs;
-                    uint32_t bits = (f2u(c2v) >> 31) | (((f2u(c2v) & kAbs) != ma) ? 2u : 0u);
-#pragma unroll
-                    for (int s = 0; s < NE; ++s) bits = (bits << 2) | (f2u(o[s]) >> 31) | (((f2u(o[s]) & kAbs) != ma) ? 2u : 0u);
-                    const uint32_t ca = lane4 + static_cast<uint32_t>(I::lds_bytes) + 256u * (2 * r);
-                    sd |= (f2u(lds_f(ca)) ^ ma) | (f2u(lds_f(ca + 256u)) ^ mb);
-                    lds_sf(ca, u2f(ma));
-                    lds_sf(ca + 256u, u2f(mb));
-                    sb = (r & 1) ? (sb | (bits << 16)) : bits;
-                    if constexpr ((r & 1) || r == S::NR - 1) {
-                        const uint32_t cb = lane4 + static_cast<uint32_t>(I::lds_bytes) + 256u * (2 * S::NR + r / 2);
-                        sd |= f2u(lds_f(cb)) ^ sb;
-                        lds_sf(cb, u2f(sb));
-                    }
-                }
             }
         });
         if (it > 0 && __ballot(static_cast<int>(syn) < 0) == 0ull) return 1;
-        if constexpr (SNAP) {   // the first copy has nothing to be compared with (what the area held is a past decode's)
-            if (it != kExitFirst && __ballot(sd != 0u) == 0ull) return 2;
-        }
         hi = 50.0f;
         wave_sync();
         // information columns: tot = llr + sum of c2v in ascending check order
@@ -462,27 +481,68 @@ __device__ inline int fast_decode(FastState<S>& st, const FastCode& c, unsigned 
             for (int i = 0; i < gn; ++i) tv[i] = totv[g0 + i];
             lds_store_tid_n<gn, 4 * (I::tot_word + 64 * g0), 256>(m0base, tv);
         });
+        if constexpr (EX) {
+            // the identity columns' words are computed by here, among the waits of the column pass, whatever follows the loop
+#pragma unroll
+            for (int r = 0; r < S::NR; ++r) asm volatile("" : "+v"(st.pv[r]), "+v"(st.pt[r]));
+        }
         wave_sync();
         return 0;
     };
-    // The ordinary iterations run in a loop of their own, up to the next copy iteration (or the end); a copy iteration is a
-    // second instance of the body between two such runs.
-    int snap_at = (EX && exits != nullptr) ? kExitFirst : 0x7fffffff;   // wave-uniform
+    // The ordinary iterations run in a loop of their own, up to and including the next copy iteration (or the end); the copy
+    // block between two such runs works on the registers the iteration leaves.
+    int snap_at = (EX && exits != nullptr) ? kExitFirst : 0x7fffffff;   // wave-uniform: the iteration the next copy block follows
     int status = 0;
     for (;;) {
-        const int stop = snap_at < max_iter ? snap_at : max_iter;
+        const int stop = snap_at < max_iter ? snap_at + 1 : max_iter;
         for (; it < stop; ++it) {
-            status = iteration(std::false_type{});
+            status = iteration();
             if (status != 0) break;
         }
-        if (status != 0 || it >= max_iter) break;
+        if (status != 0 || it <= snap_at) break;
         if constexpr (!EX) break;
         else {
-            status = iteration(std::true_type{});
-            if (status != 0) break;
-            ++it;
+            uint32_t w[I::state_words];
+#pragma unroll
+            for (int i = 0; i < I::TS; ++i) w[i] = f2u(st.cv[i]);
+#pragma unroll
+            for (int r = 0; r < S::NR; ++r) { w[I::TS + r] = f2u(st.pv[r]); w[I::TS + S::NR + r] = f2u(st.pt[r]); }
+            const uint32_t g4 = static_cast<uint32_t>(lane) * 4u;
+            constexpr int NCH = I::state_words / kStateChunk;
+            // the first copy of a decode has nothing to be compared with (what the area holds is a past decode's): every
+            // comparison follows a store of the same decode
+            // A comparison first tests one word per lane, the xor of the lane's state words, kept in the lane's dump word of the
+            // wave's LDS region (nothing else uses it during a decode): a filter only, it spares the decodes that do not repeat
+            // (five in six) the round trip to the copy.  Equal sums in every lane are followed by the comparison of the state.
+            uint32_t sum = 0;
+#pragma unroll
+            for (int i = 0; i < I::state_words; ++i) sum ^= w[i];
+            const uint32_t sum_at = lane4 + 4u * I::dump_word;
+            if (snap_at != kExitFirst && __ballot(f2u(lds_f(sum_at)) != sum) == 0ull) {
+                uint32_t sd = 0;
+                static_for<0, (NCH + RIA_EXIT_FLIGHT - 1) / RIA_EXIT_FLIGHT>([&](auto G_) __attribute__((always_inline)) {
+                    constexpr int c0 = RIA_EXIT_FLIGHT * decltype(G_)::value, cn = (NCH - c0 < RIA_EXIT_FLIGHT) ? NCH - c0 : RIA_EXIT_FLIGHT;
+                    uint32_t t[cn][kStateChunk];
+                    static_for<0, cn>([&](auto C_) __attribute__((always_inline)) { state_load_chunk<c0 + decltype(C_)::value>(state_ws, g4, t[decltype(C_)::value]); });
+                    static_for<0, cn>([&](auto C_) __attribute__((always_inline)) { state_wait_chunk(t[decltype(C_)::value]); });
+#pragma unroll
+                    for (int c = 0; c < cn; ++c)
+#pragma unroll
+                        for (int j = 0; j < kStateChunk; ++j) sd |= t[c][j] ^ w[kStateChunk * (c0 + c) + j];
+                });
+                if (__ballot(sd != 0u) == 0ull) { status = 2; break; }
+            }
+            if (snap_at + kExitStride < max_iter) {   // a copy no comparison will read is not taken
+                static_for<0, NCH>([&](auto C_) __attribute__((always_inline)) { state_store_chunk<decltype(C_)::value>(state_ws, g4, w); });
+                lds_sf(sum_at, u2f(sum));
+            }
             snap_at += kExitStride;
         }
+    }
+    if constexpr (EX) {
+        // the copy's stores are not waited for where they are issued, and the compiler's own counts of outstanding memory
+        // operations do not include them: drain them here, long after they were issued, before any counted wait can follow
+        if (exits != nullptr) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     if (status == 1) { success = true; --it; }
     if constexpr (EX) {
@@ -591,9 +651,12 @@ struct FastDecodeArgs {
     unsigned int* l1idx;     // [4*n_frames]  codeword -> its list1 index, kNotListed for the others (written by fast_mark_kernel when a retry flag is set)
     unsigned int* l1hash;    // [4*n_frames]  list1 entry -> hash of its first 16 soft bits (seed of the perturbation RNG)
     uint32_t* seed_ws;       // [cascade grid][kSeedWsWords]  seeded mt19937 states of the attempt group a cascade workgroup is on (this stream slot's)
+    uint32_t* state_ws;      // [max(persistent grid, fill grid)][kStateWsWords]  copy of the decoder state a retry workgroup compares with (fast_decode, EX; this stream slot's)
     int state_exit;          // RIA_OPT_STATE_EXIT: the retry kernels end a failing decode whose message state repeats (fast_decode, EX)
     // the counter of kernel `which` (kExits*), or nullptr = exit off: wave-uniform, fast_decode's run-time switch
     __device__ unsigned int* exit_counter(int which) const { return state_exit ? &ctl->exits[which] : nullptr; }
+    // the area of the calling workgroup: phase 0, the cascade and the fill of a slot run one after the other on one stream
+    __device__ uint32_t* state_area() const { return state_ws + static_cast<size_t>(blockIdx.x) * kStateWsWords; }
 };
 
 // A codeword that needs more than its first decode is decoded up to 4 + 34 more times.  Its soft bits are gathered
@@ -649,12 +712,12 @@ __device__ inline void fast_publish(CwResult* res, unsigned fc, int f, bool ok, 
 // codeword's de-interleaved input (fast_stage_kernel) instead of the gather from the frame
 template <class S, int NCV = S::kCv, bool EX = false>
 __device__ inline void fast_unit(FastState<S>& st, const FastDecodeArgs& A, unsigned char* lds, unsigned fc, int f, int lane,
-                                 const float* staged = nullptr, unsigned int* exits = nullptr) {
+                                 const float* staged = nullptr, unsigned int* exits = nullptr, uint32_t* state_ws = nullptr) {
     const FastCode& c = A.c;
     if (staged) fast_load_staged(st, staged, lane);
     else fast_gather_llr(st, c, A.llr + static_cast<size_t>(fc >> 2) * A.llr_stride, A.gather, fc & 3, lane);
     bool ok;
-    int it = fast_decode<S, NCV, RIA_SINGLE_PREFETCH, EX>(st, c, lds, kFactors[f], c.max_iter, lane, &ok, exits);
+    int it = fast_decode<S, NCV, RIA_SINGLE_PREFETCH, EX>(st, c, lds, kFactors[f], c.max_iter, lane, &ok, exits, state_ws);
     if (ok) fast_pack(st, c, lds, A.res_bytes + (static_cast<size_t>(fc) * kNumFactors + f) * c.bytes_per_cw,
                       c.bytes_per_cw, lane);
     fast_publish(A.res, fc, f, ok, it, lane);
@@ -766,7 +829,7 @@ __global__ __launch_bounds__(256) void fast_stage_kernel(FastDecodeArgs A) {
 #ifndef RIA_EAGER_FACTORS
 #define RIA_EAGER_FACTORS 0
 #endif
-template <class S, bool EX = false>   // EX: with the repeated-state exit (RIA_OPT_STATE_EXIT; launched with ShapeInfo::exit_lds_bytes)
+template <class S>
 __global__ __launch_bounds__(64) void fast_phase0_kernel(FastDecodeArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x;
@@ -796,8 +859,8 @@ __global__ __launch_bounds__(64) void fast_phase0_kernel(FastDecodeArgs A) {
         if (done) continue;
 #endif
         // a failed unit publishes its state and iteration count only: the repeated-state exit applies (fast_decode, EX)
-        fast_unit<S, S::kCv, EX>(st, A, smem, fc, t, lane, A.staged + static_cast<size_t>(entry) * kStageFloats,
-                                 A.exit_counter(kExitsPhase0));
+        fast_unit<S, S::kCv, S::kStateExit>(st, A, smem, fc, t, lane, A.staged + static_cast<size_t>(entry) * kStageFloats,
+                                            A.exit_counter(kExitsPhase0), A.state_area());
     }
 }
 
@@ -904,7 +967,7 @@ __device__ inline float fast_perturb(FastState<S>& st, const FastCode& c, const 
 // wave touches.  best[e] is still the smallest successful attempt: an attempt runs unless a smaller one has been
 // published, a success ends the group (its later attempts can never win), and the result slot is written under the
 // lock by the current best only.  No wave waits for another.
-template <class S, bool EX = false>   // EX: with the repeated-state exit (RIA_OPT_STATE_EXIT; launched with ShapeInfo::exit_lds_bytes)
+template <class S>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(S::kCascadeWaves))) void fast_cascade_kernel(FastDecodeArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const FastCode& c = A.c;
@@ -948,8 +1011,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(S::kCascadeW
             float factor = fast_perturb(st, c, bi, bp, reinterpret_cast<uint32_t*>(msg), msg + 640, ws, j, static_cast<int>(a), lane);
             bool ok;
             // a failed attempt leaves nothing behind: the repeated-state exit applies (fast_decode, EX)
-            const int it = fast_decode<S, (kCvRegs ? 1024 : S::kCv), RIA_SINGLE_PREFETCH, EX>(st, c, smem, factor, c.max_iter, lane, &ok,
-                                                                                     A.exit_counter(kExitsCascade));
+            const int it = fast_decode<S, (kCvRegs ? 1024 : S::kCv), RIA_SINGLE_PREFETCH, S::kStateExit>(st, c, smem, factor, c.max_iter, lane, &ok,
+                                                                                                A.exit_counter(kExitsCascade), A.state_area());
             if (!ok) continue;
             // all-lane forms here too (no lane-0-only atomic inside the loop): only lane 0's operand can change the word
             unsigned int prev = atomicMin(&A.best[e], lane == 0 ? a : 0xFFFFFFFFu);

@@ -513,7 +513,7 @@ __global__ void recovery_list_kernel(RecoveryArgs R) {
         if (mask) R.list2[atomicAdd(R.n_list2, 1u)] = (fc << 4) | mask;
     }
 }
-template <class S, bool EX = false>   // EX: with the repeated-state exit (RIA_OPT_STATE_EXIT; launched with ShapeInfo::exit_lds_bytes)
+template <class S>
 __global__ __launch_bounds__(64) void recovery_fill_kernel(RecoveryArgs R) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const unsigned total = *R.n_list2 * 4u;
@@ -540,8 +540,8 @@ __global__ __launch_bounds__(64) void recovery_fill_kernel(RecoveryArgs R) {
         if (li != kNotListed) fast_load_staged(st, R.d.staged + static_cast<size_t>(li) * kStageFloats, lane);
         else fast_gather_llr(st, c, R.d.llr + static_cast<size_t>(fc >> 2) * R.d.llr_stride, R.d.gather, fc & 3, lane);
         bool ok;
-        const int it = fast_decode<S, (kCvRegs ? 1024 : S::kCv), RIA_SINGLE_PREFETCH, EX>(st, c, smem, kFactors[f], c.max_iter, lane, &ok,
-                                                                                 R.d.exit_counter(kExitsFill));
+        const int it = fast_decode<S, (kCvRegs ? 1024 : S::kCv), RIA_SINGLE_PREFETCH, S::kStateExit>(st, c, smem, kFactors[f], c.max_iter, lane, &ok,
+                                                                                            R.d.exit_counter(kExitsFill), R.d.state_area());
         if (ok) fast_pack(st, c, smem, R.d.res_bytes + (static_cast<size_t>(fc) * kNumFactors + f) * c.bytes_per_cw, c.bytes_per_cw, lane);
         fast_publish(R.d.res, fc, f, ok, it, lane);
     }

@@ -91,7 +91,8 @@ struct ria_gpu {
     int split_parts = 0;                  // RIA_OPT_SPLIT_PARTS (0 = library default)
     int dual_decoder = 0;                 // RIA_OPT_DUAL_DECODER: 0 = default (environment RIA_DUAL, else off), 1 = on, -1 = off
     int fallback_queue_all = 0;           // RIA_OPT_FALLBACK_QUEUE_ALL: 1 = the recovery fill also runs the re-decodes no trial can read
-    int state_exit = 0;                   // RIA_OPT_STATE_EXIT: 1 = the retry kernels end a failing decode whose message state repeats (measured slower: off)
+    DevBuf d_state_ws;              // uint32_t [kMaxParts][state grid][kStateWsWords]: per stream slot, per persistent workgroup (rates with the repeated-state exit only)
+    int state_exit = 1;                   // RIA_OPT_STATE_EXIT: 1 (default) = the retry kernels end a failing decode whose message state repeats
     // host-buffer entry points (the single-frame IWaveform adaptor path): one device + one pinned staging block and a
     // stream, kept for the life of the handle, grown on demand - no allocation and no device-wide sync per call
     DevBuf d_hstage; PinBuf p_hstage; hipStream_t hstream = nullptr;
@@ -209,8 +210,13 @@ static DecodeWs decode_ws_carve(Carver& c, size_t n_frames, size_t bytes_per_cw)
     w.l1hash = c.take<unsigned int>(n4);
     return w;
 }
+// workgroups that own an area of d_state_ws: the persistent grid of phase 0 and the cascade, or the fill's
+constexpr int kFillGrid = 3072;
+static int state_grid_size() { return std::max(persist_grid_size(false), kFillGrid); }
 static hipError_t ensure_decode_ws(ria_gpu_handle h, int n_frames) {
-    if (n_frames <= h->ws_frames && h->d_ctl && h->d_seed_ws) return hipSuccess;
+    bool state_exit_rate = false;
+    dispatch_shape(h->cfg.code_rate, [&](auto sh) { state_exit_rate = decltype(sh)::kStateExit; });
+    if (n_frames <= h->ws_frames && h->d_ctl && h->d_seed_ws && (h->d_state_ws || !state_exit_rate)) return hipSuccess;
     h->ws_frames = 0;   // nothing is valid until every allocation below has succeeded
     hipError_t e;
     if (!h->d_ctl) {   // one per stream slot; zeroed here because ria_gpu_debug_queue_fault reads the slots no call has used yet as well
@@ -219,19 +225,13 @@ static hipError_t ensure_decode_ws(ria_gpu_handle h, int n_frames) {
     }
     // the cascade's seeded RNG states: one area per workgroup of its grid and per stream slot (the parts of a batch run concurrently)
     if ((e = h->d_seed_ws.reserve(static_cast<size_t>(kMaxParts) * persist_grid_size(false) * kSeedWsWords * sizeof(uint32_t))) != hipSuccess) return e;
+    // the state copies of the repeated-state exit, likewise (phase 0, the cascade and the fill of a slot follow each other on one stream)
+    if (state_exit_rate &&
+        (e = h->d_state_ws.reserve(static_cast<size_t>(kMaxParts) * state_grid_size() * kStateWsWords * sizeof(uint32_t))) != hipSuccess) return e;
     const size_t bpc = h->geo.bytes_per_codeword;
     if ((e = h->d_decode_ws.reserve(carved_size([&](Carver& c) { return decode_ws_carve(c, n_frames, bpc); }))) != hipSuccess) return e;
     h->ws_frames = n_frames;
     return hipSuccess;
-}
-// Phase 0, the cascade and the recovery fill exist twice: as they are without the repeated-state exit, and (shapes with
-// room for the state copy) with it and the copy behind the wave's LDS region.  RIA_OPT_STATE_EXIT picks per call.
-template <class S, class F>
-static void with_state_exit(ria_gpu_handle h, F&& f) {
-    if constexpr (S::kStateExit) {
-        if (h->state_exit) { f(std::true_type{}, ShapeInfo<S>::exit_lds_bytes); return; }
-    }
-    f(std::false_type{}, ShapeInfo<S>::lds_bytes);
 }
 static void set_fast_attributes(int rate, int wb) {
     dispatch_shape(rate, [&](auto s) {
@@ -239,12 +239,6 @@ static void set_fast_attributes(int rate, int wb) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fast_primary_kernel<S>), hipFuncAttributeMaxDynamicSharedMemorySize, wb);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fast_phase0_kernel<S>), hipFuncAttributeMaxDynamicSharedMemorySize, wb);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fast_cascade_kernel<S>), hipFuncAttributeMaxDynamicSharedMemorySize, wb);
-        if constexpr (S::kStateExit) {   // the instances with the repeated-state exit: the state copy behind the wave's region
-            const int wbx = ShapeInfo<S>::exit_lds_bytes;
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fast_phase0_kernel<S, true>), hipFuncAttributeMaxDynamicSharedMemorySize, wbx);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fast_cascade_kernel<S, true>), hipFuncAttributeMaxDynamicSharedMemorySize, wbx);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(recovery_fill_kernel<S, true>), hipFuncAttributeMaxDynamicSharedMemorySize, wbx);
-        }
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fast_rows_kernel<S>), hipFuncAttributeMaxDynamicSharedMemorySize, wb);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fast_robust_kernel<S>), hipFuncAttributeMaxDynamicSharedMemorySize, wb);
 #ifdef RIA_WITH_DUAL_DECODER
@@ -366,9 +360,7 @@ static int run_crc_recovery(ria_gpu_handle h, const FastDecodeArgs& D, hipStream
     hipLaunchKernelGGL(recovery_stage1_kernel, dim3(n_frames), dim3(64), rl, s, R);
     dispatch_shape(h->cfg.code_rate, [&](auto sh) {
         using S = decltype(sh);
-        with_state_exit<S>(h, [&](auto ex, int lds) {
-            hipLaunchKernelGGL((recovery_fill_kernel<S, decltype(ex)::value>), dim3(std::min(n_frames * 16, 3072)), dim3(64), lds, s, R);
-        });
+        hipLaunchKernelGGL(recovery_fill_kernel<S>, dim3(std::min(n_frames * 16, kFillGrid)), dim3(64), h->wave_lds, s, R);
     });
     hipLaunchKernelGGL(recovery_stage2_kernel, dim3(n_frames), dim3(64), rl, s, R);
     // a work-queue fault recorded anywhere in this call (cascade, phase 0, recovery fill) turns every frame into a failure
@@ -399,7 +391,7 @@ static int run_crc_recovery_host(ria_gpu_handle h, const FastDecodeArgs& D, hipS
     const int wb = h->wave_lds;
     dispatch_shape(h->cfg.code_rate, [&](auto sh) {
         using S = decltype(sh);
-        hipLaunchKernelGGL(recovery_fill_kernel<S>, dim3(std::min(n_frames * 16, 3072)), dim3(64), wb, s, R);
+        hipLaunchKernelGGL(recovery_fill_kernel<S>, dim3(std::min(n_frames * 16, kFillGrid)), dim3(64), wb, s, R);
     });
     hipLaunchKernelGGL(recovery_gather_kernel, dim3(n_frames), dim3(256), 0, s, R);
     hipLaunchKernelGGL(recovery_status_gather_kernel, dim3((n_frames + 255) / 256), dim3(256), 0, s, W.rctl, W.flagged,
@@ -714,6 +706,7 @@ static int launch_decode(ria_gpu_handle h, const float* llr_dev, int llr_stride,
     A.l1hash = W.l1hash + o4;
     A.seed_ws = h->d_seed_ws.as<uint32_t>() + static_cast<size_t>(slot) * persist_grid_size(false) * kSeedWsWords;
     dispatch_shape(h->cfg.code_rate, [&](auto sh) { A.state_exit = decltype(sh)::kStateExit ? h->state_exit : 0; });
+    A.state_ws = h->d_state_ws ? h->d_state_ws.as<uint32_t>() + static_cast<size_t>(slot) * state_grid_size() * kStateWsWords : nullptr;
     if ((e = hipMemsetAsync(A.ctl, 0, sizeof(DecodeCtl), s)) != hipSuccess)
         return fail(h, RIA_ERR_HIP, "hipMemsetAsync: %s", hipGetErrorString(e));
     const int wb = h->wave_lds;
@@ -749,9 +742,7 @@ static int launch_decode(ria_gpu_handle h, const float* llr_dev, int llr_stride,
             if (dual) hipLaunchKernelGGL(dual_phase0_kernel<S>, dim3(std::min(n_frames * 8, persist_grid)), dim3(64), DualInfo<S>::lds_bytes, s, A);
             else
 #endif
-            with_state_exit<S>(h, [&](auto ex, int lds) {
-                hipLaunchKernelGGL((fast_phase0_kernel<S, decltype(ex)::value>), dim3(std::min(n_frames * 16, persist_grid)), dim3(64), lds, s, A);
-            });
+            hipLaunchKernelGGL(fast_phase0_kernel<S>, dim3(std::min(n_frames * 16, persist_grid)), dim3(64), wb, s, A);
         }
         stage("phase0");
         hipLaunchKernelGGL(fast_chain_kernel, dim3((n_frames + 255) / 256), dim3(256), 0, s, A);
@@ -762,9 +753,7 @@ static int launch_decode(ria_gpu_handle h, const float* llr_dev, int llr_stride,
             if (dual) hipLaunchKernelGGL(dual_cascade_kernel<S>, dim3(persist_grid), dim3(64), DualInfo<S>::lds_bytes, s, A);
             else
 #endif
-            with_state_exit<S>(h, [&](auto ex, int lds) {
-                hipLaunchKernelGGL((fast_cascade_kernel<S, decltype(ex)::value>), dim3(persist_grid), dim3(64), lds, s, A);
-            });
+            hipLaunchKernelGGL(fast_cascade_kernel<S>, dim3(persist_grid), dim3(64), wb, s, A);
             stage("cascade");
             hipLaunchKernelGGL(fast_finalize_kernel, dim3(std::min((4 * n_frames + 255) / 256, 1024)), dim3(256), 0, s, A);
             stage("finalize");

@@ -122,7 +122,7 @@ class RxEngine:
         return {"flagged": int(out[0]), "fallback": int(out[1]), "list2": int(out[2]), "queued": int(out[3])}
 
     def set_state_exit(self, on):
-        """1: the retry kernels end a failing decode whose message state repeats (R1/2, R1/3); 0 (default): every failing decode
+        """1 (default): the retry kernels end a failing decode whose message state repeats (R1/2, R1/3); 0: every failing decode
         runs to its end"""
         self._check(self.lib.ria_gpu_set_option(self.h, capi.OPT_STATE_EXIT, int(on)))
 
