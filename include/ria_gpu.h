@@ -379,7 +379,7 @@ int ria_gpu_sync_host(ria_gpu_handle h, int kind, const float* samples_host, int
  * and initial CFO phase (rad) may be NULL (0).  LLRs come out as demodulateSoft returns them
  * ((frame_samples/512 - 9)/spreading * carriers * bits_per_symbol values), bit-identical. */
 typedef struct ria_mcdpsk_config {
-    int32_t num_carriers;      /* 3..20 (reference default 8; MC-DPSK modes use 10) */
+    int32_t num_carriers;      /* 1..20 (reference default 8; MC-DPSK modes use 10); one carrier sits on 1500 Hz; MCDPSKWaveform clamps to 3..20 */
     int32_t bits_per_symbol;   /* 1 DBPSK, 2 DQPSK */
     int32_t spreading;         /* 1, 2 or 4 (SpreadingMode) */
     int32_t reserved;

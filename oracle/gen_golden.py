@@ -362,6 +362,35 @@ def demod_domain_fixture(R):
     return rec
 
 
+def mcdpsk_domain_fixture(R):
+    """MultiCarrierDPSKDemodulator (driven as MCDPSKWaveform::process drives it after an external chirp detection) and
+    MultiCarrierDPSKModulator of the reference over their input domain (tests/mcdpsk_domain_inputs.py builds the inputs; only
+    their sha256 is kept here).  Per (configuration, family): sha_*; n_llr_* int32 [n]; dig_* uint8 [n, 32] sha256 of every
+    frame's LLR bits (NaN canonical); aux_* uint32 [n, 4] bit patterns of cfo_hz, fading_index, freq_fading_index,
+    temporal_fading_index; llr0_* the first frame's LLR bits.  mod_cases / mod_dig: the modulator cases and the sha256 of
+    their audio bits."""
+    sys.path.insert(0, os.path.join(os.path.dirname(po.HERE), "tests"))
+    import mcdpsk_domain_inputs as M
+    O = po.Oracle()
+    rec = {}
+    for cfg, fam in M.CASES:
+        F = M.family(O, cfg, fam)
+        key = M.key(cfg, fam)
+        llr, aux = M.reference_answers(R, cfg, F)
+        rec[f"sha_{key}"] = np.array(M.digest(F))
+        rec[f"aux_{key}"] = aux
+        rec[f"n_llr_{key}"] = np.array([len(l) for l in llr], np.int32)
+        rec[f"llr0_{key}"] = llr[0].view(np.uint32)
+        rec[f"dig_{key}"] = np.stack([np.frombuffer(bytes.fromhex(M.llr_digest(l)), np.uint8) for l in llr])
+        print("mcdpsk domain", key, "frames", len(llr), "NaN LLRs", sum(int(np.isnan(l).sum()) for l in llr),
+              "inf LLRs", sum(int(np.isinf(l).sum()) for l in llr), flush=True)
+    rec["mod_cases"] = np.array([c[:4] + (("random", "zero", "one").index(c[4]),) for c in M.MOD_CASES], np.int32)
+    rec["mod_dig"] = np.stack([np.frombuffer(bytes.fromhex(M.audio_digest(R.mcdpsk_modulate(*c[:3], M.mod_data(c, i)))), np.uint8)
+                               for i, c in enumerate(M.MOD_CASES)])
+    print("mcdpsk domain modulator cases", len(M.MOD_CASES), flush=True)
+    return rec
+
+
 def sync_domain_fixture(R):
     """ZCSync::detect, ChirpSync::detectDualChirp, OFDMChirpWaveform::detectDataSync and OFDMDemodulator::searchForSync of the
     reference over the detectors' input domain (tests/sync_domain_inputs.py builds the buffers; only their sha256 is kept
@@ -665,6 +694,9 @@ def main():
     if only == "demod_domain":
         np.savez_compressed(os.path.join(OUT, "demod_domain.npz"), **demod_domain_fixture(R))
         return 0
+    if only == "mcdpsk_domain":
+        np.savez_compressed(os.path.join(OUT, "mcdpsk_domain.npz"), **mcdpsk_domain_fixture(R))
+        return 0
     if only == "sync_domain":
         np.savez_compressed(os.path.join(OUT, "sync_domain.npz"), **sync_domain_fixture(R))
         return 0
@@ -756,6 +788,7 @@ def main():
     np.savez_compressed(os.path.join(OUT, "ldpc_domain.npz"), **ldpc_domain_fixture(R))
     np.savez_compressed(os.path.join(OUT, "demod_domain.npz"), **demod_domain_fixture(R))
     np.savez_compressed(os.path.join(OUT, "sync_domain.npz"), **sync_domain_fixture(R))
+    np.savez_compressed(os.path.join(OUT, "mcdpsk_domain.npz"), **mcdpsk_domain_fixture(R))
     np.savez_compressed(os.path.join(OUT, "harq_trials.npz"), **harq_fixture(R))
     np.savez_compressed(os.path.join(OUT, "cfo_impairment.npz"), **cfo_fixture(R))
     np.savez_compressed(os.path.join(OUT, "mcdpsk_waveform.npz"), **mcwf_fixture(R))

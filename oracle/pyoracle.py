@@ -62,6 +62,22 @@ class RxAux(C.Structure):
         "corr_phase", "snr_symbol_count")] + [("h", C.c_float * (2 * NCAR))]
 
 
+# RO_MBC_PAIRS of oracle/ria_oracle.h: the data-dependent conditions of the MC-DPSK demodulator, counted true / false
+MBC = ("CFO_GATE", "REF_AMP", "SYM_MAG", "NDS4", "REF_MAG", "TRIM_ROOM", "TRIM_LOW", "PNV_FLOOR", "SCALE_CAP", "MEAN_OK", "MEAN_DEAD",
+       "GMEAN_DEAD", "VAR_POS", "RATIO_CAP", "MW_FLOOR", "RATIO_020", "RATIO_035", "W_CAP", "W_FLOOR", "LLR_HI", "LLR_LO", "VALID4",
+       "TFI_MEAN", "FFI_MEAN", "REF_AMP_EDGE", "SYM_MAG_EDGE")
+
+
+def mcdpsk_frame_samples(nc, bps, spreading, n_bytes):
+    """samples of training + reference + the data symbols of n_bytes coded bytes (multi_carrier_dpsk.hpp:202-281)"""
+    return (9 + -(-8 * n_bytes // (nc * bps)) * spreading) * 512
+
+
+def mcdpsk_max_llr(nc, bps, n_samples):
+    """room for the soft bits of a frame of n_samples at any spreading (at least the 8192 the wrappers always offered)"""
+    return max(8192, max(1, (n_samples - 9 * 512) // 512) * nc * bps)
+
+
 def build_oracle():
     so = os.path.join(HERE, "libria_oracle.so")
     srcs = [os.path.join(HERE, f) for f in ("ria_oracle.c", "ria_oracle_sync.c", "ria_oracle.h")]
@@ -117,6 +133,9 @@ class Oracle:
         L.ro_cox_lts_template.argtypes = [C.POINTER(Geom), _f, _f]
         L.ro_mcdpsk_modulate.argtypes = [C.c_int, C.c_int, C.c_int, _u8, C.c_int, _f, C.c_int]
         L.ro_mcdpsk_demod.argtypes = [C.c_int, C.c_int, C.c_int, _f, C.c_int, C.c_float, C.c_float, _f, C.c_int, _f]
+        L.ro_mcdpsk_demod_ex.argtypes = L.ro_mcdpsk_demod.argtypes + [_f, _i]
+        L.ro_mcdpsk_branch_counts.argtypes = [C.POINTER(C.c_uint)]
+        L.ro_mcdpsk_branch_counts.restype = None
         self._geoms = {}
         self._codes = {}
 
@@ -159,7 +178,7 @@ class Oracle:
 
     def mcdpsk_modulate(self, nc, bps, spreading, data):
         data = np.ascontiguousarray(data, np.uint8)
-        out = np.zeros(600000, np.float32)
+        out = np.zeros(mcdpsk_frame_samples(nc, bps, spreading, len(data)), np.float32)
         n = self.lib.ro_mcdpsk_modulate(nc, bps, spreading, up(data), len(data), fp(out), len(out))
         assert n > 0
         return out[:n].copy()
@@ -167,11 +186,28 @@ class Oracle:
     def mcdpsk_demod(self, nc, bps, spreading, samples, cfo_hz=0.0, phase0=0.0):
         """-> (llr float32[n], aux float32[4] {cfo, fading, freq fading, temporal fading})"""
         x = np.ascontiguousarray(samples, np.float32)
-        llr = np.zeros(8192, np.float32)
+        llr = np.zeros(mcdpsk_max_llr(nc, bps, len(x)), np.float32)
         aux = np.zeros(4, np.float32)
         n = self.lib.ro_mcdpsk_demod(nc, bps, spreading, fp(x), len(x), cfo_hz, phase0, fp(llr), len(llr), fp(aux))
         assert n > 0, n
         return llr[:n].copy(), aux
+
+    def mcdpsk_demod_ex(self, nc, bps, spreading, samples, cfo_hz=0.0, phase0=0.0):
+        """-> (llr float32[n], aux float32[4], training CFO residual float32, valid data symbols int).  The compiled reference
+        has no getter for the last two (Ref.mcdpsk_demod returns neither), so for them this restatement is the reference;
+        the LLRs and the four aux words are pinned to the compiled reference by the golden fixtures."""
+        x = np.ascontiguousarray(samples, np.float32)
+        llr = np.zeros(mcdpsk_max_llr(nc, bps, len(x)), np.float32)
+        aux, res, valid = np.zeros(4, np.float32), np.zeros(1, np.float32), np.zeros(1, np.int32)
+        n = self.lib.ro_mcdpsk_demod_ex(nc, bps, spreading, fp(x), len(x), cfo_hz, phase0, fp(llr), len(llr), fp(aux), fp(res), ip(valid))
+        assert n > 0, n
+        return llr[:n].copy(), aux, res[0], int(valid[0])
+
+    def mcdpsk_branch_counts(self):
+        """the RO_MBC_* counters of this thread's last mcdpsk_demod / mcdpsk_demod_ex -> uint32 [2 * len(MBC)] (true, false pairs)"""
+        out = np.zeros(self.lib.ro_mcdpsk_branch_n(), np.uint32)
+        self.lib.ro_mcdpsk_branch_counts(out.ctypes.data_as(C.POINTER(C.c_uint)))
+        return out
 
     def chirp_detect(self, samples, threshold=0.15):
         """-> float32[6] {success, up_start, down_start, cfo_hz, up_corr, down_corr}"""
@@ -710,14 +746,14 @@ class Ref:
 
     def mcdpsk_modulate(self, nc, bps, spreading, data):
         data = np.ascontiguousarray(data, np.uint8)
-        out = np.zeros(600000, np.float32)
+        out = np.zeros(mcdpsk_frame_samples(nc, bps, spreading, len(data)), np.float32)
         n = self.lib.ref_mcdpsk_modulate(nc, bps, spreading, up(data), len(data), fp(out), len(out))
         assert n > 0
         return out[:n].copy()
 
     def mcdpsk_demod(self, nc, bps, spreading, samples, cfo_hz=0.0, phase0=0.0):
         x = np.ascontiguousarray(samples, np.float32)
-        llr = np.zeros(8192, np.float32)
+        llr = np.zeros(mcdpsk_max_llr(nc, bps, len(x)), np.float32)
         aux = np.zeros(4, np.float32)
         n = self.lib.ref_mcdpsk_demod(nc, bps, spreading, fp(x), len(x), cfo_hz, phase0, fp(llr), len(llr), fp(aux))
         assert n > 0, n

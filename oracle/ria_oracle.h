@@ -167,6 +167,28 @@ int ro_chirp_detect(const float* s, int n, float threshold, float* out6);
 int ro_mcdpsk_modulate(int nc, int bps, int spreading, const uint8_t* data, int n_bytes, float* out, int max_n);
 int ro_mcdpsk_demod(int nc, int bps, int spreading, const float* samples, int n, float cfo_hz, float phase0,
                     float* llr_out, int max_llr, float* aux4);
+/* the same chain, also returning what processTraining and demodulateSoft compute and the reference exposes no getter for:
+ * the training CFO residual (:473-505, Hz) and the number of data symbols kept by the trailing-silence trim (:600-640).
+ * Returns the LLR count like ro_mcdpsk_demod. */
+int ro_mcdpsk_demod_ex(int nc, int bps, int spreading, const float* samples, int n, float cfo_hz, float phase0,
+                       float* llr_out, int max_llr, float* aux4, float* residual_out, int* valid_out);
+/* How often each data-dependent condition of the MC-DPSK demodulator was true (_T) and false (_F) during this thread's last
+ * ro_mcdpsk_demod / ro_mcdpsk_demod_ex.  Test instrumentation only: no result depends on it.
+ * CFO_GATE |cfo| > 0.1 (:857); REF_AMP reference-symbol amplitude > 0.001 (:512); SYM_MAG combined magnitude > 0.0001 (:567);
+ * NDS4 nds >= 4 (:604); REF_MAG mean total of the first four symbols > 0.001 (:611); TRIM_ROOM valid > 4 and TRIM_LOW last
+ * symbol's total < 0.2 ref_mag (:614); PNV_FLOOR 0.01 < noise variance, SCALE_CAP 20 < scale (:640-642); MEAN_OK carrier
+ * mean > 1e-4 (:652); MEAN_DEAD mean <= 1e-4 and GMEAN_DEAD gmean <= 1e-4 (:665); VAR_POS 0 < var; RATIO_CAP ratio < 1.25;
+ * MW_FLOOR 0.10 < min(1.25, ratio); RATIO_020 ratio < 0.20; RATIO_035 ratio < 0.35; W_CAP w < 1.25; W_FLOOR 0.12 < w
+ * (:668-690); LLR_HI soft bit < 20 and LLR_LO -20 < soft bit (:650-667); VALID4 valid >= 4 and TFI_MEAN carrier mean < 0.001
+ * (:705-733); FFI_MEAN mean over the carriers < 0.001 (:404-437).  REF_AMP_EDGE / SYM_MAG_EDGE: the amplitude / magnitude equals
+ * its threshold exactly (where `>` and `>=` part). */
+#define RO_MBC_PAIRS(X) X(CFO_GATE) X(REF_AMP) X(SYM_MAG) X(NDS4) X(REF_MAG) X(TRIM_ROOM) X(TRIM_LOW) X(PNV_FLOOR) X(SCALE_CAP) \
+    X(MEAN_OK) X(MEAN_DEAD) X(GMEAN_DEAD) X(VAR_POS) X(RATIO_CAP) X(MW_FLOOR) X(RATIO_020) X(RATIO_035) X(W_CAP) X(W_FLOOR) \
+    X(LLR_HI) X(LLR_LO) X(VALID4) X(TFI_MEAN) X(FFI_MEAN) X(REF_AMP_EDGE) X(SYM_MAG_EDGE)
+#define RO_MBC_ENUM(n) RO_MBC_##n##_T, RO_MBC_##n##_F,
+enum { RO_MBC_PAIRS(RO_MBC_ENUM) RO_MBC_N };
+void ro_mcdpsk_branch_counts(unsigned* out /* [RO_MBC_N] */);
+int ro_mcdpsk_branch_n(void);
 /* OFDMChirpWaveform::detectDataSync (LTS light sync); out4 = {detected, start_sample, correlation, burst_interleaved} */
 int ro_detect_data_sync(const float* x, int n, float known_cfo_hz, float threshold, float* out4);
 /* SimulatedChannel::applyTxCFO (tools/cli_simulator.cpp:298-341): the simulator's transmitter frequency offset - FFT of

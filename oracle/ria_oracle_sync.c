@@ -579,9 +579,15 @@ static void mc_apply_cfo(float* x, int n, float cfo_hz, float phase0) { /* :901-
     free(ar); free(ai);
 }
 
+static _Thread_local unsigned ro_mbc[RO_MBC_N];   /* test instrumentation only: no result depends on it */
+void ro_mcdpsk_branch_counts(unsigned* out) { memcpy(out, ro_mbc, sizeof(ro_mbc)); }
+int ro_mcdpsk_branch_n(void) { return RO_MBC_N; }
+#define MBC(n, cond) ((cond) ? (ro_mbc[RO_MBC_##n##_T]++, 1) : (ro_mbc[RO_MBC_##n##_F]++, 0))
+
 /* aux4 = {cfo after the frame, fading index, frequency fading index, temporal fading index}; returns #LLRs */
-int ro_mcdpsk_demod(int nc, int bps, int spreading, const float* samples, int n, float cfo_hz, float phase0,
-                    float* llr_out, int max_llr, float* aux4) {
+int ro_mcdpsk_demod_ex(int nc, int bps, int spreading, const float* samples, int n, float cfo_hz, float phase0,
+                       float* llr_out, int max_llr, float* aux4, float* residual_out, int* valid_out) {
+    memset(ro_mbc, 0, sizeof(ro_mbc));
     float freqs[MC_MAXC];
     mcf prev[MC_MAXC];
     mc_freqs(nc, freqs);
@@ -593,7 +599,7 @@ int ro_mcdpsk_demod(int nc, int bps, int spreading, const float* samples, int n,
     float* x = (float*)malloc(sizeof(float) * (size_t)n);
     memcpy(x, samples, sizeof(float) * (size_t)n);
     float cfo = cfo_hz;
-    if (fabsf(cfo) > 0.1f) { mc_apply_cfo(x, n, cfo, phase0); cfo = 0.0f; }
+    if (MBC(CFO_GATE, fabsf(cfo) > 0.1f)) { mc_apply_cfo(x, n, cfo, phase0); cfo = 0.0f; }
     /* processTraining (its estimate is discarded after an external chirp detection, :857-861) */
     float saved_cfo = cfo;
     {
@@ -609,6 +615,7 @@ int ro_mcdpsk_demod(int nc, int bps, int spreading, const float* samples, int n,
         float avg = sum / nc;
         float symbol_duration = MC_SPS / kMcFs;
         float residual = (float)(avg / (2.0f * M_PI * symbol_duration));
+        if (residual_out) *residual_out = residual;
         cfo += residual;
         float lo = (50.0f < cfo) ? 50.0f : cfo;
         cfo = (-50.0f < lo) ? lo : -50.0f;
@@ -619,7 +626,8 @@ int ro_mcdpsk_demod(int nc, int bps, int spreading, const float* samples, int n,
     for (int c = 0; c < nc; ++c) {
         mcf p = mc_demod_symbol(rsym, freqs[c]);
         float a = hypotf(p.re, p.im);
-        if (a > 0.001f) { float a2 = hypotf(p.re, p.im); p.re /= a2; p.im /= a2; } else { p.re = 1.0f; p.im = 0.0f; }
+        (void)MBC(REF_AMP_EDGE, a == 0.001f);
+        if (MBC(REF_AMP, a > 0.001f)) { float a2 = hypotf(p.re, p.im); p.re /= a2; p.im /= a2; } else { p.re = 1.0f; p.im = 0.0f; }
         prev[c] = p;
     }
     /* demodulateSoft */
@@ -651,7 +659,8 @@ int ro_mcdpsk_demod(int nc, int bps, int spreading, const float* samples, int n,
             mag_sum[c] += mag;
             mag_sq[c] += mag * mag;
             mcf nrm;
-            if (mag > 0.0001f) { nrm.re = comb.re / mag; nrm.im = comb.im / mag; } else { nrm.re = 1.0f; nrm.im = 0.0f; }
+            (void)MBC(SYM_MAG_EDGE, mag == 0.0001f);
+            if (MBC(SYM_MAG, mag > 0.0001f)) { nrm.re = comb.re / mag; nrm.im = comb.im / mag; } else { nrm.re = 1.0f; nrm.im = 0.0f; }
             mcf diff = mc_mul(nrm, mc_conj(prev[c]));
             prev[c] = nrm;
             float phase = atan2f(diff.im, diff.re);
@@ -673,13 +682,13 @@ int ro_mcdpsk_demod(int nc, int bps, int spreading, const float* samples, int n,
             noise_count++;
         }
     int valid = nds;
-    if (nds >= 4) {
+    if (MBC(NDS4, nds >= 4)) {
         float ref_mag = 0.0f;
         for (int s = 0; s < 4; ++s) ref_mag += sym_total[s];
         ref_mag /= 4.0f;
-        if (ref_mag > 0.001f) {
+        if (MBC(REF_MAG, ref_mag > 0.001f)) {
             float thr = ref_mag * 0.2f;
-            while (valid > 4 && sym_total[valid - 1] < thr) valid--;
+            while (MBC(TRIM_ROOM, valid > 4) && MBC(TRIM_LOW, sym_total[valid - 1] < thr)) valid--;
             if (valid < nds) {
                 for (int c = 0; c < nc; ++c) { mag_sum[c] = 0.0f; mag_sq[c] = 0.0f; }
                 for (int s = 0; s < valid; ++s)
@@ -688,9 +697,9 @@ int ro_mcdpsk_demod(int nc, int bps, int spreading, const float* samples, int n,
         }
     }
     float pnv = (noise_count > 0) ? noise_sum / noise_count : 0.5f;
-    pnv = (0.01f < pnv) ? pnv : 0.01f;                  /* std::max(0.01f, pnv) */
+    pnv = MBC(PNV_FLOOR, 0.01f < pnv) ? pnv : 0.01f;                  /* std::max(0.01f, pnv) */
     float scale = 2.0f * sqrtf(1.0f / pnv);
-    scale = (20.0f < scale) ? 20.0f : scale;            /* std::min(scale, 20.0f) */
+    scale = MBC(SCALE_CAP, 20.0f < scale) ? 20.0f : scale;            /* std::min(scale, 20.0f) */
     float rel[MC_MAXC];
     for (int c = 0; c < nc; ++c) rel[c] = 1.0f;
     if (bps == 1 && valid > 0) {
@@ -700,25 +709,25 @@ int ro_mcdpsk_demod(int nc, int bps, int spreading, const float* samples, int n,
         for (int c = 0; c < nc; ++c) {
             float mean = mag_sum[c] / valid;
             mean_mag[c] = mean;
-            if (mean > 1e-4f) { gsum += mean; gcount++; }
+            if (MBC(MEAN_OK, mean > 1e-4f)) { gsum += mean; gcount++; }
         }
         float gmean = (gcount > 0) ? gsum / gcount : 0.0f;
         for (int c = 0; c < nc; ++c) {
             float mean = mean_mag[c];
-            if (mean <= 1e-4f || gmean <= 1e-4f) { rel[c] = 0.12f; continue; }
+            if (MBC(MEAN_DEAD, mean <= 1e-4f) || MBC(GMEAN_DEAD, gmean <= 1e-4f)) { rel[c] = 0.12f; continue; }
             float mean_sq = mag_sq[c] / valid;
             float var = mean_sq - mean * mean;
-            var = (0.0f < var) ? var : 0.0f;            /* std::max(0.0f, var) */
+            var = MBC(VAR_POS, 0.0f < var) ? var : 0.0f; /* std::max(0.0f, var) */
             float cv = sqrtf(var) / (mean + 1e-6f);
             float ratio = mean / gmean;
-            float t1 = (ratio < 1.25f) ? ratio : 1.25f; /* std::min(1.25f, ratio) */
-            float mw = (0.10f < t1) ? t1 : 0.10f;
+            float t1 = MBC(RATIO_CAP, ratio < 1.25f) ? ratio : 1.25f; /* std::min(1.25f, ratio) */
+            float mw = MBC(MW_FLOOR, 0.10f < t1) ? t1 : 0.10f;
             float sw = 1.0f / (1.0f + 1.5f * cv);
             float wd = 1.0f;
-            if (ratio < 0.20f) wd = 0.25f; else if (ratio < 0.35f) wd = 0.50f;
+            if (MBC(RATIO_020, ratio < 0.20f)) wd = 0.25f; else if (MBC(RATIO_035, ratio < 0.35f)) wd = 0.50f;
             float w = mw * sw * wd;
-            float t2 = (w < 1.25f) ? w : 1.25f;
-            rel[c] = (0.12f < t2) ? t2 : 0.12f;
+            float t2 = MBC(W_CAP, w < 1.25f) ? w : 1.25f;
+            rel[c] = MBC(W_FLOOR, 0.12f < t2) ? t2 : 0.12f;
         }
     }
     int o = 0;
@@ -728,23 +737,23 @@ int ro_mcdpsk_demod(int nc, int bps, int spreading, const float* samples, int n,
             float cs = scale * rel[c];
             if (bps == 2) {
                 float sb0 = cs * sinf(phase), sb1 = cs * sinf(2.0f * phase);
-                float a = (sb0 < 20.0f) ? sb0 : 20.0f; llr_out[o++] = (-20.0f < a) ? a : -20.0f;
-                float b = (sb1 < 20.0f) ? sb1 : 20.0f; llr_out[o++] = (-20.0f < b) ? b : -20.0f;
+                float a = MBC(LLR_HI, sb0 < 20.0f) ? sb0 : 20.0f; llr_out[o++] = MBC(LLR_LO, -20.0f < a) ? a : -20.0f;
+                float b = MBC(LLR_HI, sb1 < 20.0f) ? sb1 : 20.0f; llr_out[o++] = MBC(LLR_LO, -20.0f < b) ? b : -20.0f;
             } else {
                 float sb = cs * cosf(phase);
-                float a = (sb < 20.0f) ? sb : 20.0f; llr_out[o++] = (-20.0f < a) ? a : -20.0f;
+                float a = MBC(LLR_HI, sb < 20.0f) ? sb : 20.0f; llr_out[o++] = MBC(LLR_LO, -20.0f < a) ? a : -20.0f;
             }
         }
     /* fading indices :404-437, :705-733 */
     float cmagn[MC_MAXC];
     for (int c = 0; c < nc; ++c) cmagn[c] = (valid > 0) ? mag_sum[c] / valid : 0.0f;
     float tfi = 0.0f;
-    if (valid >= 4) {
+    if (MBC(VALID4, valid >= 4)) {
         float cvsum = 0.0f;
         int vc = 0;
         for (int c = 0; c < nc; ++c) {
             float mean = mag_sum[c] / valid;
-            if (mean < 0.001f) continue;
+            if (MBC(TFI_MEAN, mean < 0.001f)) continue;
             float mean_sq = mag_sq[c] / valid;
             float var = mean_sq - mean * mean;
             var = (0.0f < var) ? var : 0.0f;
@@ -759,15 +768,21 @@ int ro_mcdpsk_demod(int nc, int bps, int spreading, const float* samples, int n,
         float sum = 0.0f;
         for (int c = 0; c < nc; ++c) sum += cmagn[c];
         float mean = sum / nc;
-        if (!(mean < 0.001f)) {
+        if (!MBC(FFI_MEAN, mean < 0.001f)) {
             float vs = 0.0f;
             for (int c = 0; c < nc; ++c) { float d = cmagn[c] - mean; vs += d * d; }
             ffi = sqrtf(vs / nc) / mean;
         }
     }
     aux4[0] = cfo; aux4[1] = ffi + 1.0f * tfi; aux4[2] = ffi; aux4[3] = tfi;
+    if (valid_out) *valid_out = valid;
     free(x); free(sym_total); free(cph); free(cmag);
     return n_llr;
+}
+
+int ro_mcdpsk_demod(int nc, int bps, int spreading, const float* samples, int n, float cfo_hz, float phase0,
+                    float* llr_out, int max_llr, float* aux4) {
+    return ro_mcdpsk_demod_ex(nc, bps, spreading, samples, n, cfo_hz, phase0, llr_out, max_llr, aux4, NULL, NULL);
 }
 
 /* ChaseCacheEntry combine (chase_cache.cpp:27-88): count/decoded bookkeeping of ONE codeword slot */

@@ -364,11 +364,18 @@ __global__ __launch_bounds__(256) void mcdpsk_llr_kernel(McArgs A) {
 }
 
 // samples of a symbol staged per pass of the correlations: the largest power of two whose padded rows (every symbol of the
-// frame + every carrier's mixer) stay within 48 KB, so that three workgroups share a CU
+// frame + every carrier's mixer) stay within 48 KB, so that three workgroups share a CU, and which leaves the whole
+// workgroup (running sums + padded rows + 64) within the 160 KB of a CU where a smaller chunk can: without the second
+// rule a frame of 718..720 symbols at 20 carriers was refused while frames of 721..844 symbols were taken
 __host__ __device__ inline int mcdpsk_corr_chunk(int nc, int frame_samples) {
     const int n_sym = 3 + (frame_samples - (kMcTrain + 1) * kMcSps) / kMcSps;
+    const int sums = ((n_sym * nc * 8 + 15) & ~15) + 64;
     int ch = 128;
-    while (ch > 8 && mc_sym_row(n_sym) * ch * 4 + nc * (ch + 2) * 8 > 48 * 1024) ch >>= 1;
+    while (ch > 8) {
+        const int rows = mc_sym_row(n_sym) * ch * 4 + nc * (ch + 2) * 8;
+        if (rows <= 48 * 1024 && sums + rows <= 160 * 1024) break;
+        ch >>= 1;
+    }
     return ch;
 }
 __host__ __device__ inline int mcdpsk_lds_bytes(int nc, int frame_samples) {
