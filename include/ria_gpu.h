@@ -677,8 +677,10 @@ int ria_gpu_rx_burst_batch(ria_gpu_handle h, const float* samples_dev, int64_t s
  * (frame_bytes of them), zero elsewhere; llr_out_dev (nullable) rows of llr_stride floats with the reported candidate's
  * soft bits (n_llr of them, the rest zero; llr_stride must hold every candidate that can run), e.g. for
  * ria_gpu_chase_combine_batch.  This call leaves out the chase cache (:2729-2731, :2766-2789, :2796-2799, :2808-2811):
- * ria_gpu_mcdpsk_acquire_harq_batch below is the same call with it.  Channel interleaving (RIA_MACQ_CHANNEL_INTERLEAVE is
- * RIA_ERR_UNSUPPORTED), PING/PONG classification and the CW0-peek escalation stay with the caller.
+ * ria_gpu_mcdpsk_acquire_harq_batch below is the same call with it.  It also leaves out channel interleaving
+ * (:2614-2623, :2651-2672, :2741; RIA_MACQ_CHANNEL_INTERLEAVE is RIA_ERR_UNSUPPORTED here and in the HARQ call):
+ * ria_gpu_mcdpsk_acquire_ci_batch below is the same call with both.  PING/PONG classification and the CW0-peek escalation
+ * stay with the caller.
  *
  * Work: round r demodulates and decodes the list of windows still searching, each at its own next candidate that fits,
  * with two small device-to-host reads (the round's codeword-row count and the next list's length); no samples, soft bits
@@ -717,7 +719,7 @@ typedef struct ria_mcdpsk_acq_result {   /* 64 bytes */
 #define RIA_MACQ_SYNC_CHIRP           0x1u   /* dual-chirp detectSync instead of ZC detectDataSync */
 #define RIA_MACQ_DISCONNECTED         0x2u   /* handshake fallbacks on, connected CFO rule off (ZC + DISCONNECTED: RIA_ERR_INVALID) */
 #define RIA_MACQ_NO_RETRY             0x4u   /* primary candidate only */
-#define RIA_MACQ_CHANNEL_INTERLEAVE   0x8u   /* use_mc_dpsk_channel_interleave_: RIA_ERR_UNSUPPORTED */
+#define RIA_MACQ_CHANNEL_INTERLEAVE   0x8u   /* use_mc_dpsk_channel_interleave_: the *_ci_batch calls; RIA_ERR_UNSUPPORTED in the others */
 #define RIA_MACQ_FRAME_BYTES(frame_cw) (40 * (frame_cw))
 
 int ria_gpu_mcdpsk_acquire_batch(ria_gpu_handle h, const ria_mcdpsk_config* cfg, const float* samples_dev, int64_t stride,
@@ -850,6 +852,49 @@ int ria_gpu_mcdpsk_acquire_harq_batch(ria_gpu_handle h, const ria_mcdpsk_config*
                                       float* llr_out_dev /* nullable */, int llr_stride,
                                       ria_chase_pool pool /* nullable */, const int32_t* cache_id_dev, const uint64_t* now_ms_dev,
                                       ria_mcdpsk_harq_result* harq_dev /* nullable */, void* stream);
+
+/* ---- MC-DPSK channel interleaving (use_mc_dpsk_channel_interleave_, negotiated per link) -------------------------------
+ * With the mode on, the encoder permutes every codeword of every MC-DPSK frame that is not a 20-byte control frame
+ * (streaming_encoder.cpp:778-787) with ChannelInterleaver(B, 648) (ldpc_decoder.cpp:552-650): step = findCoprimeStep(B, 648),
+ * bit i of the 648 coded bits (81 bytes, MSB first) goes to bit (i * step) % 648; deinterleave(x)[i] = x[(i * step) % 648].
+ * B = interleaver_bits is the width of the receiver's interleaver_, an argument of the call and the same for every
+ * candidate of a window: carriers * bits(modulation) after setMCDPSKCarriers / setModulation (and in the encoder),
+ * carriers * 2 after setMode whatever the modulation.
+ *
+ * decodeMCDPSKFrame with the mode on (flags = RIA_MACQ_CHANNEL_INTERLEAVE, interleaver_bits 1..648 or RIA_ERR_INVALID):
+ *   - the raw CW0 first; ok with the magic: the frame is handled as without the mode, CW1.. raw (cw0_deinterleaved false)
+ *   - else deinterleave(CW0); ok with the magic: its bytes are CW0's, cw0_deinterleaved true; else the default result
+ *   - header, CONNECT guard, 1-CW success and the partial result on whichever CW0 won
+ *   - CW1.. and the combined sums of the chase cache are de-interleaved iff cw0_deinterleaved; store() receives the raw
+ *     soft bits, so a pool's sums are raw sums whatever the frames were (ria_gpu_chase_export returns them raw)
+ * The two bits of the reported candidate: ria_mcdpsk_dframe_result.reserved / ria_mcdpsk_acq_result.reserved[0]
+ * bit0 = cw0_deinterleaved, bit1 = the de-interleaved CW0 decode ran; both 0 without the flag.
+ *
+ * ria_gpu_mcdpsk_decode_frame_ci_batch is ria_gpu_mcdpsk_decode_frame_batch plus (flags, interleaver_bits): flags 0 or
+ * RIA_MACQ_CHANNEL_INTERLEAVE (anything else RIA_ERR_INVALID); with 0, interleaver_bits is ignored and every output is
+ * the old call's.  ria_gpu_mcdpsk_acquire_ci_batch is ria_gpu_mcdpsk_acquire_harq_batch (pool nullable) plus
+ * interleaver_bits, and accepts RIA_MACQ_CHANNEL_INTERLEAVE in flags; without it, it is that call.
+ * Work with the flag: round A2 after a round's CW0 decode - a compact ascending list of the entries whose raw CW0 is not
+ * (ok and magic) and that hold 648 soft bits, their de-interleaved CW0 decoded, merged into what the header stage reads.
+ * Each round (the decode-frame call is one round) makes one more small device-to-host read, the length of that list;
+ * without the flag there is no additional read or launch.  A list longer than the round's is RIA_ERR_HIP.
+ *
+ * ria_gpu_mcdpsk_interleave_batch is ChannelInterleaver::interleave(Bytes) over n_cw rows of 81 coded bytes (coded_dev ->
+ * out_dev, not in place), e.g. ria_gpu_ldpc_encode_host output before ria_gpu_mcdpsk_modulate_batch. */
+int ria_gpu_mcdpsk_decode_frame_ci_batch(ria_gpu_handle h, const float* llr_dev, int llr_stride, const int32_t* n_llr_dev /* nullable */,
+                                         int n_frames, ria_chase_pool pool /* nullable */, const int32_t* cache_id_dev,
+                                         const uint64_t* now_ms_dev, uint8_t* frame_out_dev, int frame_row,
+                                         ria_mcdpsk_dframe_result* result_dev, ria_mcdpsk_harq_result* harq_dev /* nullable */,
+                                         uint32_t flags, int interleaver_bits, void* stream);
+int ria_gpu_mcdpsk_acquire_ci_batch(ria_gpu_handle h, const ria_mcdpsk_config* cfg, const float* samples_dev, int64_t stride,
+                                    int search_len, int window_len, int n_windows, int frame_cw,
+                                    const ria_mcdpsk_acq_params* params_dev, uint32_t flags,
+                                    uint8_t* frame_out_dev, ria_mcdpsk_acq_result* acq_dev,
+                                    float* llr_out_dev /* nullable */, int llr_stride,
+                                    ria_chase_pool pool /* nullable */, const int32_t* cache_id_dev, const uint64_t* now_ms_dev,
+                                    ria_mcdpsk_harq_result* harq_dev /* nullable */, int interleaver_bits, void* stream);
+int ria_gpu_mcdpsk_interleave_batch(ria_gpu_handle h, int interleaver_bits, const uint8_t* coded_dev, int n_cw, uint8_t* out_dev,
+                                    void* stream);
 
 /* ---- RX: decodeFrame, OFDM branch (StreamingDecoder::decodeFrame, src/gui/modem/streaming_decoder.cpp:2821-3059) ----
  * The "try both" strategy every OFDM frame's soft bits go through, statement for statement, over a batch of rows.  Row f is

@@ -44,6 +44,7 @@ EXPORTS = [
     "ria_gpu_decode_frame_batch", "ria_gpu_decode_frame_host",
     "ria_gpu_chase_default_config", "ria_gpu_chase_create", "ria_gpu_chase_destroy", "ria_gpu_chase_clear", "ria_gpu_chase_stats", "ria_gpu_chase_export",
     "ria_gpu_mcdpsk_decode_frame_batch", "ria_gpu_mcdpsk_acquire_harq_batch",
+    "ria_gpu_mcdpsk_decode_frame_ci_batch", "ria_gpu_mcdpsk_acquire_ci_batch", "ria_gpu_mcdpsk_interleave_batch",
     "ria_link_recommend", "ria_link_data_mode", "ria_link_ofdm_code_rate", "ria_link_cap_initial_rate",
 ]
 
@@ -238,6 +239,9 @@ def load(build_if_needed=True):
     L.ria_gpu_chase_export.argtypes = [vp, i32, vp, vp]
     L.ria_gpu_mcdpsk_decode_frame_batch.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp]
     L.ria_gpu_mcdpsk_acquire_harq_batch.argtypes = [vp, vp, vp, C.c_int64, i32, i32, i32, i32, vp, u32, vp, vp, vp, i32, vp, vp, vp, vp, vp]
+    L.ria_gpu_mcdpsk_decode_frame_ci_batch.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, vp, u32, i32, vp]
+    L.ria_gpu_mcdpsk_acquire_ci_batch.argtypes = [vp, vp, vp, C.c_int64, i32, i32, i32, i32, vp, u32, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp]
+    L.ria_gpu_mcdpsk_interleave_batch.argtypes = [vp, i32, vp, i32, vp, vp]
     L.ria_link_recommend.argtypes = [f32, f32, C.POINTER(LinkRecommendation)]
     L.ria_link_recommend.restype = None
     L.ria_link_data_mode.argtypes = [f32, i32, f32, C.POINTER(LinkRecommendation)]

@@ -8,6 +8,11 @@
 // so its order - and with it every result - does not depend on scheduling.  A round demodulates its list with the MC-DPSK
 // demodulator's offset-list form, decodes CW0 of every entry (round A), parses the headers (one wave per entry), decodes
 // CW1..n-1 of the entries whose header asks for them (round B, a compact list of (entry, codeword) rows) and reassembles.
+//
+// With channel interleaving (RIA_MACQ_CHANNEL_INTERLEAVE, :2614-2623, :2651-2672, :2741) round A2 sits between round A and
+// the headers: the entries whose raw CW0 is not (ok and magic) are listed, their CW0 is decoded again through
+// ChannelInterleaver::deinterleave (row[i] = llr[(i * step) % 648]) and a merge puts the winning CW0 where the header
+// kernel reads it; the entry's flag then makes round B, and the chase stage's sum gather, apply the same permutation.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -30,6 +35,9 @@ struct MacqCtl {                 // read back by the host twice per round
     unsigned int n_rows;         // codeword rows of this round's round B
     unsigned int dup;            // HARQ calls: two windows claimed one cache, or a cache id the pool does not have
     unsigned int n_sums;         // HARQ calls: combined sums this round decodes
+};
+struct MacqCiCtl {               // channel interleaving: a control word of its own, so that the other reads stay what they were
+    unsigned int n_a2;           // entries of this round's A2 list
 };
 
 struct MacqList {
@@ -68,7 +76,15 @@ struct MacqArgs {
     const uint16_t* crc_bit; const uint16_t* crc_init;
     uint8_t* frame_out; int frame_row;   // [n_windows][frame_row]
     float* llr_out; int llr_stride;      // nullable
+    // channel interleaving; ci_flag null = off
+    int ci_step;                         // ChannelInterleaver(interleaver_bits, 648)'s step
+    uint8_t* ci_flag;                    // [n_cur] kMacqCiDeint | kMacqCiTried
+    uint32_t* ci_list;                   // [n_a2] round A2's entries, ascending
+    MacqCiCtl* ci_ctl;
 };
+constexpr uint8_t kMacqCiDeint = 1, kMacqCiTried = 2;   // cw0_deinterleaved / the de-interleaved CW0 decode ran
+
+__device__ __forceinline__ size_t macq_ci_src(size_t j, int step) { return (j * static_cast<size_t>(step)) % kMacqLdpcBlock; }
 
 __device__ inline bool macq_fits(int s, int frame_len, int window_len) {
     return s >= 0 && static_cast<long long>(s) + frame_len <= window_len;
@@ -133,14 +149,82 @@ __global__ __launch_bounds__(kAcqScanThreads) void macq_plan_kernel(MacqArgs A) 
     if (threadIdx.x == 0) { A.ctl->n_list = static_cast<unsigned>(running); A.ctl->n_rows = 0u; }
 }
 
-// rows of 648 LLRs for the robust decoder: round A (row_entry null) row r = CW0 of entry r, round B the listed rows
+// rows of 648 LLRs for the robust decoder: round A (row_entry null) row r = CW0 of entry r, round B the listed rows,
+// de-interleaved for the entries whose CW0 was (:2741, :2764)
 __global__ __launch_bounds__(256) void macq_gather_kernel(MacqArgs A, int n_rows) {
     const size_t total = static_cast<size_t>(n_rows) * kMacqLdpcBlock;
     for (size_t i = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x; i < total; i += static_cast<size_t>(gridDim.x) * 256) {
         const size_t r = i / kMacqLdpcBlock, j = i - r * kMacqLdpcBlock;
         const size_t e = A.row_entry ? A.row_entry[r] : r;
         const size_t cw = A.row_entry ? A.row_cw[r] : 0;
-        A.rows[i] = A.llr[e * A.llr_ws + cw * kMacqLdpcBlock + j];
+        const size_t src = (A.ci_flag && A.row_entry && (A.ci_flag[e] & kMacqCiDeint)) ? macq_ci_src(j, A.ci_step) : j;
+        A.rows[i] = A.llr[e * A.llr_ws + cw * kMacqLdpcBlock + src];
+    }
+}
+
+// ---- round A2 (channel interleaving)
+// One block: the entries whose raw CW0 is not (ok and magic) and that hold a codeword, ascending, and every entry's flag.
+__global__ __launch_bounds__(kAcqScanThreads) void macq_ci_list_kernel(MacqArgs A) {
+    int running = 0;
+    for (int base = 0; base < A.n_cur; base += kAcqScanThreads) {
+        const int i = base + static_cast<int>(threadIdx.x);
+        bool f = false;
+        if (i < A.n_cur) {
+            const uint8_t* d = A.out_a + static_cast<size_t>(i) * A.dec_bytes;
+            f = A.mst[i].n_llr >= kMacqLdpcBlock && !(A.ok_a[i] && d[0] == 0x55 && d[1] == 0x4C);
+            A.ci_flag[i] = f ? kMacqCiTried : 0;
+        }
+        int total;
+        const int pos = running + acq_block_scan(f, &total);
+        if (f) A.ci_list[pos] = static_cast<uint32_t>(i);
+        running += total;
+    }
+    if (threadIdx.x == 0) A.ci_ctl->n_a2 = static_cast<unsigned>(running);
+}
+// row r = deinterleave(CW0 of entry ci_list[r])
+__global__ __launch_bounds__(256) void macq_ci_gather_kernel(MacqArgs A, int n_a2) {
+    const size_t total = static_cast<size_t>(n_a2) * kMacqLdpcBlock;
+    for (size_t i = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x; i < total; i += static_cast<size_t>(gridDim.x) * 256) {
+        const size_t r = i / kMacqLdpcBlock, j = i - r * kMacqLdpcBlock;
+        A.rows[i] = A.llr[static_cast<size_t>(A.ci_list[r]) * A.llr_ws + macq_ci_src(j, A.ci_step)];
+    }
+}
+// One thread per A2 row: a de-interleaved CW0 that is ok with the magic becomes the entry's CW0 (:2666-2670); otherwise the
+// raw one stays, which the header kernel rejects as before.
+__global__ __launch_bounds__(256) void macq_ci_merge_kernel(MacqArgs A, int n_a2, uint8_t* out_a, uint8_t* ok_a, const uint8_t* out_a2, const uint8_t* ok_a2) {
+    for (int r = blockIdx.x * 256 + threadIdx.x; r < n_a2; r += gridDim.x * 256) {
+        const uint8_t* d = out_a2 + static_cast<size_t>(r) * A.dec_bytes;
+        if (!(ok_a2[r] && d[0] == 0x55 && d[1] == 0x4C)) continue;
+        const uint32_t e = A.ci_list[r];
+        uint8_t* dst = out_a + static_cast<size_t>(e) * A.dec_bytes;
+        for (int q = 0; q < A.dec_bytes; ++q) dst[q] = d[q];
+        ok_a[e] = 1;
+        A.ci_flag[e] = kMacqCiTried | kMacqCiDeint;
+    }
+}
+
+// ---- ChannelInterleaver::interleave(Bytes) over rows of 81 coded bytes (ldpc_decoder.cpp:627-650): bit i of a row, MSB
+// first, goes to bit (i * step) % 648.  One wave per codeword: the row is staged in LDS, each lane assembles output bytes
+// in a register from the bits at p * step_inv (step * step_inv = 1 mod 648) and stores them.
+constexpr int kMacqCwCoded = kMacqLdpcBlock / 8;   // 81
+__global__ __launch_bounds__(256) void macq_interleave_kernel(const uint8_t* in, uint8_t* out, int n_cw, int step_inv) {
+    __shared__ uint8_t stage[4][kMacqCwCoded + 3];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    for (int base = blockIdx.x * 4; base < n_cw; base += gridDim.x * 4) {   // the same trip count for the block's four waves
+        const int cw = base + wv;
+        if (cw < n_cw)
+            for (int q = lane; q < kMacqCwCoded; q += 64) stage[wv][q] = in[static_cast<size_t>(cw) * kMacqCwCoded + q];
+        __syncthreads();
+        if (cw < n_cw)
+            for (int q = lane; q < kMacqCwCoded; q += 64) {
+                unsigned v = 0;
+                for (int b = 0; b < 8; ++b) {
+                    const int i = ((q * 8 + b) * step_inv) % kMacqLdpcBlock;
+                    v = (v << 1) | ((stage[wv][i >> 3] >> (7 - (i & 7))) & 1u);
+                }
+                out[static_cast<size_t>(cw) * kMacqCwCoded + q] = static_cast<uint8_t>(v);
+            }
+        __syncthreads();
     }
 }
 
@@ -250,6 +334,7 @@ __global__ __launch_bounds__(256) void macq_finish_kernel(MacqArgs A) {
                 o.header_total_cw = T;
                 o.frame_bytes = nbytes;
                 o.n_llr = n_llr;
+                if (A.ci_flag) o.reserved[0] = A.ci_flag[i];
             }
             o.candidates = static_cast<uint8_t>(o.candidates + 1);
             // the primary stops on a success, on header salvage (codewords_ok > 0) and without the handshake fallbacks;

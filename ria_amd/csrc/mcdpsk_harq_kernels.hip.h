@@ -127,12 +127,16 @@ __global__ __launch_bounds__(kAcqScanThreads) void harq_sum_list_kernel(HarqArgs
     if (threadIdx.x == 0) ctl->n_sums = static_cast<unsigned>(running);
 }
 
-// Stage 5's rows: the listed sums out of the pool.
-__global__ __launch_bounds__(256) void harq_sum_gather_kernel(HarqArgs H, float* rows, int n_sums) {
+// Stage 5's rows: the listed sums out of the pool.  The pool holds raw sums (the store stage copies and adds the soft bits
+// as received, :2769-2770); a sum of an entry whose CW0 was de-interleaved is de-interleaved here, as it is gathered (:2778).
+__global__ __launch_bounds__(256) void harq_sum_gather_kernel(HarqArgs H, float* rows, int n_sums, const uint32_t* row_entry,
+                                                              const uint8_t* ci_flag, int ci_step) {
     const size_t total = static_cast<size_t>(n_sums) * kMacqLdpcBlock;
     for (size_t i = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x; i < total; i += static_cast<size_t>(gridDim.x) * 256) {
         const size_t q = i / kMacqLdpcBlock, j = i - q * kMacqLdpcBlock;
-        rows[i] = H.sums[static_cast<size_t>(H.sum_src[H.sum_list[q]]) * kMacqLdpcBlock + j];
+        const uint32_t row = H.sum_list[q];
+        const size_t src = (ci_flag && (ci_flag[row_entry[row]] & kMacqCiDeint)) ? macq_ci_src(j, ci_step) : j;
+        rows[i] = H.sums[static_cast<size_t>(H.sum_src[row]) * kMacqLdpcBlock + src];
     }
 }
 
@@ -214,6 +218,7 @@ __global__ __launch_bounds__(256) void mdf_result_kernel(const ria_mcdpsk_acq_re
         ria_mcdpsk_dframe_result o{};
         o.success = a.success; o.codewords_ok = a.codewords_ok; o.codewords_failed = a.codewords_failed; o.frame_type = a.frame_type;
         o.header_total_cw = a.header_total_cw; o.frame_bytes = a.frame_bytes;
+        o.reserved = a.reserved[0];          // the channel-interleaving bits of the ci call, 0 otherwise
         out[f] = o;
     }
 }

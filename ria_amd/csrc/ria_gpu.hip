@@ -452,6 +452,7 @@ static int run_crc_recovery_host(ria_gpu_handle h, const FastDecodeArgs& D, hipS
 // control block -> its pinned mirror (allocated by the caller), one stream sync; a set fault flag fails the call with fault_fmt,
 // which may print `arg`
 static unsigned int ctl_fault(const MacqCtl&) { return 0; }   // the robust decoder has no work queue
+static unsigned int ctl_fault(const MacqCiCtl&) { return 0; }
 template <class Ctl>
 static unsigned int ctl_fault(const Ctl& c) { return c.fault; }
 template <class Ctl>
@@ -1865,8 +1866,10 @@ struct MacqWs {
     uint8_t *out_b, *ok_b; uint16_t* it_b;   // round B: n * (max_cw - 1) rows
     int *hdr, *need; uint32_t* base; uint8_t* done;
     MacqCtl* ctl;
+    uint8_t* ci_flag; uint32_t* ci_list; uint8_t *out_a2, *ok_a2; uint16_t* it_a2;   // round A2: n rows with channel interleaving, else none
+    MacqCiCtl* ci_ctl;
 };
-static MacqWs macq_carve(Carver& c, size_t n, size_t llr_ws, size_t max_cw, size_t dec_bytes) {
+static MacqWs macq_carve(Carver& c, size_t n, size_t llr_ws, size_t max_cw, size_t dec_bytes, bool ci) {
     const size_t nr = n * max_cw;   // rows of round A (n) and round B (n * (max_cw - 1))
     MacqWs w;
     w.det = c.take<uint8_t>(n * 32);
@@ -1887,7 +1890,38 @@ static MacqWs macq_carve(Carver& c, size_t n, size_t llr_ws, size_t max_cw, size
     w.base = c.take<uint32_t>(n);
     w.done = c.take<uint8_t>(n);
     w.ctl = c.take<MacqCtl>(1);
+    const size_t n2 = ci ? n : 0;
+    w.ci_flag = c.take<uint8_t>(n2);
+    w.ci_list = c.take<uint32_t>(n2);
+    w.out_a2 = c.take<uint8_t>(n2 * dec_bytes);
+    w.ok_a2 = c.take<uint8_t>(n2);
+    w.it_a2 = c.take<uint16_t>(n2);
+    w.ci_ctl = c.take<MacqCiCtl>(ci ? 1 : 0);
     return w;
+}
+// ChannelInterleaver(interleaver_bits, 648)'s step (coprime with 648: 647 is prime, so the first search always ends)
+static bool macq_ci_step(int interleaver_bits, int* step) {
+    if (interleaver_bits < 1 || interleaver_bits > kMacqLdpcBlock) return false;
+    *step = channel_interleaver_step(interleaver_bits, kMacqLdpcBlock);
+    return true;
+}
+// Round A2 of a round whose round A has run (mcdpsk_acquire_kernels.hip.h), shared by the acquire and the decode-frame
+// call: the A2 list, one control read for its length, the de-interleaved CW0 decodes and the merge into round A's outputs.
+static int macq_round_a2(ria_gpu_handle h, const char* who, const MacqArgs& A, const MacqWs& W, PinBuf& mirror, hipStream_t s) {
+    hipLaunchKernelGGL(macq_ci_list_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A);
+    HIP_TRY(h, hipGetLastError());
+    if (int rc = read_ctl(h, mirror, A.ci_ctl, s)) return rc;     // the mirror's other words are read again before they are used
+    const int n_a2 = static_cast<int>(mirror.as<MacqCiCtl>()->n_a2);
+    if (n_a2 < 0 || n_a2 > A.n_cur) return fail(h, RIA_ERR_HIP, "%s: the list of de-interleaved CW0 decodes broke its bound (%d)", who, n_a2);
+    if (n_a2 == 0) return RIA_OK;
+    hipLaunchKernelGGL(macq_ci_gather_kernel, dim3(static_cast<unsigned>(std::min<size_t>((static_cast<size_t>(n_a2) * kMacqLdpcBlock + 255) / 256, 16384))),
+                       dim3(256), 0, s, A, n_a2);
+    int rc = ria_gpu_ldpc_decode_robust_batch(h, A.rows, n_a2, W.out_a2, W.ok_a2, W.it_a2, nullptr, s);
+    if (rc != RIA_OK) return rc;
+    hipLaunchKernelGGL(macq_ci_merge_kernel, dim3(static_cast<unsigned>(std::min((n_a2 + 255) / 256, 1024))), dim3(256), 0, s, A, n_a2,
+                       W.out_a, W.ok_a, W.out_a2, W.ok_a2);
+    HIP_TRY(h, hipGetLastError());
+    return RIA_OK;
 }
 
 // ---- the chase stages of decodeMCDPSKFrame (mcdpsk_harq_kernels.hip.h), shared by the two HARQ calls
@@ -1954,7 +1988,7 @@ static int harq_stages(ria_gpu_handle h, const char* who, const MacqArgs& A, Har
     }
     if (n_sums > 0) {
         hipLaunchKernelGGL(harq_sum_gather_kernel, dim3(static_cast<unsigned>(std::min<size_t>((static_cast<size_t>(n_sums) * kMacqLdpcBlock + 255) / 256, 16384))),
-                           dim3(256), 0, s, H, A.rows, n_sums);
+                           dim3(256), 0, s, H, A.rows, n_sums, A.row_entry, A.ci_flag, A.ci_step);
         int rc = ria_gpu_ldpc_decode_robust_batch(h, A.rows, n_sums, HW.out_c, HW.ok_c, HW.it_c, nullptr, s);
         if (rc != RIA_OK) return rc;
     }
@@ -1968,7 +2002,7 @@ static int macq_impl(ria_gpu_handle h, const char* who, const ria_mcdpsk_config*
                      const ria_mcdpsk_acq_params* params_dev, uint32_t flags,
                      uint8_t* frame_out_dev, ria_mcdpsk_acq_result* acq_dev,
                      float* llr_out_dev, int llr_stride, ria_chase_pool pool, const int32_t* cache_id_dev, const uint64_t* now_ms_dev,
-                     ria_mcdpsk_harq_result* harq_dev, void* stream) {
+                     ria_mcdpsk_harq_result* harq_dev, bool ci_call, int interleaver_bits, void* stream) {
     if (!h) return RIA_ERR_INVALID;
     const uint32_t known_flags = RIA_MACQ_SYNC_CHIRP | RIA_MACQ_DISCONNECTED | RIA_MACQ_NO_RETRY | RIA_MACQ_CHANNEL_INTERLEAVE;
     const bool chirp = (flags & RIA_MACQ_SYNC_CHIRP) != 0, disconnected = (flags & RIA_MACQ_DISCONNECTED) != 0;
@@ -1977,7 +2011,11 @@ static int macq_impl(ria_gpu_handle h, const char* who, const ria_mcdpsk_config*
         return fail(h, RIA_ERR_INVALID, "%s: bad argument (config, 0 <= search_len <= window_len <= stride, "
                                         "frame_cw 1..8, known flags, ZC only when connected)", who);
     if (h->cfg.code_rate != RIA_RATE_1_4) return fail(h, RIA_ERR_INVALID, "%s: MC-DPSK frames are R1/4: the handle's rate must be RIA_RATE_1_4", who);
-    if (flags & RIA_MACQ_CHANNEL_INTERLEAVE) return fail(h, RIA_ERR_UNSUPPORTED, "%s: MC-DPSK channel interleaving is not implemented", who);
+    const bool ci = ci_call && (flags & RIA_MACQ_CHANNEL_INTERLEAVE) != 0;
+    if ((flags & RIA_MACQ_CHANNEL_INTERLEAVE) && !ci_call)
+        return fail(h, RIA_ERR_UNSUPPORTED, "%s: MC-DPSK channel interleaving is ria_gpu_mcdpsk_acquire_ci_batch's", who);
+    int ci_step = 0;
+    if (ci && !macq_ci_step(interleaver_bits, &ci_step)) return fail(h, RIA_ERR_INVALID, "%s: interleaver_bits %d outside 1..648", who, interleaver_bits);
     const int nc = cfg->num_carriers, bps = cfg->bits_per_symbol, sp = cfg->spreading;
     const bool retry = disconnected && !(flags & RIA_MACQ_NO_RETRY);
     const int sym_per_cw = (kMacqLdpcBlock + nc * bps - 1) / (nc * bps);
@@ -1997,7 +2035,7 @@ static int macq_impl(ria_gpu_handle h, const char* who, const ria_mcdpsk_config*
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t n = static_cast<size_t>(n_windows), dec_bytes = static_cast<size_t>((h->geo.ldpc_k + 7) / 8);
-    auto carve = [&](Carver& c) { return macq_carve(c, n, static_cast<size_t>(llr_ws), static_cast<size_t>(max_cw), dec_bytes); };
+    auto carve = [&](Carver& c) { return macq_carve(c, n, static_cast<size_t>(llr_ws), static_cast<size_t>(max_cw), dec_bytes, ci); };
     HIP_TRY(h, h->d_macq_ws.reserve(carved_size(carve)));   // nothing of an earlier call is in flight: every call ends on a stream sync
     HIP_TRY(h, h->p_macq_ctl.reserve(sizeof(MacqCtl)));
     const MacqWs W = carve_at(h->d_macq_ws.as<>(), carve);
@@ -2045,6 +2083,7 @@ static int macq_impl(ria_gpu_handle h, const char* who, const ria_mcdpsk_config*
     A.row_base = W.base; A.done = W.done;
     A.crc_bit = h->d_crc_bit.as<const uint16_t>(); A.crc_init = h->d_crc_init.as<const uint16_t>();
     A.frame_out = frame_out_dev; A.frame_row = frame_row; A.llr_out = llr_out_dev; A.llr_stride = llr_stride;
+    if (ci) { A.ci_step = ci_step; A.ci_flag = W.ci_flag; A.ci_list = W.ci_list; A.ci_ctl = W.ci_ctl; }
     const ria_mcdpsk_config c = *cfg;
     // 3.-5. rounds: round 0 runs every accepted window at its primary candidate, round r >= 1 the windows still searching at
     // their next candidate that fits (at most 25 more rounds: each advances every window it holds by at least one candidate)
@@ -2068,6 +2107,7 @@ static int macq_impl(ria_gpu_handle h, const char* who, const ria_mcdpsk_config*
                            dim3(256), 0, s, G, n_list);
         rc = ria_gpu_ldpc_decode_robust_batch(h, A.rows, n_list, W.out_a, W.ok_a, W.it_a, nullptr, s);
         if (rc != RIA_OK) return rc;
+        if (ci && (rc = macq_round_a2(h, who, A, W, h->p_macq_ctl, s)) != RIA_OK) return rc;
         const unsigned waves = static_cast<unsigned>(std::min((n_list + 3) / 4, 4096));
         hipLaunchKernelGGL(macq_header_kernel, dim3(waves), dim3(256), 0, s, A);
         hipLaunchKernelGGL(macq_rows_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A);
@@ -2097,7 +2137,7 @@ int ria_gpu_mcdpsk_acquire_batch(ria_gpu_handle h, const ria_mcdpsk_config* cfg,
                                  uint8_t* frame_out_dev, ria_mcdpsk_acq_result* acq_dev,
                                  float* llr_out_dev, int llr_stride, void* stream) {
     return macq_impl(h, "ria_gpu_mcdpsk_acquire_batch", cfg, samples_dev, stride, search_len, window_len, n_windows, frame_cw, params_dev, flags,
-                     frame_out_dev, acq_dev, llr_out_dev, llr_stride, nullptr, nullptr, nullptr, nullptr, stream);
+                     frame_out_dev, acq_dev, llr_out_dev, llr_stride, nullptr, nullptr, nullptr, nullptr, false, 0, stream);
 }
 int ria_gpu_mcdpsk_acquire_harq_batch(ria_gpu_handle h, const ria_mcdpsk_config* cfg, const float* samples_dev, int64_t stride,
                                       int search_len, int window_len, int n_windows, int frame_cw,
@@ -2107,7 +2147,33 @@ int ria_gpu_mcdpsk_acquire_harq_batch(ria_gpu_handle h, const ria_mcdpsk_config*
                                       ria_chase_pool pool, const int32_t* cache_id_dev, const uint64_t* now_ms_dev,
                                       ria_mcdpsk_harq_result* harq_dev, void* stream) {
     return macq_impl(h, "ria_gpu_mcdpsk_acquire_harq_batch", cfg, samples_dev, stride, search_len, window_len, n_windows, frame_cw, params_dev, flags,
-                     frame_out_dev, acq_dev, llr_out_dev, llr_stride, pool, cache_id_dev, now_ms_dev, harq_dev, stream);
+                     frame_out_dev, acq_dev, llr_out_dev, llr_stride, pool, cache_id_dev, now_ms_dev, harq_dev, false, 0, stream);
+}
+int ria_gpu_mcdpsk_acquire_ci_batch(ria_gpu_handle h, const ria_mcdpsk_config* cfg, const float* samples_dev, int64_t stride,
+                                    int search_len, int window_len, int n_windows, int frame_cw,
+                                    const ria_mcdpsk_acq_params* params_dev, uint32_t flags,
+                                    uint8_t* frame_out_dev, ria_mcdpsk_acq_result* acq_dev,
+                                    float* llr_out_dev, int llr_stride,
+                                    ria_chase_pool pool, const int32_t* cache_id_dev, const uint64_t* now_ms_dev,
+                                    ria_mcdpsk_harq_result* harq_dev, int interleaver_bits, void* stream) {
+    return macq_impl(h, "ria_gpu_mcdpsk_acquire_ci_batch", cfg, samples_dev, stride, search_len, window_len, n_windows, frame_cw, params_dev, flags,
+                     frame_out_dev, acq_dev, llr_out_dev, llr_stride, pool, cache_id_dev, now_ms_dev, harq_dev, true, interleaver_bits, stream);
+}
+
+int ria_gpu_mcdpsk_interleave_batch(ria_gpu_handle h, int interleaver_bits, const uint8_t* coded_dev, int n_cw, uint8_t* out_dev, void* stream) {
+    if (!h) return RIA_ERR_INVALID;
+    int step = 0;
+    if (!macq_ci_step(interleaver_bits, &step) || n_cw < 0)
+        return fail(h, RIA_ERR_INVALID, "ria_gpu_mcdpsk_interleave_batch: bad argument (interleaver_bits 1..648, n_cw >= 0)");
+    if (n_cw == 0) return RIA_OK;
+    if (!coded_dev || !out_dev || coded_dev == out_dev) return fail(h, RIA_ERR_INVALID, "ria_gpu_mcdpsk_interleave_batch: null pointer, or in place");
+    int step_inv = 1;
+    while ((step * step_inv) % kMacqLdpcBlock != 1) ++step_inv;       // step is coprime with 648
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipLaunchKernelGGL(macq_interleave_kernel, dim3(static_cast<unsigned>(std::min((n_cw + 3) / 4, 4096))), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       coded_dev, out_dev, n_cw, step_inv);
+    HIP_TRY(h, hipGetLastError());
+    return RIA_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ the chase pool
@@ -2200,12 +2266,15 @@ int ria_gpu_chase_export(ria_chase_pool pool, int cache_id, ria_chase_entry* ent
 
 // ------------------------------------------------------------------------------------------------ decodeMCDPSKFrame on soft bits
 struct MdfWs { MacqWs m; ria_mcdpsk_acq_result* acq; };
-int ria_gpu_mcdpsk_decode_frame_batch(ria_gpu_handle h, const float* llr_dev, int llr_stride, const int32_t* n_llr_dev, int n_frames,
-                                      ria_chase_pool pool, const int32_t* cache_id_dev, const uint64_t* now_ms_dev,
-                                      uint8_t* frame_out_dev, int frame_row, ria_mcdpsk_dframe_result* result_dev,
-                                      ria_mcdpsk_harq_result* harq_dev, void* stream) {
+static int mdf_impl(ria_gpu_handle h, const char* who, const float* llr_dev, int llr_stride, const int32_t* n_llr_dev, int n_frames,
+                    ria_chase_pool pool, const int32_t* cache_id_dev, const uint64_t* now_ms_dev,
+                    uint8_t* frame_out_dev, int frame_row, ria_mcdpsk_dframe_result* result_dev,
+                    ria_mcdpsk_harq_result* harq_dev, uint32_t flags, int interleaver_bits, void* stream) {
     if (!h) return RIA_ERR_INVALID;
-    const char* who = "ria_gpu_mcdpsk_decode_frame_batch";
+    if (flags & ~RIA_MACQ_CHANNEL_INTERLEAVE) return fail(h, RIA_ERR_INVALID, "%s: flags is 0 or RIA_MACQ_CHANNEL_INTERLEAVE", who);
+    const bool ci = flags != 0;
+    int ci_step = 0;
+    if (ci && !macq_ci_step(interleaver_bits, &ci_step)) return fail(h, RIA_ERR_INVALID, "%s: interleaver_bits %d outside 1..648", who, interleaver_bits);
     if (n_frames < 0 || llr_stride < kMacqLdpcBlock || llr_stride > RIA_CHASE_MAX_CW * kMacqLdpcBlock || frame_row < kMacqCwBytes * (llr_stride / kMacqLdpcBlock))
         return fail(h, RIA_ERR_INVALID, "%s: bad argument (648 <= llr_stride <= 16 * 648, frame_row >= 20 * (llr_stride / 648))", who);
     if (h->cfg.code_rate != RIA_RATE_1_4) return fail(h, RIA_ERR_INVALID, "%s: MC-DPSK frames are R1/4: the handle's rate must be RIA_RATE_1_4", who);
@@ -2215,7 +2284,7 @@ int ria_gpu_mcdpsk_decode_frame_batch(ria_gpu_handle h, const float* llr_dev, in
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t n = static_cast<size_t>(n_frames), max_cw = static_cast<size_t>(llr_stride / kMacqLdpcBlock);
     const size_t dec_bytes = static_cast<size_t>((h->geo.ldpc_k + 7) / 8);
-    auto carve = [&](Carver& c) { MdfWs w; w.m = macq_carve(c, n, 0, max_cw, dec_bytes); w.acq = c.take<ria_mcdpsk_acq_result>(n); return w; };
+    auto carve = [&](Carver& c) { MdfWs w; w.m = macq_carve(c, n, 0, max_cw, dec_bytes, ci); w.acq = c.take<ria_mcdpsk_acq_result>(n); return w; };
     HIP_TRY(h, h->d_mdf_ws.reserve(carved_size(carve), &s));
     HIP_TRY(h, h->p_mdf_ctl.reserve(sizeof(MacqCtl)));
     const MdfWs MW = carve_at(h->d_mdf_ws.as<>(), carve);
@@ -2238,6 +2307,7 @@ int ria_gpu_mcdpsk_decode_frame_batch(ria_gpu_handle h, const float* llr_dev, in
     A.hdr_total = W.hdr; A.need_rows = W.need; A.row_base = W.base; A.done = W.done;
     A.crc_bit = h->d_crc_bit.as<const uint16_t>(); A.crc_init = h->d_crc_init.as<const uint16_t>();
     A.frame_out = frame_out_dev; A.frame_row = frame_row;
+    if (ci) { A.ci_step = ci_step; A.ci_flag = W.ci_flag; A.ci_list = W.ci_list; A.ci_ctl = W.ci_ctl; }
     // the rows as one round's list (every row, in order), then that round's stages
     const unsigned tgrid = static_cast<unsigned>(std::min((n_frames + 255) / 256, 1024));
     hipLaunchKernelGGL(mdf_list_kernel, dim3(tgrid), dim3(256), 0, s, A, n_llr_dev, W.mst);
@@ -2246,6 +2316,7 @@ int ria_gpu_mcdpsk_decode_frame_batch(ria_gpu_handle h, const float* llr_dev, in
     hipLaunchKernelGGL(macq_gather_kernel, dim3(static_cast<unsigned>(std::min<size_t>((n * kMacqLdpcBlock + 255) / 256, 16384))), dim3(256), 0, s, G, n_frames);
     int rc = ria_gpu_ldpc_decode_robust_batch(h, A.rows, n_frames, W.out_a, W.ok_a, W.it_a, nullptr, s);
     if (rc != RIA_OK) return rc;
+    if (ci && (rc = macq_round_a2(h, who, A, W, h->p_mdf_ctl, s)) != RIA_OK) return rc;
     const unsigned waves = static_cast<unsigned>(std::min((n_frames + 3) / 4, 4096));
     hipLaunchKernelGGL(macq_header_kernel, dim3(waves), dim3(256), 0, s, A);
     hipLaunchKernelGGL(macq_rows_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A);
@@ -2266,6 +2337,20 @@ int ria_gpu_mcdpsk_decode_frame_batch(ria_gpu_handle h, const float* llr_dev, in
     hipLaunchKernelGGL(mdf_result_kernel, dim3(tgrid), dim3(256), 0, s, MW.acq, n_frames, result_dev);
     HIP_TRY(h, hipGetLastError());
     return RIA_OK;
+}
+int ria_gpu_mcdpsk_decode_frame_batch(ria_gpu_handle h, const float* llr_dev, int llr_stride, const int32_t* n_llr_dev, int n_frames,
+                                      ria_chase_pool pool, const int32_t* cache_id_dev, const uint64_t* now_ms_dev,
+                                      uint8_t* frame_out_dev, int frame_row, ria_mcdpsk_dframe_result* result_dev,
+                                      ria_mcdpsk_harq_result* harq_dev, void* stream) {
+    return mdf_impl(h, "ria_gpu_mcdpsk_decode_frame_batch", llr_dev, llr_stride, n_llr_dev, n_frames, pool, cache_id_dev, now_ms_dev, frame_out_dev,
+                    frame_row, result_dev, harq_dev, 0u, 0, stream);
+}
+int ria_gpu_mcdpsk_decode_frame_ci_batch(ria_gpu_handle h, const float* llr_dev, int llr_stride, const int32_t* n_llr_dev, int n_frames,
+                                         ria_chase_pool pool, const int32_t* cache_id_dev, const uint64_t* now_ms_dev,
+                                         uint8_t* frame_out_dev, int frame_row, ria_mcdpsk_dframe_result* result_dev,
+                                         ria_mcdpsk_harq_result* harq_dev, uint32_t flags, int interleaver_bits, void* stream) {
+    return mdf_impl(h, "ria_gpu_mcdpsk_decode_frame_ci_batch", llr_dev, llr_stride, n_llr_dev, n_frames, pool, cache_id_dev, now_ms_dev, frame_out_dev,
+                    frame_row, result_dev, harq_dev, flags, interleaver_bits, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ decodeFrame (OFDM branch)

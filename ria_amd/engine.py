@@ -476,7 +476,8 @@ class RxEngine:
 
     def mcdpsk_acquire(self, windows, search_len, frame_cw, carriers=10, modulation="DBPSK", spreading=1, sync="chirp",
                        disconnected=None, known_cfo=None, detect_threshold=None, min_confidence=None, abs_base=None, retry=True,
-                       want_llr=False, chase=None, cache_id=None, now_ms=None, harq_entry=False):
+                       want_llr=False, chase=None, cache_id=None, now_ms=None, harq_entry=False, channel_interleave=False,
+                       interleaver_bits=None):
         """MC-DPSK frames from capture windows (ria_gpu_mcdpsk_acquire_batch): ZC ("zc") or dual-chirp ("chirp") detection
         on the first search_len samples of each row of `windows` (float32 [n, window_len] on the device), the acceptance
         test, demodulation + decodeMCDPSKFrame at R1/4 and, when `disconnected` (default: chirp), the handshake fallbacks.
@@ -485,6 +486,10 @@ class RxEngine:
         chase: a ChasePool routes the call to ria_gpu_mcdpsk_acquire_harq_batch; window b then uses cache cache_id[b] (default
         b, -1 = off) at time now_ms (scalar or one per window, default 0).  harq_entry: use that entry point without a pool too
         (the same outputs as the plain call, plus an all-zero harq array).
+        channel_interleave: the link negotiated MC-DPSK channel interleaving (ria_gpu_mcdpsk_acquire_ci_batch, with or
+        without a pool); interleaver_bits is the width of the receiver's interleaver (None: carriers x bits of the primary
+        modulation; a receiver configured by setMode alone has carriers x 2).  The result then carries
+        two more fields, cw0_deinterleaved and ci_tried, of the reported candidate.
         Returns (frames uint8 [n, 40 * frame_cw], acq_result structured array (MCACQ_RESULT)[, llr float32 [n, stride]]
         [, harq result structured array (HARQ_RESULT) when chase is given])."""
         from .acquire import zc_min_confidence
@@ -508,13 +513,23 @@ class RxEngine:
             stride = frame_cw * -(-648 // (carriers * bps)) * carriers * 2        # room for either modulation
             llr = torch.empty((n, stride), dtype=torch.float32, device=self.device)
         cfg = capi.McdpskConfig(carriers, bps, spreading, 0)
-        if chase is None and not harq_entry:
+        if chase is None and not harq_entry and not channel_interleave:
             self._check(self.lib.ria_gpu_mcdpsk_acquire_batch(self.h, C.byref(cfg), _ptr(windows), window_len, int(search_len), window_len, n,
                                                               int(frame_cw), _ptr(params), fl, _ptr(frames), _ptr(acq), _ptr(llr), stride,
                                                               _stream_ptr()))
             res = self._status_array(acq, self.MCACQ_RESULT)
             return (frames, res, llr) if want_llr else (frames, res)
         ids, now, harq = self._harq_in(n, cache_id, now_ms)
+        if channel_interleave:
+            bits = carriers * bps if interleaver_bits is None else int(interleaver_bits)
+            self._check(self.lib.ria_gpu_mcdpsk_acquire_ci_batch(self.h, C.byref(cfg), _ptr(windows), window_len, int(search_len), window_len, n,
+                                                                 int(frame_cw), _ptr(params), fl | capi.MACQ_CHANNEL_INTERLEAVE, _ptr(frames), _ptr(acq),
+                                                                 _ptr(llr), stride, chase.p if chase is not None else None, _ptr(ids), _ptr(now),
+                                                                 _ptr(harq), bits, _stream_ptr()))
+            res = self._status_array(acq, self.MCACQ_RESULT)
+            res = self._ci_fields(res, res["reserved"][:, 0])
+            out = (frames, res, llr) if want_llr else (frames, res)
+            return out + (self._status_array(harq, self.HARQ_RESULT),) if (chase is not None or harq_entry) else out
         self._check(self.lib.ria_gpu_mcdpsk_acquire_harq_batch(self.h, C.byref(cfg), _ptr(windows), window_len, int(search_len), window_len, n,
                                                                int(frame_cw), _ptr(params), fl, _ptr(frames), _ptr(acq), _ptr(llr), stride,
                                                                chase.p if chase is not None else None, _ptr(ids), _ptr(now), _ptr(harq),
@@ -522,6 +537,16 @@ class RxEngine:
         res = self._status_array(acq, self.MCACQ_RESULT)
         hq = self._status_array(harq, self.HARQ_RESULT)
         return (frames, res, llr, hq) if want_llr else (frames, res, hq)
+
+    @staticmethod
+    def _ci_fields(res, bits):
+        """res with the two channel-interleaving bits of its reserved word as fields of their own"""
+        out = np.zeros(res.shape, np.dtype(res.dtype.descr + [("cw0_deinterleaved", "u1"), ("ci_tried", "u1")]))
+        for f in res.dtype.names:
+            out[f] = res[f]
+        out["cw0_deinterleaved"] = np.asarray(bits) & 1
+        out["ci_tried"] = (np.asarray(bits) >> 1) & 1
+        return out
 
     MCDFRAME_RESULT = np.dtype([("success", "u1"), ("codewords_ok", "u1"), ("codewords_failed", "u1"), ("frame_type", "u1"),
                                 ("header_total_cw", "<i4"), ("frame_bytes", "<i4"), ("reserved", "<i4")])
@@ -538,10 +563,13 @@ class RxEngine:
         return (torch.from_numpy(ids.copy()).to(self.device), torch.from_numpy(now.view(np.int64).copy()).to(self.device),
                 torch.empty((n, 32), dtype=torch.uint8, device=self.device))
 
-    def mcdpsk_decode_frame(self, llr, n_llr=None, chase=None, cache_id=None, now_ms=None):
+    def mcdpsk_decode_frame(self, llr, n_llr=None, chase=None, cache_id=None, now_ms=None, channel_interleave=False, interleaver_bits=None,
+                            carriers=10, modulation="DBPSK"):
         """StreamingDecoder::decodeMCDPSKFrame at R1/4 over rows of soft bits (ria_gpu_mcdpsk_decode_frame_batch): llr float32
         [n, 648 .. 16 * 648], n_llr the soft bits of each row (None: the whole row).  chase: a ChasePool; row f then uses cache
         cache_id[f] (default f, -1 = off) at time now_ms (scalar or per row, default 0).
+        channel_interleave: decodeMCDPSKFrame with use_mc_dpsk_channel_interleave_ (ria_gpu_mcdpsk_decode_frame_ci_batch);
+        interleaver_bits None: carriers x bits of `modulation`.  The result then has the fields cw0_deinterleaved and ci_tried.
         Returns (frame bytes uint8 [n, 20 * (cols // 648)], result (MCDFRAME_RESULT), harq result (HARQ_RESULT))."""
         n, stride = llr.shape
         assert llr.dtype == torch.float32 and llr.is_contiguous()
@@ -553,6 +581,14 @@ class RxEngine:
             nl = torch.as_tensor(np.ascontiguousarray(n_llr, np.int32)).to(self.device) if not torch.is_tensor(n_llr) else n_llr
             assert nl.dtype == torch.int32 and nl.numel() == n and nl.is_contiguous()
         ids, now, harq = self._harq_in(n, cache_id, now_ms)
+        if channel_interleave:
+            bps = {"DBPSK": 1, "DQPSK": 2}[modulation] if isinstance(modulation, str) else int(modulation)
+            bits = carriers * bps if interleaver_bits is None else int(interleaver_bits)
+            self._check(self.lib.ria_gpu_mcdpsk_decode_frame_ci_batch(self.h, _ptr(llr), stride, _ptr(nl), n, chase.p if chase is not None else None,
+                                                                      _ptr(ids), _ptr(now), _ptr(frames), row, _ptr(res), _ptr(harq),
+                                                                      capi.MACQ_CHANNEL_INTERLEAVE, bits, _stream_ptr()))
+            r = self._status_array(res, self.MCDFRAME_RESULT)
+            return frames, self._ci_fields(r, r["reserved"]), self._status_array(harq, self.HARQ_RESULT)
         self._check(self.lib.ria_gpu_mcdpsk_decode_frame_batch(self.h, _ptr(llr), stride, _ptr(nl), n, chase.p if chase is not None else None,
                                                                _ptr(ids), _ptr(now), _ptr(frames), row, _ptr(res), _ptr(harq), _stream_ptr()))
         return frames, self._status_array(res, self.MCDFRAME_RESULT), self._status_array(harq, self.HARQ_RESULT)
@@ -565,6 +601,16 @@ class RxEngine:
         if n < 0:
             raise capi.RiaError("mcdpsk_modulate failed")
         return out[:n].copy()
+
+    def mcdpsk_interleave(self, coded, interleaver_bits):
+        """ChannelInterleaver(interleaver_bits, 648)::interleave over codewords of 81 coded bytes
+        (ria_gpu_mcdpsk_interleave_batch): coded uint8 [..., 81 * k] (device tensor or host array) -> a new tensor of that shape"""
+        if not torch.is_tensor(coded):
+            coded = torch.from_numpy(np.ascontiguousarray(coded, np.uint8)).to(self.device)
+        assert coded.dtype == torch.uint8 and coded.is_contiguous() and coded.shape[-1] % 81 == 0
+        out = torch.empty_like(coded)
+        self._check(self.lib.ria_gpu_mcdpsk_interleave_batch(self.h, int(interleaver_bits), _ptr(coded), coded.numel() // 81, _ptr(out), _stream_ptr()))
+        return out
 
     def mcdpsk_modulate_batch(self, data, carriers=10, bits_per_symbol=1, spreading=1):
         """MultiCarrierDPSKModulator on the device: data uint8 [n, n_bytes] (device tensor or host array) -> float32 [n, samples]"""

@@ -12,6 +12,10 @@ Workloads (all windows built and channelled on the device, ria_amd.acquire.make_
   transmission).  Times the plain call and the HARQ entry without a pool on transmission 0, then the N transmissions into
   the pool (cleared before each repetition), with the HARQ counters of every transmission (ria_amd.acquire.harq_tally: the
   windows' last candidates) and what the transmission added to the caches' own statistics, summed over the pool.  --harq-call-only: one pass of the pool calls alone, for a kernel trace.
+
+--channel-interleave: the link negotiated MC-DPSK channel interleaving.  The data frames (the CONNECT; not the 20-byte ACK)
+  are interleaved on the device (ria_gpu_mcdpsk_interleave_batch, width carriers x bits = 10) before they are modulated, and
+  every acquire call sets RIA_MACQ_CHANNEL_INTERLEAVE (ria_gpu_mcdpsk_acquire_ci_batch).
 """
 import argparse
 import json
@@ -37,13 +41,20 @@ def timed(fn, reps):
     return (time.perf_counter() - t) / reps, out
 
 
+def ci_args(e, a, coded):
+    """-> (the coded bytes the windows carry, the keyword arguments of every acquire call)"""
+    if not a.channel_interleave:
+        return coded, {}
+    return e.mcdpsk_interleave(coded, 10).cpu().numpy(), {"channel_interleave": True, "interleaver_bits": 10}
+
+
 def harq_mode(e, a):
     from mcdpsk_acquire_restatement import CONNECT, data_frame, encode_frame
     from ria_amd.acquire import HARQ_COUNTERS, harq_tally, make_mcdpsk_windows
     from ria_amd.engine import ChasePool
     from ria_amd.srchash import csrc_sha256
     n, N = a.windows, a.harq
-    connect = encode_frame(data_frame(CONNECT, 7, np.arange(25, dtype=np.uint8)))[None, :]
+    connect, ci = ci_args(e, a, encode_frame(data_frame(CONNECT, 7, np.arange(25, dtype=np.uint8)))[None, :])
     chirp = e.chirp_preamble()
     base = np.arange(1, n + 1, dtype=np.uint32) * np.uint32(2654435761)
     wins = []
@@ -52,7 +63,7 @@ def harq_mode(e, a):
         wins.append(w)
     pool = e.chase_pool(n, max_entries=a.harq_entries)
     out = {"metric": "mcdpsk_acquire_harq_ms", "windows": n, "transmissions": N, "snr_db": a.harq_snr, "channel": "moderate",
-           "pool_entries": a.harq_entries, "pool_bytes": n * a.harq_entries * 16 * 648 * 4, "source_hash": csrc_sha256()}
+           "channel_interleave": bool(a.channel_interleave), "pool_entries": a.harq_entries, "pool_bytes": n * a.harq_entries * 16 * 648 * 4, "source_hash": csrc_sha256()}
 
     def pass_(record):
         pool.clear()
@@ -60,7 +71,7 @@ def harq_mode(e, a):
         rows = []
         for t in range(N):
             t0 = time.perf_counter()
-            frames, res, hq = e.mcdpsk_acquire(wins[t], sl, 3, chase=pool, now_ms=1000 * t)
+            frames, res, hq = e.mcdpsk_acquire(wins[t], sl, 3, chase=pool, now_ms=1000 * t, **ci)
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
             if record:
@@ -71,9 +82,9 @@ def harq_mode(e, a):
         print(json.dumps(out))
         return
     reps = [pass_(True) for _ in range(a.reps)]
-    dt, (_, res0) = timed(lambda: e.mcdpsk_acquire(wins[0], sl, 3), a.reps)
+    dt, (_, res0) = timed(lambda: e.mcdpsk_acquire(wins[0], sl, 3, **ci), a.reps)
     out["plain_call"] = {"ms": dt * 1e3, "success": int(res0["success"].sum()), "candidates": int(res0["candidates"].sum())}
-    dt, (_, res1, _) = timed(lambda: e.mcdpsk_acquire(wins[0], sl, 3, harq_entry=True), a.reps)
+    dt, (_, res1, _) = timed(lambda: e.mcdpsk_acquire(wins[0], sl, 3, harq_entry=True, **ci), a.reps)
     out["harq_entry_no_pool"] = {"ms": dt * 1e3, "equal_to_plain": bool(res0.tobytes() == res1.tobytes())}
     out["with_pool"] = []
     for t in range(N):
@@ -92,7 +103,7 @@ def harq_mode(e, a):
     pool.clear()
     before = totals()
     for t in range(N):
-        e.mcdpsk_acquire(wins[t], sl, 3, chase=pool, now_ms=1000 * t)
+        e.mcdpsk_acquire(wins[t], sl, 3, chase=pool, now_ms=1000 * t, **ci)
         after = totals()
         out["with_pool"][t]["cache_stats"] = {k: after[k] - before[k] for k in ChasePool.STATS}
         before = after
@@ -106,6 +117,7 @@ def main():
     ap.add_argument("--harq-snr", type=float, default=-8.0)
     ap.add_argument("--harq-entries", type=int, default=2)
     ap.add_argument("--harq-call-only", action="store_true")
+    ap.add_argument("--channel-interleave", action="store_true", help="interleave the data frames and set RIA_MACQ_CHANNEL_INTERLEAVE")
     ap.add_argument("--windows", type=int, default=1024)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--snr", type=float, default=0.0)
@@ -120,12 +132,13 @@ def main():
         return harq_mode(e, a)
     n = a.windows
     seeds = np.arange(1, n + 1, dtype=np.uint32) * np.uint32(2654435761)
-    connect = encode_frame(data_frame(CONNECT, 7, np.arange(25, dtype=np.uint8)))[None, :]
+    connect, ci = ci_args(e, a, encode_frame(data_frame(CONNECT, 7, np.arange(25, dtype=np.uint8)))[None, :])
     chirp = e.chirp_preamble()
-    out = {"metric": "mcdpsk_acquire_windows_per_s", "windows": n, "snr_db": a.snr, "source_hash": csrc_sha256()}
+    out = {"metric": "mcdpsk_acquire_windows_per_s", "windows": n, "snr_db": a.snr, "channel_interleave": bool(a.channel_interleave),
+           "source_hash": csrc_sha256()}
     for name, kind in (("connect_awgn", 0), ("connect_moderate", 2)):
         w, sl = make_mcdpsk_windows(e, connect, chirp, n, 3, kind, a.snr, seeds)
-        dt, (frames, res) = timed(lambda: e.mcdpsk_acquire(w, sl, 3), a.reps)
+        dt, (frames, res) = timed(lambda: e.mcdpsk_acquire(w, sl, 3, **ci), a.reps)
         out[name] = {"windows_per_s": n / dt, "ms": dt * 1e3, "success": int(res["success"].sum()),
                      "recovered": int(((res["success"] != 0) & (res["candidates"] > 1)).sum()),
                      "candidates": int(res["candidates"].sum())}
@@ -153,7 +166,7 @@ def main():
     # windows whose frame sits 288 samples behind the preamble: the primary and the alternate fail, the timing recovery
     # decodes them (at +48 samples in the restatement's AWGN windows)
     w, sl = make_mcdpsk_windows(e, connect, chirp, n, 3, 0, a.snr, seeds, gap=288)
-    dt, (frames, res) = timed(lambda: e.mcdpsk_acquire(w, sl, 3), a.reps)
+    dt, (frames, res) = timed(lambda: e.mcdpsk_acquire(w, sl, 3, **ci), a.reps)
     out["connect_recovery"] = {"windows_per_s": n / dt, "ms": dt * 1e3, "success": int(res["success"].sum()),
                                "recovered": int(((res["success"] != 0) & (res["candidates"] > 1)).sum()),
                                "candidates": int(res["candidates"].sum())}
@@ -163,7 +176,7 @@ def main():
     ack = encode_frame(control_frame(ACK, 3))[None, :]
     zc = e.zc_preamble(5)
     w, sl = make_mcdpsk_windows(e, ack, zc, n, 1, 0, a.zc_snr, seeds)
-    dt, (frames, res) = timed(lambda: e.mcdpsk_acquire(w, sl, 1, sync="zc", min_confidence=0.25), a.reps)
+    dt, (frames, res) = timed(lambda: e.mcdpsk_acquire(w, sl, 1, sync="zc", min_confidence=0.25, **ci), a.reps)
     out["zc_connected"] = {"snr_db": a.zc_snr, "windows_per_s": n / dt, "ms": dt * 1e3, "accepted": int(res["accepted"].sum()),
                            "candidates": int(res["candidates"].sum())}
     print(json.dumps(out))
