@@ -243,9 +243,16 @@ int ria_gpu_decode_frames_host(ria_gpu_handle h, const float* llr_host, int llr_
 
 /* ---- TX synthesis for Monte-Carlo sweeps (v2::encodeFixedFrame frame_v2.cpp:1285-1328 +
  *      OFDMModulator::generateTrainingSymbols/modulate modulator.cpp:534-583, :348-477) ---------- */
-/* info_dev: n_frames * info_bytes_per_frame (already serialized frames, zero padded);
+/* info_dev: n_frames * info_bytes_per_frame (already serialized frames, zero padded; any bytes are taken: the encoder reads
+ * the first min(ldpc_k, 8 * bytes_per_codeword) bits of each codeword's bytes and pads the rest of the code's k bits with zeros);
  * samples_out_dev: n_frames * frame_samples.  peak_normalize: scale every frame to this peak
- * (0 = leave the modulator's output_scale 40 level; tools/test_waveform_simple.cpp:365-371 uses 0.8) */
+ * (0 = leave the modulator's output_scale 40 level; tools/test_waveform_simple.cpp:365-371 uses 0.8).
+ * The rule, in float32, per frame: where peak_normalize > 0 is true, every sample s becomes s * (peak_normalize / max|s|),
+ * the quotient correctly rounded; otherwise (0, -0.0, any negative value, NaN) the samples stay at the modulator's level.
+ * Nothing else is checked: a tiny value gives denormal samples (not flushed), a value whose quotient or products overflow
+ * gives +-inf there (3e38 does for a frame that peaks under 0.88), and +inf gives +-inf at every non-zero sample and, by
+ * the same rule, NaN at an exactly zero sample (0 * inf; the tests have no such sample, the NaN's bits are not pinned).
+ * max|s| > 0 always, the two training symbols are never silent.  n_frames 0 is RIA_OK and writes nothing. */
 int ria_gpu_tx_batch(ria_gpu_handle h, const uint8_t* info_dev, int n_frames, float peak_normalize,
                      float* samples_out_dev, void* stream);
 /* The same in two steps, split at the coded bytes where the burst interleaver works (streaming_encoder.cpp:302-389):
@@ -256,7 +263,11 @@ int ria_gpu_tx_coded_batch(ria_gpu_handle h, const uint8_t* coded_dev, int n_fra
                            float* samples_out_dev, void* stream);
 
 /* Builds serialized v2 data frames (makeFixedDataFrame("TEST","RX",seq,payload).serialize(),
- * frame_v2.cpp:1890-1912, :502-554) with payload bytes drawn from a counter RNG: seq = first_seq + f. */
+ * frame_v2.cpp:1890-1912, :502-554) with payload bytes drawn from a counter RNG: seq = first_seq + f.
+ * Frame f depends on (seed, first_seq + f) alone, not on how a batch is split: its payload comes from Philox4x32-10 with
+ * key = the two 32-bit words of seed and counter word 0 = (first_seq + f) mod 2^32, all 32 bits; the frame's seq field is
+ * the low 16 bits of that number.  So first_seq and first_seq + 65536 give the same seq and different payloads.  A negative
+ * first_seq is taken as first_seq + 2^32 (make_frames(seed, -1, 2) builds the frames 2^32 - 1 and 0): it is not refused. */
 int ria_gpu_make_frames(ria_gpu_handle h, uint64_t seed, int first_seq, int n_frames,
                         uint8_t* info_out_dev, void* stream);
 

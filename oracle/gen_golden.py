@@ -391,6 +391,64 @@ def mcdpsk_domain_fixture(R):
     return rec
 
 
+TX_FRAME_RATE = "R3_4"      # the rate whose frames are kept in full, one per modulation (the fewest symbols)
+
+
+def tx_domain_fixture(R):
+    """v2::encodeFixedFrame and OFDMModulator (generateTrainingSymbols(2) + modulate, through OFDMChirpWaveform; through the
+    OFDM-COX object for QAM256) of the reference over the transmit chain's input domain (tests/tx_domain_inputs.py builds the
+    inputs; only their sha256 is kept here).  Per configuration: sha_*; geom_* int32 [7] as the reference's objects show it;
+    coded_* uint8 [n_info, 324] the coded bytes of every info row; dig_* uint8 [rows, 32] sha256 of the sample bytes of every
+    row (info rows, then coded rows); mx_* float32 [rows] max |s|.  frame_<modulation>: the samples of one row (frame_row_*: the
+    first counter row) at TX_FRAME_RATE, uint8 [4, n] byte planes (tx_domain_inputs.frame_planes; lossless).  refused: the configurations the reference's object turned into another modulation."""
+    sys.path.insert(0, os.path.join(os.path.dirname(po.HERE), "tests"))
+    import tx_domain_inputs as T
+    O = po.Oracle()
+    rec, refused = {}, []
+    for mode in T.MODES:
+        S = T.input_set(O, mode)
+        geom, ref = T.reference_geometry(R, mode)
+        rec[f"sha_{mode}"] = np.array(T.digest(S))
+        if ref:
+            refused.append(mode)
+            continue
+        coded, samples = T.answers(R, O, mode)
+        rec[f"geom_{mode}"] = geom
+        rec[f"coded_{mode}"] = coded
+        rec[f"dig_{mode}"] = np.stack([np.frombuffer(bytes.fromhex(T.sample_digest(s)), np.uint8) for s in samples])
+        rec[f"mx_{mode}"] = np.array([np.abs(s).max() for s in samples], np.float32)
+        if mode.endswith(TX_FRAME_RATE):
+            row = len(S["info"]) + [i for i, l in enumerate(S["coded_labels"]) if l.startswith("counter")][0]
+            rec[f"frame_{mode[:-len(TX_FRAME_RATE) - 1]}"] = T.frame_planes(samples[row])
+            rec[f"frame_row_{mode[:-len(TX_FRAME_RATE) - 1]}"] = np.int32(row)
+        print("tx domain", mode, "rows", len(samples), "symbols", int(geom[5]), flush=True)
+    rec["refused"] = np.array(refused, dtype="U16")
+    print("tx domain: refused by the reference:", refused or "none", flush=True)
+    return rec
+
+
+def write_reproducible(path, rec):
+    """an .npz whose bytes depend on the arrays alone (np.savez stamps every member with the time of day); says whether the
+    file that was there had the same bytes"""
+    import io
+    import zipfile
+    buf = io.BytesIO()
+    with zipfile.ZipFile(buf, "w", zipfile.ZIP_DEFLATED, compresslevel=9) as z:
+        for k in sorted(rec):
+            b = io.BytesIO()
+            np.lib.format.write_array(b, np.asanyarray(rec[k]), allow_pickle=False)
+            info = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            z.writestr(info, b.getvalue(), compresslevel=9)
+    data = buf.getvalue()
+    old = open(path, "rb").read() if os.path.exists(path) else None
+    with open(path, "wb") as f:
+        f.write(data)
+    print(os.path.basename(path), len(data), "bytes:", "new file" if old is None else
+          "reproduced byte for byte" if old == data else "DIFFERS from the file that was there")
+
+
 def sync_domain_fixture(R):
     """ZCSync::detect, ChirpSync::detectDualChirp, OFDMChirpWaveform::detectDataSync and OFDMDemodulator::searchForSync of the
     reference over the detectors' input domain (tests/sync_domain_inputs.py builds the buffers; only their sha256 is kept
@@ -697,6 +755,9 @@ def main():
     if only == "mcdpsk_domain":
         np.savez_compressed(os.path.join(OUT, "mcdpsk_domain.npz"), **mcdpsk_domain_fixture(R))
         return 0
+    if only == "tx_domain":
+        write_reproducible(os.path.join(OUT, "tx_domain.npz"), tx_domain_fixture(R))
+        return 0
     if only == "sync_domain":
         np.savez_compressed(os.path.join(OUT, "sync_domain.npz"), **sync_domain_fixture(R))
         return 0
@@ -793,6 +854,7 @@ def main():
     np.savez_compressed(os.path.join(OUT, "cfo_impairment.npz"), **cfo_fixture(R))
     np.savez_compressed(os.path.join(OUT, "mcdpsk_waveform.npz"), **mcwf_fixture(R))
     np.savez_compressed(os.path.join(OUT, "ref_tool_tables.npz"), **tool_tables_fixture(R))
+    write_reproducible(os.path.join(OUT, "tx_domain.npz"), tx_domain_fixture(R))
     print("done ->", OUT)
     return 0
 

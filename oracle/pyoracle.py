@@ -783,12 +783,19 @@ class Ref:
         self.lib.ref_encode_fixed_frame(up(info), len(info), rate, int(ch_il), bps, up(out), 324)
         return out
 
-    def modulate(self, mod, rate, coded):
+    def modulate(self, mod, rate, coded, nvis=False):
+        """nvis: through the OFDM-COX waveform object (the only one that accepts QAM256)"""
         coded = np.ascontiguousarray(coded, np.uint8)
         out = np.zeros(80000, np.float32)
-        n = self.lib.ref_modulate(mod, rate, up(coded), len(coded), fp(out), len(out))
+        n = (self.lib.ref_modulate_nvis if nvis else self.lib.ref_modulate)(mod, rate, up(coded), len(coded), fp(out), len(out))
         assert n > 0
         return out[:n].copy()
+
+    def tx_config(self, mod, rate, nvis=False):
+        """what configure(mod, rate) leaves in the waveform's config -> int32[4] {modulation, pilot_spacing, use_pilots, num_carriers}"""
+        out = np.zeros(4, np.int32)
+        self.lib.ref_tx_config(mod, rate, int(nvis), ip(out))
+        return out
 
     def channel(self, kind, snr_db, seed, x):
         x = np.ascontiguousarray(x, np.float32)

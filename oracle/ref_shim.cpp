@@ -570,6 +570,30 @@ int ref_tx_frame_nvis(int mod, int rate, const uint8_t* payload, int payload_len
     std::memcpy(samples_out + pre.size(), dat.data(), dat.size() * sizeof(float));
     return n;
 }
+// ref_modulate on the OFDM-COX object: 2 training symbols + modulate(coded), no LDPC.
+int ref_modulate_nvis(int mod, int rate, const uint8_t* coded, int n_coded, float* samples_out, int max_samples) {
+    ref_quiet();
+    OFDMNvisWaveform tx(named_config(mod, rate));
+    tx.configure(static_cast<Modulation>(mod), static_cast<CodeRate>(rate));
+    Samples pre = tx.modulator_->generateTrainingSymbols(2);
+    Samples dat = tx.modulate(Bytes(coded, coded + n_coded));
+    int n = static_cast<int>(pre.size() + dat.size());
+    if (n > max_samples) return -n;
+    std::memcpy(samples_out, pre.data(), pre.size() * sizeof(float));
+    std::memcpy(samples_out + pre.size(), dat.data(), dat.size() * sizeof(float));
+    return n;
+}
+// What configure(mod, rate) leaves in the waveform's ModemConfig: out4 = {modulation, pilot_spacing, use_pilots, num_carriers}.
+// A modulation other than the one asked for means the object refused it (ofdm_chirp_waveform.cpp:82-89).
+int ref_tx_config(int mod, int rate, int nvis, int* out4) {
+    ref_quiet();
+    ModemConfig c;
+    if (nvis) { OFDMNvisWaveform tx(named_config(mod, rate)); tx.configure(static_cast<Modulation>(mod), static_cast<CodeRate>(rate)); c = tx.config_; }
+    else { OFDMChirpWaveform tx(named_config(mod, rate)); tx.configure(static_cast<Modulation>(mod), static_cast<CodeRate>(rate)); c = tx.config_; }
+    out4[0] = static_cast<int>(c.modulation); out4[1] = static_cast<int>(c.pilot_spacing);
+    out4[2] = c.use_pilots ? 1 : 0; out4[3] = static_cast<int>(c.num_carriers);
+    return 0;
+}
 int ref_rx_process_nvis(int mod, int rate, const float* samples, int n, float cfo_hz, long long abs_pos, int use_abs,
                         float* llr_out, int max_llr, float* aux_out, float* h_out) {
     ref_quiet();

@@ -562,6 +562,11 @@ int ria_gpu_create(const ria_gpu_config* cfg, ria_gpu_handle* out) {
     g.ldpc_max_iterations = recommended_iterations(cfg->code_rate);
     g.ldpc_edges = h->code.n_edges;
     g.ldpc_k = h->code.k;
+    if (const char* why = tx_const_misfit(h->plan, h->code, g)) {   // before build_tx_const copies by these counts
+        fprintf(stderr, "ria_gpu_create: the transmit constant block does not hold this configuration: %s\n", why);
+        delete h;
+        return RIA_ERR_UNSUPPORTED;
+    }
 
 #define CREATE_TRY(expr)                                                                              \
     do {                                                                                              \

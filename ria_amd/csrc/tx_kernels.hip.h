@@ -18,35 +18,11 @@
 #include "demod_kernels.hip.h"
 #include "host_tables.hpp"
 #include "ldpc_kernels.hip.h"
+#include "tx_const.hpp"
 
 namespace ria {
 
-struct TxConst {
-    int mod, n_data, n_pilot, bits_per_carrier, bits_per_symbol, n_data_symbols;
-    int k, m, bytes_per_cw;
-    int data_bin[64], pilot_bin[64];
-    float pilot_seq[64];
-    float sync_re[64], sync_im[64];   // by data ordinal
-    uint8_t row_deg[648];
-    uint16_t row_var[7 * 648];        // [7][m]
-    uint16_t scatter[4 * 648];        // coded bit i of codeword cw -> position in the 2592-bit stream
-};
-
-inline TxConst build_tx_const(const CarrierPlan& p, const LdpcCode& c, int mod, const ria_gpu_geometry& g) {
-    TxConst t{};
-    t.mod = mod;
-    t.n_data = p.n_data; t.n_pilot = p.n_pilot;
-    t.bits_per_carrier = g.bits_per_carrier; t.bits_per_symbol = g.bits_per_symbol;
-    t.n_data_symbols = g.n_data_symbols;
-    t.k = c.k; t.m = c.m; t.bytes_per_cw = g.bytes_per_codeword;
-    for (int i = 0; i < p.n_data; ++i) { t.data_bin[i] = p.data_bin[i]; t.sync_re[i] = p.sync_re[i % kCarriers]; t.sync_im[i] = p.sync_im[i % kCarriers]; }
-    for (int i = 0; i < p.n_pilot; ++i) { t.pilot_bin[i] = p.pilot_bin[i]; t.pilot_seq[i] = p.pilot_seq[i]; }
-    for (int i = 0; i < c.m; ++i) t.row_deg[i] = c.row_deg[i];
-    for (size_t i = 0; i < c.row_var.size(); ++i) t.row_var[i] = c.row_var[i];
-    auto sc = build_rx_gather(g.bits_per_symbol, true);
-    for (size_t i = 0; i < sc.size(); ++i) t.scatter[i] = sc[i];
-    return t;
-}
+static_assert(kTxFftTile == kFftBufFloats2, "tx_const.hpp sizes the IFFT tiles of tx_frames_kernel");
 
 // ---------------------------------------------------------------- counter RNG
 __device__ __forceinline__ void philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
@@ -74,10 +50,11 @@ __device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float* n0, fl
 __global__ __launch_bounds__(64) void make_frames_kernel(const TxConst* __restrict__ T, const uint16_t* crc_bit,
                                                          const uint16_t* crc_init, uint64_t seed, int first_seq,
                                                          int n_frames, uint8_t* __restrict__ out) {
-    __shared__ uint8_t fr[4 * 68];
+    __shared__ uint8_t fr[4 * kTxMaxBytesPerCw];
     const int lane = threadIdx.x, frame = blockIdx.x;
     const int total = 4 * T->bytes_per_cw, plen = total - 19;
-    const int seq = (first_seq + frame) & 0xFFFF;
+    // the counter is (first_seq + frame) mod 2^32 (a negative first_seq counts as first_seq + 2^32), seq its low 16 bits
+    const int seq = static_cast<int>((static_cast<uint32_t>(first_seq) + static_cast<uint32_t>(frame)) & 0xFFFFu);
     for (int b = lane; b < total; b += 64) {
         uint32_t r[4];
         philox4x32(static_cast<uint32_t>(frame + static_cast<uint32_t>(first_seq)), static_cast<uint32_t>(b >> 2), 0x5249u, 0,
@@ -214,7 +191,8 @@ __global__ __launch_bounds__(256) void tx_frames_kernel(const TxConst* __restric
     uint8_t* bits = reinterpret_cast<uint8_t*>(tiles + 4 * kFftBufFloats2);   // [2592] interleaved coded bits
     uint8_t* cwbits = bits + 2592;                                            // [4][648] codeword bits
     float2* dstate = reinterpret_cast<float2*>(cwbits + 2592);                // [n_sym][64] differential symbols
-    float* red = reinterpret_cast<float*>(dstate + 64 * 64);                  // [8] reduction scratch
+    float* red = reinterpret_cast<float*>(dstate + kTxMaxSymbols * kTxMaxCarriers);   // [8] reduction scratch
+    static_assert(kTxMaxCarriers == 64, "dstate rows and the lane-per-carrier loops are 64 wide");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, frame = blockIdx.x;
     const int k = T->k, m = T->m, bpc = T->bytes_per_cw, mod = T->mod;
     const uint8_t* fi = info + static_cast<size_t>(frame) * (kMode == 2 ? kTxCodedBytes : 4 * bpc);
@@ -317,8 +295,6 @@ __global__ __launch_bounds__(256) void tx_frames_kernel(const TxConst* __restric
         }
     }
 }
-
-inline int tx_lds_bytes() { return 4 * kFftBufFloats2 * 8 + 2592 * 2 + 64 * 64 * 8 + 64; }
 
 inline void launch_make_frames(const TxConst* T, const uint16_t* crc_bit, const uint16_t* crc_init, uint64_t seed,
                                int first_seq, int n_frames, const ria_gpu_geometry&, uint8_t* out, hipStream_t s) {
