@@ -523,8 +523,9 @@ int ria_gpu_burst_interleave_batch(ria_gpu_handle h, const uint8_t* logical_byte
  *
  * Not covered (the caller's side or other paths): decodeFrame's control-frame hypotheses on the soft bits (the R1/4 fast
  * path, the raw CW0 probe, the 1-CW salvage and the legacy path, :2866-3058) are ria_gpu_decode_frame_batch's, which takes
- * the soft bits this call can return; the control-first re-demodulation with the DQPSK R1/4 profile (:1268-1344), the
- * 1-CW peek buffer and the pending_total_cw_ escalation (:1505-1597), the weak-accept and reject-streak state (fold them into min_confidence), the PING
+ * the soft bits this call can return; the control-first re-demodulation with the DQPSK R1/4 profile (:1268-1344) is
+ * ria_gpu_control_acquire_batch's, run ahead of this call on a control handle; the short-span data-profile demodulation that
+ * moves last_cfo_ (:1346-1434), the 1-CW peek buffer and the pending_total_cw_ escalation (:1505-1597), the weak-accept and reject-streak state (fold them into min_confidence), the PING
  * energy check, burst groups and burst continuation (ria_gpu_rx_burst_batch), chase combining, Schmidl-Cox
  * acquisition, OFDM-COX, ring-buffer wrap-around, and the +-2 Hz clamp of the reported CFO the host applies before it
  * feeds it back (:1912-1918).  MC-DPSK frames (ZC and dual-chirp acquisition, the disconnected handshake fallbacks) are
@@ -955,7 +956,8 @@ int ria_gpu_mcdpsk_interleave_batch(ria_gpu_handle h, int interleaver_bits, cons
  * or payloads go to the host.  A decode work-queue fault in the fixed stage fails the whole call with RIA_ERR_HIP.  A handle
  * whose rate is not R1/4 builds its R1/4 code at the first call; all workspace lives on the handle, is grown on demand
  * (about 11 KB per row plus the size of the soft-bit rows behind the first codeword) and is allocated before anything of
- * the call is in flight.  Not covered: see ria_gpu_rx_acquire_batch. */
+ * the call is in flight.  Not covered: see ria_gpu_rx_acquire_batch; the control hypothesis on SAMPLES (a span demodulated
+ * with the DQPSK R1/4 profile, :1268-1344) is ria_gpu_rx_control_batch's, the escalation (:1505-1597) stays the caller's. */
 typedef struct ria_dframe_result {      /* 32 bytes, one per row */
     uint8_t  success;          /* DecodeResult: success, codewords_ok, codewords_failed, frame_type */
     uint8_t  codewords_ok;
@@ -988,6 +990,98 @@ int ria_gpu_decode_frame_batch(ria_gpu_handle h, const float* llr_dev, int llr_s
  * result_out->frame_bytes hold frame_data and the rest is zeroed. */
 int ria_gpu_decode_frame_host(ria_gpu_handle h, const float* llr_host, int n_llr, uint32_t flags, uint8_t* frame_out_host, int max_bytes,
                               ria_dframe_result* result_out, ria_decode_status* decode_status_out /* nullable */);
+
+/* ---- frames of any length: 1..324 coded bytes on the air, spans of 3 symbols up to a frame at the receiver ------------
+ * A connected-mode link carries, beside the fixed 4-codeword data frames, control frames of ONE codeword (81 coded bytes:
+ * 2 training + ceil(648 / bits_per_symbol) data symbols; 9 symbols = 10 368 samples with the DQPSK R1/4 control profile,
+ * streaming_encoder.cpp:216-245), and the receiver runs process() on spans shorter than a frame (streaming_decoder.cpp:1284).
+ *
+ * ria_gpu_var_frame_samples: getMinSamplesForCWCount's formula for any byte count (ofdm_chirp_waveform.cpp:616-648):
+ * (2 + ceil(8 * coded_bytes / bits_per_symbol)) * 1152, the samples ria_gpu_tx_coded_var_batch writes per frame; a negative
+ * ria_status for coded_bytes outside 1..324.
+ * ria_gpu_control_frame_samples: getOFDMControlFrameSamples (streaming_decoder.cpp:42-69) for a data handle and its control
+ * handle (RIA_MOD_DQPSK / RIA_RATE_1_4): the data handle's own 1-codeword size when it is DQPSK R1/4 itself, else the larger
+ * of that size and (2 + ceil(648 / (2 * (carriers - ceil(carriers / 10))))) * 1152.  Negative ria_status on a bad handle. */
+int ria_gpu_var_frame_samples(ria_gpu_handle h, int coded_bytes);
+int ria_gpu_control_frame_samples(ria_gpu_handle control_h, ria_gpu_handle data_h);
+
+/* generateDataPreamble() ++ modulate(coded) (modulator.cpp:534-583, :348-477) for coded_bytes bytes per frame, 1..324, at the
+ * handle's modulation: coded_dev holds n_frames rows of coded_bytes bytes, read MSB first; a carrier whose bits run out is
+ * filled with zero bits, the carriers behind the last bit are silent, differential references carry on per carrier; frame f
+ * is ria_gpu_var_frame_samples(h, coded_bytes) samples at samples_out_dev + f * out_stride (out_stride at least that; the
+ * floats between two frames are not written).  peak_normalize: ria_gpu_tx_batch's rule.  At coded_bytes 324 the samples are
+ * ria_gpu_tx_coded_batch's bit for bit. */
+int ria_gpu_tx_coded_var_batch(ria_gpu_handle h, const uint8_t* coded_dev, int coded_bytes, int n_frames, float peak_normalize,
+                               float* samples_out_dev, int64_t out_stride, void* stream);
+
+/* process() + getSoftBits() on spans of n_samples samples (one value per call), 3 * 1152 <= n_samples <= frame_samples, else
+ * RIA_ERR_INVALID (below two whole symbols the reference reads past its buffer).  Frame f starts at samples_dev +
+ * (frame_offsets_dev ? frame_offsets_dev[f] : f * n_samples); meta_dev as ria_gpu_demod_batch (NULL: CFO 0 and correction phase
+ * +0.0; a meta of zeros gives the reference's own product, -0.0).  The demodulator works on whole
+ * symbols (demodulator.cpp:1362): data symbols = n_samples / 1152 - 2, the samples behind the last whole symbol are not
+ * read.  Row f of llr_out_dev (llr_stride floats apart, llr_stride >= data symbols * bits_per_symbol) takes the soft bits in
+ * order; the rest of the row is not written.  Every status word is the reference's after the last symbol present:
+ * corr_phase is freq_correction_phase after the last sample of the last whole symbol, where the phase walk ends; n_llr is
+ * the count produced if that is at least 648, else 0 (process() returns false, demodulator.cpp:1413) - the row holds what
+ * was produced all the same.  At n_samples == frame_samples soft bits and status are ria_gpu_demod_batch's bit for bit.
+ * Every modulation of the demodulator.  Under RIA_DEMOD_FUSED=1 (the one-wave-per-frame A/B kernel, whose symbol count is a
+ * constant of the handle) the call returns RIA_ERR_UNSUPPORTED. */
+int ria_gpu_demod_var_batch(ria_gpu_handle h, const float* samples_dev, const uint64_t* frame_offsets_dev,
+                            const ria_frame_meta* meta_dev, int n_frames, int n_samples,
+                            float* llr_out_dev, int llr_stride, ria_frame_status* status_dev, void* stream);
+/* One span from host memory, staged like ria_gpu_rx_frames_host: llr_out_host takes up to max_llr soft bits (the count
+ * produced is (n_samples / 1152 - 2) * bits_per_symbol; status_out->n_llr follows the rule above).  meta_host and status_out
+ * may be NULL. */
+int ria_gpu_demod_var_host(ria_gpu_handle h, const float* samples_host, int n_samples, const ria_frame_meta* meta_host,
+                           float* llr_out_host, int max_llr, ria_frame_status* status_out);
+
+/* ---- the control hypothesis: a connected-mode window tried as a DQPSK R1/4 control frame first --------------------------
+ * (src/gui/modem/streaming_decoder.cpp:1268-1344).  control_h is an ordinary handle created at RIA_MOD_DQPSK / RIA_RATE_1_4
+ * with the data handle's carrier configuration; any other handle is RIA_ERR_INVALID.  configure() keeps the waveform's
+ * position, CFO and one-shot marker and only rebuilds the demodulator (ofdm_chirp_waveform.cpp:81-107, :421-440), so a span
+ * demodulated on the control handle with the window's meta is what the reconfigured waveform computes.
+ *
+ * ria_gpu_rx_control_batch runs :1284-1338 on pre-synced spans (arguments as ria_gpu_demod_var_batch), in this order:
+ * process() on the span; with at least 648 soft bits, robustDecodeSingleCW of the first 648 at R1/4; then ok, at least 4
+ * bytes, magic 55 4C, truncation to 20 bytes, parseHeader valid, total_cw == 1, isControlFrame(type).  frame_out_dev takes
+ * 20 bytes per row: the frame on success, zeros otherwise.  Every row of every output is written, zero where nothing
+ * applies; no soft bits or payloads go to the host; the call makes no synchronisation.  Escalation (pending_total_cw_,
+ * :1505-1597) and the short-span data-profile CFO feedback (:1346-1434) stay the caller's. */
+typedef struct ria_control_result {      /* 32 bytes, one per row / window */
+    uint8_t  process_ok;       /* process() returned true: the span gave at least 648 soft bits */
+    uint8_t  cw_ok;            /* robustDecodeSingleCW converged */
+    uint8_t  magic;            /* cw_ok, at least 4 bytes, 55 4C */
+    uint8_t  header_valid;     /* parseHeader(...).valid on the 20 bytes */
+    uint8_t  total_cw;         /* of a valid header (1 for a control type, byte 12 for a data type), else 0 */
+    uint8_t  frame_type;       /* byte 2 where magic holds, else 0 */
+    uint8_t  success;          /* header_valid && total_cw == 1 && isControlFrame(frame_type) */
+    uint8_t  tries;            /* decodes the robust decoder made, 1..5; 0 where it did not run */
+    uint16_t seq;              /* of a valid header, else 0 */
+    uint16_t iterations;       /* lastIterations() of the last decode */
+    int32_t  n_llr;            /* ria_frame_status.n_llr of the span */
+    uint8_t  tried;            /* 1: the hypothesis ran for this row (always in ria_gpu_rx_control_batch) */
+    uint8_t  reserved0[3];
+    int32_t  reserved[3];
+} ria_control_result;
+int ria_gpu_rx_control_batch(ria_gpu_handle control_h, const float* samples_dev, const uint64_t* frame_offsets_dev,
+                             const ria_frame_meta* meta_dev, int n_frames, int n_samples,
+                             uint8_t* frame_out_dev /* n_frames * 20 */, ria_control_result* result_dev,
+                             ria_frame_status* demod_status_dev /* nullable */, void* stream);
+
+/* ria_gpu_rx_acquire_batch's window geometry, ria_acq_params, LTS detection and acceptance rule, then the control
+ * hypothesis on the span of n_samples samples at sync_start (n_samples: ria_gpu_control_frame_samples of the link), with
+ * abs_position = abs_base + sync_start, the known CFO and the detector's marker in meta.flags bit 0.  There is no timing
+ * recovery: the reference has none on this path.  Not tried (tried 0, every other field of the row zero): a window that is
+ * not accepted - not detected, below min_confidence, or sync_start + n_samples > window_len, where the reference would wait
+ * for samples - and, under the flag RIA_BURST_INTERLEAVE (the only flag; anything else RIA_ERR_INVALID), an accepted window
+ * whose detector reports the marker (:1087-1092: such a window is accumulated as a burst group, full buffer, no peek).
+ * acq_dev is a ria_acq_result with delta 0, candidates = tried, frame_start = sync_start where accepted and cfo_hz = the
+ * span's ria_frame_status.cfo_hz where tried.  The call synchronises its stream once, for the length of the list of windows
+ * to try.  Workspaces live on the handle, are carved once per size and reserved before anything of the call is in flight. */
+int ria_gpu_control_acquire_batch(ria_gpu_handle control_h, const float* samples_dev, int64_t stride, int search_len,
+                                  int window_len, int n_windows, int n_samples, const ria_acq_params* params_dev, uint32_t flags,
+                                  uint8_t* frame_out_dev /* n_windows * 20 */, ria_control_result* result_dev,
+                                  ria_acq_result* acq_dev, ria_frame_status* demod_status_dev /* nullable */, void* stream);
 
 /* ---- debug / test hooks ----------------------------------------------------------------------- */
 /* op: 0 sinf 1 cosf 2 logf 3 atan2f(a,b) 4 hypotf(a,b) 5 a/b 6 sqrtf(a); evaluates the device

@@ -193,6 +193,96 @@ def run_burst_point(engine, point, base_seed, point_index, start, n, n_frames, i
     return burst_tally(out, sent)
 
 
+# ---- control frames and the control hypothesis (ria_gpu_control_acquire_batch)
+ACK, NACK = 0x20, 0x21                          # v2::FrameType
+CONTROL_COUNTERS = ("windows", "detected", "accepted", "tried", "process_ok", "cw_ok", "magic", "header_valid", "success",
+                    "delivered", "decodes")
+
+
+def _crc16(b):
+    """ControlFrame::calculateCRC (frame_v2.cpp:115-128): CRC-16/CCITT-FALSE"""
+    crc = 0xFFFF
+    for v in bytes(b):
+        crc ^= v << 8
+        for _ in range(8):
+            crc = ((crc << 1) ^ 0x1021) & 0xFFFF if crc & 0x8000 else (crc << 1) & 0xFFFF
+    return crc
+
+
+def control_frames(seqs, types=None):
+    """Serialized 20-byte control frames (ControlFrame::serialize, frame_v2.cpp): magic 55 4C, type, flags 0, seq, the
+    hashes of "TEST" / "RX" as make_frames uses them, 6 zero payload bytes, CRC-16 over 18.  types None: ACK for an even seq,
+    NACK for an odd one.  uint8 [n, 20]."""
+    seqs = np.asarray(seqs, np.int64)
+    out = np.zeros((len(seqs), 20), np.uint8)
+
+    def djb2(s):
+        h = 5381
+        for c in s.upper().encode():
+            h = (((h << 5) + h) ^ c) & 0xFFFFFFFF
+        return h & 0xFFFFFF
+    hs, hd = djb2("TEST"), djb2("RX")
+    for i, q in enumerate(seqs):
+        t = (ACK if q % 2 == 0 else NACK) if types is None else int(np.asarray(types).reshape(-1)[i])
+        out[i, :12] = [0x55, 0x4C, t, 0, (q >> 8) & 255, q & 255, hs >> 16, (hs >> 8) & 255, hs & 255, hd >> 16, (hd >> 8) & 255, hd & 255]
+        c = _crc16(out[i, :18])
+        out[i, 18], out[i, 19] = c >> 8, c & 255
+    return out
+
+
+def make_control_windows(control_engine, base_seed, point, point_index, start, n, n_samples, search_len=SEARCH_LEN, window_len=None):
+    """ACK / NACK windows of trials [start, start + n) of one sweep point on the control engine's device, as encodeFrame's
+    control branch sends them (streaming_encoder.cpp:216-245): the 20-byte frame (seq = trial) -> one R1/4 codeword
+    (ldpc_encode) -> tx_coded_var at DQPSK (peak 0.8) -> placed like make_windows at the recipe offset in a zero window of
+    window_len samples (default search_len + n_samples, so that every detected span fits) -> the reference-identical channel
+    over the whole window.  Returns (windows float32 [n, window_len], sent frames uint8 [n, 20] on the device, offsets)."""
+    e = control_engine
+    window_len = int(search_len) + int(n_samples) if window_len is None else int(window_len)
+    offs, seeds = window_recipe(base_seed, point_index, np.arange(start, start + n), search_len)
+    frames = control_frames(np.arange(start, start + n) & 0xFFFF)
+    info = np.zeros((n, (e.geo.ldpc_k + 7) // 8), np.uint8)
+    info[:, :20] = frames
+    coded = torch.from_numpy(e.ldpc_encode(info)).to(e.device)
+    x = e.tx_coded_var(coded, peak=0.8)
+    win = torch.zeros((n, window_len), dtype=torch.float32, device=e.device)
+    offs_t = torch.from_numpy(offs).to(e.device)
+    win.scatter_(1, offs_t[:, None] + torch.arange(x.shape[1], device=e.device)[None, :], x)   # placement only
+    e.channel_exact_seeded_(win, point.channel, point.snr_db, seeds)
+    return win, torch.from_numpy(frames).to(e.device), offs
+
+
+def control_tally(frames, res, acq, sent):
+    """Counter row (CONTROL_COUNTERS) of one chunk from control_acquire's outputs and the sent frames: windows, detected,
+    accepted, tried, the five tests of the hypothesis in the reference's order, frames delivered (success and the 20 bytes
+    equal to what was sent), robust decodes made."""
+    same = (frames == sent).all(dim=1).cpu().numpy()
+    row = [len(res), int((acq["detected"] != 0).sum()), int((acq["accepted"] != 0).sum())]
+    row += [int((res[k] != 0).sum()) for k in ("tried", "process_ok", "cw_ok", "magic", "header_valid", "success")]
+    row += [int(((res["success"] != 0) & same).sum()), int(res["tries"].astype(np.int64).sum())]
+    return np.array(row, dtype=np.int64)
+
+
+def rx_acquire_control_first(control_engine, data_engine, windows, search_len, n_samples=None, known_cfo=None,
+                             detect_threshold=DETECT_THRESHOLD, min_confidence=None, abs_base=None, interleave=False, **kw):
+    """What the connected receiver does with a window (streaming_decoder.cpp:1268-1344, then the data path): the control
+    hypothesis on every window (control_acquire on the DQPSK R1/4 engine, with the DATA profile's min_confidence), then
+    data_engine.rx_acquire with the same ria_acq_params except that min_confidence is +inf for the windows the hypothesis
+    took - set by one torch op on the device - so that those windows are not accepted and cost the data call nothing.
+    Returns (control frames [n, 20], control result, control acq, info, decode status, data acq)."""
+    n = windows.shape[0]
+    if n_samples is None:
+        n_samples = control_engine.control_frame_samples(data_engine)
+    if min_confidence is None:
+        min_confidence = lts_min_confidence(data_engine.modulation)
+    params = data_engine.acq_params(n, known_cfo, detect_threshold, min_confidence, abs_base)
+    frames, res, acq, _, res_dev = control_engine.control_acquire(windows, search_len, n_samples, params=params, interleave=interleave,
+                                                                  want_device_result=True)
+    taken = res_dev[:, 6] != 0                                         # ria_control_result.success
+    p2 = params.clone()
+    p2.view(torch.float32)[:, 2] = torch.where(taken, torch.full_like(taken, float("inf"), dtype=torch.float32), params.view(torch.float32)[:, 2])
+    info, st, dacq = data_engine.rx_acquire(windows, search_len, params=p2, **kw)
+    return frames, res, acq, info, st, dacq
+
 # ---- MC-DPSK (ria_gpu_mcdpsk_acquire_batch)
 def _zc_relax(streak):
     return min(np.float32(0.15), np.float32(0.025) * np.float32(streak - 3)) if streak >= 4 else np.float32(0.0)

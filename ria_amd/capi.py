@@ -45,6 +45,8 @@ EXPORTS = [
     "ria_gpu_chase_default_config", "ria_gpu_chase_create", "ria_gpu_chase_destroy", "ria_gpu_chase_clear", "ria_gpu_chase_stats", "ria_gpu_chase_export",
     "ria_gpu_mcdpsk_decode_frame_batch", "ria_gpu_mcdpsk_acquire_harq_batch",
     "ria_gpu_mcdpsk_decode_frame_ci_batch", "ria_gpu_mcdpsk_acquire_ci_batch", "ria_gpu_mcdpsk_interleave_batch",
+    "ria_gpu_var_frame_samples", "ria_gpu_control_frame_samples", "ria_gpu_tx_coded_var_batch", "ria_gpu_demod_var_batch", "ria_gpu_demod_var_host",
+    "ria_gpu_rx_control_batch", "ria_gpu_control_acquire_batch",
     "ria_link_recommend", "ria_link_data_mode", "ria_link_ofdm_code_rate", "ria_link_cap_initial_rate",
 ]
 
@@ -122,6 +124,12 @@ class DframeResult(C.Structure):
                 ("path", C.c_uint8), ("header_total_cw", C.c_uint8), ("stages", C.c_uint8), ("reserved0", C.c_uint8),
                 ("frame_bytes", C.c_int32), ("iters_r14", C.c_uint16), ("iters_cw0", C.c_uint16), ("tries_r14", C.c_uint8),
                 ("tries_rate", C.c_uint8), ("reserved1", C.c_uint8 * 2), ("reserved", C.c_int32 * 3)]
+
+
+class ControlResult(C.Structure):
+    _fields_ = [(n, C.c_uint8) for n in ("process_ok", "cw_ok", "magic", "header_valid", "total_cw", "frame_type", "success", "tries")] + \
+               [("seq", C.c_uint16), ("iterations", C.c_uint16), ("n_llr", C.c_int32), ("tried", C.c_uint8), ("reserved0", C.c_uint8 * 3),
+                ("reserved", C.c_int32 * 3)]
 
 
 class ChaseConfig(C.Structure):
@@ -242,6 +250,13 @@ def load(build_if_needed=True):
     L.ria_gpu_mcdpsk_decode_frame_ci_batch.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, vp, u32, i32, vp]
     L.ria_gpu_mcdpsk_acquire_ci_batch.argtypes = [vp, vp, vp, C.c_int64, i32, i32, i32, i32, vp, u32, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp]
     L.ria_gpu_mcdpsk_interleave_batch.argtypes = [vp, i32, vp, i32, vp, vp]
+    L.ria_gpu_var_frame_samples.argtypes = [vp, i32]
+    L.ria_gpu_control_frame_samples.argtypes = [vp, vp]
+    L.ria_gpu_tx_coded_var_batch.argtypes = [vp, vp, i32, i32, f32, vp, C.c_int64, vp]
+    L.ria_gpu_demod_var_batch.argtypes = [vp, vp, vp, vp, i32, i32, vp, i32, vp, vp]
+    L.ria_gpu_demod_var_host.argtypes = [vp, vp, i32, vp, vp, i32, vp]
+    L.ria_gpu_rx_control_batch.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
+    L.ria_gpu_control_acquire_batch.argtypes = [vp, vp, C.c_int64, i32, i32, i32, i32, vp, u32, vp, vp, vp, vp, vp]
     L.ria_link_recommend.argtypes = [f32, f32, C.POINTER(LinkRecommendation)]
     L.ria_link_recommend.restype = None
     L.ria_link_data_mode.argtypes = [f32, i32, f32, C.POINTER(LinkRecommendation)]

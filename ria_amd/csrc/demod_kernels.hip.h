@@ -1254,13 +1254,16 @@ __global__ __launch_bounds__(64) void demod_walk_kernel(DemodSplitArgs S, int in
 constexpr int kEstLds = (8 * kSumRow + 8 * kPilotRow) * 4 + 16;
 // MOD: the modulation as a compile-time constant - every instantiation carries one demapper and one decision-directed
 // path instead of all of them (a run-time switch over the nine modulations needs 165 VGPRs, the QAM16 body 1/2 of that)
-template <int MOD>
+// kVar: the span of the call holds S.n_sym - 2 data symbols instead of the fixed frame's (ria_gpu_demod_var_batch); its own
+// instantiation, so that the fixed-frame kernels keep their symbol count in the constant block and their code as it was
+template <int MOD, bool kVar = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RIA_EST_WAVES))) void demod_est_kernel(DemodSplitArgs S) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const DemodArgs& A = S.a;
     const DemodConst& K = *A.k;
     const int lane = threadIdx.x;
     const int q = blockIdx.x, frame = S.first + q;
+    const int n_dsym = kVar ? S.n_sym - 2 : K.n_data_symbols;
     float* T = reinterpret_cast<float*>(smem);
     float* TP = T + 8 * kSumRow;
     for (int i = lane; i < 8 * kSumRow; i += 64) T[i] = 0.0f;       // ordered-sum scratch: +0.0 everywhere (see ordered_sums)
@@ -1284,7 +1287,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RIA_EST_WAVE
         y0 = make_float2(lsign * y0.x, lsign * y0.y);    // burst marker: first LTS was negated on air
         if (is_car) { H0 = cdivc(y0, txv); H1 = cdivc(y1, txv); }
     }
-    float2 y_next = (K.n_data_symbols > 0) ? Yf[2 * 64 + lane] : make_float2(0, 0);
+    float2 y_next = (n_dsym > 0) ? Yf[2 * 64 + lane] : make_float2(0, 0);
     {
         // H := last LTS symbol
         H = is_car ? H1 : make_float2(1.0f, 0.0f);
@@ -1351,9 +1354,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RIA_EST_WAVE
         const float2 rot_des = make_float2(cosf_glibc(ph_des), sinf_glibc(ph_des));
         const float2 rot_res = make_float2(cosf_glibc(ph_res), sinf_glibc(ph_res));
 
-        for (int ds = 0; ds < K.n_data_symbols; ++ds) {
+        for (int ds = 0; ds < n_dsym; ++ds) {
             const float2 y = y_next;
-            if (ds + 1 < K.n_data_symbols) y_next = Yf[(3 + ds) * 64 + lane];   // the next symbol's bins are on their way while this one is worked on
+            if (ds + 1 < n_dsym) y_next = Yf[(3 + ds) * 64 + lane];   // the next symbol's bins are on their way while this one is worked on
             const bool first = (ds == 0);
             // ---------- updateChannelEstimate (channel_equalizer.cpp:645-1043)
             if (K.n_pilot > 0) {
@@ -1560,7 +1563,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RIA_EST_WAVE
             st.lts_phase_slope = slope;
             st.snr_linear = snr_lin;
             st.corr_phase = S.ws.th_end[q];
-            st.n_llr = K.n_llr;
+            if constexpr (kVar) { const int made = n_dsym * K.bits_per_symbol; st.n_llr = made >= 648 ? made : 0; }   // demodulator.cpp:1413
+            else st.n_llr = K.n_llr;
             A.status[frame] = st;
         }
     }
@@ -1584,8 +1588,12 @@ inline size_t demod_ws_bytes(int n_sym) {
     const size_t c = static_cast<size_t>(demod_chunk_frames(n_sym));
     return c * n_sym * 64 * sizeof(float2) + c * 4 * sizeof(float) + c * n_sym * 16 * sizeof(float) + 512;
 }
-inline void launch_demod(const DemodArgs& A, const ria_gpu_geometry& g, int mod, void* ws, hipStream_t s) {
-    const int n_sym = 2 + g.n_data_symbols, chunk = demod_chunk_frames(n_sym);
+// n_sym_var (0 = the fixed frame): spans of n_sym_var whole symbols, 3 .. 2 + g.n_data_symbols, through the same pipeline.  The
+// workspace is the fixed frame's (the chunk is sized for it, the arrays are laid out for the shorter span), A.offsets must
+// be given, and the estimator is the kVar instantiation.
+template <bool kVar = false>
+inline void launch_demod(const DemodArgs& A, const ria_gpu_geometry& g, int mod, void* ws, hipStream_t s, int n_sym_var = 0) {
+    const int chunk = demod_chunk_frames(2 + g.n_data_symbols), n_sym = kVar ? n_sym_var : 2 + g.n_data_symbols;
     DemodSplitArgs S{};
     S.a = A; S.n_sym = n_sym;
     unsigned char* p = static_cast<unsigned char*>(ws);
@@ -1614,15 +1622,15 @@ inline void launch_demod(const DemodArgs& A, const ria_gpu_geometry& g, int mod,
         fft(2, n_sym - 2, 1, nullptr, nullptr, S.n);                                     // data symbols, final CFO
         fft(0, 2, 1, S.ws.rerun + 1, S.ws.rerun, S.n);                                   // training symbols again where the CFO changed
         switch (mod) {
-            case RIA_MOD_DBPSK: hipLaunchKernelGGL(demod_est_kernel<RIA_MOD_DBPSK>, dim3(S.n), dim3(64), kEstLds, s, S); break;
-            case RIA_MOD_BPSK: hipLaunchKernelGGL(demod_est_kernel<RIA_MOD_BPSK>, dim3(S.n), dim3(64), kEstLds, s, S); break;
-            case RIA_MOD_DQPSK: hipLaunchKernelGGL(demod_est_kernel<RIA_MOD_DQPSK>, dim3(S.n), dim3(64), kEstLds, s, S); break;
-            case RIA_MOD_QPSK: hipLaunchKernelGGL(demod_est_kernel<RIA_MOD_QPSK>, dim3(S.n), dim3(64), kEstLds, s, S); break;
-            case RIA_MOD_D8PSK: hipLaunchKernelGGL(demod_est_kernel<RIA_MOD_D8PSK>, dim3(S.n), dim3(64), kEstLds, s, S); break;
-            case RIA_MOD_QAM32: hipLaunchKernelGGL(demod_est_kernel<RIA_MOD_QAM32>, dim3(S.n), dim3(64), kEstLds, s, S); break;
-            case RIA_MOD_QAM64: hipLaunchKernelGGL(demod_est_kernel<RIA_MOD_QAM64>, dim3(S.n), dim3(64), kEstLds, s, S); break;
-            case RIA_MOD_QAM256: hipLaunchKernelGGL(demod_est_kernel<RIA_MOD_QAM256>, dim3(S.n), dim3(64), kEstLds, s, S); break;
-            default: hipLaunchKernelGGL(demod_est_kernel<RIA_MOD_QAM16>, dim3(S.n), dim3(64), kEstLds, s, S); break;
+            case RIA_MOD_DBPSK: hipLaunchKernelGGL((demod_est_kernel<RIA_MOD_DBPSK, kVar>), dim3(S.n), dim3(64), kEstLds, s, S); break;
+            case RIA_MOD_BPSK: hipLaunchKernelGGL((demod_est_kernel<RIA_MOD_BPSK, kVar>), dim3(S.n), dim3(64), kEstLds, s, S); break;
+            case RIA_MOD_DQPSK: hipLaunchKernelGGL((demod_est_kernel<RIA_MOD_DQPSK, kVar>), dim3(S.n), dim3(64), kEstLds, s, S); break;
+            case RIA_MOD_QPSK: hipLaunchKernelGGL((demod_est_kernel<RIA_MOD_QPSK, kVar>), dim3(S.n), dim3(64), kEstLds, s, S); break;
+            case RIA_MOD_D8PSK: hipLaunchKernelGGL((demod_est_kernel<RIA_MOD_D8PSK, kVar>), dim3(S.n), dim3(64), kEstLds, s, S); break;
+            case RIA_MOD_QAM32: hipLaunchKernelGGL((demod_est_kernel<RIA_MOD_QAM32, kVar>), dim3(S.n), dim3(64), kEstLds, s, S); break;
+            case RIA_MOD_QAM64: hipLaunchKernelGGL((demod_est_kernel<RIA_MOD_QAM64, kVar>), dim3(S.n), dim3(64), kEstLds, s, S); break;
+            case RIA_MOD_QAM256: hipLaunchKernelGGL((demod_est_kernel<RIA_MOD_QAM256, kVar>), dim3(S.n), dim3(64), kEstLds, s, S); break;
+            default: hipLaunchKernelGGL((demod_est_kernel<RIA_MOD_QAM16, kVar>), dim3(S.n), dim3(64), kEstLds, s, S); break;
         }
     }
 }

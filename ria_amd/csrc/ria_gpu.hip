@@ -40,6 +40,8 @@
 #include "burst_kernels.hip.h"
 #include "decode_frame_kernels.hip.h"
 #include "mcdpsk_harq_kernels.hip.h"
+#include "var_frames.hpp"
+#include "control_kernels.hip.h"
 
 using namespace ria;
 
@@ -121,6 +123,9 @@ struct ria_gpu {
     // ria_gpu_mcdpsk_decode_frame_batch, the round's arrays (macq_carve without soft bits) with their control block
     std::vector<std::unique_ptr<ria_chase_pool_s>> chase_pools;
     DevBuf d_harq_ws, d_mdf_ws; PinBuf p_mdf_ctl;
+    // variable-length demodulation and the control hypothesis (control_carve): frame offsets, the spans' soft bits and
+    // status, detector results, the work list and the control block (device + pinned mirror), for ctrl_rows rows
+    DevBuf d_ctrl_ws; int ctrl_rows = 0; PinBuf p_ctrl_ctl;
 };
 
 namespace {
@@ -1509,6 +1514,224 @@ int ria_gpu_rx_acquire_batch(ria_gpu_handle h, const float* samples_dev, int64_t
     HIP_TRY(h, hipGetLastError());
     A.info_bytes = static_cast<int>(ib); A.info_out = info_out_dev; A.dst_out = decode_status_dev; A.fst_out = demod_status_dev;
     return acq_run_rounds(h, "ria_gpu_rx_acquire_batch", samples_dev, A, W, n_windows, flags, s);
+}
+
+// ------------------------------------------------------------------------------------------------ frames of any length, control hypothesis
+int ria_gpu_var_frame_samples(ria_gpu_handle h, int coded_bytes) {
+    if (!h) return RIA_ERR_INVALID;
+    if (coded_bytes < 1 || coded_bytes > kVarMaxCodedBytes) return fail(h, RIA_ERR_INVALID, "ria_gpu_var_frame_samples: coded_bytes must be 1..324");
+    return var_frame_samples(h->geo.bits_per_symbol, coded_bytes);
+}
+
+static bool is_control_handle(ria_gpu_handle h) { return h && h->cfg.modulation == RIA_MOD_DQPSK && h->cfg.code_rate == RIA_RATE_1_4; }
+
+int ria_gpu_control_frame_samples(ria_gpu_handle control_h, ria_gpu_handle data_h) {
+    if (!control_h || !data_h) return RIA_ERR_INVALID;
+    if (!is_control_handle(control_h) || control_h->cfg.num_carriers != data_h->cfg.num_carriers)
+        return fail(control_h, RIA_ERR_INVALID, "ria_gpu_control_frame_samples: the control handle must be DQPSK R1/4 with the data handle's carriers");
+    if (is_control_handle(data_h)) return var_frame_samples(control_h->geo.bits_per_symbol, 81);
+    return control_frame_samples(data_h->geo.bits_per_symbol, false, data_h->cfg.num_carriers);
+}
+
+int ria_gpu_tx_coded_var_batch(ria_gpu_handle h, const uint8_t* coded_dev, int coded_bytes, int n_frames, float peak_normalize,
+                               float* samples_out_dev, int64_t out_stride, void* stream) {
+    if (!h || n_frames < 0 || coded_bytes < 1 || coded_bytes > kVarMaxCodedBytes)
+        return fail(h, RIA_ERR_INVALID, "ria_gpu_tx_coded_var_batch: bad argument (coded_bytes 1..324)");
+    const int n_out = var_frame_samples(h->geo.bits_per_symbol, coded_bytes);
+    if (out_stride < n_out || out_stride > 0x7fffffff) return fail(h, RIA_ERR_INVALID, "ria_gpu_tx_coded_var_batch: out_stride must hold the frame's %d samples", n_out);
+    if (n_frames == 0) return RIA_OK;
+    if (!coded_dev || !samples_out_dev) return fail(h, RIA_ERR_INVALID, "ria_gpu_tx_coded_var_batch: null pointer");
+    HIP_TRY(h, hipSetDevice(h->device));
+    launch_tx_mode<3>(h->d_tx_const.as<const TxConst>(), h->d_twiddle.as<const float2>(), h->d_nco.as<const float2>(), coded_dev,
+                      n_frames, peak_normalize, h->geo, samples_out_dev, nullptr, static_cast<hipStream_t>(stream), coded_bytes,
+                      static_cast<int>(out_stride));
+    HIP_TRY(h, hipGetLastError());
+    return RIA_OK;
+}
+
+// the workspace of the calls below for n rows (spans or windows); llr_row = soft bits of a whole frame
+struct ControlWs {
+    uint64_t* offsets;            // frame starts of a call without offsets
+    float* llr; ria_frame_status* fst;
+    ria_lts_result* lts;
+    FrameList list;
+    AcqCtl* ctl;
+};
+static ControlWs control_carve(Carver& c, size_t n, size_t llr_row) {
+    ControlWs w;
+    w.offsets = c.take<uint64_t>(n);
+    w.llr = c.take<float>(n * llr_row);
+    w.fst = c.take<ria_frame_status>(n);
+    w.lts = c.take<ria_lts_result>(n);
+    take_frame_list(c, w.list, n);
+    w.ctl = c.take<AcqCtl>(1);
+    return w;
+}
+// grows the workspace to n rows; the caller's stream is drained first when the block has to move (an earlier call on it
+// may still read the old one)
+static int control_ensure_ws(ria_gpu_handle h, int n, hipStream_t s, ControlWs* out) {
+    const size_t row = static_cast<size_t>(h->geo.llrs_per_frame);
+    if (n > h->ctrl_rows) {
+        if (h->ctrl_rows) HIP_TRY(h, hipStreamSynchronize(s));
+        h->ctrl_rows = 0;
+        HIP_TRY(h, h->d_ctrl_ws.reserve(carved_size([&](Carver& c) { return control_carve(c, static_cast<size_t>(n), row); })));
+        h->ctrl_rows = n;
+    }
+    HIP_TRY(h, h->p_ctrl_ctl.reserve(sizeof(AcqCtl)));
+    *out = carve_at(h->d_ctrl_ws.as<>(), [&](Carver& c) { return control_carve(c, static_cast<size_t>(h->ctrl_rows), row); });
+    return RIA_OK;
+}
+
+// spans of n_samples at offsets (never NULL here) through the split pipeline
+static int demod_var_launch(ria_gpu_handle h, const char* who, const float* samples_dev, const uint64_t* offsets_dev, const ria_frame_meta* meta_dev,
+                            int n_frames, int n_samples, float* llr_out_dev, int llr_stride, ria_frame_status* status_dev, hipStream_t s) {
+    if (demod_fused_selected()) return fail(h, RIA_ERR_UNSUPPORTED, "%s: RIA_DEMOD_FUSED=1 demodulates fixed frames only", who);
+    DemodArgs A{};
+    A.k = h->d_demod_const.as<const DemodConst>();
+    A.twiddle = h->d_twiddle.as<const float2>();
+    A.nco = h->d_nco.as<const float2>();
+    A.samples = samples_dev; A.offsets = offsets_dev; A.meta = meta_dev; A.n_frames = n_frames;
+    A.llr_out = llr_out_dev; A.llr_stride = llr_stride; A.status = status_dev; A.dbg = nullptr;
+    HIP_TRY(h, h->d_demod_ws[0].reserve(demod_ws_bytes(2 + h->geo.n_data_symbols)));
+    launch_demod<true>(A, h->geo, h->cfg.modulation, h->d_demod_ws[0].as<>(), s, n_samples / kSym);
+    HIP_TRY(h, hipGetLastError());
+    return RIA_OK;
+}
+static bool var_span_ok(ria_gpu_handle h, int n_samples) { return n_samples >= 3 * kSym && n_samples <= h->geo.frame_samples; }
+
+int ria_gpu_demod_var_batch(ria_gpu_handle h, const float* samples_dev, const uint64_t* frame_offsets_dev,
+                            const ria_frame_meta* meta_dev, int n_frames, int n_samples,
+                            float* llr_out_dev, int llr_stride, ria_frame_status* status_dev, void* stream) {
+    if (!h) return RIA_ERR_INVALID;
+    if (n_frames < 0 || !var_span_ok(h, n_samples))
+        return fail(h, RIA_ERR_INVALID, "ria_gpu_demod_var_batch: bad argument (3 * 1152 <= n_samples <= frame_samples)");
+    if (llr_stride < (n_samples / kSym - 2) * h->geo.bits_per_symbol)
+        return fail(h, RIA_ERR_INVALID, "ria_gpu_demod_var_batch: llr_stride must hold the span's %d soft bits", (n_samples / kSym - 2) * h->geo.bits_per_symbol);
+    if (n_frames == 0) return RIA_OK;
+    if (!samples_dev || !llr_out_dev) return fail(h, RIA_ERR_INVALID, "ria_gpu_demod_var_batch: null pointer");
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (demod_fused_selected()) return fail(h, RIA_ERR_UNSUPPORTED, "ria_gpu_demod_var_batch: RIA_DEMOD_FUSED=1 demodulates fixed frames only");
+    HIP_TRY(h, h->d_demod_ws[0].reserve(demod_ws_bytes(2 + h->geo.n_data_symbols)));   // before anything is in flight
+    if (!frame_offsets_dev) {
+        ControlWs W;
+        if (int rc = control_ensure_ws(h, n_frames, s, &W)) return rc;
+        hipLaunchKernelGGL(var_offsets_kernel, dim3((n_frames + 255) / 256), dim3(256), 0, s, W.offsets, n_frames, n_samples);
+        frame_offsets_dev = W.offsets;
+    }
+    return demod_var_launch(h, "ria_gpu_demod_var_batch", samples_dev, frame_offsets_dev, meta_dev, n_frames, n_samples, llr_out_dev, llr_stride, status_dev, s);
+}
+
+int ria_gpu_demod_var_host(ria_gpu_handle h, const float* samples_host, int n_samples, const ria_frame_meta* meta_host,
+                           float* llr_out_host, int max_llr, ria_frame_status* status_out) {
+    if (!h) return RIA_ERR_INVALID;
+    if (!samples_host || !llr_out_host || max_llr < 0 || !var_span_ok(h, n_samples))
+        return fail(h, RIA_ERR_INVALID, "ria_gpu_demod_var_host: bad argument (3 * 1152 <= n_samples <= frame_samples)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int made = (n_samples / kSym - 2) * h->geo.bits_per_symbol;
+    const size_t o_s = 0, b_s = static_cast<size_t>(n_samples) * sizeof(float);
+    const size_t o_m = up256(o_s + b_s), b_m = sizeof(ria_frame_meta);
+    const size_t o_llr = up256(o_m + b_m), b_llr = static_cast<size_t>(made) * sizeof(float);
+    const size_t o_fs = up256(o_llr + b_llr), total = up256(o_fs + sizeof(ria_frame_status));
+    if (int rc = ensure_host_stage(h, total)) return rc;
+    unsigned char *D = h->d_hstage.as<unsigned char>(), *P = h->p_hstage.as<unsigned char>();
+    hipStream_t s = h->hstream;
+    std::memcpy(P + o_s, samples_host, b_s);
+    if (meta_host) std::memcpy(P + o_m, meta_host, b_m);
+    HIP_TRY(h, hipMemcpyAsync(D, P, meta_host ? o_m + b_m : b_s, hipMemcpyHostToDevice, s));
+    int rc = ria_gpu_demod_var_batch(h, reinterpret_cast<const float*>(D + o_s), nullptr, meta_host ? reinterpret_cast<const ria_frame_meta*>(D + o_m) : nullptr,
+                                     1, n_samples, reinterpret_cast<float*>(D + o_llr), made, reinterpret_cast<ria_frame_status*>(D + o_fs), s);
+    if (rc != RIA_OK) return rc;
+    HIP_TRY(h, hipMemcpyAsync(P + o_llr, D + o_llr, total - o_llr, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    std::memcpy(llr_out_host, P + o_llr, static_cast<size_t>(std::min(made, max_llr)) * sizeof(float));
+    if (status_out) std::memcpy(status_out, P + o_fs, sizeof(ria_frame_status));
+    return RIA_OK;
+}
+
+static_assert(sizeof(ria_control_result) == 32, "ria_control_result is 32 bytes (include/ria_gpu.h)");
+static_assert(offsetof(ria_control_result, seq) == 8 && offsetof(ria_control_result, n_llr) == 12 && offsetof(ria_control_result, tried) == 16,
+              "ria_control_result layout (ria_amd/engine.py CONTROL_RESULT)");
+
+static void launch_control_decode(ria_gpu_handle h, const ControlArgs& A, hipStream_t s) {
+    dispatch_shape(h->cfg.code_rate, [&](auto sh) {
+        using S = decltype(sh);
+        static bool attr = false;
+        if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(control_decode_kernel<S>), hipFuncAttributeMaxDynamicSharedMemorySize, h->wave_lds); attr = true; }
+        hipLaunchKernelGGL(control_decode_kernel<S>, dim3(std::min(A.n_rows, 16384)), dim3(64), h->wave_lds, s, h->fast, A);
+    });
+}
+
+int ria_gpu_rx_control_batch(ria_gpu_handle h, const float* samples_dev, const uint64_t* frame_offsets_dev,
+                             const ria_frame_meta* meta_dev, int n_frames, int n_samples,
+                             uint8_t* frame_out_dev, ria_control_result* result_dev, ria_frame_status* demod_status_dev, void* stream) {
+    if (!h) return RIA_ERR_INVALID;
+    if (!is_control_handle(h)) return fail(h, RIA_ERR_INVALID, "ria_gpu_rx_control_batch: the handle must be DQPSK R1/4");
+    if (n_frames < 0 || !var_span_ok(h, n_samples))
+        return fail(h, RIA_ERR_INVALID, "ria_gpu_rx_control_batch: bad argument (3 * 1152 <= n_samples <= frame_samples)");
+    if (n_frames == 0) return RIA_OK;
+    if (!samples_dev || !frame_out_dev || !result_dev) return fail(h, RIA_ERR_INVALID, "ria_gpu_rx_control_batch: null pointer");
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (demod_fused_selected()) return fail(h, RIA_ERR_UNSUPPORTED, "ria_gpu_rx_control_batch: RIA_DEMOD_FUSED=1 demodulates fixed frames only");
+    ControlWs W;
+    if (int rc = control_ensure_ws(h, n_frames, s, &W)) return rc;
+    HIP_TRY(h, h->d_demod_ws[0].reserve(demod_ws_bytes(2 + h->geo.n_data_symbols)));   // before anything is in flight
+    if (!frame_offsets_dev) {
+        hipLaunchKernelGGL(var_offsets_kernel, dim3((n_frames + 255) / 256), dim3(256), 0, s, W.offsets, n_frames, n_samples);
+        frame_offsets_dev = W.offsets;
+    }
+    if (int rc = demod_var_launch(h, "ria_gpu_rx_control_batch", samples_dev, frame_offsets_dev, meta_dev, n_frames, n_samples, W.llr,
+                                  h->geo.llrs_per_frame, W.fst, s)) return rc;
+    ControlArgs A{};
+    A.llr = W.llr; A.llr_stride = h->geo.llrs_per_frame; A.fst = W.fst; A.window = nullptr; A.n_rows = n_frames;
+    A.crc_bit = h->d_crc_bit.as<const uint16_t>(); A.crc_init = h->d_crc_init.as<const uint16_t>();
+    A.frame_out = frame_out_dev; A.result = result_dev; A.fst_out = demod_status_dev; A.acq = nullptr;
+    launch_control_decode(h, A, s);
+    HIP_TRY(h, hipGetLastError());
+    return RIA_OK;
+}
+
+int ria_gpu_control_acquire_batch(ria_gpu_handle h, const float* samples_dev, int64_t stride, int search_len, int window_len,
+                                  int n_windows, int n_samples, const ria_acq_params* params_dev, uint32_t flags,
+                                  uint8_t* frame_out_dev, ria_control_result* result_dev, ria_acq_result* acq_dev,
+                                  ria_frame_status* demod_status_dev, void* stream) {
+    if (!h) return RIA_ERR_INVALID;
+    if (!is_control_handle(h)) return fail(h, RIA_ERR_INVALID, "ria_gpu_control_acquire_batch: the handle must be DQPSK R1/4");
+    if (n_windows < 0 || search_len < 0 || window_len < search_len || stride < window_len || (flags & ~RIA_BURST_INTERLEAVE) != 0 || !var_span_ok(h, n_samples))
+        return fail(h, RIA_ERR_INVALID, "ria_gpu_control_acquire_batch: bad argument (0 <= search_len <= window_len <= stride; 3 * 1152 <= n_samples <= frame_samples; flags: RIA_BURST_INTERLEAVE only)");
+    if (n_windows == 0) return RIA_OK;
+    if (!samples_dev || !params_dev || !frame_out_dev || !result_dev || !acq_dev)
+        return fail(h, RIA_ERR_INVALID, "ria_gpu_control_acquire_batch: null pointer");
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (demod_fused_selected()) return fail(h, RIA_ERR_UNSUPPORTED, "ria_gpu_control_acquire_batch: RIA_DEMOD_FUSED=1 demodulates fixed frames only");
+    if (int rc = lts_prepare(h)) return rc;
+    const size_t n = static_cast<size_t>(n_windows);
+    ControlWs W;
+    if (int rc = control_ensure_ws(h, n_windows, s, &W)) return rc;
+    HIP_TRY(h, h->d_demod_ws[0].reserve(demod_ws_bytes(2 + h->geo.n_data_symbols)));   // before anything is in flight
+    HIP_TRY(h, hipMemsetAsync(frame_out_dev, 0, n * kCtlFrameBytes, s));
+    HIP_TRY(h, hipMemsetAsync(result_dev, 0, n * sizeof(ria_control_result), s));
+    if (demod_status_dev) HIP_TRY(h, hipMemsetAsync(demod_status_dev, 0, n * sizeof(ria_frame_status), s));
+    launch_lts_acquire(h, samples_dev, stride, search_len, n_windows, params_dev, W.lts, s);
+    ControlArgs A{};
+    A.lts = W.lts; A.params = params_dev; A.n_windows = n_windows; A.window_len = window_len; A.n_samples = n_samples;
+    A.skip_marked = (flags & RIA_BURST_INTERLEAVE) ? 1 : 0; A.stride = stride; A.acq = acq_dev; A.ctl = W.ctl; A.list = W.list;
+    hipLaunchKernelGGL(control_plan_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A);
+    HIP_TRY(h, hipGetLastError());
+    if (int rc = read_ctl(h, h->p_ctrl_ctl, W.ctl, s)) return rc;          // the call's one synchronisation
+    const int n_list = static_cast<int>(h->p_ctrl_ctl.as<AcqCtl>()->n_list);
+    if (n_list == 0) return RIA_OK;
+    if (n_list > n_windows) return fail(h, RIA_ERR_HIP, "ria_gpu_control_acquire_batch: work list broke its bound (%d)", n_list);
+    if (int rc = demod_var_launch(h, "ria_gpu_control_acquire_batch", samples_dev, W.list.offset, W.list.meta, n_list, n_samples, W.llr,
+                                  h->geo.llrs_per_frame, W.fst, s)) return rc;
+    A.llr = W.llr; A.llr_stride = h->geo.llrs_per_frame; A.fst = W.fst; A.window = W.list.window; A.n_rows = n_list;
+    A.crc_bit = h->d_crc_bit.as<const uint16_t>(); A.crc_init = h->d_crc_init.as<const uint16_t>();
+    A.frame_out = frame_out_dev; A.result = result_dev; A.fst_out = demod_status_dev;
+    launch_control_decode(h, A, s);
+    HIP_TRY(h, hipGetLastError());
+    return RIA_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ burst groups + continuation

@@ -181,11 +181,14 @@ constexpr int kTxCodedBytes = 324;   // 4 codewords of 648 bits
 // kMode 0: serialized frame -> samples.  The other two split it at the coded bytes (324 per frame, MSB first, channel
 // interleaved: what encodeFixedFrame returns), where the burst interleaver works (streaming_encoder.cpp:302-389):
 // kMode 1 stops there and writes them to coded_out, kMode 2 starts there (`info` holds coded bytes).
+// kMode 3 is kMode 2 for a frame of any length (ria_gpu_tx_coded_var_batch): `coded_bytes` bytes per frame, 1..324, give
+// ceil(8 coded_bytes / bits_per_symbol) data symbols behind the two training symbols, and frame f is written at
+// out + f * frame_samples (the caller's row stride).  The other modes do not read `coded_bytes`.
 template <int kMode>
 __global__ __launch_bounds__(256) void tx_frames_kernel(const TxConst* __restrict__ T, const float2* __restrict__ tw,
                                                         const float2* __restrict__ nco, const uint8_t* __restrict__ info,
                                                         int n_frames, float peak, int frame_samples,
-                                                        float* __restrict__ out, uint8_t* __restrict__ coded_out) {
+                                                        float* __restrict__ out, uint8_t* __restrict__ coded_out, int coded_bytes) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float2* tiles = reinterpret_cast<float2*>(smem);
     uint8_t* bits = reinterpret_cast<uint8_t*>(tiles + 4 * kFftBufFloats2);   // [2592] interleaved coded bits
@@ -195,9 +198,10 @@ __global__ __launch_bounds__(256) void tx_frames_kernel(const TxConst* __restric
     static_assert(kTxMaxCarriers == 64, "dstate rows and the lane-per-carrier loops are 64 wide");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, frame = blockIdx.x;
     const int k = T->k, m = T->m, bpc = T->bytes_per_cw, mod = T->mod;
-    const uint8_t* fi = info + static_cast<size_t>(frame) * (kMode == 2 ? kTxCodedBytes : 4 * bpc);
-    if constexpr (kMode == 2) {
-        for (int idx = tid; idx < 2592; idx += 256) bits[idx] = (fi[idx >> 3] >> (7 - (idx & 7))) & 1;
+    const int nbits = (kMode == 3) ? 8 * coded_bytes : 2592;                 // coded bits the frame carries
+    const uint8_t* fi = info + static_cast<size_t>(frame) * (kMode == 3 ? coded_bytes : kMode == 2 ? kTxCodedBytes : 4 * bpc);
+    if constexpr (kMode >= 2) {
+        for (int idx = tid; idx < nbits; idx += 256) bits[idx] = (fi[idx >> 3] >> (7 - (idx & 7))) & 1;
     } else {
     // ---- LDPC encode: information bits, then parity[i] = XOR of the information bits in check i
     for (int idx = tid; idx < 4 * 648; idx += 256) {
@@ -226,15 +230,16 @@ __global__ __launch_bounds__(256) void tx_frames_kernel(const TxConst* __restric
         return;
     }
     // ---- differential pre-pass (sequential over symbols, parallel over carriers)
-    const int n_sym = 2 + T->n_data_symbols, bps = T->bits_per_symbol, bcar = T->bits_per_carrier;
+    const int bps = T->bits_per_symbol, bcar = T->bits_per_carrier;
+    const int n_dsym = (kMode == 3) ? (nbits + bps - 1) / bps : T->n_data_symbols, n_sym = 2 + n_dsym;
     const bool diff = (mod == RIA_MOD_DBPSK || mod == RIA_MOD_DQPSK || mod == RIA_MOD_D8PSK);
     if (diff && tid < T->n_data) {
         float2 prev = make_float2(1.0f, 0.0f);
-        for (int d = 0; d < T->n_data_symbols; ++d) {
+        for (int d = 0; d < n_dsym; ++d) {
             int b0 = d * bps + tid * bcar;
-            if (b0 < 2592) {
+            if (b0 < nbits) {
                 uint32_t v = 0;
-                for (int b = 0; b < bcar; ++b) v = (v << 1) | ((b0 + b < 2592) ? bits[b0 + b] : 0);
+                for (int b = 0; b < bcar; ++b) v = (v << 1) | ((b0 + b < nbits) ? bits[b0 + b] : 0);
                 float2 pc;
                 if (mod == RIA_MOD_DBPSK) pc = (v & 1) ? make_float2(-1, 0) : make_float2(1, 0);
                 else if (mod == RIA_MOD_D8PSK) {   // natural-binary octant + 22.5 deg offset (modulator.cpp D8PSK branch)
@@ -261,9 +266,9 @@ __global__ __launch_bounds__(256) void tx_frames_kernel(const TxConst* __restric
             else if (diff) v = dstate[(s - 2) * 64 + lane];
             else {
                 int b0 = (s - 2) * bps + lane * bcar;
-                if (b0 < 2592) {
+                if (b0 < nbits) {
                     uint32_t bv = 0;
-                    for (int b = 0; b < bcar; ++b) bv = (bv << 1) | ((b0 + b < 2592) ? bits[b0 + b] : 0);
+                    for (int b = 0; b < bcar; ++b) bv = (bv << 1) | ((b0 + b < nbits) ? bits[b0 + b] : 0);
                     v = map_bits(bv, mod);
                 } else v = make_float2(0, 0);
             }
@@ -291,7 +296,8 @@ __global__ __launch_bounds__(256) void tx_frames_kernel(const TxConst* __restric
         if (mx > 0.0f) {
             float sc = fdiv(peak, mx);
             __threadfence_block();
-            for (int i = tid; i < frame_samples; i += 256) fo[i] = fo[i] * sc;
+            const int n_out = (kMode == 3) ? n_sym * kSym : frame_samples;
+            for (int i = tid; i < n_out; i += 256) fo[i] = fo[i] * sc;
         }
     }
 }
@@ -303,7 +309,8 @@ inline void launch_make_frames(const TxConst* T, const uint16_t* crc_bit, const 
 }
 template <int kMode>
 inline void launch_tx_mode(const TxConst* T, const float2* tw, const float2* nco, const uint8_t* in, int n_frames,
-                           float peak, const ria_gpu_geometry& g, float* out, uint8_t* coded_out, hipStream_t s) {
+                           float peak, const ria_gpu_geometry& g, float* out, uint8_t* coded_out, hipStream_t s,
+                           int coded_bytes = 0, int out_stride = 0 /* kMode 3: bytes per frame, floats between two frames */) {
     static bool attr = false;
     if (!attr) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(tx_frames_kernel<kMode>),
@@ -311,7 +318,7 @@ inline void launch_tx_mode(const TxConst* T, const float2* tw, const float2* nco
         attr = true;
     }
     hipLaunchKernelGGL(tx_frames_kernel<kMode>, dim3(n_frames), dim3(256), tx_lds_bytes(), s, T, tw, nco, in, n_frames, peak,
-                       g.frame_samples, out, coded_out);
+                       kMode == 3 ? out_stride : g.frame_samples, out, coded_out, coded_bytes);
 }
 inline void launch_tx(const TxConst* T, const float2* tw, const float2* nco, const uint8_t* info, int n_frames,
                       float peak, const ria_gpu_geometry& g, float* out, hipStream_t s) {

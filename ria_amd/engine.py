@@ -356,17 +356,9 @@ class RxEngine:
                            ("correlation", "<f4"), ("cfo_hz", "<f4"), ("delta", "<i2"), ("candidates", "u1"),
                            ("burst_interleaved", "u1"), ("reserved", "<i4")])
 
-    def rx_acquire(self, windows, search_len, known_cfo=None, detect_threshold=0.15, min_confidence=None, abs_base=None,
-                   flags=capi.DECODE_FULL, retry=True, want_demod_status=False):
-        """Connected-mode OFDM data frames from capture windows (ria_gpu_rx_acquire_batch): LTS detection on the first
-        search_len samples of each row of `windows` (float32 [n, window_len] on the device), the acceptance test,
-        demodulation + decodeFixedFrame at the detected start and, where no codeword decodes, the reference's timing
-        recovery at +-8 .. +-32 samples.  known_cfo / detect_threshold / min_confidence / abs_base: scalars or one value per
-        window (min_confidence None: acquire.lts_min_confidence of the handle's modulation without fading or SNR hints).
-        Returns (info, decode_status, acq_result[, frame_status]); acq_result is a structured array (ACQ_RESULT)."""
+    def acq_params(self, n, known_cfo=None, detect_threshold=0.15, min_confidence=None, abs_base=None):
+        """ria_acq_params for n windows as a uint8 [n, 32] device tensor (scalars or one value per window)"""
         from .acquire import lts_min_confidence
-        n, window_len = windows.shape
-        assert windows.dtype == torch.float32 and windows.is_contiguous()
         if min_confidence is None:
             min_confidence = lts_min_confidence(self.modulation)
         p = np.zeros(n, self.ACQ_PARAMS)
@@ -374,7 +366,22 @@ class RxEngine:
         p["detect_threshold"] = detect_threshold
         p["min_confidence"] = min_confidence
         p["abs_base"] = 0 if abs_base is None else abs_base
-        params = torch.from_numpy(p.view(np.uint8).reshape(n, 32)).to(self.device)
+        return torch.from_numpy(p.view(np.uint8).reshape(n, 32)).to(self.device)
+
+    def rx_acquire(self, windows, search_len, known_cfo=None, detect_threshold=0.15, min_confidence=None, abs_base=None,
+                   flags=capi.DECODE_FULL, retry=True, want_demod_status=False, params=None):
+        """Connected-mode OFDM data frames from capture windows (ria_gpu_rx_acquire_batch): LTS detection on the first
+        search_len samples of each row of `windows` (float32 [n, window_len] on the device), the acceptance test,
+        demodulation + decodeFixedFrame at the detected start and, where no codeword decodes, the reference's timing
+        recovery at +-8 .. +-32 samples.  known_cfo / detect_threshold / min_confidence / abs_base: scalars or one value per
+        window (min_confidence None: acquire.lts_min_confidence of the handle's modulation without fading or SNR hints).
+        params: the ria_acq_params already on the device (acq_params), instead of the four values.
+        Returns (info, decode_status, acq_result[, frame_status]); acq_result is a structured array (ACQ_RESULT)."""
+        n, window_len = windows.shape
+        assert windows.dtype == torch.float32 and windows.is_contiguous()
+        if params is None:
+            params = self.acq_params(n, known_cfo, detect_threshold, min_confidence, abs_base)
+        assert params.dtype == torch.uint8 and params.shape == (n, 32) and params.is_contiguous()
         info = torch.empty((n, self.geo.info_bytes_per_frame), dtype=torch.uint8, device=self.device)
         st = torch.empty((n, 20), dtype=torch.uint8, device=self.device)
         acq = torch.empty((n, 32), dtype=torch.uint8, device=self.device)
@@ -384,6 +391,103 @@ class RxEngine:
                                                       _ptr(info), _ptr(st), _ptr(acq), _ptr(fst), _stream_ptr()))
         res = self._status_array(acq, self.ACQ_RESULT)
         return (info, st, res, fst) if want_demod_status else (info, st, res)
+
+    # ---- frames of any length and the control hypothesis
+    CONTROL_RESULT = np.dtype([("process_ok", "u1"), ("cw_ok", "u1"), ("magic", "u1"), ("header_valid", "u1"), ("total_cw", "u1"),
+                               ("frame_type", "u1"), ("success", "u1"), ("tries", "u1"), ("seq", "<u2"), ("iterations", "<u2"),
+                               ("n_llr", "<i4"), ("tried", "u1"), ("reserved0", "u1", 3), ("reserved", "<i4", 3)])
+
+    def var_frame_samples(self, coded_bytes):
+        """samples of a frame of coded_bytes coded bytes (1..324) at this engine's modulation"""
+        n = self.lib.ria_gpu_var_frame_samples(self.h, int(coded_bytes))
+        if n < 0:
+            self._check(n)
+        return n
+
+    def control_frame_samples(self, data_engine):
+        """getOFDMControlFrameSamples: the span the receiver tries the control hypothesis on; self is the control engine"""
+        n = self.lib.ria_gpu_control_frame_samples(self.h, data_engine.h)
+        if n < 0:
+            self._check(n)
+        return n
+
+    def tx_coded_var(self, coded, peak=0.8, out_stride=None):
+        """The modulator on any number of coded bytes: coded uint8 [n, 1..324] -> samples [n, out_stride or the frame's length]"""
+        n, nb = coded.shape
+        assert coded.dtype == torch.uint8 and coded.is_contiguous()
+        ns = self.var_frame_samples(nb)
+        stride = ns if out_stride is None else int(out_stride)
+        s = torch.zeros((n, stride), dtype=torch.float32, device=self.device)
+        self._check(self.lib.ria_gpu_tx_coded_var_batch(self.h, _ptr(coded), nb, n, float(peak), _ptr(s), stride, _stream_ptr()))
+        return s
+
+    def _spans_in(self, samples, offsets, n_samples):
+        assert samples.dtype == torch.float32 and samples.is_contiguous()
+        if offsets is None:
+            assert samples.dim() == 2 and samples.shape[1] == n_samples
+            return samples.shape[0], None
+        off = np.ascontiguousarray(offsets, np.uint64)
+        assert off.size == 0 or int(off.max()) + n_samples <= samples.numel(), "span runs past the capture"
+        return len(off), torch.from_numpy(off.view(np.int64)).to(self.device)
+
+    def demod_var(self, samples, n_samples=None, cfo_hz=None, abs_pos=None, flags=None, offsets=None):
+        """process() + getSoftBits() on spans of n_samples samples: float32 [n, n_samples] rows, or one capture + offsets
+        -> (llr [n, (n_samples // 1152 - 2) * bits_per_symbol], status)"""
+        n_samples = samples.shape[1] if n_samples is None else int(n_samples)
+        n, off = self._spans_in(samples, offsets, n_samples)
+        row = max(0, n_samples // 1152 - 2) * self.geo.bits_per_symbol
+        llr = torch.zeros((n, max(row, 1)), dtype=torch.float32, device=self.device)
+        st = torch.zeros((n, 32), dtype=torch.uint8, device=self.device)
+        meta = self._meta(n, cfo_hz, abs_pos, flags)
+        self._check(self.lib.ria_gpu_demod_var_batch(self.h, _ptr(samples), _ptr(off), _ptr(meta), n, n_samples, _ptr(llr),
+                                                     llr.shape[1], _ptr(st), _stream_ptr()))
+        return llr[:, :row], st
+
+    def demod_var_host(self, samples, cfo_hz=0.0, abs_pos=0, flags=0):
+        """One span from host memory (ria_gpu_demod_var_host, the IWaveform adaptor's path for spans shorter than a frame):
+        samples float32 numpy [n_samples] -> (llr numpy, status structured scalar)"""
+        x = np.ascontiguousarray(samples, np.float32)
+        row = max(0, len(x) // 1152 - 2) * self.geo.bits_per_symbol
+        llr = np.zeros(max(row, 1), np.float32)
+        meta = capi.FrameMeta(float(cfo_hz), int(flags), int(abs_pos))
+        st = np.zeros(1, self.FRAME_STATUS)
+        self._check(self.lib.ria_gpu_demod_var_host(self.h, x.ctypes.data, len(x), C.addressof(meta), llr.ctypes.data, row, st.ctypes.data))
+        return llr[:row], st[0]
+
+    def rx_control(self, samples, n_samples=None, cfo_hz=None, abs_pos=None, flags=None, offsets=None):
+        """The control hypothesis on pre-synced spans (ria_gpu_rx_control_batch; a DQPSK R1/4 engine):
+        -> (frame bytes uint8 [n, 20], result structured array (CONTROL_RESULT), frame status)"""
+        n_samples = samples.shape[1] if n_samples is None else int(n_samples)
+        n, off = self._spans_in(samples, offsets, n_samples)
+        frames = torch.empty((n, 20), dtype=torch.uint8, device=self.device)
+        res = torch.empty((n, 32), dtype=torch.uint8, device=self.device)
+        st = torch.empty((n, 32), dtype=torch.uint8, device=self.device)
+        meta = self._meta(n, cfo_hz, abs_pos, flags)
+        self._check(self.lib.ria_gpu_rx_control_batch(self.h, _ptr(samples), _ptr(off), _ptr(meta), n, n_samples, _ptr(frames),
+                                                      _ptr(res), _ptr(st), _stream_ptr()))
+        return frames, self._status_array(res, self.CONTROL_RESULT), st
+
+    def control_acquire(self, windows, search_len, n_samples, known_cfo=None, detect_threshold=0.15, min_confidence=None,
+                        abs_base=None, interleave=False, params=None, want_device_result=False):
+        """The control hypothesis from capture windows (ria_gpu_control_acquire_batch): rx_acquire's detection and acceptance,
+        then rx_control on the span of n_samples at the detected start.  min_confidence None: that of the DATA profile has to be
+        passed by the caller; here it defaults to this engine's (DQPSK).  interleave: RIA_BURST_INTERLEAVE (marked windows are
+        left to the burst path).  Returns (frame bytes [n, 20], result (CONTROL_RESULT), acq (ACQ_RESULT), frame status[,
+        the result rows as a uint8 [n, 32] device tensor])."""
+        n, window_len = windows.shape
+        assert windows.dtype == torch.float32 and windows.is_contiguous()
+        if params is None:
+            params = self.acq_params(n, known_cfo, detect_threshold, min_confidence, abs_base)
+        assert params.dtype == torch.uint8 and params.shape == (n, 32) and params.is_contiguous()
+        frames = torch.empty((n, 20), dtype=torch.uint8, device=self.device)
+        res = torch.empty((n, 32), dtype=torch.uint8, device=self.device)
+        acq = torch.empty((n, 32), dtype=torch.uint8, device=self.device)
+        st = torch.empty((n, 32), dtype=torch.uint8, device=self.device)
+        self._check(self.lib.ria_gpu_control_acquire_batch(self.h, _ptr(windows), window_len, int(search_len), window_len, n,
+                                                           int(n_samples), _ptr(params), capi.BURST_INTERLEAVE if interleave else 0,
+                                                           _ptr(frames), _ptr(res), _ptr(acq), _ptr(st), _stream_ptr()))
+        out = (frames, self._status_array(res, self.CONTROL_RESULT), self._status_array(acq, self.ACQ_RESULT), st)
+        return out + (res,) if want_device_result else out
 
     BURST_RESULT = np.dtype([("detected", "<i4"), ("accepted", "<i4"), ("sync_start", "<i4"), ("frame_start", "<i4"),
                              ("correlation", "<f4"), ("cfo_hz", "<f4"), ("delta", "<i2"), ("candidates", "u1"),

@@ -104,16 +104,24 @@ public:
         const ria_gpu_geometry& g = gpu_->geo();
         soft_bits_.clear();
         if (samples.size() < static_cast<size_t>(g.samples_per_symbol)) return false;
-        // The kernel consumes whole frames; shorter spans (the host's 1-CW peeks, Appendix B of
-        // SURVEY.md) are zero padded and only the symbols actually present are reported.
-        std::vector<float> buf(static_cast<size_t>(g.frame_samples), 0.0f);
-        size_t n = std::min(samples.size(), buf.size());
-        std::memcpy(buf.data(), samples.data(), n * sizeof(float));
         ria_frame_meta meta{cfo_hz_, burst_marker_ ? 1u : 0u, has_abs_ ? abs_pos_ : training_start_};
         burst_marker_ = false;  // one-shot (ofdm_chirp_waveform.cpp:423); burst_latched_ stays for wasBurstInterleaved()
         std::vector<float> llr(static_cast<size_t>(g.llrs_per_frame));
         ria_frame_status fs{};
-        int rc = ria_gpu_rx_frames_host(gpu_->get(), buf.data(), &meta, 1, RIA_RX_DEMOD_ONLY, nullptr, nullptr, llr.data(), &fs);
+        int rc;
+        if (samples.size() >= static_cast<size_t>(3 * g.samples_per_symbol) && samples.size() < static_cast<size_t>(g.frame_samples)) {
+            // A span shorter than a frame (the host's 1-CW peeks and control frames, Appendix B of SURVEY.md) is demodulated
+            // as it is: the status words - fading index, SNR, CFO - are those of the symbols present, as in the reference.
+            rc = ria_gpu_demod_var_host(gpu_->get(), samples.data(), static_cast<int>(samples.size()), &meta, llr.data(),
+                                        static_cast<int>(llr.size()), &fs);
+        } else {
+            // A whole frame (what lies behind it is not read); below three symbols the span is zero padded to a frame and
+            // only the symbols actually present are reported.
+            std::vector<float> buf(static_cast<size_t>(g.frame_samples), 0.0f);
+            size_t n = std::min(samples.size(), buf.size());
+            std::memcpy(buf.data(), samples.data(), n * sizeof(float));
+            rc = ria_gpu_rx_frames_host(gpu_->get(), buf.data(), &meta, 1, RIA_RX_DEMOD_ONLY, nullptr, nullptr, llr.data(), &fs);
+        }
         if (rc != RIA_OK) return false;
         size_t data_syms = samples.size() / g.samples_per_symbol;
         data_syms = data_syms >= 2 ? data_syms - 2 : 0;
