@@ -525,7 +525,8 @@ int ria_gpu_burst_interleave_batch(ria_gpu_handle h, const uint8_t* logical_byte
  * path, the raw CW0 probe, the 1-CW salvage and the legacy path, :2866-3058) are ria_gpu_decode_frame_batch's, which takes
  * the soft bits this call can return; the control-first re-demodulation with the DQPSK R1/4 profile (:1268-1344) is
  * ria_gpu_control_acquire_batch's, run ahead of this call on a control handle; the short-span data-profile demodulation that
- * moves last_cfo_ (:1346-1434), the 1-CW peek buffer and the pending_total_cw_ escalation (:1505-1597), the weak-accept and reject-streak state (fold them into min_confidence), the PING
+ * moves last_cfo_ (:1346-1434), the 1-CW peek buffer, the pending_total_cw_ escalation (:1505-1597) and the small-frame
+ * recovery (:1806-1853) are ria_gpu_rx_window_batch's, which runs the whole window in one call; the weak-accept and reject-streak state (fold them into min_confidence), the PING
  * energy check, burst groups and burst continuation (ria_gpu_rx_burst_batch), chase combining, Schmidl-Cox
  * acquisition, OFDM-COX, ring-buffer wrap-around, and the +-2 Hz clamp of the reported CFO the host applies before it
  * feeds it back (:1912-1918).  MC-DPSK frames (ZC and dual-chirp acquisition, the disconnected handshake fallbacks) are
@@ -957,7 +958,8 @@ int ria_gpu_mcdpsk_interleave_batch(ria_gpu_handle h, int interleaver_bits, cons
  * whose rate is not R1/4 builds its R1/4 code at the first call; all workspace lives on the handle, is grown on demand
  * (about 11 KB per row plus the size of the soft-bit rows behind the first codeword) and is allocated before anything of
  * the call is in flight.  Not covered: see ria_gpu_rx_acquire_batch; the control hypothesis on SAMPLES (a span demodulated
- * with the DQPSK R1/4 profile, :1268-1344) is ria_gpu_rx_control_batch's, the escalation (:1505-1597) stays the caller's. */
+ * with the DQPSK R1/4 profile, :1268-1344) is ria_gpu_rx_control_batch's, the escalation (:1505-1597) and the small-frame
+ * recovery (:1806-1853) are ria_gpu_rx_window_batch's. */
 typedef struct ria_dframe_result {      /* 32 bytes, one per row */
     uint8_t  success;          /* DecodeResult: success, codewords_ok, codewords_failed, frame_type */
     uint8_t  codewords_ok;
@@ -1046,7 +1048,7 @@ int ria_gpu_demod_var_host(ria_gpu_handle h, const float* samples_host, int n_sa
  * bytes, magic 55 4C, truncation to 20 bytes, parseHeader valid, total_cw == 1, isControlFrame(type).  frame_out_dev takes
  * 20 bytes per row: the frame on success, zeros otherwise.  Every row of every output is written, zero where nothing
  * applies; no soft bits or payloads go to the host; the call makes no synchronisation.  Escalation (pending_total_cw_,
- * :1505-1597) and the short-span data-profile CFO feedback (:1346-1434) stay the caller's. */
+ * :1505-1597) and the short-span data-profile CFO feedback (:1346-1434) are ria_gpu_rx_window_batch's. */
 typedef struct ria_control_result {      /* 32 bytes, one per row / window */
     uint8_t  process_ok;       /* process() returned true: the span gave at least 648 soft bits */
     uint8_t  cw_ok;            /* robustDecodeSingleCW converged */
@@ -1082,6 +1084,93 @@ int ria_gpu_control_acquire_batch(ria_gpu_handle control_h, const float* samples
                                   int window_len, int n_windows, int n_samples, const ria_acq_params* params_dev, uint32_t flags,
                                   uint8_t* frame_out_dev /* n_windows * 20 */, ria_control_result* result_dev,
                                   ria_acq_result* acq_dev, ria_frame_status* demod_status_dev /* nullable */, void* stream);
+
+/* ---- one connected-mode OFDM-CHIRP window: peek, escalation, small-frame recovery, timing recovery ---------------------------
+ * ria_gpu_rx_window_batch joins the calls above into what gui::StreamingDecoder does with one window of a connected link
+ * (src/gui/modem/streaming_decoder.cpp), statement by statement per window, and leaves the DecodeResult and the receiver state
+ * (sync_cfo_ / last_cfo_, last_fading_index_, frame_len, the position behind the consumed samples).  control_h: the DQPSK R1/4
+ * handle with data_h's carrier configuration, on its device (else RIA_ERR_INVALID).  Window geometry and ria_acq_params are
+ * ria_gpu_rx_acquire_batch's.  "The rate" is data_h's code rate.
+ *   1. Detection and acceptance, then the control hypothesis (:1268-1344): exactly ria_gpu_control_acquire_batch on control_h
+ *      with n_ctl = ria_gpu_control_frame_samples(control_h, data_h): a window is accepted iff detected, correlation >=
+ *      min_confidence and sync_start + n_ctl <= window_len (RIA_WIN_NOT_ACCEPTED otherwise); under RIA_BURST_INTERLEAVE an
+ *      accepted window with the detector's marker is left to ria_gpu_rx_burst_batch (RIA_WIN_BURST, :1087-1092); a control frame
+ *      ends the window (RIA_WIN_CONTROL_PROFILE: frame = its 20 bytes, success 1, codewords 1 / 0, frame_len = n_ctl, next_pos =
+ *      sync_start + n_ctl (:1328), fading_index = the control span's, sync_cfo_hz = known_cfo_hz: no feedback on this path).
+ *   2. Pass 1, the peek (:1346-1434): process() with the data profile on the same n_ctl samples, known CFO, abs_position =
+ *      abs_base + sync_start, marker OFF - the control hypothesis's process() has consumed the one-shot
+ *      (ofdm_chirp_waveform.cpp:421-440) - in this and every later pass.  Kept object: when data_h is DQPSK R1/4 itself the
+ *      reference runs process() twice on one demodulator without reset(); processPresynced() (demodulator.cpp:1264-1309) clears
+ *      every per-frame member and process() sets CFO and phase anew, so nothing carries over and the second pass equals a pass
+ *      on a fresh object; the same holds for every later process() of the ladder.  Fewer than 648 soft bits: the window ends
+ *      (RIA_WIN_DECODED with an all-zero frame, :1352-1360).  Then last_fading_index_, and the CFO feedback in float32:
+ *      sync_cfo = estimatedCFO, moved to known +- 2.0 when it lies further away (a NaN estimate stays); peek_cfo_hz is the
+ *      estimate before the clamp.
+ *   3. The CW0 peek (:1511-1597) on S1 = the span's soft bits.  648 <= S1 < 1296: robustDecodeSingleCW at R1/4, magic,
+ *      truncation to 20 bytes, parseHeader: total_cw 1 falls through (RIA_PEEK_R14_ONE), > 1 is pending (R14_MULTI); otherwise,
+ *      if the rate is not R1/4, the same at the rate: RATE_ONE, RATE_MULTI, magic with an invalid header pending 4
+ *      (RATE_BAD_HEADER); nothing resolved: pending 4 (FAILED).  1296 <= S1 < 2592 on QAM16/32/64/256: pending 4 (QAM_PARTIAL).
+ *      Otherwise the peek span's own soft bits are decoded (DIRECT).  A data header with total_cw 0 is an invalid header, as in
+ *      ria_gpu_decode_frame_batch.
+ *   4. Pass 2, if pending > 0: frame_len = getMinSamplesForCWCount(pending).  sync_start + frame_len > window_len: the reference
+ *      would wait for samples - RIA_WIN_NEED_SAMPLES, need_samples = that frame_len.  Else pending > 4: RIA_WIN_TOO_LONG - this
+ *      library's limit, the span demodulator takes at most a 4-codeword frame; pending_total_cw holds the header's count.  Else
+ *      process() at sync_cfo, then fading index and CFO feedback again against the updated last_cfo_.
+ *   5. decodeFrame (:1626) on that pass's soft bits: ria_gpu_decode_frame_batch's stages with the span's n_llr.
+ *   6. Small-frame recovery (:1806-1853), if !success: process() at sync_cfo on the first getMinSamplesForCWCount(1) samples;
+ *      with >= 648 soft bits trySmallFrame at R1/4 and then, if the rate is not R1/4, at the rate: robust decode, magic,
+ *      parseHeader; total_cw 1: decodeFrame of the short span's bits, frame_len = that size; total_cw 2 or 3: process() on
+ *      min(getMinSamplesForCWCount(total_cw), frame_len) samples and decodeFrame of those, frame_len = that size; the new result
+ *      replaces the old one also where it fails.  No CFO feedback and no fading index are taken here (the reference reads neither).
+ *   7. Timing recovery (:1859-1965), if !success && codewords_ok == 0 and RIA_ACQ_NO_TIMING_RETRY is clear:
+ *      ria_gpu_rx_acquire_batch's candidates and fit rule on spans of the current frame_len at the current sync_cfo, marker off,
+ *      abs_position = abs_base + sync_start + delta; a candidate with fewer than 648 soft bits is counted and skipped; each is
+ *      decoded with decodeFrame; the first with success || codewords_ok > 0 is kept, its CFO estimate clamped against the
+ *      current last_cfo_, its fading index taken.  A candidate that does not fit the window is skipped and not counted (the
+ *      reference reads older ring-buffer samples, or a shorter span, there).
+ *   8. Consumed (:1994-2013): frame_len, or for a successful control / connect frame min(frame_len,
+ *      getMinSamplesForCWCount(codewords_ok + codewords_failed)); next_pos = frame_start + consumed, where a caller continues
+ *      (ria_gpu_rx_burst_batch's continuation).
+ * Out of scope: the PING energy test (disconnected only, :1168), burst groups and continuation, ring-buffer wrap-around, the
+ * frame timeout, chase combining, OFDM-COX, and the weak-accept / reject-streak state (fold it into min_confidence).
+ *
+ * flags: the RIA_DECODE_* bits, RIA_DECODE_NO_CHANNEL_DEINTERLEAVE, RIA_BURST_INTERLEAVE, RIA_ACQ_NO_TIMING_RETRY; anything
+ * else RIA_ERR_INVALID.  frame_row >= max(4, llrs_per_frame / 648) * bytes_per_codeword.  Under RIA_DEMOD_FUSED=1 the call
+ * returns RIA_ERR_UNSUPPORTED.  n_windows == 0 is RIA_OK.  Every row of every output is written, zero where nothing applies.
+ * acq_dev: ria_gpu_control_acquire_batch's row, with cfo_hz = ria_frame_status.cfo_hz of the reported span, delta / frame_start
+ * of the reported candidate and candidates = spans demodulated at a timing candidate (1 + recovery candidates).  control_dev
+ * (nullable): the control hypothesis's rows.  demod_status_dev (nullable): the status of the span behind the reported result
+ * (the control span for RIA_WIN_CONTROL_PROFILE; zero for NEED_SAMPLES / TOO_LONG).
+ * Work: every stage runs on ascending lists of the windows still open, one span-demodulator launch per span length (a pass
+ * has at most five: n_ctl and 1..4 codewords), so results do not depend on scheduling or on the batch a window is in.  The
+ * call synchronises its stream once per list whose length the host needs: at most 1 (control) + 4 demodulation passes + 2 x 2
+ * (decodeFrame) + 8 x (1 + 2) recovery rounds + 1 = 34 small device-to-host reads; no samples, soft bits or payloads go to the
+ * host.  A decode work-queue fault in a fixed stage fails the call with RIA_ERR_HIP.  Workspaces live on the two handles, are
+ * carved once per size and reserved before anything of the call is in flight. */
+enum { RIA_WIN_NOT_ACCEPTED = 0, RIA_WIN_BURST = 1, RIA_WIN_CONTROL_PROFILE = 2, RIA_WIN_DECODED = 3, RIA_WIN_NEED_SAMPLES = 4,
+       RIA_WIN_TOO_LONG = 5 };
+enum { RIA_PEEK_NONE = 0, RIA_PEEK_R14_ONE = 1, RIA_PEEK_R14_MULTI = 2, RIA_PEEK_RATE_ONE = 3, RIA_PEEK_RATE_MULTI = 4,
+       RIA_PEEK_RATE_BAD_HEADER = 5, RIA_PEEK_FAILED = 6, RIA_PEEK_QAM_PARTIAL = 7, RIA_PEEK_DIRECT = 8 };
+typedef struct ria_window_result {   /* 64 bytes, one per window */
+    ria_dframe_result frame;         /* result: the DecodeResult delivered (all zero where nothing was decoded) */
+    uint8_t  outcome;                /* RIA_WIN_* */
+    uint8_t  peek;                   /* RIA_PEEK_*: which statement of :1505-1597 decided pass 1; NONE where the peek did not run */
+    uint8_t  pending_total_cw;       /* pending_total_cw_ after the peek; 0 = fell through on the peek span */
+    uint8_t  small_frame;            /* 0 not run, 1 ran and found nothing, 2 one-codeword branch, 3 exact-size (2..3) branch; bit 4: taken at the rate, not R1/4 */
+    uint8_t  tries_peek_r14, tries_peek_rate, tries_small_r14, tries_small_rate;   /* decodes of the robust decoder, 0..5 */
+    int32_t  frame_len;              /* frame_len as the reference leaves it, in samples */
+    int32_t  next_pos;               /* sync_position_ + consumed within the window, -1 where nothing was consumed */
+    int32_t  need_samples;           /* RIA_WIN_NEED_SAMPLES: the samples from sync_start pass 2 asks for, else 0 */
+    float    sync_cfo_hz;            /* last_cfo_ / sync_cfo_ as the reference leaves them */
+    float    peek_cfo_hz;            /* estimatedCFO() of the peek span before the clamp */
+    float    fading_index;           /* last_fading_index_ as this window leaves it, 0 where no process() of the window set it */
+} ria_window_result;
+
+int ria_gpu_rx_window_batch(ria_gpu_handle control_h, ria_gpu_handle data_h, const float* samples_dev, int64_t stride,
+                            int search_len, int window_len, int n_windows, const ria_acq_params* params_dev, uint32_t flags,
+                            uint8_t* frame_out_dev, int frame_row, ria_window_result* result_dev, ria_acq_result* acq_dev,
+                            ria_control_result* control_dev /* nullable */, ria_frame_status* demod_status_dev /* nullable: the reported span's */,
+                            void* stream);
 
 /* ---- debug / test hooks ----------------------------------------------------------------------- */
 /* op: 0 sinf 1 cosf 2 logf 3 atan2f(a,b) 4 hypotf(a,b) 5 a/b 6 sqrtf(a); evaluates the device

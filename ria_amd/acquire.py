@@ -283,6 +283,42 @@ def rx_acquire_control_first(control_engine, data_engine, windows, search_len, n
     info, st, dacq = data_engine.rx_acquire(windows, search_len, params=p2, **kw)
     return frames, res, acq, info, st, dacq
 
+
+def make_mixed_windows(control_engine, data_engine, base_seed, point, n, search_len=12000):
+    """Mixed connected-mode traffic for RxEngine.rx_window and rx_acquire_control_first, on the device: n windows (n even) of
+    search_len + a data frame's samples; even windows carry an ACK / NACK control frame (make_control_windows), odd windows a
+    fixed 4-codeword data frame of data_engine's profile (make_windows), each through the reference-identical channel of
+    `point`.  Returns (windows float32 [n, window_len], sent control frames uint8 [n / 2, 20], sent data info [n / 2, info
+    bytes], control span in samples)."""
+    h = n // 2
+    span = control_engine.control_frame_samples(data_engine)
+    wlen = int(search_len) + data_engine.geo.frame_samples
+    wd, sent_d, _ = make_windows(data_engine, base_seed, point, 0, 0, h, search_len)
+    wc, sent_c, _ = make_control_windows(control_engine, base_seed + 1, point, 0, 0, h, span, search_len, window_len=wlen)
+    w = torch.stack([wc, wd], dim=1).reshape(2 * h, wlen).contiguous()
+    return w, sent_c, sent_d, span
+
+
+WINDOW_COUNTERS = tuple(f"outcome_{k.lower()}" for k in capi.WIN_OUTCOME) + tuple(f"peek_{k.lower()}" for k in capi.WIN_PEEK) + \
+    ("small_not_run", "small_nothing", "small_one_cw", "small_exact", "small_at_rate", "success", "partial") + \
+    tuple(f"delta_{d:+d}" for d in (0, 8, -8, 16, -16, 24, -24, 32, -32))
+
+
+def window_tally(res, acq):
+    """Counter row (WINDOW_COUNTERS) of one rx_window call: windows per outcome, per peek statement and per small-frame branch
+    (and how many took theirs at the link rate), frames delivered (success), results with some codewords only, and the timing
+    candidate reported for the decoded windows."""
+    row = [int((res["outcome"] == v).sum()) for v in capi.WIN_OUTCOME.values()]
+    row += [int((res["peek"] == v).sum()) for v in capi.WIN_PEEK.values()]
+    small = res["small_frame"] & 0xF
+    row += [int((small == v).sum()) for v in range(4)] + [int(((res["small_frame"] & 0x10) != 0).sum())]
+    ok = res["frame"]["success"] != 0
+    row += [int(ok.sum()), int((~ok & (res["frame"]["codewords_ok"] != 0)).sum())]
+    decoded = res["outcome"] == capi.WIN_OUTCOME["DECODED"]
+    row += [int((decoded & (acq["delta"] == d)).sum()) for d in (0, 8, -8, 16, -16, 24, -24, 32, -32)]
+    return np.array(row, dtype=np.int64)
+
+
 # ---- MC-DPSK (ria_gpu_mcdpsk_acquire_batch)
 def _zc_relax(streak):
     return min(np.float32(0.15), np.float32(0.025) * np.float32(streak - 3)) if streak >= 4 else np.float32(0.0)

@@ -28,6 +28,10 @@ MACQ_CHANNEL_INTERLEAVE = 0x8
 DFRAME_PATH = {"NONE": 0, "CONTROL_R14": 1, "CONTROL_CW0": 2, "FIXED": 3, "SALVAGE_R14": 4, "SALVAGE_RATE": 5, "FIXED_FAILED": 6,
                "LEGACY": 7, "PARTIAL": 8, "BAD_HEADER": 9}
 DFRAME_MAX_CW = 32
+# RIA_WIN_* (ria_window_result.outcome) and RIA_PEEK_* (ria_window_result.peek)
+WIN_OUTCOME = {"NOT_ACCEPTED": 0, "BURST": 1, "CONTROL_PROFILE": 2, "DECODED": 3, "NEED_SAMPLES": 4, "TOO_LONG": 5}
+WIN_PEEK = {"NONE": 0, "R14_ONE": 1, "R14_MULTI": 2, "RATE_ONE": 3, "RATE_MULTI": 4, "RATE_BAD_HEADER": 5, "FAILED": 6, "QAM_PARTIAL": 7,
+            "DIRECT": 8}
 CHASE_MAX_CW, CHASE_MAX_ENTRIES, CHASE_MAX_COMBINES = 16, 16, 4
 HARQ_ENTRY = {"NONE": 0, "KEPT": 1, "REMOVED": 2}
 
@@ -46,7 +50,7 @@ EXPORTS = [
     "ria_gpu_mcdpsk_decode_frame_batch", "ria_gpu_mcdpsk_acquire_harq_batch",
     "ria_gpu_mcdpsk_decode_frame_ci_batch", "ria_gpu_mcdpsk_acquire_ci_batch", "ria_gpu_mcdpsk_interleave_batch",
     "ria_gpu_var_frame_samples", "ria_gpu_control_frame_samples", "ria_gpu_tx_coded_var_batch", "ria_gpu_demod_var_batch", "ria_gpu_demod_var_host",
-    "ria_gpu_rx_control_batch", "ria_gpu_control_acquire_batch",
+    "ria_gpu_rx_control_batch", "ria_gpu_control_acquire_batch", "ria_gpu_rx_window_batch",
     "ria_link_recommend", "ria_link_data_mode", "ria_link_ofdm_code_rate", "ria_link_cap_initial_rate",
 ]
 
@@ -158,6 +162,14 @@ class McHarqResult(C.Structure):
                 ("reserved0", C.c_uint8), ("cache_id", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+class WindowResult(C.Structure):
+    _fields_ = [("frame", DframeResult)] + \
+               [(n, C.c_uint8) for n in ("outcome", "peek", "pending_total_cw", "small_frame", "tries_peek_r14", "tries_peek_rate",
+                                         "tries_small_r14", "tries_small_rate")] + \
+               [("frame_len", C.c_int32), ("next_pos", C.c_int32), ("need_samples", C.c_int32), ("sync_cfo_hz", C.c_float),
+                ("peek_cfo_hz", C.c_float), ("fading_index", C.c_float)]
+
+
 def macq_frame_bytes(frame_cw):
     """RIA_MACQ_FRAME_BYTES: bytes of one frame_out row of ria_gpu_mcdpsk_acquire_batch"""
     return 40 * int(frame_cw)
@@ -257,6 +269,7 @@ def load(build_if_needed=True):
     L.ria_gpu_demod_var_host.argtypes = [vp, vp, i32, vp, vp, i32, vp]
     L.ria_gpu_rx_control_batch.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
     L.ria_gpu_control_acquire_batch.argtypes = [vp, vp, C.c_int64, i32, i32, i32, i32, vp, u32, vp, vp, vp, vp, vp]
+    L.ria_gpu_rx_window_batch.argtypes = [vp, vp, vp, C.c_int64, i32, i32, i32, vp, u32, vp, i32, vp, vp, vp, vp, vp]
     L.ria_link_recommend.argtypes = [f32, f32, C.POINTER(LinkRecommendation)]
     L.ria_link_recommend.restype = None
     L.ria_link_data_mode.argtypes = [f32, i32, f32, C.POINTER(LinkRecommendation)]

@@ -42,6 +42,7 @@
 #include "mcdpsk_harq_kernels.hip.h"
 #include "var_frames.hpp"
 #include "control_kernels.hip.h"
+#include "window_kernels.hip.h"
 
 using namespace ria;
 
@@ -126,6 +127,9 @@ struct ria_gpu {
     // variable-length demodulation and the control hypothesis (control_carve): frame offsets, the spans' soft bits and
     // status, detector results, the work list and the control block (device + pinned mirror), for ctrl_rows rows
     DevBuf d_ctrl_ws; int ctrl_rows = 0; PinBuf p_ctrl_ctl;
+    // ria_gpu_rx_window_batch (window_carve): per-window state, soft bits and status, the span lists, one pass's compact
+    // demodulations, probe records, decodeFrame's outputs and the control hypothesis's, with the control block's pinned mirror
+    DevBuf d_win_ws; PinBuf p_win_ctl;
 };
 
 namespace {
@@ -458,6 +462,7 @@ static int run_crc_recovery_host(ria_gpu_handle h, const FastDecodeArgs& D, hipS
 // which may print `arg`
 static unsigned int ctl_fault(const MacqCtl&) { return 0; }   // the robust decoder has no work queue
 static unsigned int ctl_fault(const MacqCiCtl&) { return 0; }
+static unsigned int ctl_fault(const WinCtl&) { return 0; }    // list lengths only: the stages behind them report their own faults
 template <class Ctl>
 static unsigned int ctl_fault(const Ctl& c) { return c.fault; }
 template <class Ctl>
@@ -2755,6 +2760,219 @@ int ria_gpu_decode_frame_host(ria_gpu_handle h, const float* llr_host, int n_llr
     std::memcpy(result_out, P + o_res, sizeof(ria_dframe_result));
     if (decode_status_out) std::memcpy(decode_status_out, P + o_ds, sizeof(ria_decode_status));
     return RIA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ one connected-mode window
+static_assert(sizeof(ria_window_result) == 64, "ria_window_result is 64 bytes (include/ria_gpu.h)");
+static_assert(offsetof(ria_window_result, outcome) == 32 && offsetof(ria_window_result, frame_len) == 40 &&
+              offsetof(ria_window_result, sync_cfo_hz) == 52 && offsetof(ria_window_result, fading_index) == 60, "ria_window_result field offsets");
+static_assert(sizeof(WinRow) == 32 && sizeof(WinCtl) == 32, "window_kernels.hip.h record sizes");
+
+// the window workspace for n windows: soft-bit rows of llr_row floats, decodeFrame rows of df_row bytes
+struct WinWs {
+    WinCtl* ctl; DfCtl* pctl; WinRow* row; uint32_t* plist; DfProbe* probe; int32_t* n_llr_d;
+    FrameList list[kWinGroups];
+    float* llr_c; ria_frame_status* fst_c;           // one pass's demodulations, compact
+    float* llr_w; ria_frame_status* fst_w;           // per window
+    uint8_t* df_frames; ria_dframe_result* df_res;   // decodeFrame's outputs, per window
+    ria_control_result* cres; uint8_t* cframes; ria_frame_status* cfst;   // the control hypothesis's, per window
+};
+static WinWs window_carve(Carver& c, size_t n, size_t llr_row, size_t df_row) {
+    WinWs w;
+    w.ctl = c.take<WinCtl>(1);
+    w.pctl = c.take<DfCtl>(1);
+    w.row = c.take<WinRow>(n);
+    w.plist = c.take<uint32_t>(n);
+    w.probe = c.take<DfProbe>(2 * n);
+    w.n_llr_d = c.take<int32_t>(n);
+    for (FrameList& l : w.list) take_frame_list(c, l, n);
+    w.llr_c = c.take<float>(n * llr_row);
+    w.fst_c = c.take<ria_frame_status>(n);
+    w.llr_w = c.take<float>(n * llr_row);
+    w.fst_w = c.take<ria_frame_status>(n);
+    w.df_frames = c.take<uint8_t>(n * df_row);
+    w.df_res = c.take<ria_dframe_result>(n);
+    w.cres = c.take<ria_control_result>(n);
+    w.cframes = c.take<uint8_t>(n * kCtlFrameBytes);
+    w.cfst = c.take<ria_frame_status>(n);
+    return w;
+}
+
+// One demodulation pass: the windows with a job, listed per span length; the host reads the five lengths (one
+// synchronisation), launches the span demodulator once per non-empty list and scatters the rows to their windows.
+static int win_demod_pass(ria_gpu_handle h, const float* samples_dev, WinArgs& A, const WinWs& W, hipStream_t s, int* total_out) {
+    hipLaunchKernelGGL(win_list_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A, 0);
+    HIP_TRY(h, hipGetLastError());
+    if (int rc = read_ctl(h, h->p_win_ctl, W.ctl, s)) return rc;
+    const WinCtl c = *h->p_win_ctl.as<WinCtl>();
+    long long total = 0;
+    for (int g = 0; g < kWinGroups; ++g) {
+        A.base[g] = static_cast<int>(total);
+        A.cnt[g] = static_cast<int>(c.n[g]);
+        total += c.n[g];
+        if (total > A.n) return fail(h, RIA_ERR_HIP, "ria_gpu_rx_window_batch: a span list broke its bound (%lld)", total);
+    }
+    *total_out = static_cast<int>(total);
+    if (total == 0) return RIA_OK;
+    for (int g = 0; g < kWinGroups; ++g) {
+        if (A.cnt[g] == 0) continue;
+        if (int rc = demod_var_launch(h, "ria_gpu_rx_window_batch", samples_dev, A.list[g].offset, A.list[g].meta, A.cnt[g], A.len[g],
+                                      W.llr_c + static_cast<size_t>(A.base[g]) * A.llr_stride, A.llr_stride, W.fst_c + A.base[g], s)) return rc;
+    }
+    hipLaunchKernelGGL(win_scatter_kernel, dim3(static_cast<unsigned>(std::min<long long>(total, 16384))), dim3(256), 0, s, A, static_cast<int>(total));
+    HIP_TRY(h, hipGetLastError());
+    return RIA_OK;
+}
+
+int ria_gpu_rx_window_batch(ria_gpu_handle control_h, ria_gpu_handle h, const float* samples_dev, int64_t stride, int search_len,
+                            int window_len, int n_windows, const ria_acq_params* params_dev, uint32_t flags, uint8_t* frame_out_dev,
+                            int frame_row, ria_window_result* result_dev, ria_acq_result* acq_dev, ria_control_result* control_dev,
+                            ria_frame_status* demod_status_dev, void* stream) {
+    if (!h || !control_h) return RIA_ERR_INVALID;
+    const char* who = "ria_gpu_rx_window_batch";
+    if (!is_control_handle(control_h) || control_h->cfg.num_carriers != h->cfg.num_carriers || control_h->device != h->device)
+        return fail(h, RIA_ERR_INVALID, "%s: the control handle must be DQPSK R1/4 with the data handle's carriers, on its device", who);
+    const uint32_t known_flags = RIA_DECODE_FULL | RIA_DECODE_NO_CHANNEL_DEINTERLEAVE | RIA_BURST_INTERLEAVE | RIA_ACQ_NO_TIMING_RETRY;
+    const int bpc = h->geo.bytes_per_codeword, llr_row = h->geo.llrs_per_frame;
+    const int df_row = std::max(4, llr_row / kDfBlock) * bpc;
+    if (n_windows < 0 || search_len < 0 || window_len < search_len || stride < window_len || (flags & ~known_flags) != 0 || frame_row < std::max(df_row, kCtlFrameBytes))
+        return fail(h, RIA_ERR_INVALID, "%s: bad argument (0 <= search_len <= window_len <= stride; frame_row >= max(4, llrs_per_frame / 648) * bytes_per_codeword; "
+                                        "flags: RIA_DECODE_*, RIA_BURST_INTERLEAVE, RIA_ACQ_NO_TIMING_RETRY)", who);
+    if (n_windows == 0) return RIA_OK;
+    if (!samples_dev || !params_dev || !frame_out_dev || !result_dev || !acq_dev) return fail(h, RIA_ERR_INVALID, "%s: null pointer", who);
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (demod_fused_selected()) return fail(h, RIA_ERR_UNSUPPORTED, "%s: RIA_DEMOD_FUSED=1 demodulates fixed frames only", who);
+    const int n_ctl = ria_gpu_control_frame_samples(control_h, h);
+    if (n_ctl < 0) return n_ctl;
+    if (n_ctl > h->geo.frame_samples) return fail(h, RIA_ERR_UNSUPPORTED, "%s: the control span (%d samples) is longer than a frame of the data profile", who, n_ctl);
+    const bool r14 = h->cfg.code_rate == RIA_RATE_1_4;
+    const uint32_t dflags = flags & (RIA_DECODE_FULL | RIA_DECODE_NO_CHANNEL_DEINTERLEAVE);
+    const size_t n = static_cast<size_t>(n_windows);
+
+    // every workspace of the call and of the calls it makes, before anything is in flight
+    if (!r14) { if (int rc = dframe_ensure_r14(h)) return rc; }
+    if (int rc = lts_prepare(control_h)) return fail(h, rc, "%s: %s", who, ria_gpu_last_error(control_h));
+    {
+        DevBuf& perm = h->d_cw_perm[(flags & RIA_DECODE_NO_CHANNEL_DEINTERLEAVE) ? 0 : 1];   // decodeFrame's per-codeword de-interleave table
+        if (!perm) HIP_TRY(h, upload(perm, build_cw_deinterleave(h->geo.bits_per_symbol, (flags & RIA_DECODE_NO_CHANNEL_DEINTERLEAVE) == 0)));
+        ControlWs cw;
+        if (int rc = control_ensure_ws(control_h, n_windows, s, &cw)) return fail(h, rc, "%s: %s", who, ria_gpu_last_error(control_h));
+        hipError_t e = control_h->d_demod_ws[0].reserve(demod_ws_bytes(2 + control_h->geo.n_data_symbols));
+        if (e == hipSuccess) e = h->d_demod_ws[0].reserve(demod_ws_bytes(2 + h->geo.n_data_symbols));
+        if (e == hipSuccess) e = ensure_decode_ws(h, n_windows);
+        if (e == hipSuccess && (flags & RIA_DECODE_CRC_RECOVER)) e = ensure_recovery_ws(h, std::max(n_windows, h->cfg.max_batch), false);
+        const size_t dec_bytes = static_cast<size_t>((h->geo.ldpc_k + 7) / 8);
+        if (e == hipSuccess) e = h->d_df_ws.reserve(carved_size([&](Carver& c) { return dframe_carve(c, n, static_cast<size_t>(llr_row / kDfBlock), static_cast<size_t>(bpc), dec_bytes); }));
+        if (e == hipSuccess) e = h->p_df_ctl.reserve(sizeof(DfCtl));
+        if (e != hipSuccess) return fail(h, RIA_ERR_HIP, "%s workspace: %s", who, hipGetErrorString(e));
+    }
+    auto carve = [&](Carver& c) { return window_carve(c, n, static_cast<size_t>(llr_row), static_cast<size_t>(df_row)); };
+    HIP_TRY(h, h->d_win_ws.reserve(carved_size(carve), &s));
+    HIP_TRY(h, h->p_win_ctl.reserve(sizeof(WinCtl)));
+    const WinWs W = carve_at(h->d_win_ws.as<>(), carve);
+
+    HIP_TRY(h, hipMemsetAsync(frame_out_dev, 0, n * static_cast<size_t>(frame_row), s));
+    if (demod_status_dev) HIP_TRY(h, hipMemsetAsync(demod_status_dev, 0, n * sizeof(ria_frame_status), s));
+    ria_control_result* cres = control_dev ? control_dev : W.cres;
+
+    // 1.-2. detection, acceptance and the control hypothesis: ria_gpu_control_acquire_batch's
+    if (int rc = ria_gpu_control_acquire_batch(control_h, samples_dev, stride, search_len, window_len, n_windows, n_ctl, params_dev,
+                                               flags & RIA_BURST_INTERLEAVE, W.cframes, cres, acq_dev, W.cfst, s))
+        return fail(h, rc, "%s: %s", who, ria_gpu_last_error(control_h));
+
+    WinArgs A{};
+    A.n = n_windows; A.window_len = window_len; A.stride = stride; A.params = params_dev; A.acq = acq_dev;
+    A.cres = cres; A.cframes = W.cframes; A.cfst = W.cfst;
+    A.bps = h->geo.bits_per_symbol;
+    A.len[0] = n_ctl;
+    for (int c = 1; c < kWinGroups; ++c) A.len[c] = win_samples_for_cw(A.bps, c);
+    A.is_qam = (h->cfg.modulation == RIA_MOD_QAM16 || h->cfg.modulation == RIA_MOD_QAM32 || h->cfg.modulation == RIA_MOD_QAM64 ||
+                h->cfg.modulation == RIA_MOD_QAM256) ? 1 : 0;
+    A.rate_is_r14 = r14 ? 1 : 0; A.retry = (flags & RIA_ACQ_NO_TIMING_RETRY) ? 0 : 1;
+    A.row = W.row; A.ctl = W.ctl;
+    for (int g = 0; g < kWinGroups; ++g) A.list[g] = W.list[g];
+    A.llr_c = W.llr_c; A.fst_c = W.fst_c; A.llr_w = W.llr_w; A.fst_w = W.fst_w; A.llr_stride = llr_row; A.n_llr_d = W.n_llr_d;
+    A.probe = W.probe; A.plist = W.plist; A.pctl = W.pctl;
+    A.df_frames = W.df_frames; A.df_row = df_row; A.df_res = W.df_res;
+    A.frame_out = frame_out_dev; A.frame_row = frame_row; A.result = result_dev; A.fst_out = demod_status_dev;
+
+    // a launch that fails is reported under its own stage: the lambdas keep the first error, `launched` hands it on
+    hipError_t launch_err = hipSuccess;
+    auto note = [&]() { const hipError_t e = hipGetLastError(); if (launch_err == hipSuccess) launch_err = e; };
+    auto stage = [&](int st) { hipLaunchKernelGGL(win_stage_kernel, dim3(static_cast<unsigned>((n_windows + 255) / 256)), dim3(256), 0, s, A, st); note(); };
+    // robustDecodeSingleCW of the listed windows' first 648 soft bits, with magic, truncation and parseHeader (dframe_probe_kernel)
+    auto probe = [&](bool at_rate) {
+        hipLaunchKernelGGL(win_list_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A, at_rate ? 2 : 1);
+        note();
+        DfArgs D{};
+        D.llr = W.llr_w; D.llr_stride = llr_row; D.n_frames = n_windows; D.probe = W.probe; D.list = W.plist; D.ctl = W.pctl;
+        D.crc_bit = h->d_crc_bit.as<const uint16_t>(); D.crc_init = h->d_crc_init.as<const uint16_t>();
+        const unsigned grid = static_cast<unsigned>(std::min(n_windows, 16384));
+        const int bpc14 = info_bits_for(RIA_RATE_1_4) / 8;
+        if (at_rate || r14) {
+            dispatch_shape(h->cfg.code_rate, [&](auto sh) {
+                using S = decltype(sh);
+                hipLaunchKernelGGL((dframe_probe_kernel<S, true>), dim3(grid), dim3(64), ShapeInfo<S>::lds_bytes, s, h->fast, D, 0,
+                                   at_rate ? kWinProbeRate : kWinProbeR14, at_rate ? bpc : bpc14);
+            });
+        } else {
+            hipLaunchKernelGGL((dframe_probe_kernel<ShapeR14, true>), dim3(grid), dim3(64), ShapeInfo<ShapeR14>::lds_bytes, s, h->fast14, D, 0, kWinProbeR14, bpc14);
+        }
+        note();
+    };
+    // decodeFrame of the windows with the decode flag: ria_gpu_decode_frame_batch over all rows, n_llr 0 where a window has none
+    auto decode = [&]() -> int {
+        stage(kWinPrepDecode);
+        HIP_TRY(h, launch_err);
+        return ria_gpu_decode_frame_batch(h, W.llr_w, llr_row, W.n_llr_d, n_windows, dflags, W.df_frames, df_row, W.df_res, nullptr, nullptr, s);
+    };
+    auto finish = [&]() -> int {
+        stage(kWinFinal);
+        HIP_TRY(h, launch_err);
+        return RIA_OK;
+    };
+
+    int total = 0;
+    stage(kWinInit);
+    // 3. pass 1, the peek span with the data profile at the known CFO; CFO feedback; the CW0 peek
+    if (int rc = win_demod_pass(h, samples_dev, A, W, s, &total)) return rc;
+    if (total == 0) return finish();
+    stage(kWinPeek1);
+    probe(false);
+    stage(kWinPeekR14);
+    if (!r14) { probe(true); stage(kWinPeekRate); }
+    stage(kWinEscalate);
+    // 4. pass 2 at the fed-back CFO, one launch per span length
+    if (int rc = win_demod_pass(h, samples_dev, A, W, s, &total)) return rc;
+    if (total) stage(kWinPass2);
+    // 5. decodeFrame
+    if (int rc = decode()) return rc;
+    stage(kWinDecoded1);
+    // 6. small-frame recovery
+    if (int rc = win_demod_pass(h, samples_dev, A, W, s, &total)) return rc;
+    if (total) {
+        stage(kWinSmall1);
+        probe(false);
+        stage(kWinSmallR14);
+        if (!r14) { probe(true); stage(kWinSmallRate); }
+        if (int rc = win_demod_pass(h, samples_dev, A, W, s, &total)) return rc;
+        if (total) stage(kWinSmallExact);
+        if (int rc = decode()) return rc;
+        stage(kWinDecoded2);
+    }
+    // 7. timing recovery: every round runs the windows still failing, each at its own next candidate that fits
+    stage(kWinRecInit);
+    for (int round = 1;; ++round) {
+        if (int rc = win_demod_pass(h, samples_dev, A, W, s, &total)) return rc;
+        if (total == 0) break;
+        if (round >= kAcqCandidates) return fail(h, RIA_ERR_HIP, "%s: the recovery rounds broke their bound", who);
+        stage(kWinRecDemod);
+        if (int rc = decode()) return rc;
+        stage(kWinRecDecoded);
+    }
+    // 8. consumed samples and the receiver state
+    return finish();
 }
 
 int ria_gpu_chase_combine_batch(ria_gpu_handle h, float* acc_dev, int32_t* count_dev, const uint8_t* decoded_dev,

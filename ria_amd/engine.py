@@ -489,6 +489,41 @@ class RxEngine:
         out = (frames, self._status_array(res, self.CONTROL_RESULT), self._status_array(acq, self.ACQ_RESULT), st)
         return out + (res,) if want_device_result else out
 
+    WINDOW_RESULT = np.dtype([("frame", DFRAME_RESULT), ("outcome", "u1"), ("peek", "u1"), ("pending_total_cw", "u1"), ("small_frame", "u1"),
+                              ("tries_peek_r14", "u1"), ("tries_peek_rate", "u1"), ("tries_small_r14", "u1"), ("tries_small_rate", "u1"),
+                              ("frame_len", "<i4"), ("next_pos", "<i4"), ("need_samples", "<i4"), ("sync_cfo_hz", "<f4"),
+                              ("peek_cfo_hz", "<f4"), ("fading_index", "<f4")])
+
+    def window_frame_row(self):
+        """bytes of one frame row of rx_window: decodeFrame's row for a whole frame's soft bits"""
+        return max(4, self.geo.llrs_per_frame // 648) * self.geo.bytes_per_codeword
+
+    def rx_window(self, control_engine, windows, search_len, known_cfo=None, detect_threshold=0.15, min_confidence=None, abs_base=None,
+                  flags=capi.DECODE_FULL, interleave=False, retry=True, params=None):
+        """One connected-mode OFDM-CHIRP window per row of `windows` (float32 [n, window_len] on the device), as
+        StreamingDecoder handles it (ria_gpu_rx_window_batch): detection and acceptance, the control hypothesis on
+        control_engine (DQPSK R1/4), the peek with this engine's profile and its CFO feedback, the escalation to the frame the
+        CW0 header announces, decodeFrame, small-frame recovery, timing recovery and the consumed samples.  self is the data
+        engine.  Returns (frame bytes uint8 [n, window_frame_row()], result (WINDOW_RESULT), acq (ACQ_RESULT), control result
+        (CONTROL_RESULT), frame status of the reported span)."""
+        n, window_len = windows.shape
+        assert windows.dtype == torch.float32 and windows.is_contiguous()
+        if params is None:
+            params = self.acq_params(n, known_cfo, detect_threshold, min_confidence, abs_base)
+        assert params.dtype == torch.uint8 and params.shape == (n, 32) and params.is_contiguous()
+        row = self.window_frame_row()
+        frames = torch.empty((n, row), dtype=torch.uint8, device=self.device)
+        res = torch.empty((n, 64), dtype=torch.uint8, device=self.device)
+        acq = torch.empty((n, 32), dtype=torch.uint8, device=self.device)
+        cres = torch.empty((n, 32), dtype=torch.uint8, device=self.device)
+        st = torch.empty((n, 32), dtype=torch.uint8, device=self.device)
+        fl = int(flags) | (capi.BURST_INTERLEAVE if interleave else 0) | (0 if retry else capi.ACQ_NO_TIMING_RETRY)
+        self._check(self.lib.ria_gpu_rx_window_batch(control_engine.h, self.h, _ptr(windows), window_len, int(search_len), window_len, n,
+                                                     _ptr(params), fl, _ptr(frames), row, _ptr(res), _ptr(acq), _ptr(cres), _ptr(st),
+                                                     _stream_ptr()))
+        return (frames, self._status_array(res, self.WINDOW_RESULT), self._status_array(acq, self.ACQ_RESULT),
+                self._status_array(cres, self.CONTROL_RESULT), st)
+
     BURST_RESULT = np.dtype([("detected", "<i4"), ("accepted", "<i4"), ("sync_start", "<i4"), ("frame_start", "<i4"),
                              ("correlation", "<f4"), ("cfo_hz", "<f4"), ("delta", "<i2"), ("candidates", "u1"),
                              ("burst_interleaved", "u1"), ("mode", "u1"), ("frames", "u1"), ("frames_decoded", "u1"),
