@@ -295,54 +295,52 @@ __device__ __forceinline__ float llr_canon(float x) {
 // all of them: NCV >= TS), st.pv and st.pt.  The column totals in LDS are a function of every lane's cv and of the constant
 // li, hi is 50 from iteration 1 on, so equality of these words in every lane IS equality of the decoder's state.  They are
 // live registers between two iterations anyway: the copy is plain stores of them, after iterations kExitFirst,
-// + kExitStride, ..., into `state_ws`, an area of global memory that this workgroup owns ([state_words][64] words,
-// lane-linear), and the comparison loads them back.  Nothing of it is inside the iteration body: the ordinary loop runs up
-// to and including a copy iteration and the copy block sits between two runs of it.  The accesses are inline assembly in
-// the scalar-base form (one VGPR of lane * 4, the area in SGPRs, the word's position as the immediate offset): written in
-// C++ they cost 64-bit address pairs in VGPRs, which the function that holds the hot loop does not have.
+// + kExitStride, ..., into `state_ws`, an area of global memory that this workgroup owns ([state_words / 4][64][4] words:
+// a lane's words in quads, the quads lane-linear), and the comparison loads them back.  Nothing of it is inside the
+// iteration body: the ordinary loop runs up to and including a copy iteration and the copy block sits between two runs of
+// it.  The accesses are inline assembly in the scalar-base form (one VGPR of lane * 16, the area in SGPRs, the quad's
+// position as the immediate offset; 16 bytes per lane and instruction, a quarter of the instructions of the word-wise form
+// at the same bytes and, measured, the same time: DESIGN.md section 4 (31)): written in C++ they cost 64-bit address pairs
+// in VGPRs, which the function that holds the hot loop does not have.
 // `exits` == nullptr switches the exit off at run time (no copy traffic, no counter); otherwise it is the counter an exit
 // bumps.  ONLY for callers that never read the bits of a failed decode: the exit leaves the column totals of iteration t
 // in LDS, not those of iteration max_iter - 1.
-constexpr int kStateChunk = 12;                  // words behind one SGPR base: 12 x 256 B stays inside the 13-bit immediate offset
+constexpr int kStateChunk = 12;                  // words behind one SGPR base: three quads, 3 x 1 KiB stays inside the 13-bit immediate offset
+constexpr int kStateQuads = kStateChunk / 4;     // 16-byte accesses of a chunk
 constexpr int kStateWsWords = 36 * 64;           // per workgroup: state_words of the shapes with the exit (R1/2, R1/3) x 64 lanes
+static_assert(kStateChunk % 4 == 0 && (kStateWsWords * sizeof(uint32_t)) % 16 == 0 && (64 * kStateChunk * sizeof(uint32_t)) % 16 == 0,
+              "16-byte accesses: the area of a workgroup (and with it the stride of a stream slot) and every chunk base are multiples of 16 bytes");
 #ifndef RIA_EXIT_FLIGHT
 #define RIA_EXIT_FLIGHT 3                        // chunks of a comparison loaded behind one wait (3: the whole state in one round trip)
 #endif
-// stores words w[12 C .. 12 C + 11] of this lane: no wait (fast_decode waits once, after its loop)
+typedef uint32_t state_quad __attribute__((ext_vector_type(4)));
+// stores words w[12 C .. 12 C + 11] of this lane, four words per instruction (one wave store = 1 KiB contiguous): no wait
+// (fast_decode waits once, after its loop).  The s_nop closes the string because a store of more than 64 bits reads its
+// data registers late: what follows the statement may rewrite them
 template <int C, int N>
-__device__ __forceinline__ void state_store_chunk(const uint32_t* area, uint32_t lane4, const uint32_t (&w)[N]) {
-    static_assert(kStateChunk == 12 && 12 * C + 12 <= N && 256 * 11 < 4096, "twelve immediate offsets");
+__device__ __forceinline__ void state_store_chunk(const uint32_t* area, uint32_t lane16, const uint32_t (&w)[N]) {
+    static_assert(kStateQuads == 3 && 12 * C + 12 <= N && 1024 * 2 < 4096, "three immediate offsets");
     const uint32_t* base = area + 64 * kStateChunk * C;
-    asm volatile("global_store_dword %0, %1, %13\n\tglobal_store_dword %0, %2, %13 offset:256\n\t"
-                 "global_store_dword %0, %3, %13 offset:512\n\tglobal_store_dword %0, %4, %13 offset:768\n\t"
-                 "global_store_dword %0, %5, %13 offset:1024\n\tglobal_store_dword %0, %6, %13 offset:1280\n\t"
-                 "global_store_dword %0, %7, %13 offset:1536\n\tglobal_store_dword %0, %8, %13 offset:1792\n\t"
-                 "global_store_dword %0, %9, %13 offset:2048\n\tglobal_store_dword %0, %10, %13 offset:2304\n\t"
-                 "global_store_dword %0, %11, %13 offset:2560\n\tglobal_store_dword %0, %12, %13 offset:2816"
-                 : : "v"(lane4), "v"(w[12 * C]), "v"(w[12 * C + 1]), "v"(w[12 * C + 2]), "v"(w[12 * C + 3]), "v"(w[12 * C + 4]),
-                     "v"(w[12 * C + 5]), "v"(w[12 * C + 6]), "v"(w[12 * C + 7]), "v"(w[12 * C + 8]), "v"(w[12 * C + 9]),
-                     "v"(w[12 * C + 10]), "v"(w[12 * C + 11]), "s"(base) : "memory");
+    const state_quad q0 = {w[12 * C], w[12 * C + 1], w[12 * C + 2], w[12 * C + 3]};
+    const state_quad q1 = {w[12 * C + 4], w[12 * C + 5], w[12 * C + 6], w[12 * C + 7]};
+    const state_quad q2 = {w[12 * C + 8], w[12 * C + 9], w[12 * C + 10], w[12 * C + 11]};
+    asm volatile("global_store_dwordx4 %0, %1, %4\n\tglobal_store_dwordx4 %0, %2, %4 offset:1024\n\t"
+                 "global_store_dwordx4 %0, %3, %4 offset:2048\n\ts_nop 1"
+                 : : "v"(lane16), "v"(q0), "v"(q1), "v"(q2), "s"(base) : "memory");
 }
 // issues the loads of words 12 C .. 12 C + 11 of this lane's copy; t is valid after state_wait_chunk only
 template <int C>
-__device__ __forceinline__ void state_load_chunk(const uint32_t* area, uint32_t lane4, uint32_t (&t)[kStateChunk]) {
+__device__ __forceinline__ void state_load_chunk(const uint32_t* area, uint32_t lane16, state_quad (&t)[kStateQuads]) {
     const uint32_t* base = area + 64 * kStateChunk * C;
-    asm volatile("global_load_dword %0, %12, %13\n\tglobal_load_dword %1, %12, %13 offset:256\n\t"
-                 "global_load_dword %2, %12, %13 offset:512\n\tglobal_load_dword %3, %12, %13 offset:768\n\t"
-                 "global_load_dword %4, %12, %13 offset:1024\n\tglobal_load_dword %5, %12, %13 offset:1280\n\t"
-                 "global_load_dword %6, %12, %13 offset:1536\n\tglobal_load_dword %7, %12, %13 offset:1792\n\t"
-                 "global_load_dword %8, %12, %13 offset:2048\n\tglobal_load_dword %9, %12, %13 offset:2304\n\t"
-                 "global_load_dword %10, %12, %13 offset:2560\n\tglobal_load_dword %11, %12, %13 offset:2816"
-                 : "=&v"(t[0]), "=&v"(t[1]), "=&v"(t[2]), "=&v"(t[3]), "=&v"(t[4]), "=&v"(t[5]), "=&v"(t[6]), "=&v"(t[7]),
-                   "=&v"(t[8]), "=&v"(t[9]), "=&v"(t[10]), "=&v"(t[11])
-                 : "v"(lane4), "s"(base) : "memory");
+    asm volatile("global_load_dwordx4 %0, %3, %4\n\tglobal_load_dwordx4 %1, %3, %4 offset:1024\n\t"
+                 "global_load_dwordx4 %2, %3, %4 offset:2048"
+                 : "=&v"(t[0]), "=&v"(t[1]), "=&v"(t[2])
+                 : "v"(lane16), "s"(base) : "memory");
 }
-// the compiler does not count the loads of an asm statement: the wait is ours, and the words pass through it as operands
+// the compiler does not count the loads of an asm statement: the wait is ours, and the quads pass through it as operands
 // so that no use of them can be scheduled in front of it
-__device__ __forceinline__ void state_wait_chunk(uint32_t (&t)[kStateChunk]) {
-    asm volatile("s_waitcnt vmcnt(0)"
-                 : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4]), "+v"(t[5]), "+v"(t[6]), "+v"(t[7]),
-                   "+v"(t[8]), "+v"(t[9]), "+v"(t[10]), "+v"(t[11]) : : "memory");
+__device__ __forceinline__ void state_wait_chunk(state_quad (&t)[kStateQuads]) {
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]) : : "memory");
 }
 constexpr int kExitFirst = 22, kExitStride = 24;
 template <class S, int NCV = (kCvRegs ? 1024 : S::kCv), int PF = RIA_SINGLE_PREFETCH, bool EX = false>
@@ -507,7 +505,7 @@ __device__ inline int fast_decode(FastState<S>& st, const FastCode& c, unsigned 
             for (int i = 0; i < I::TS; ++i) w[i] = f2u(st.cv[i]);
 #pragma unroll
             for (int r = 0; r < S::NR; ++r) { w[I::TS + r] = f2u(st.pv[r]); w[I::TS + S::NR + r] = f2u(st.pt[r]); }
-            const uint32_t g4 = static_cast<uint32_t>(lane) * 4u;
+            const uint32_t g16 = static_cast<uint32_t>(lane) * 16u;
             constexpr int NCH = I::state_words / kStateChunk;
             // the first copy of a decode has nothing to be compared with (what the area holds is a past decode's): every
             // comparison follows a store of the same decode
@@ -522,18 +520,18 @@ __device__ inline int fast_decode(FastState<S>& st, const FastCode& c, unsigned 
                 uint32_t sd = 0;
                 static_for<0, (NCH + RIA_EXIT_FLIGHT - 1) / RIA_EXIT_FLIGHT>([&](auto G_) __attribute__((always_inline)) {
                     constexpr int c0 = RIA_EXIT_FLIGHT * decltype(G_)::value, cn = (NCH - c0 < RIA_EXIT_FLIGHT) ? NCH - c0 : RIA_EXIT_FLIGHT;
-                    uint32_t t[cn][kStateChunk];
-                    static_for<0, cn>([&](auto C_) __attribute__((always_inline)) { state_load_chunk<c0 + decltype(C_)::value>(state_ws, g4, t[decltype(C_)::value]); });
+                    state_quad t[cn][kStateQuads];
+                    static_for<0, cn>([&](auto C_) __attribute__((always_inline)) { state_load_chunk<c0 + decltype(C_)::value>(state_ws, g16, t[decltype(C_)::value]); });
                     static_for<0, cn>([&](auto C_) __attribute__((always_inline)) { state_wait_chunk(t[decltype(C_)::value]); });
 #pragma unroll
                     for (int c = 0; c < cn; ++c)
 #pragma unroll
-                        for (int j = 0; j < kStateChunk; ++j) sd |= t[c][j] ^ w[kStateChunk * (c0 + c) + j];
+                        for (int j = 0; j < kStateChunk; ++j) sd |= t[c][j / 4][j % 4] ^ w[kStateChunk * (c0 + c) + j];
                 });
                 if (__ballot(sd != 0u) == 0ull) { status = 2; break; }
             }
             if (snap_at + kExitStride < max_iter) {   // a copy no comparison will read is not taken
-                static_for<0, NCH>([&](auto C_) __attribute__((always_inline)) { state_store_chunk<decltype(C_)::value>(state_ws, g4, w); });
+                static_for<0, NCH>([&](auto C_) __attribute__((always_inline)) { state_store_chunk<decltype(C_)::value>(state_ws, g16, w); });
                 lds_sf(sum_at, u2f(sum));
             }
             snap_at += kExitStride;

@@ -166,21 +166,28 @@ __device__ inline void retry_transform_params(int a, uint32_t h, uint32_t* seed,
 
 // The retry cascade seeds the mt19937 of up to G attempts of one codeword at once: the seeding recurrence is serial, but
 // the attempts' seeds differ by constants only (retry_transform_params), so lane j < G runs the recurrence of attempt
-// a0 + j in plain VALU code and the G chains cost the issue slots of one.  Word i of attempt j goes to ws[i * G + j]
-// (each step stores G adjacent words), a global-memory area that belongs to this workgroup alone.
+// a0 + j in plain VALU code and the G chains cost the issue slots of one.  The area is attempt-major, word i of attempt j
+// at ws[j * 624 + i], in global memory that belongs to this workgroup alone: a lane keeps four consecutive words of its
+// recurrence and writes them with one 16-byte store (156 store instructions per group, not 623), and the read-back is
+// consecutive over the lanes.  ws is 16-byte aligned.
 constexpr unsigned kRetryAttempts = 34;
 template <int G>
 __device__ inline void mt_seed_group(uint32_t* ws, uint32_t h, unsigned a0, int lane) {
     static_assert(G >= 1 && G <= 64, "one lane per attempt of the group");
+    static_assert(624 % 4 == 0 && (624 * sizeof(uint32_t)) % 16 == 0, "an attempt's words are whole 16-byte quads, every attempt's base is aligned");
     const unsigned a = a0 + static_cast<unsigned>(lane);
     if (lane < G && a < kRetryAttempts) {
         uint32_t x; float sigma, factor; int kind;
         retry_transform_params(static_cast<int>(a), h, &x, &sigma, &factor, &kind);
-        uint32_t* w = ws + lane;
-        w[0] = x;
-        for (uint32_t i = 1; i < 624; ++i) {
-            x = 1812433253u * (x ^ (x >> 30)) + i;
-            w[i * G] = x;
+        uint4* w = reinterpret_cast<uint4*>(ws + lane * 624);
+        for (uint32_t i = 0; i < 624; i += 4) {
+            uint4 q;
+            if (i > 0) x = 1812433253u * (x ^ (x >> 30)) + i;
+            q.x = x;
+            x = 1812433253u * (x ^ (x >> 30)) + (i + 1); q.y = x;
+            x = 1812433253u * (x ^ (x >> 30)) + (i + 2); q.z = x;
+            x = 1812433253u * (x ^ (x >> 30)) + (i + 3); q.w = x;
+            w[i / 4] = q;
         }
     }
     // the wave reads these words back itself (other lanes than the ones that wrote them)
@@ -191,7 +198,8 @@ __device__ inline void mt_seed_group(uint32_t* ws, uint32_t h, unsigned a0, int 
 // state of the group's attempt j into the LDS area normal648_state works on
 template <int G>
 __device__ inline void mt_load_group_state(uint32_t* st, const uint32_t* ws, int j, int lane) {
-    for (int i = lane; i < 624; i += 64) st[i] = ws[i * G + j];
+    static_assert(G >= 1 && G <= 64, "one lane per attempt of the group");
+    for (int i = lane; i < 624; i += 64) st[i] = ws[j * 624 + i];
     wave_sync();
 }
 
