@@ -692,8 +692,8 @@ int ria_gpu_rx_burst_batch(ria_gpu_handle h, const float* samples_dev, int64_t s
  * ria_gpu_chase_combine_batch.  This call leaves out the chase cache (:2729-2731, :2766-2789, :2796-2799, :2808-2811):
  * ria_gpu_mcdpsk_acquire_harq_batch below is the same call with it.  It also leaves out channel interleaving
  * (:2614-2623, :2651-2672, :2741; RIA_MACQ_CHANNEL_INTERLEAVE is RIA_ERR_UNSUPPORTED here and in the HARQ call):
- * ria_gpu_mcdpsk_acquire_ci_batch below is the same call with both.  PING/PONG classification and the CW0-peek escalation
- * stay with the caller.
+ * ria_gpu_mcdpsk_acquire_ci_batch below is the same call with both.  PING classification and the CW0-peek escalation are
+ * ria_gpu_mcdpsk_window_batch's, further below.
  *
  * Work: round r demodulates and decodes the list of windows still searching, each at its own next candidate that fits,
  * with two small device-to-host reads (the round's codeword-row count and the next list's length); no samples, soft bits
@@ -703,9 +703,10 @@ typedef struct ria_mcdpsk_acq_params {   /* one per window, 32 bytes */
     float    known_cfo_hz;               /* connected: detectDataSync's known CFO and the CFO rule's reference */
     float    detect_threshold;           /* ZC 0.2 / chirp 0.15 in the reference's MC-DPSK calls */
     float    min_confidence;             /* accepted iff detected && correlation >= min_confidence && the frame fits */
-    uint32_t reserved0;
+    uint32_t pending_total_cw;           /* the next three: ria_gpu_mcdpsk_window_batch only, ignored by the other calls */
     uint64_t abs_base;                   /* absolute sample index of window sample 0: reported only (not used) */
-    uint32_t reserved[2];
+    uint32_t first_avail;
+    int32_t  last_decoded_sync;
 } ria_mcdpsk_acq_params;
 
 typedef struct ria_mcdpsk_acq_result {   /* 64 bytes */
@@ -908,6 +909,121 @@ int ria_gpu_mcdpsk_acquire_ci_batch(ria_gpu_handle h, const ria_mcdpsk_config* c
                                     ria_mcdpsk_harq_result* harq_dev /* nullable */, int interleaver_bits, void* stream);
 int ria_gpu_mcdpsk_interleave_batch(ria_gpu_handle h, int interleaver_bits, const uint8_t* coded_dev, int n_cw, uint8_t* out_dev,
                                     void* stream);
+
+/* ---- one MC-DPSK window: anti-replay, PING energy test, CW0 peek, escalation, decode, handshake fallbacks ---------------------
+ * ria_gpu_mcdpsk_window_batch is StreamingDecoder::decodeCurrentFrame() for the MC-DPSK mode (src/gui/modem/
+ * streaming_decoder.cpp:1060-1266, :1346-1376, :1436-1503, :1599-1797, :1967-2013) for a batch of windows, statement for
+ * statement.  h is created at R1/4; cfg, the window geometry and the flags are ria_gpu_mcdpsk_acquire_ci_batch's
+ * (RIA_MACQ_SYNC_CHIRP, RIA_MACQ_DISCONNECTED, RIA_MACQ_NO_RETRY, RIA_MACQ_CHANNEL_INTERLEAVE).  There is no frame_cw: the call
+ * finds the codeword count.  Per-window inputs in ria_mcdpsk_acq_params, read by this call only:
+ *   pending_total_cw   0 for a fresh sync; n > 0 (<= 255, else RIA_ERR_INVALID) is the re-entry of a window that answered
+ *                      RIA_MWIN_NEED_SAMPLES: the peek is skipped, as the reference skips it when pending_total_cw_ != 0.
+ *   first_avail        the samples behind the sync that were there when the first pass ran (checkIfReadyToDecode's early
+ *                      half-window, :1005-1011; frame_len = min(1-CW length, available), :1110).  0: a whole 1-codeword span.
+ *                      Otherwise >= 9608, else RIA_ERR_INVALID; so is a value below the 1-codeword span without
+ *                      RIA_MACQ_DISCONNECTED (a connected decoder waits for the whole span, :1007).
+ *   last_decoded_sync  window-relative position of the last decoded frame for the anti-replay rule (:876-889); INT32_MIN: off.
+ * Per window, in the reference's order:
+ *   1. Detection, acceptance and CFO: steps 1-2 of ria_gpu_mcdpsk_acquire_batch; the fit rule uses the pass-0 span,
+ *      min(getMinSamplesForCWCount(1), first_avail), or getMinSamplesForCWCount(pending) on re-entry.  Else RIA_MWIN_NOT_ACCEPTED.
+ *   2. Anti-replay: |sync_start - last_decoded_sync| < 200 is RIA_MWIN_REPLAY, next_pos = sync_start + 9600 + 4800; nothing else runs.
+ *   3. The PING energy test, under RIA_MACQ_DISCONNECTED only (allow_ping_detection = !connected_): training_rms over samples
+ *      [0, min(4608, len)) of the span, rms over the next min(len - 4608, 5000); each a float32 sum of squares in ascending
+ *      order divided by the count, then sqrtf; ratio = training_rms > 0.001f ? rms / training_rms : 0; a PING iff ratio < 0.6f:
+ *      RIA_MWIN_PING, success 1, frame type 0x01, no bytes, next_pos = sync_start + getMinSamplesForCWCount(1), last_decoded_sync
+ *      = sync_start.  Both values are reported on every accepted window that is no replay.  Every later pass of the reference
+ *      repeats the test on a span that starts with the same >= 9608 samples (carriers 1..20 and two modulations make the
+ *      shortest 1-codeword span 4608 + 17 * 512 = 13 312 samples), so it is computed once.  The CSS branch is out of scope.
+ *   4. Pass 0 and the CW0 peek: process() on the pass-0 span at the window's CFO.  With >= 648 soft bits and pending 0:
+ *      robustDecodeSingleCW of CW0 at R1/4; without the magic and under RIA_MACQ_CHANNEL_INTERLEAVE the de-interleaved CW0
+ *      (:1456-1467); parseHeader on the whole decoded vector - it reads bytes 0..19 only (frame_v2.cpp:1195-1252), so
+ *      decodeMCDPSKFrame's truncation to 20 bytes cannot differ; the peek's CONNECT guard FORCES a CONNECT / CONNECT_ACK /
+ *      CONNECT_NAK with total_cw < 3 up to 3 when disconnected (:1473-1480; decodeMCDPSKFrame's guard rejects);
+ *      needed_cw > 1 && avail_cw < needed_cw: pending = needed_cw; otherwise, disconnected, pending = 3 while avail_cw < 3
+ *      (:1496-1502).  With < 648 soft bits, disconnected and pending 0: pending = 1 (:1600-1609).  Disconnected with avail_cw < 3
+ *      and pending < 3: pending = 3 (:1611-1624) - the rule a re-entry with pending 1 or 2, or an early window, hits.  A data
+ *      header with total_cw 0 is valid for the peek (needed_cw 0: no escalation) and invalid for the decode, as in the older calls.
+ *      A span of >= 9608 samples holds >= 2 data symbols at any spreading, so process() cannot fail and the soft bits are never
+ *      empty: RIA_MWIN_PROCESS_FAILED (:1352-1372) is defined and never produced.  An early window gives fewer than 648 soft
+ *      bits whatever the samples are, so it is not demodulated.
+ *   5. Escalation, pending n > 0: frame_len = getMinSamplesForCWCount(n); sync_start + frame_len > window_len is
+ *      RIA_MWIN_NEED_SAMPLES (the reference's SYNC_FOUND wait; need_samples = frame_len and pending_total_cw = n to come back
+ *      with); else n > 8, or a span the MC-DPSK demodulator's workgroup cannot hold, is RIA_MWIN_TOO_LONG (pending_total_cw = the
+ *      header's count); else process() on the longer span, without another peek.
+ *   6. decodeFrame -> decodeMCDPSKFrame on the last pass's soft bits: ria_gpu_mcdpsk_acquire_ci_batch's rounds at frame_cw = n
+ *      (chase store / combine / resolve with a pool, channel-interleave rounds with the flag).
+ *   7. Header salvage (:1631-1644): !success, pending 0, codewords_ok > 0 and a valid header with total_cw > avail_cw: pending =
+ *      total_cw, back to 5.  The peek of the same pass has parsed the same CW0 decode and has escalated every such header
+ *      already (the only headers it treats differently are the CONNECT ones, which decodeMCDPSKFrame rejects with codewords_ok
+ *      0), so no input reaches this at R1/4; it is implemented all the same (RIA_MPEEK_SALVAGE).
+ *   8. Handshake fallbacks under RIA_MACQ_DISCONNECTED without RIA_MACQ_NO_RETRY, if !success && codewords_ok == 0: steps 4-5
+ *      of ria_gpu_mcdpsk_acquire_batch at frame_cw = pending, its fit rule, first full success wins; a recovered candidate
+ *      moves sync_position_, so next_pos follows it.
+ *   9. Consumed: next_pos = frame_start + frame_len (MC-DPSK never takes the exact-size shortcut of :2001).
+ *  10. deliver = success || codewords_ok > 0 (:1977); last_decoded_sync = frame_start (:2121).  RIA_MWIN_DECODED.
+ * Out of scope: the ZC-miss -> chirp fallback of connected search (:790-828; call again with RIA_MACQ_SYNC_CHIRP),
+ * estimateSNRFromChirp (the correlation is reported), the frame timeout, CSS, ring-buffer wrap, MFSK.
+ *
+ * Outputs, every row written, zero where nothing applies: result_dev; acq_dev (the reported candidate's DecodeResult, as in the
+ * acquire call; candidates counts the last pass's); frame_out_dev rows of frame_row >= RIA_MACQ_FRAME_BYTES(8) bytes; llr_out_dev
+ * (nullable) rows of llr_stride floats, llr_stride >= the soft bits of the longest pass the window length allows (either
+ * modulation when the fallbacks can run); harq_dev (nullable).  pool NULL: no chase.  Duplicate cache ids are RIA_ERR_INVALID,
+ * read with the first control read, as are the per-window input errors above.  n_windows == 0 is RIA_OK.
+ * Work: one wavefront per window for the energy test (the serial float32 chain runs on one lane out of LDS); the peek pass is
+ * one demodulator launch, round A (and A2) of the acquire rounds and one wave per window for the rules; then, for each
+ * codeword count 1..8 in ascending order - escalation only ever raises a window's count - the open windows of that count as
+ * one ascending list through the acquire call's rounds, on one stream, one after the other: no result depends on scheduling
+ * or on which batch a window is in, and chase rounds keep ria_gpu_mcdpsk_acquire_harq_batch's order.  A window that falls
+ * through the peek is demodulated again at count 1 (the reference decodes its CW0 twice as well).
+ * Small device-to-host reads, worst case: 2 (the per-window input check, the peek list with the duplicate-id flag) + 1 (the
+ * peek's A2 list) + 8 counts x (26 rounds x 4 + 1) = 843; a connected call without pool or interleaving makes at most
+ * 2 + 8 x 3 = 26, one per count that no window is at.  No samples, soft bits or payloads go to the host.  Workspaces live on the handle, are carved once
+ * per size and reserved before anything of the call is in flight. */
+enum { RIA_MWIN_NOT_ACCEPTED = 0, RIA_MWIN_REPLAY = 1, RIA_MWIN_PING = 2, RIA_MWIN_PROCESS_FAILED = 3, RIA_MWIN_DECODED = 4,
+       RIA_MWIN_NEED_SAMPLES = 5, RIA_MWIN_TOO_LONG = 6 };
+/* ria_mcdpsk_window_result.peek: what CW0 said in the low four bits, then the statements that set pending_total_cw_ */
+enum { RIA_MPEEK_NONE = 0,                   /* the peek did not run (pending on input, early window, fewer than 648 soft bits) */
+       RIA_MPEEK_NO_HEADER = 1,              /* no CW0 with the magic and a valid header */
+       RIA_MPEEK_HEADER_SINGLE = 2,          /* a valid header that asks for no more than the span holds */
+       RIA_MPEEK_HEADER_MULTI = 3,           /* needed_cw > 1 && avail_cw < needed_cw (:1482-1489) */
+       RIA_MPEEK_CONNECT_FORCED = 4,         /* the same after the CONNECT guard forced total_cw up to 3 (:1475-1480) */
+       RIA_MPEEK_WHAT_MASK = 0x0F,
+       RIA_MPEEK_HANDSHAKE_FALLBACK = 0x10,  /* :1496-1502 */
+       RIA_MPEEK_EARLY_WINDOW = 0x20,        /* :1600-1609 */
+       RIA_MPEEK_HANDSHAKE_WINDOW = 0x40,    /* :1611-1624 */
+       RIA_MPEEK_DEINTERLEAVED = 0x80,       /* the de-interleaved CW0 was the one that spoke */
+       RIA_MPEEK_SALVAGE = 0x100 };          /* :1631-1644 (unreached at R1/4, see above) */
+typedef struct ria_mcdpsk_window_result {    /* 64 bytes, one per window */
+    int32_t outcome;                     /* RIA_MWIN_* */
+    int32_t peek;                        /* RIA_MPEEK_* */
+    int32_t next_pos;                    /* position behind the consumed samples within the window, -1 where nothing was consumed */
+    int32_t need_samples;                /* RIA_MWIN_NEED_SAMPLES: the samples from sync_start the next pass waits for, else 0 */
+    int32_t pending_total_cw;            /* pending_total_cw_ as the window leaves it (0: pass 0's own soft bits were decoded) */
+    int32_t frame_len;                   /* RIA_MWIN_DECODED: the decoded pass's span in samples, else 0 */
+    int32_t passes;                      /* passes of decodeCurrentFrame up to the outcome (every one runs the energy test and process()) */
+    int32_t peek_total_cw;               /* total_cw of the header the peek parsed, before the guard; 0 if none */
+    float   training_rms;
+    float   rms;
+    int32_t last_decoded_sync;           /* last_decoded_sync_pos_ as the window leaves it (the input where it does not move) */
+    uint8_t deliver;                     /* the host queues the DecodeResult: success || codewords_ok > 0, or a PING */
+    uint8_t is_ping;
+    uint8_t peek_tries;                  /* decodes of the robust decoder in the peek: raw CW0 plus the de-interleaved one */
+    uint8_t reserved0;
+    int32_t reserved[4];
+} ria_mcdpsk_window_result;
+int ria_gpu_mcdpsk_window_batch(ria_gpu_handle h, const ria_mcdpsk_config* cfg, const float* samples_dev, int64_t stride,
+                                int search_len, int window_len, int n_windows,
+                                const ria_mcdpsk_acq_params* params_dev, uint32_t flags,
+                                uint8_t* frame_out_dev, int frame_row, ria_mcdpsk_window_result* result_dev,
+                                ria_mcdpsk_acq_result* acq_dev, float* llr_out_dev /* nullable */, int llr_stride,
+                                ria_chase_pool pool /* nullable */, const int32_t* cache_id_dev, const uint64_t* now_ms_dev,
+                                ria_mcdpsk_harq_result* harq_dev /* nullable */, int interleaver_bits, void* stream);
+/* One window from host memory, without a chase pool (the single-window adaptor path, ria_host::mcdpskWindow): staged through
+ * the handle's pinned block on the handle's own stream; synchronises that stream.  frame_out_host takes
+ * RIA_MACQ_FRAME_BYTES(8) bytes (max_bytes below that is RIA_ERR_INVALID). */
+int ria_gpu_mcdpsk_window_host(ria_gpu_handle h, const ria_mcdpsk_config* cfg, const float* samples_host, int search_len, int window_len,
+                               const ria_mcdpsk_acq_params* params_host, uint32_t flags, uint8_t* frame_out_host, int max_bytes,
+                               ria_mcdpsk_window_result* result_out, ria_mcdpsk_acq_result* acq_out, int interleaver_bits);
 
 /* ---- RX: decodeFrame, OFDM branch (StreamingDecoder::decodeFrame, src/gui/modem/streaming_decoder.cpp:2821-3059) ----
  * The "try both" strategy every OFDM frame's soft bits go through, statement for statement, over a batch of rows.  Row f is

@@ -396,3 +396,91 @@ def harq_tally(result, harq):
                entries_kept=int((harq["entry"] == capi.HARQ_ENTRY["KEPT"]).sum()),
                entries_removed=int((harq["entry"] == capi.HARQ_ENTRY["REMOVED"]).sum()))
     return np.array([row[k] for k in HARQ_COUNTERS], dtype=np.int64)
+
+
+# ---- one MC-DPSK window per call (ria_gpu_mcdpsk_window_batch)
+_MWIN_DELTAS = (8, -8, 16, -16, 24, -24, 32, -32, 48, -48, 64, -64)
+MCDPSK_WINDOW_COUNTERS = ("windows",) + tuple(f"outcome_{k.lower()}" for k in capi.MWIN_OUTCOME) + \
+    tuple(f"peek_{k.lower()}" for k in capi.MPEEK_WHAT) + tuple(f"peek_{k.lower()}" for k in capi.MPEEK_BITS) + \
+    ("pings", "success", "partial", "delivered", "recovered_alternate") + tuple(f"recovered_{d:+d}" for d in _MWIN_DELTAS)
+
+
+def mcdpsk_window_tally(res, acq):
+    """Counter row (MCDPSK_WINDOW_COUNTERS) of one mcdpsk_window call: windows, windows per outcome, per statement of the CW0
+    peek (what CW0 said, then every escalation statement that fired), PINGs, frames decoded in full (success, PINGs not
+    counted), results with some codewords only, results the host queues, and - among the decoded frames - those the alternate
+    modulation recovered in place and those each timing delta recovered."""
+    row = [len(res)] + [int((res["outcome"] == v).sum()) for v in capi.MWIN_OUTCOME.values()]
+    what = res["peek"] & capi.MPEEK_WHAT_MASK
+    row += [int((what == v).sum()) for v in capi.MPEEK_WHAT.values()]
+    row += [int(((res["peek"] & v) != 0).sum()) for v in capi.MPEEK_BITS.values()]
+    decoded = res["outcome"] == capi.MWIN_OUTCOME["DECODED"]
+    ok = decoded & (acq["success"] != 0)
+    row += [int((res["is_ping"] != 0).sum()), int(ok.sum()), int((decoded & ~ok & (acq["codewords_ok"] != 0)).sum()),
+            int((res["deliver"] != 0).sum()), int((ok & (acq["delta"] == 0) & (acq["candidates"] > 1)).sum())]
+    row += [int((ok & (acq["delta"] == d)).sum()) for d in _MWIN_DELTAS]
+    return np.array(row, dtype=np.int64)
+
+
+def _data_frame(ftype, seq, payload, hs=0x123456, hd=0x654321):
+    """a serialized v2 data / connect frame (frame_v2.cpp): 17-byte header with TOTAL_CW at R1/4, LEN and the header CRC,
+    the payload, the frame CRC"""
+    payload = np.asarray(payload, np.uint8)
+    total_cw = -(-(17 + len(payload) + 2) * 8 // 162)
+    h = np.zeros(17, np.uint8)
+    h[:15] = [0x55, 0x4C, ftype, 0, seq >> 8, seq & 255, hs >> 16, (hs >> 8) & 255, hs & 255, hd >> 16, (hd >> 8) & 255, hd & 255,
+              total_cw, len(payload) >> 8, len(payload) & 255]
+    c = _crc16(h[:15])
+    h[15], h[16] = c >> 8, c & 255
+    f = np.concatenate([h, payload])
+    c = _crc16(f)
+    return np.concatenate([f, np.array([c >> 8, c & 255], np.uint8)])
+
+
+def _encode_r14(engine, frame, n_cw):
+    """encodeFrameWithLDPC at R1/4 (frame_v2.cpp:1098-1130) through ria_gpu_ldpc_encode_host: CW0 = the first 20 bytes,
+    CW1+ = 0xD5, index, 18 bytes.  uint8 [81 * n_cw]"""
+    info = np.zeros((n_cw, 21), np.uint8)
+    info[0, :min(20, len(frame))] = frame[:20]
+    off, i = 20, 1
+    while off < len(frame):
+        info[i, 0], info[i, 1] = 0xD5, i
+        chunk = frame[off:off + 18]
+        info[i, 2:2 + len(chunk)] = chunk
+        off += 18
+        i += 1
+    assert i == n_cw
+    return engine.ldpc_encode(info).reshape(-1)
+
+
+CONNECT_TYPE = 0x12                             # v2::FrameType::CONNECT
+HANDSHAKE_KINDS = ("ping", "connect", "control", "data", "noise")
+
+
+def make_handshake_windows(engine, n, kind, snr_db, seeds, mix=HANDSHAKE_KINDS, lead=2000, tail=2000, carriers=10, data_cw=3):
+    """n disconnected-handshake windows on the engine's device, window i of kind mix[i % len(mix)]: a PING (the whole preamble -
+    dual chirp, training, reference symbol - and no data, StreamingEncoder::encodePing), a CONNECT of 3 codewords, a 1-codeword ACK, a data frame of data_cw codewords, noise only.  Built from
+    engine.chirp_preamble(), ria_gpu_ldpc_encode_host, the device modulator (DBPSK) and the reference-identical channel (one
+    seed per window), peak 0.8 at sample `lead` of a window that holds 3 codewords behind the preamble (data_cw > 3: that many).
+    Returns (windows float32 [n, window_len], search_len, kinds: the index into mix of every window)."""
+    chirp = engine.chirp_preamble()
+    frame_cw = max(3, int(data_cw))
+    search_len, window_len = mcdpsk_window_recipe(len(chirp), frame_cw, lead, tail, carriers)
+    frames = {"connect": (_data_frame(CONNECT_TYPE, 7, np.arange(25, dtype=np.uint8)), 3),
+              "control": (control_frames([40], [ACK])[0], 1),
+              "data": (_data_frame(0x30, 9, (np.arange(18 * (data_cw - 1) - 1 if data_cw > 1 else 1) % 251).astype(np.uint8)), int(data_cw))}
+    pre = torch.from_numpy(np.ascontiguousarray(chirp, np.float32)).to(engine.device)
+    win = torch.zeros((n, window_len), dtype=torch.float32, device=engine.device)
+    kinds = np.arange(n) % len(mix)
+    for k, name in enumerate(mix):
+        idx = torch.from_numpy(np.nonzero(kinds == k)[0]).to(engine.device)
+        if name == "noise" or len(idx) == 0:
+            continue
+        frame, n_cw = frames["control" if name == "ping" else name]
+        body = engine.mcdpsk_modulate_batch(_encode_r14(engine, frame, n_cw)[None, :], carriers, 1, 1)[0]
+        tx = torch.cat([pre, body[:9 * 512] if name == "ping" else body])       # training (8 symbols) + reference
+        tx = tx * (0.8 / tx.abs().max())
+        m = min(tx.shape[0], window_len - lead)
+        win[idx, lead:lead + m] = tx[:m]
+    engine.channel_exact_seeded_(win, kind, snr_db, np.ascontiguousarray(seeds, np.uint32))
+    return win, search_len, kinds

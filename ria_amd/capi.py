@@ -32,6 +32,12 @@ DFRAME_MAX_CW = 32
 WIN_OUTCOME = {"NOT_ACCEPTED": 0, "BURST": 1, "CONTROL_PROFILE": 2, "DECODED": 3, "NEED_SAMPLES": 4, "TOO_LONG": 5}
 WIN_PEEK = {"NONE": 0, "R14_ONE": 1, "R14_MULTI": 2, "RATE_ONE": 3, "RATE_MULTI": 4, "RATE_BAD_HEADER": 5, "FAILED": 6, "QAM_PARTIAL": 7,
             "DIRECT": 8}
+# RIA_MWIN_* (ria_mcdpsk_window_result.outcome) and RIA_MPEEK_* (its peek word: MPEEK_WHAT in the low four bits, then MPEEK_BITS)
+MWIN_OUTCOME = {"NOT_ACCEPTED": 0, "REPLAY": 1, "PING": 2, "PROCESS_FAILED": 3, "DECODED": 4, "NEED_SAMPLES": 5, "TOO_LONG": 6}
+MPEEK_WHAT = {"NONE": 0, "NO_HEADER": 1, "HEADER_SINGLE": 2, "HEADER_MULTI": 3, "CONNECT_FORCED": 4}
+MPEEK_WHAT_MASK = 0x0F
+MPEEK_BITS = {"HANDSHAKE_FALLBACK": 0x10, "EARLY_WINDOW": 0x20, "HANDSHAKE_WINDOW": 0x40, "DEINTERLEAVED": 0x80, "SALVAGE": 0x100}
+MWIN_NO_LAST_SYNC = -2 ** 31
 CHASE_MAX_CW, CHASE_MAX_ENTRIES, CHASE_MAX_COMBINES = 16, 16, 4
 HARQ_ENTRY = {"NONE": 0, "KEPT": 1, "REMOVED": 2}
 
@@ -51,6 +57,7 @@ EXPORTS = [
     "ria_gpu_mcdpsk_decode_frame_ci_batch", "ria_gpu_mcdpsk_acquire_ci_batch", "ria_gpu_mcdpsk_interleave_batch",
     "ria_gpu_var_frame_samples", "ria_gpu_control_frame_samples", "ria_gpu_tx_coded_var_batch", "ria_gpu_demod_var_batch", "ria_gpu_demod_var_host",
     "ria_gpu_rx_control_batch", "ria_gpu_control_acquire_batch", "ria_gpu_rx_window_batch",
+    "ria_gpu_mcdpsk_window_batch", "ria_gpu_mcdpsk_window_host",
     "ria_link_recommend", "ria_link_data_mode", "ria_link_ofdm_code_rate", "ria_link_cap_initial_rate",
 ]
 
@@ -111,8 +118,16 @@ class BurstResult(C.Structure):
 
 
 class McAcqParams(C.Structure):
+    """pending_total_cw, first_avail and last_decoded_sync are read by ria_gpu_mcdpsk_window_batch only"""
     _fields_ = [("known_cfo_hz", C.c_float), ("detect_threshold", C.c_float), ("min_confidence", C.c_float),
-                ("reserved0", C.c_uint32), ("abs_base", C.c_uint64), ("reserved", C.c_uint32 * 2)]
+                ("pending_total_cw", C.c_uint32), ("abs_base", C.c_uint64), ("first_avail", C.c_uint32), ("last_decoded_sync", C.c_int32)]
+
+
+class McWindowResult(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("outcome", "peek", "next_pos", "need_samples", "pending_total_cw", "frame_len", "passes",
+                                          "peek_total_cw")] + \
+               [("training_rms", C.c_float), ("rms", C.c_float), ("last_decoded_sync", C.c_int32), ("deliver", C.c_uint8),
+                ("is_ping", C.c_uint8), ("peek_tries", C.c_uint8), ("reserved0", C.c_uint8), ("reserved", C.c_int32 * 4)]
 
 
 class McAcqResult(C.Structure):
@@ -270,6 +285,8 @@ def load(build_if_needed=True):
     L.ria_gpu_rx_control_batch.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
     L.ria_gpu_control_acquire_batch.argtypes = [vp, vp, C.c_int64, i32, i32, i32, i32, vp, u32, vp, vp, vp, vp, vp]
     L.ria_gpu_rx_window_batch.argtypes = [vp, vp, vp, C.c_int64, i32, i32, i32, vp, u32, vp, i32, vp, vp, vp, vp, vp]
+    L.ria_gpu_mcdpsk_window_batch.argtypes = [vp, vp, vp, C.c_int64, i32, i32, i32, vp, u32, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp]
+    L.ria_gpu_mcdpsk_window_host.argtypes = [vp, vp, vp, i32, i32, vp, u32, vp, i32, vp, vp, i32]
     L.ria_link_recommend.argtypes = [f32, f32, C.POINTER(LinkRecommendation)]
     L.ria_link_recommend.restype = None
     L.ria_link_data_mode.argtypes = [f32, i32, f32, C.POINTER(LinkRecommendation)]

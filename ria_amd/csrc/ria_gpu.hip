@@ -43,6 +43,7 @@
 #include "var_frames.hpp"
 #include "control_kernels.hip.h"
 #include "window_kernels.hip.h"
+#include "mcdpsk_window_kernels.hip.h"
 
 using namespace ria;
 
@@ -130,6 +131,9 @@ struct ria_gpu {
     // ria_gpu_rx_window_batch (window_carve): per-window state, soft bits and status, the span lists, one pass's compact
     // demodulations, probe records, decodeFrame's outputs and the control hypothesis's, with the control block's pinned mirror
     DevBuf d_win_ws; PinBuf p_win_ctl;
+    // ria_gpu_mcdpsk_window_batch (mwin_carve): per-window pass state, the peek's decoder tries and the control word with its
+    // pinned mirror; the rounds use d_macq_ws, carved for the longest pass
+    DevBuf d_mwin_ws; PinBuf p_mwin_ctl;
 };
 
 namespace {
@@ -462,6 +466,7 @@ static int run_crc_recovery_host(ria_gpu_handle h, const FastDecodeArgs& D, hipS
 // which may print `arg`
 static unsigned int ctl_fault(const MacqCtl&) { return 0; }   // the robust decoder has no work queue
 static unsigned int ctl_fault(const MacqCiCtl&) { return 0; }
+static unsigned int ctl_fault(const MwinCtl&) { return 0; }   // a flag of its own, read by the caller
 static unsigned int ctl_fault(const WinCtl&) { return 0; }    // list lengths only: the stages behind them report their own faults
 template <class Ctl>
 static unsigned int ctl_fault(const Ctl& c) { return c.fault; }
@@ -2140,7 +2145,8 @@ static bool macq_ci_step(int interleaver_bits, int* step) {
 }
 // Round A2 of a round whose round A has run (mcdpsk_acquire_kernels.hip.h), shared by the acquire and the decode-frame
 // call: the A2 list, one control read for its length, the de-interleaved CW0 decodes and the merge into round A's outputs.
-static int macq_round_a2(ria_gpu_handle h, const char* who, const MacqArgs& A, const MacqWs& W, PinBuf& mirror, hipStream_t s) {
+static int macq_round_a2(ria_gpu_handle h, const char* who, const MacqArgs& A, const MacqWs& W, PinBuf& mirror, hipStream_t s,
+                         uint8_t* tries_a2 = nullptr /* [n_cur], the window call's peek */) {
     hipLaunchKernelGGL(macq_ci_list_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A);
     HIP_TRY(h, hipGetLastError());
     if (int rc = read_ctl(h, mirror, A.ci_ctl, s)) return rc;     // the mirror's other words are read again before they are used
@@ -2149,7 +2155,7 @@ static int macq_round_a2(ria_gpu_handle h, const char* who, const MacqArgs& A, c
     if (n_a2 == 0) return RIA_OK;
     hipLaunchKernelGGL(macq_ci_gather_kernel, dim3(static_cast<unsigned>(std::min<size_t>((static_cast<size_t>(n_a2) * kMacqLdpcBlock + 255) / 256, 16384))),
                        dim3(256), 0, s, A, n_a2);
-    int rc = ria_gpu_ldpc_decode_robust_batch(h, A.rows, n_a2, W.out_a2, W.ok_a2, W.it_a2, nullptr, s);
+    int rc = ria_gpu_ldpc_decode_robust_batch(h, A.rows, n_a2, W.out_a2, W.ok_a2, W.it_a2, tries_a2, s);
     if (rc != RIA_OK) return rc;
     hipLaunchKernelGGL(macq_ci_merge_kernel, dim3(static_cast<unsigned>(std::min((n_a2 + 255) / 256, 1024))), dim3(256), 0, s, A, n_a2,
                        W.out_a, W.ok_a, W.out_a2, W.ok_a2);
@@ -2230,6 +2236,58 @@ static int harq_stages(ria_gpu_handle h, const char* who, const MacqArgs& A, Har
     return RIA_OK;
 }
 
+// The rounds of one list (steps 3-5): round 0 runs W.list[0] (its length in ctl.n_list) at the primary candidate, round r >= 1
+// the windows still searching at their next candidate that fits (at most 25 more rounds: each advances every window it holds by
+// at least one candidate).  A carries everything but the per-round fields; llr_ws and max_cw belong to A.frame_len.
+static int macq_rounds(ria_gpu_handle h, const char* who, const ria_mcdpsk_config& c, const float* samples_dev, int64_t stride, MacqArgs& A,
+                       const MacqWs& W, ria_chase_pool pool, const HarqArgs& H, const HarqWs& HW, bool ci, int llr_ws, int max_cw,
+                       bool check_dup, hipStream_t s) {
+    const MacqCtl& ctl = *h->p_macq_ctl.as<MacqCtl>();
+    const int n_windows = A.n_windows, frame_len = A.frame_len;
+    for (int round = 0;; ++round) {
+        if (int rc = read_ctl(h, h->p_macq_ctl, A.ctl, s)) return rc;
+        if (pool && check_dup && round == 0 && ctl.dup)
+            return fail(h, RIA_ERR_INVALID, "%s: two windows of one call use one cache id, or an id is not below n_caches; no cache was touched", who);
+        const int n_list = static_cast<int>(ctl.n_list);
+        if (n_list == 0) break;
+        if (n_list > n_windows || round >= kMacqCandidates)
+            return fail(h, RIA_ERR_HIP, "%s: work list of round %d broke its bound (%d)", who, round, n_list);
+        A.cur = W.list[round & 1];
+        A.next = W.list[(round + 1) & 1];
+        A.n_cur = n_list;
+        int rc = mcdpsk_demod_impl(h, &c, samples_dev, stride, A.cur.offset, A.cur.bps, frame_len, n_list, A.cur.cfo, nullptr, W.llr, llr_ws, W.mst, s);
+        if (rc != RIA_OK) return rc;
+        // round A: CW0 of every entry, then the headers and the round-B row list
+        MacqArgs G = A;
+        G.row_entry = nullptr;
+        hipLaunchKernelGGL(macq_gather_kernel, dim3(static_cast<unsigned>(std::min<size_t>((static_cast<size_t>(n_list) * kMacqLdpcBlock + 255) / 256, 16384))),
+                           dim3(256), 0, s, G, n_list);
+        rc = ria_gpu_ldpc_decode_robust_batch(h, A.rows, n_list, W.out_a, W.ok_a, W.it_a, nullptr, s);
+        if (rc != RIA_OK) return rc;
+        if (ci && (rc = macq_round_a2(h, who, A, W, h->p_macq_ctl, s)) != RIA_OK) return rc;
+        const unsigned waves = static_cast<unsigned>(std::min((n_list + 3) / 4, 4096));
+        hipLaunchKernelGGL(macq_header_kernel, dim3(waves), dim3(256), 0, s, A);
+        hipLaunchKernelGGL(macq_rows_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A);
+        HIP_TRY(h, hipGetLastError());
+        if ((rc = read_ctl(h, h->p_macq_ctl, A.ctl, s)) != RIA_OK) return rc;
+        const int n_rows = static_cast<int>(ctl.n_rows);
+        if (n_rows < 0 || n_rows > n_list * (max_cw - 1))
+            return fail(h, RIA_ERR_HIP, "%s: codeword rows of round %d broke their bound (%d)", who, round, n_rows);
+        // round B: CW1..total_cw-1 of the entries whose header asks for them
+        if (n_rows > 0) {
+            hipLaunchKernelGGL(macq_gather_kernel, dim3(static_cast<unsigned>(std::min<size_t>((static_cast<size_t>(n_rows) * kMacqLdpcBlock + 255) / 256, 16384))),
+                               dim3(256), 0, s, A, n_rows);
+            rc = ria_gpu_ldpc_decode_robust_batch(h, A.rows, n_rows, W.out_b, W.ok_b, W.it_b, nullptr, s);
+            if (rc != RIA_OK) return rc;
+        }
+        if (pool && (rc = harq_stages(h, who, A, H, HW, h->p_macq_ctl, n_rows, waves, s)) != RIA_OK) return rc;
+        hipLaunchKernelGGL(macq_finish_kernel, dim3(waves), dim3(256), 0, s, A);
+        hipLaunchKernelGGL(macq_next_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A);
+        HIP_TRY(h, hipGetLastError());
+    }
+    return RIA_OK;
+}
+
 static int macq_impl(ria_gpu_handle h, const char* who, const ria_mcdpsk_config* cfg, const float* samples_dev, int64_t stride,
                      int search_len, int window_len, int n_windows, int frame_cw,
                      const ria_mcdpsk_acq_params* params_dev, uint32_t flags,
@@ -2272,7 +2330,6 @@ static int macq_impl(ria_gpu_handle h, const char* who, const ria_mcdpsk_config*
     HIP_TRY(h, h->d_macq_ws.reserve(carved_size(carve)));   // nothing of an earlier call is in flight: every call ends on a stream sync
     HIP_TRY(h, h->p_macq_ctl.reserve(sizeof(MacqCtl)));
     const MacqWs W = carve_at(h->d_macq_ws.as<>(), carve);
-    const MacqCtl& ctl = *h->p_macq_ctl.as<MacqCtl>();
     const int frame_row = RIA_MACQ_FRAME_BYTES(frame_cw);
     HIP_TRY(h, hipMemsetAsync(frame_out_dev, 0, n * frame_row, s));
     if (llr_out_dev) HIP_TRY(h, hipMemsetAsync(llr_out_dev, 0, n * static_cast<size_t>(llr_stride) * sizeof(float), s));
@@ -2318,50 +2375,8 @@ static int macq_impl(ria_gpu_handle h, const char* who, const ria_mcdpsk_config*
     A.frame_out = frame_out_dev; A.frame_row = frame_row; A.llr_out = llr_out_dev; A.llr_stride = llr_stride;
     if (ci) { A.ci_step = ci_step; A.ci_flag = W.ci_flag; A.ci_list = W.ci_list; A.ci_ctl = W.ci_ctl; }
     const ria_mcdpsk_config c = *cfg;
-    // 3.-5. rounds: round 0 runs every accepted window at its primary candidate, round r >= 1 the windows still searching at
-    // their next candidate that fits (at most 25 more rounds: each advances every window it holds by at least one candidate)
-    for (int round = 0;; ++round) {
-        if (int rc = read_ctl(h, h->p_macq_ctl, A.ctl, s)) return rc;
-        if (pool && round == 0 && ctl.dup)
-            return fail(h, RIA_ERR_INVALID, "%s: two windows of one call use one cache id, or an id is not below n_caches; no cache was touched", who);
-        const int n_list = static_cast<int>(ctl.n_list);
-        if (n_list == 0) break;
-        if (n_list > n_windows || round >= kMacqCandidates)
-            return fail(h, RIA_ERR_HIP, "%s: work list of round %d broke its bound (%d)", who, round, n_list);
-        A.cur = W.list[round & 1];
-        A.next = W.list[(round + 1) & 1];
-        A.n_cur = n_list;
-        int rc = mcdpsk_demod_impl(h, &c, samples_dev, stride, A.cur.offset, A.cur.bps, frame_len, n_list, A.cur.cfo, nullptr, W.llr, llr_ws, W.mst, s);
-        if (rc != RIA_OK) return rc;
-        // round A: CW0 of every entry, then the headers and the round-B row list
-        MacqArgs G = A;
-        G.row_entry = nullptr;
-        hipLaunchKernelGGL(macq_gather_kernel, dim3(static_cast<unsigned>(std::min<size_t>((static_cast<size_t>(n_list) * kMacqLdpcBlock + 255) / 256, 16384))),
-                           dim3(256), 0, s, G, n_list);
-        rc = ria_gpu_ldpc_decode_robust_batch(h, A.rows, n_list, W.out_a, W.ok_a, W.it_a, nullptr, s);
-        if (rc != RIA_OK) return rc;
-        if (ci && (rc = macq_round_a2(h, who, A, W, h->p_macq_ctl, s)) != RIA_OK) return rc;
-        const unsigned waves = static_cast<unsigned>(std::min((n_list + 3) / 4, 4096));
-        hipLaunchKernelGGL(macq_header_kernel, dim3(waves), dim3(256), 0, s, A);
-        hipLaunchKernelGGL(macq_rows_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A);
-        HIP_TRY(h, hipGetLastError());
-        if ((rc = read_ctl(h, h->p_macq_ctl, A.ctl, s)) != RIA_OK) return rc;
-        const int n_rows = static_cast<int>(ctl.n_rows);
-        if (n_rows < 0 || n_rows > n_list * (max_cw - 1))
-            return fail(h, RIA_ERR_HIP, "%s: codeword rows of round %d broke their bound (%d)", who, round, n_rows);
-        // round B: CW1..total_cw-1 of the entries whose header asks for them
-        if (n_rows > 0) {
-            hipLaunchKernelGGL(macq_gather_kernel, dim3(static_cast<unsigned>(std::min<size_t>((static_cast<size_t>(n_rows) * kMacqLdpcBlock + 255) / 256, 16384))),
-                               dim3(256), 0, s, A, n_rows);
-            rc = ria_gpu_ldpc_decode_robust_batch(h, A.rows, n_rows, W.out_b, W.ok_b, W.it_b, nullptr, s);
-            if (rc != RIA_OK) return rc;
-        }
-        if (pool && (rc = harq_stages(h, who, A, H, HW, h->p_macq_ctl, n_rows, waves, s)) != RIA_OK) return rc;
-        hipLaunchKernelGGL(macq_finish_kernel, dim3(waves), dim3(256), 0, s, A);
-        hipLaunchKernelGGL(macq_next_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A);
-        HIP_TRY(h, hipGetLastError());
-    }
-    return RIA_OK;
+    // 3.-5. the rounds
+    return macq_rounds(h, who, c, samples_dev, stride, A, W, pool, H, HW, ci, llr_ws, max_cw, true, s);
 }
 
 int ria_gpu_mcdpsk_acquire_batch(ria_gpu_handle h, const ria_mcdpsk_config* cfg, const float* samples_dev, int64_t stride,
@@ -2391,6 +2406,198 @@ int ria_gpu_mcdpsk_acquire_ci_batch(ria_gpu_handle h, const ria_mcdpsk_config* c
                                     ria_mcdpsk_harq_result* harq_dev, int interleaver_bits, void* stream) {
     return macq_impl(h, "ria_gpu_mcdpsk_acquire_ci_batch", cfg, samples_dev, stride, search_len, window_len, n_windows, frame_cw, params_dev, flags,
                      frame_out_dev, acq_dev, llr_out_dev, llr_stride, pool, cache_id_dev, now_ms_dev, harq_dev, true, interleaver_bits, stream);
+}
+
+// ------------------------------------------------------------------------------------------------ one MC-DPSK window
+static_assert(sizeof(ria_mcdpsk_window_result) == 64, "ria_mcdpsk_window_result is 64 bytes (include/ria_gpu.h)");
+static_assert(offsetof(ria_mcdpsk_acq_params, pending_total_cw) == 12 && offsetof(ria_mcdpsk_acq_params, first_avail) == 24 &&
+              offsetof(ria_mcdpsk_acq_params, last_decoded_sync) == 28 && offsetof(ria_mcdpsk_window_result, training_rms) == 32 &&
+              offsetof(ria_mcdpsk_window_result, deliver) == 44, "ria_gpu_mcdpsk_window_batch field offsets");
+static_assert(RIA_MWIN_NOT_ACCEPTED == kMwinNotAccepted && RIA_MWIN_REPLAY == kMwinReplay && RIA_MWIN_PING == kMwinPing &&
+              RIA_MWIN_PROCESS_FAILED == kMwinProcessFailed && RIA_MWIN_DECODED == kMwinDecoded && RIA_MWIN_NEED_SAMPLES == kMwinNeedSamples &&
+              RIA_MWIN_TOO_LONG == kMwinTooLong && RIA_MPEEK_NO_HEADER == kMpeekNoHeader && RIA_MPEEK_HEADER_SINGLE == kMpeekHeaderSingle &&
+              RIA_MPEEK_HEADER_MULTI == kMpeekHeaderMulti && RIA_MPEEK_CONNECT_FORCED == kMpeekConnectForced &&
+              RIA_MPEEK_HANDSHAKE_FALLBACK == kMpeekHandshakeFallback && RIA_MPEEK_EARLY_WINDOW == kMpeekEarlyWindow &&
+              RIA_MPEEK_HANDSHAKE_WINDOW == kMpeekHandshakeWindow && RIA_MPEEK_DEINTERLEAVED == kMpeekDeinterleaved &&
+              RIA_MPEEK_SALVAGE == kMpeekSalvage, "mcdpsk_window_rules.hpp mirrors include/ria_gpu.h");
+struct MwinWs { MwinSt* st; MwinCtl* wctl; uint8_t *tries_a, *tries_deint, *tries_a2; };
+static MwinWs mwin_carve(Carver& c, size_t n) {
+    MwinWs w;
+    w.st = c.take<MwinSt>(n);
+    w.wctl = c.take<MwinCtl>(1);
+    w.tries_a = c.take<uint8_t>(n);
+    w.tries_deint = c.take<uint8_t>(n);
+    w.tries_a2 = c.take<uint8_t>(n);
+    return w;
+}
+
+int ria_gpu_mcdpsk_window_batch(ria_gpu_handle h, const ria_mcdpsk_config* cfg, const float* samples_dev, int64_t stride,
+                                int search_len, int window_len, int n_windows,
+                                const ria_mcdpsk_acq_params* params_dev, uint32_t flags,
+                                uint8_t* frame_out_dev, int frame_row, ria_mcdpsk_window_result* result_dev,
+                                ria_mcdpsk_acq_result* acq_dev, float* llr_out_dev, int llr_stride,
+                                ria_chase_pool pool, const int32_t* cache_id_dev, const uint64_t* now_ms_dev,
+                                ria_mcdpsk_harq_result* harq_dev, int interleaver_bits, void* stream) {
+    const char* who = "ria_gpu_mcdpsk_window_batch";
+    if (!h) return RIA_ERR_INVALID;
+    const uint32_t known_flags = RIA_MACQ_SYNC_CHIRP | RIA_MACQ_DISCONNECTED | RIA_MACQ_NO_RETRY | RIA_MACQ_CHANNEL_INTERLEAVE;
+    const bool chirp = (flags & RIA_MACQ_SYNC_CHIRP) != 0, disconnected = (flags & RIA_MACQ_DISCONNECTED) != 0;
+    if (!mcdpsk_config_ok(cfg) || n_windows < 0 || search_len < 0 || window_len < search_len || stride < window_len ||
+        (flags & ~known_flags) != 0 || (disconnected && !chirp) || (!chirp && search_len > kZcMaxBuf) || frame_row < RIA_MACQ_FRAME_BYTES(8))
+        return fail(h, RIA_ERR_INVALID, "%s: bad argument (config, 0 <= search_len <= window_len <= stride, known flags, ZC only when "
+                                        "connected, frame_row >= RIA_MACQ_FRAME_BYTES(8))", who);
+    if (h->cfg.code_rate != RIA_RATE_1_4) return fail(h, RIA_ERR_INVALID, "%s: MC-DPSK frames are R1/4: the handle's rate must be RIA_RATE_1_4", who);
+    const bool ci = (flags & RIA_MACQ_CHANNEL_INTERLEAVE) != 0;
+    int ci_step = 0;
+    if (ci && !macq_ci_step(interleaver_bits, &ci_step)) return fail(h, RIA_ERR_INVALID, "%s: interleaver_bits %d outside 1..648", who, interleaver_bits);
+    const int nc = cfg->num_carriers, bps = cfg->bits_per_symbol, sp = cfg->spreading;
+    const bool retry = disconnected && !(flags & RIA_MACQ_NO_RETRY);
+    const int sym_per_cw = (kMacqLdpcBlock + nc * bps - 1) / (nc * bps);
+    MwinGeom g{};
+    g.window_len = window_len; g.cw_samples = sym_per_cw * kMcSps * sp; g.cw_bits = sym_per_cw * nc * bps; g.disconnected = disconnected ? 1 : 0;
+    // the longest pass: 8 codewords, what the window holds (a longer span never fits), what the demodulator's workgroup holds
+    int max_level = 0;
+    while (max_level < 8 && mwin_frame_len(g, max_level + 1) <= window_len &&
+           mcdpsk_lds_bytes(nc, static_cast<int>(mwin_frame_len(g, max_level + 1))) <= 160 * 1024) ++max_level;
+    int lds_level = 0;
+    while (lds_level < 8 && mcdpsk_lds_bytes(nc, static_cast<int>(mwin_frame_len(g, lds_level + 1))) <= 160 * 1024) ++lds_level;
+    g.max_level = lds_level;       // a count above it that fits the window is TOO_LONG; one that does not fit is NEED_SAMPLES first
+    auto llr_ws_of = [&](int cw) { return cw * sym_per_cw * nc * 2; };                           // either modulation
+    const int top = std::max(max_level, 1);
+    const int llr_need = top * sym_per_cw * nc * (retry ? 2 : bps);
+    if (llr_out_dev && llr_stride < llr_need) return fail(h, RIA_ERR_INVALID, "%s: llr_stride %d < %d soft bits", who, llr_stride, llr_need);
+    if (n_windows == 0) return RIA_OK;
+    if (!samples_dev || !params_dev || !frame_out_dev || !result_dev || !acq_dev) return fail(h, RIA_ERR_INVALID, "%s: null pointer", who);
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t n = static_cast<size_t>(n_windows), dec_bytes = static_cast<size_t>((h->geo.ldpc_k + 7) / 8);
+    const int top_max_cw = llr_ws_of(top) / kMacqLdpcBlock;
+    auto carve = [&](Carver& c) { return macq_carve(c, n, static_cast<size_t>(llr_ws_of(top)), static_cast<size_t>(top_max_cw), dec_bytes, ci); };
+    auto wcarve = [&](Carver& c) { return mwin_carve(c, n); };
+    HIP_TRY(h, h->d_macq_ws.reserve(carved_size(carve)));   // nothing of an earlier call is in flight: every call ends on a stream sync
+    HIP_TRY(h, h->d_mwin_ws.reserve(carved_size(wcarve)));
+    HIP_TRY(h, h->p_macq_ctl.reserve(sizeof(MacqCtl)));
+    HIP_TRY(h, h->p_mwin_ctl.reserve(sizeof(MwinCtl)));
+    const MacqWs W = carve_at(h->d_macq_ws.as<>(), carve);
+    const MwinWs WW = carve_at(h->d_mwin_ws.as<>(), wcarve);
+    HIP_TRY(h, hipMemsetAsync(frame_out_dev, 0, n * static_cast<size_t>(frame_row), s));
+    if (llr_out_dev) HIP_TRY(h, hipMemsetAsync(llr_out_dev, 0, n * static_cast<size_t>(llr_stride) * sizeof(float), s));
+    HIP_TRY(h, hipMemsetAsync(WW.wctl, 0, sizeof(MwinCtl), s));
+    HIP_TRY(h, hipMemsetAsync(WW.tries_deint, 0, n, s));
+    HarqArgs H{};
+    HarqWs HW{};
+    if (pool) {
+        if (int rc = harq_begin(h, who, pool, cache_id_dev, now_ms_dev, harq_dev, n_windows, n * static_cast<size_t>(top_max_cw), dec_bytes, W.ctl, s, &H, &HW)) return rc;
+    } else if (harq_dev) {
+        HIP_TRY(h, hipMemsetAsync(harq_dev, 0, n * sizeof(ria_mcdpsk_harq_result), s));
+    }
+    // 1. detection
+    const int pstride = static_cast<int>(sizeof(ria_mcdpsk_acq_params) / sizeof(float));
+    MwinArgs B{};
+    MacqArgs& A = B.M;
+    if (chirp) {
+        ria_chirp_result* det = reinterpret_cast<ria_chirp_result*>(W.det);
+        A.chirp = det;
+        if (int rc = sync_chirp_impl(h, samples_dev, stride, search_len, n_windows, 0.15f, det, s, &params_dev->detect_threshold, pstride)) return rc;
+    } else {
+        ria_zc_result* det = reinterpret_cast<ria_zc_result*>(W.det);
+        A.zc = det;
+        if (int rc = sync_zc_impl(h, samples_dev, stride, search_len, n_windows, 0.2f, 12u /* DATA | CONTROL */, &params_dev->known_cfo_hz,
+                                  det, s, &params_dev->detect_threshold, pstride)) return rc;
+    }
+    A.params = params_dev; A.n_windows = n_windows; A.window_len = window_len; A.stride = stride;
+    A.connected = !disconnected; A.retry = retry; A.bps = bps; A.acq = acq_dev; A.ctl = W.ctl; A.next = W.list[0];
+    A.mst = W.mst; A.llr = W.llr; A.rows = W.rows; A.row_entry = W.row_entry; A.row_cw = W.row_cw;
+    A.out_a = W.out_a; A.ok_a = W.ok_a; A.out_b = W.out_b; A.ok_b = W.ok_b;
+    A.dec_bytes = static_cast<int>(dec_bytes);
+    A.hdr_total = W.hdr; A.need_rows = W.need; A.row_base = W.base; A.done = W.done;
+    A.crc_bit = h->d_crc_bit.as<const uint16_t>(); A.crc_init = h->d_crc_init.as<const uint16_t>();
+    A.frame_out = frame_out_dev; A.frame_row = frame_row; A.llr_out = llr_out_dev; A.llr_stride = llr_stride;
+    if (ci) { A.ci_step = ci_step; A.ci_flag = W.ci_flag; A.ci_list = W.ci_list; A.ci_ctl = W.ci_ctl; }
+    B.g = g; B.samples = samples_dev; B.res = result_dev; B.st = WW.st; B.wctl = WW.wctl;
+    B.tries_a = WW.tries_a; B.tries_deint = WW.tries_deint; B.tries_a2 = WW.tries_a2;
+    const ria_mcdpsk_config c = *cfg;
+    const unsigned tgrid = static_cast<unsigned>(std::min((n_windows + 255) / 256, 1024));
+    // 2.-3. acceptance, anti-replay, the energy test and the passes that need no soft bits; then the peek list
+    hipLaunchKernelGGL(mwin_plan_kernel, dim3(tgrid), dim3(256), 0, s, B);
+    hipLaunchKernelGGL(mwin_energy_kernel, dim3(static_cast<unsigned>((n_windows + kMwinEnergyWaves - 1) / kMwinEnergyWaves)), dim3(64 * kMwinEnergyWaves), 0, s, B);
+    hipLaunchKernelGGL(mwin_list_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, B, 0);
+    HIP_TRY(h, hipGetLastError());
+    if (int rc = read_ctl(h, h->p_mwin_ctl, WW.wctl, s)) return rc;
+    if (h->p_mwin_ctl.as<MwinCtl>()->bad)
+        return fail(h, RIA_ERR_INVALID, "%s: a window's pending_total_cw is above 255, or its first_avail is below 9608 (connected: below the "
+                                        "1-codeword span); no cache was touched", who);
+    if (int rc = read_ctl(h, h->p_macq_ctl, A.ctl, s)) return rc;
+    const MacqCtl& ctl = *h->p_macq_ctl.as<MacqCtl>();
+    if (pool && ctl.dup)
+        return fail(h, RIA_ERR_INVALID, "%s: two windows of one call use one cache id, or an id is not below n_caches; no cache was touched", who);
+    // 4. the peek pass: process() on the 1-codeword span, CW0 (and the de-interleaved CW0), the rules
+    const int n_peek = static_cast<int>(ctl.n_list);
+    if (n_peek < 0 || n_peek > n_windows) return fail(h, RIA_ERR_HIP, "%s: the peek list broke its bound (%d)", who, n_peek);
+    if (n_peek > 0) {
+        if (max_level < 1) return fail(h, RIA_ERR_HIP, "%s: a peek pass without a span that fits", who);
+        A.frame_len = static_cast<int>(mwin_frame_len(g, 1));
+        A.llr_ws = llr_ws_of(1);
+        A.cur = W.list[0]; A.next = W.list[1]; A.n_cur = n_peek;
+        int rc = mcdpsk_demod_impl(h, &c, samples_dev, stride, A.cur.offset, A.cur.bps, A.frame_len, n_peek, A.cur.cfo, nullptr, W.llr, A.llr_ws, W.mst, s);
+        if (rc != RIA_OK) return rc;
+        MacqArgs G = A;
+        G.row_entry = nullptr;
+        hipLaunchKernelGGL(macq_gather_kernel, dim3(static_cast<unsigned>(std::min<size_t>((static_cast<size_t>(n_peek) * kMacqLdpcBlock + 255) / 256, 16384))),
+                           dim3(256), 0, s, G, n_peek);
+        rc = ria_gpu_ldpc_decode_robust_batch(h, A.rows, n_peek, W.out_a, W.ok_a, W.it_a, WW.tries_a, s);
+        if (rc != RIA_OK) return rc;
+        if (ci) {
+            if ((rc = macq_round_a2(h, who, A, W, h->p_macq_ctl, s, WW.tries_a2)) != RIA_OK) return rc;
+            hipLaunchKernelGGL(mwin_a2_tries_kernel, dim3(static_cast<unsigned>(std::min((n_peek + 255) / 256, 1024))), dim3(256), 0, s, B);
+        }
+        hipLaunchKernelGGL(mwin_peek_kernel, dim3(static_cast<unsigned>(std::min((n_peek + 3) / 4, 4096))), dim3(256), 0, s, B);
+        HIP_TRY(h, hipGetLastError());
+    }
+    // 5.-10. one list per codeword count, ascending: escalation and salvage only ever raise a window's count
+    for (int level = 1; level <= max_level; ++level) {
+        A.frame_len = static_cast<int>(mwin_frame_len(g, level));
+        A.llr_ws = llr_ws_of(level);
+        A.next = W.list[0];
+        hipLaunchKernelGGL(mwin_list_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, B, level);
+        HIP_TRY(h, hipGetLastError());
+        if (int rc = macq_rounds(h, who, c, samples_dev, stride, A, W, pool, H, HW, ci, A.llr_ws, A.llr_ws / kMacqLdpcBlock, false, s)) return rc;
+        hipLaunchKernelGGL(mwin_close_kernel, dim3(tgrid), dim3(256), 0, s, B, level);
+        HIP_TRY(h, hipGetLastError());
+    }
+    return RIA_OK;
+}
+
+// One window from host memory (ria_host::mcdpskWindow): staged through the handle's pinned + device block on the handle's own
+// stream, like ria_gpu_decode_frame_host.  No chase pool.
+int ria_gpu_mcdpsk_window_host(ria_gpu_handle h, const ria_mcdpsk_config* cfg, const float* samples_host, int search_len, int window_len,
+                               const ria_mcdpsk_acq_params* params_host, uint32_t flags, uint8_t* frame_out_host, int max_bytes,
+                               ria_mcdpsk_window_result* result_out, ria_mcdpsk_acq_result* acq_out, int interleaver_bits) {
+    if (!h) return RIA_ERR_INVALID;
+    const int frame_row = RIA_MACQ_FRAME_BYTES(8);
+    if (!samples_host || !params_host || !frame_out_host || !result_out || !acq_out || window_len < 1 || max_bytes < frame_row)
+        return fail(h, RIA_ERR_INVALID, "ria_gpu_mcdpsk_window_host: bad argument (null pointer, window_len >= 1, max_bytes >= RIA_MACQ_FRAME_BYTES(8))");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t b_x = static_cast<size_t>(window_len) * sizeof(float), o_p = up256(b_x), o_fr = up256(o_p + sizeof(ria_mcdpsk_acq_params));
+    const size_t o_res = up256(o_fr + frame_row), o_acq = up256(o_res + sizeof(ria_mcdpsk_window_result)), total = up256(o_acq + sizeof(ria_mcdpsk_acq_result));
+    int rc = ensure_host_stage(h, total);
+    if (rc != RIA_OK) return rc;
+    unsigned char *D = h->d_hstage.as<unsigned char>(), *P = h->p_hstage.as<unsigned char>();
+    hipStream_t s = h->hstream;
+    std::memcpy(P, samples_host, b_x);
+    std::memcpy(P + o_p, params_host, sizeof(ria_mcdpsk_acq_params));
+    HIP_TRY(h, hipMemcpyAsync(D, P, o_p + sizeof(ria_mcdpsk_acq_params), hipMemcpyHostToDevice, s));
+    rc = ria_gpu_mcdpsk_window_batch(h, cfg, reinterpret_cast<const float*>(D), window_len, search_len, window_len, 1,
+                                     reinterpret_cast<const ria_mcdpsk_acq_params*>(D + o_p), flags, D + o_fr, frame_row,
+                                     reinterpret_cast<ria_mcdpsk_window_result*>(D + o_res), reinterpret_cast<ria_mcdpsk_acq_result*>(D + o_acq),
+                                     nullptr, 0, nullptr, nullptr, nullptr, nullptr, interleaver_bits, s);
+    if (rc != RIA_OK) return rc;
+    HIP_TRY(h, hipMemcpyAsync(P + o_fr, D + o_fr, total - o_fr, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    std::memcpy(frame_out_host, P + o_fr, static_cast<size_t>(frame_row));
+    std::memcpy(result_out, P + o_res, sizeof(ria_mcdpsk_window_result));
+    std::memcpy(acq_out, P + o_acq, sizeof(ria_mcdpsk_acq_result));
+    return RIA_OK;
 }
 
 int ria_gpu_mcdpsk_interleave_batch(ria_gpu_handle h, int interleaver_bits, const uint8_t* coded_dev, int n_cw, uint8_t* out_dev, void* stream) {

@@ -677,6 +677,66 @@ class RxEngine:
         hq = self._status_array(harq, self.HARQ_RESULT)
         return (frames, res, llr, hq) if want_llr else (frames, res, hq)
 
+    MCWIN_PARAMS = np.dtype([("known_cfo_hz", "<f4"), ("detect_threshold", "<f4"), ("min_confidence", "<f4"), ("pending_total_cw", "<u4"),
+                             ("abs_base", "<u8"), ("first_avail", "<u4"), ("last_decoded_sync", "<i4")])
+    MCWIN_RESULT = np.dtype([("outcome", "<i4"), ("peek", "<i4"), ("next_pos", "<i4"), ("need_samples", "<i4"), ("pending_total_cw", "<i4"),
+                             ("frame_len", "<i4"), ("passes", "<i4"), ("peek_total_cw", "<i4"), ("training_rms", "<f4"), ("rms", "<f4"),
+                             ("last_decoded_sync", "<i4"), ("deliver", "u1"), ("is_ping", "u1"), ("peek_tries", "u1"), ("reserved0", "u1"),
+                             ("reserved", "<i4", 4)])
+    MCWIN_FRAME_ROW = 320    # RIA_MACQ_FRAME_BYTES(8)
+
+    def mcdpsk_window(self, windows, search_len, carriers=10, modulation="DBPSK", spreading=1, sync="chirp", disconnected=None,
+                      known_cfo=None, detect_threshold=None, min_confidence=None, abs_base=None, retry=True, want_llr=False,
+                      chase=None, cache_id=None, now_ms=None, channel_interleave=False, interleaver_bits=None,
+                      pending_total_cw=None, first_avail=None, last_decoded_sync=None):
+        """One MC-DPSK window the way StreamingDecoder::decodeCurrentFrame handles it (ria_gpu_mcdpsk_window_batch): detection
+        and acceptance, anti-replay, the PING energy test (disconnected), the CW0 peek and its escalation, decodeMCDPSKFrame on
+        the last pass's soft bits and the handshake fallbacks.  Arguments as mcdpsk_acquire, without frame_cw; per window
+        (scalars or one value each): pending_total_cw (default 0: a fresh sync), first_avail (default 0: a whole 1-codeword
+        span), last_decoded_sync (default None: no anti-replay position).  chase: a ChasePool; window b uses cache cache_id[b]
+        (default b, -1 = off) at now_ms.  channel_interleave / interleaver_bits as in mcdpsk_acquire.
+        Returns (frames uint8 [n, 320], result (MCWIN_RESULT), acq (MCACQ_RESULT with cw0_deinterleaved and ci_tried),
+        harq (HARQ_RESULT)[, llr float32 [n, stride]])."""
+        from .acquire import zc_min_confidence
+        n, window_len = windows.shape
+        assert windows.dtype == torch.float32 and windows.is_contiguous()
+        chirp = {"chirp": True, "zc": False}[sync]
+        if disconnected is None:
+            disconnected = chirp
+        bps = {"DBPSK": 1, "DQPSK": 2}[modulation] if isinstance(modulation, str) else int(modulation)
+        p = np.zeros(n, self.MCWIN_PARAMS)
+        p["known_cfo_hz"] = 0.0 if known_cfo is None else known_cfo
+        p["detect_threshold"] = (0.15 if chirp else 0.2) if detect_threshold is None else detect_threshold
+        p["min_confidence"] = (0.0 if chirp else zc_min_confidence(0)) if min_confidence is None else min_confidence
+        p["abs_base"] = 0 if abs_base is None else abs_base
+        p["pending_total_cw"] = 0 if pending_total_cw is None else pending_total_cw
+        p["first_avail"] = 0 if first_avail is None else first_avail
+        p["last_decoded_sync"] = capi.MWIN_NO_LAST_SYNC if last_decoded_sync is None else last_decoded_sync
+        params = torch.from_numpy(p.view(np.uint8).reshape(n, 32)).to(self.device)
+        fl = (capi.MACQ_SYNC_CHIRP if chirp else 0) | (capi.MACQ_DISCONNECTED if disconnected else 0) | (0 if retry else capi.MACQ_NO_RETRY) | \
+             (capi.MACQ_CHANNEL_INTERLEAVE if channel_interleave else 0)
+        row = self.MCWIN_FRAME_ROW
+        frames = torch.empty((n, row), dtype=torch.uint8, device=self.device)
+        res = torch.empty((n, 64), dtype=torch.uint8, device=self.device)
+        acq = torch.empty((n, 64), dtype=torch.uint8, device=self.device)
+        llr, stride = None, 0
+        if want_llr:
+            cw_samples = -(-648 // (carriers * bps)) * 512 * spreading
+            top = max(1, min(8, (window_len - 9 * 512) // cw_samples))
+            stride = top * -(-648 // (carriers * bps)) * carriers * 2
+            llr = torch.empty((n, stride), dtype=torch.float32, device=self.device)
+        cfg = capi.McdpskConfig(carriers, bps, spreading, 0)
+        ids, now, harq = self._harq_in(n, cache_id, now_ms)
+        bits = (carriers * bps if interleaver_bits is None else int(interleaver_bits)) if channel_interleave else 0
+        self._check(self.lib.ria_gpu_mcdpsk_window_batch(self.h, C.byref(cfg), _ptr(windows), window_len, int(search_len), window_len, n,
+                                                         _ptr(params), fl, _ptr(frames), row, _ptr(res), _ptr(acq), _ptr(llr), stride,
+                                                         chase.p if chase is not None else None, _ptr(ids), _ptr(now), _ptr(harq), bits,
+                                                         _stream_ptr()))
+        a = self._status_array(acq, self.MCACQ_RESULT)
+        a = self._ci_fields(a, a["reserved"][:, 0])
+        out = (frames, self._status_array(res, self.MCWIN_RESULT), a, self._status_array(harq, self.HARQ_RESULT))
+        return out + (llr,) if want_llr else out
+
     @staticmethod
     def _ci_fields(res, bits):
         """res with the two channel-interleaving bits of its reserved word as fields of their own"""

@@ -452,4 +452,35 @@ inline DecodeFrameResult decodeFrame(GpuHandle& gpu, const std::vector<float>& s
     return decodeFrame(gpu, soft_bits.data(), soft_bits.size(), use_channel_interleave);
 }
 
+// StreamingDecoder::decodeCurrentFrame() for the MC-DPSK mode on one window from host memory (ria_gpu_mcdpsk_window_host):
+// anti-replay, the PING energy test, the CW0 peek and its escalation, decodeMCDPSKFrame and the handshake fallbacks.  `gpu` is
+// an R1/4 handle.  window[0 .. search_len) is what the detector sees; pending_total_cw / first_avail / last_decoded_sync are
+// the decoder's state for this sync (0, 0, INT32_MIN: a fresh sync, a whole 1-codeword span, no anti-replay position).  A
+// failure of the library leaves outcome RIA_MWIN_NOT_ACCEPTED and the default DecodeResult.
+struct McdpskWindowResult {
+    ria_mcdpsk_window_result window{};    // outcome, peek, next_pos, need_samples, pending_total_cw, the two rms values, ...
+    ria_mcdpsk_acq_result acq{};          // the sync and the reported candidate's DecodeResult fields
+    Bytes frame_data;
+};
+inline McdpskWindowResult mcdpskWindow(GpuHandle& gpu, const ria_mcdpsk_config& cfg, const float* window, size_t window_len, size_t search_len,
+                                       bool chirp_sync, bool connected, float known_cfo_hz, float min_confidence,
+                                       uint32_t pending_total_cw = 0, uint32_t first_avail = 0, int32_t last_decoded_sync = INT32_MIN,
+                                       int interleaver_bits = 0) {
+    McdpskWindowResult r;
+    r.acq.frame_type = 0x10;
+    ria_mcdpsk_acq_params p{};
+    p.known_cfo_hz = known_cfo_hz;
+    p.detect_threshold = chirp_sync ? 0.15f : 0.2f;
+    p.min_confidence = min_confidence;
+    p.pending_total_cw = pending_total_cw; p.first_avail = first_avail; p.last_decoded_sync = last_decoded_sync;
+    const uint32_t flags = (chirp_sync ? RIA_MACQ_SYNC_CHIRP : 0u) | (connected ? 0u : RIA_MACQ_DISCONNECTED) |
+                           (interleaver_bits > 0 ? RIA_MACQ_CHANNEL_INTERLEAVE : 0u);
+    Bytes buf(RIA_MACQ_FRAME_BYTES(8));
+    if (ria_gpu_mcdpsk_window_host(gpu.get(), &cfg, window, static_cast<int>(search_len), static_cast<int>(window_len), &p, flags, buf.data(),
+                                   static_cast<int>(buf.size()), &r.window, &r.acq, interleaver_bits) != RIA_OK)
+        return r;
+    r.frame_data.assign(buf.begin(), buf.begin() + r.acq.frame_bytes);
+    return r;
+}
+
 }  // namespace ria_host
