@@ -155,7 +155,7 @@ int  ria_gpu_get_geometry(ria_gpu_handle h, ria_gpu_geometry* out);
 /* Execution knobs of a handle.  None of them changes a result; the parity tests run the fused call under every
  * value and compare.
  *   RIA_OPT_SPLIT_PARTS  ria_gpu_rx_batch cuts a batch of >= 4096 frames into this many parts that run on internal
- *                        streams (1..4; 1 = one stream, no overlap; 0 = library default (3), which the environment
+ *                        streams (1..4; 1 = one stream, no overlap; 0 = library default (3; 2 from 32768 frames on), which the environment
  *                        variables RIA_SPLIT_PARTS / RIA_NO_SPLIT may override). */
 #define RIA_OPT_SPLIT_PARTS 1
 /*   RIA_OPT_DUAL_DECODER the retry kernels (phase 0, cascade) decode two codewords per wavefront on an interleaved LDS
@@ -1307,6 +1307,11 @@ int ria_gpu_debug_recovery_counts(ria_gpu_handle h, int slot, uint32_t out[4]);
  * decodes behind its first converging one run or not depending on timing, so the counts vary a little from call to call.
  * All zero before the first call, with the option off and at a rate without the exit.  Synchronises the device. */
 int ria_gpu_debug_state_exits(ria_gpu_handle h, int slot, uint32_t out[4]);
+/* First decodes (factor 0.9375) of the last decode call on stream slot `slot`: out[0] those the frame walk did not make
+ * because an earlier codeword of the frame had failed (the decoder then stays at 0.875 and nobody reads them), out[1] those
+ * of them that were made after all because a phase-0 rescue put the decoder back to 0.9375.  Both are functions of the
+ * input alone.  Zero before the first call and without RIA_DECODE_PERTURB.  Synchronises the device. */
+int ria_gpu_debug_first_decodes(ria_gpu_handle h, int slot, uint32_t out[2]);
 
 #ifdef __cplusplus
 }

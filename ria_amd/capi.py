@@ -46,7 +46,7 @@ EXPORTS = [
     "ria_gpu_abi_version", "ria_gpu_demod_variant", "ria_gpu_default_config", "ria_gpu_create", "ria_gpu_destroy", "ria_gpu_last_error",
     "ria_gpu_get_geometry", "ria_gpu_set_option", "ria_gpu_demod_batch", "ria_gpu_decode_batch", "ria_gpu_ldpc_decode_batch", "ria_gpu_ldpc_decode_robust_batch",
     "ria_gpu_rx_batch", "ria_gpu_rx_frames_host", "ria_gpu_decode_frames_host", "ria_gpu_tx_batch", "ria_gpu_make_frames",
-    "ria_gpu_channel_batch", "ria_gpu_channel_exact_batch", "ria_gpu_channel_exact_seeded_batch", "ria_gpu_debug_math", "ria_gpu_debug_queue_fault", "ria_gpu_debug_recovery_counts", "ria_gpu_debug_state_exits", "ria_gpu_sync_zc_batch", "ria_gpu_zc_preamble", "ria_gpu_sync_chirp_batch", "ria_gpu_chirp_preamble", "ria_gpu_mcdpsk_demod_batch",
+    "ria_gpu_channel_batch", "ria_gpu_channel_exact_batch", "ria_gpu_channel_exact_seeded_batch", "ria_gpu_debug_math", "ria_gpu_debug_queue_fault", "ria_gpu_debug_recovery_counts", "ria_gpu_debug_state_exits", "ria_gpu_debug_first_decodes", "ria_gpu_sync_zc_batch", "ria_gpu_zc_preamble", "ria_gpu_sync_chirp_batch", "ria_gpu_chirp_preamble", "ria_gpu_mcdpsk_demod_batch",
     "ria_gpu_mcdpsk_modulate_host", "ria_gpu_chase_combine_batch", "ria_gpu_sync_lts_batch", "ria_gpu_sync_host", "ria_gpu_ldpc_encode_host", "ria_gpu_burst_deinterleave_batch", "ria_gpu_burst_interleave_batch",
     "ria_gpu_rx_acquire_batch", "ria_gpu_mcdpsk_acquire_batch", "ria_gpu_rx_burst_batch", "ria_gpu_encode_frames_batch", "ria_gpu_tx_coded_batch",
     "ria_gpu_sync_cox_batch", "ria_gpu_cox_preamble", "ria_gpu_channel_exact_cfo_batch", "ria_gpu_tx_cfo_batch",
@@ -238,6 +238,7 @@ def load(build_if_needed=True):
     L.ria_gpu_debug_queue_fault.argtypes = [vp]
     L.ria_gpu_debug_recovery_counts.argtypes = [vp, i32, vp]
     L.ria_gpu_debug_state_exits.argtypes = [vp, i32, vp]
+    L.ria_gpu_debug_first_decodes.argtypes = [vp, i32, vp]
     L.ria_gpu_channel_exact_batch.argtypes = [vp, i32, f32, u32, u64, vp, C.c_int64, i32, i32, vp]
     L.ria_gpu_channel_exact_seeded_batch.argtypes = [vp, i32, f32, vp, vp, C.c_int64, i32, i32, vp]
     L.ria_gpu_channel_exact_cfo_batch.argtypes = [vp, i32, f32, vp, vp, f32, vp, vp, C.c_int64, i32, i32, vp]

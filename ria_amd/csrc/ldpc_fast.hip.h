@@ -601,8 +601,12 @@ struct DecodeCtl {          // zeroed by hipMemsetAsync before every decode call
     unsigned int next_z;    // phase-0 work queue head
     unsigned int queue_fault;  // set by a persistent wave whose queue loop ran past its bound (see kQueueGuard)
     unsigned int exits[3];     // decodes ended by the repeated-state exit (fast_decode, EX): phase 0, cascade, recovery fill
+    unsigned int skipped;      // first decodes fast_primary_kernel did not make (codewords behind a failure; RIA_DECODE_PERTURB only)
+    unsigned int late_made;    // of those, the decodes fast_late_kernel made after all (behind a phase-0 rescue)
+    unsigned int n_late;       // frames fast_chain_kernel left to fast_late_kernel
+    unsigned int pad;
 };
-static_assert(sizeof(DecodeCtl) == 32, "control block layout");
+static_assert(sizeof(DecodeCtl) == 48, "control block layout");
 enum { kExitsPhase0 = 0, kExitsCascade = 1, kExitsFill = 2 };
 // Queue pops are written in the all-lane form (lane 0 adds 1, the others 0, then readfirstlane).  The round-1 hang had this
 // cause, read off the ISA of tools/probes/queue_pop_probe.hip: with the pop written `u = 0; if (lane == 0) u = atomicAdd(..);
@@ -646,8 +650,9 @@ struct FastDecodeArgs {
     uint8_t* res_bytes;      // [4*n_frames][5][bytes_per_cw]
     CascadeWin* win;         // [4*n_frames]  result of the best successful cascade attempt so far, per entry
     float* staged;           // [4*n_frames][kStageFloats]  de-interleaved decoder input of list1 entry i, in register order
-    unsigned int* l1idx;     // [4*n_frames]  codeword -> its list1 index, kNotListed for the others (written by fast_mark_kernel when a retry flag is set)
+    unsigned int* l1idx;     // [4*n_frames]  codeword -> its list1 index, kNotListed for the others (written by fast_primary_kernel when a retry flag is set)
     unsigned int* l1hash;    // [4*n_frames]  list1 entry -> hash of its first 16 soft bits (seed of the perturbation RNG)
+    unsigned int* late;      // [n_frames]  frames whose walk met a slot that was not computed (fast_chain_kernel -> fast_late_kernel)
     uint32_t* seed_ws;       // [cascade grid][kSeedWsWords]  seeded mt19937 states of the attempt group a cascade workgroup is on (this stream slot's)
     uint32_t* state_ws;      // [max(persistent grid, fill grid)][kStateWsWords]  copy of the decoder state a retry workgroup compares with (fast_decode, EX; this stream slot's)
     int state_exit;          // RIA_OPT_STATE_EXIT: the retry kernels end a failing decode whose message state repeats (fast_decode, EX)
@@ -658,11 +663,10 @@ struct FastDecodeArgs {
 };
 
 // A codeword that needs more than its first decode is decoded up to 4 + 34 more times.  Its soft bits are gathered
-// from the frame's interleaved stream once (fast_stage_kernel) into the order the decoder's registers want them
+// from the frame's interleaved stream once (fast_primary_kernel, when it lists the codeword) into the order the decoder's registers want them
 // (value r of lane l at [r*64 + l], information part then parity part), so every later unit is (NC+NR) coalesced
 // loads instead of a walk over the whole 10 KB frame.
 constexpr int kStageFloats = 12 * 64;
-constexpr int kStageFrameFloats = 2688;   // largest interleaved frame: 2592 coded bits rounded up to whole symbols (D8PSK: 2650)
 
 constexpr float kIdleRowLlr = 1e30f;   // idle row lanes: a parity bit that is certainly 0 keeps their syndrome term 0
 
@@ -707,7 +711,7 @@ __device__ inline void fast_publish(CwResult* res, unsigned fc, int f, bool ok, 
 }
 
 // decode codeword `fc` (= frame*4 + cw) with factor index f and record the result; staged != nullptr: the
-// codeword's de-interleaved input (fast_stage_kernel) instead of the gather from the frame
+// codeword's de-interleaved input (fast_list_codeword) instead of the gather from the frame
 template <class S, int NCV = S::kCv, bool EX = false>
 __device__ inline void fast_unit(FastState<S>& st, const FastDecodeArgs& A, unsigned char* lds, unsigned fc, int f, int lane,
                                  const float* staged = nullptr, unsigned int* exits = nullptr, uint32_t* state_ws = nullptr) {
@@ -722,50 +726,24 @@ __device__ inline void fast_unit(FastState<S>& st, const FastDecodeArgs& A, unsi
 }
 
 // ------------------------------------------------------------------------------------------------ kernel P
-// first decode of every codeword (factor 0.9375): one single-wave workgroup per codeword, so the
-// hardware dispatcher balances converging (few iterations) and hopeless (80 iterations) codewords.
-// XCD-aware order: workgroups are dealt to the 8 XCDs round-robin (blockIdx % 8) and each XCD has its own
-// L2, while the four codewords of a frame gather from the SAME 10 KB of interleaved soft bits; the map
-// below gives the four codewords of frame 8g+x the block ids 32g + 8cw + x, i.e. one XCD per frame.
+// First decodes (factor 0.9375): one single-wave workgroup per FRAME walks the frame's four codewords in the decoder's
+// order, so it knows when the first of them fails.  From there on the reference's decoder object stays at 0.875 for the
+// rest of the frame (fast_chain_kernel below): a later codeword makes its first decode from state[1], which is phase-0
+// unit t = 1, and nobody reads its state[0].  With RIA_DECODE_PERTURB those 0.9375 decodes are therefore not made
+// (DecodeCtl::skipped counts them); the one reader left, a codeword behind a phase-0 rescue (which puts the decoder back
+// to 0.9375), is served by fast_late_kernel.  Without RIA_DECODE_PERTURB the factor never leaves 0.9375 and every
+// codeword is decoded here.
+// The wave that meets the failure holds that codeword and, in turn, every later one in registers in the decoder's order
+// (st.li / st.lp), which is the layout of `staged`: it lists them itself (list1, l1idx, the staged row, the seed hash).
+// The tables are loaded once per frame, the frame's 10 KB of soft bits are read by one wave, and the hardware dispatcher
+// still balances converging and hopeless codewords: a wave runs at most three converging decodes and one failing one.
 // The first decodes mostly converge within a few iterations: their time is input gathers and set-up latency, and a fourth
-// wave per SIMD (no own-c2v words in registers: 122 VGPRs at R1/2) hides more of it than the saved LDS re-reads are worth
-// (measured: decode stage -0.12 ms per 25 000 frames); the 80-iteration retry kernels are the other way round (Shape::kCv).
+// wave per SIMD (no own-c2v words in registers) hides more of it than the saved LDS re-reads are worth (measured: decode
+// stage -0.12 ms per 25 000 frames); the 80-iteration retry kernels are the other way round (Shape::kCv).
 #ifndef RIA_PRIMARY_NCV
 #define RIA_PRIMARY_NCV 0
 #endif
-template <class S>
-__global__ __launch_bounds__(64) void fast_primary_kernel(FastDecodeArgs A) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int lane = threadIdx.x;
-    const unsigned b = blockIdx.x, g = b >> 5, r = b & 31u, cw = r >> 3, x = r & 7u;
-    const unsigned frame = 8u * g + x;
-    if (frame >= static_cast<unsigned>(A.n_frames)) return;
-    FastState<S> st;
-    fast_load_tables(st, A.c, smem, lane);
-    fast_unit<S, RIA_PRIMARY_NCV>(st, A, smem, 4u * frame + cw, 0, lane);
-}
-
 constexpr unsigned int kNotListed = 0xFFFFFFFFu;
-
-// per frame: every codeword at or after the first one whose first decode failed may need the other
-// four factors (phase 0 itself, or a first decode that inherits factor 0.875 through the chain)
-__global__ void fast_mark_kernel(FastDecodeArgs A) {
-    int frame = blockIdx.x * blockDim.x + threadIdx.x;
-    if (frame >= A.n_frames) return;
-    if (!(A.flags & (RIA_DECODE_PHASE0 | RIA_DECODE_PERTURB))) return;
-    bool failed = false;
-    for (int cw = 0; cw < 4; ++cw) {
-        unsigned fc = static_cast<unsigned>(frame) * 4u + cw;
-        failed = failed || A.res[fc].state[0] != 2;
-        if (failed) {
-            const unsigned i = atomicAdd(&A.ctl->n_list1, 1u);
-            A.list1[i] = fc;
-            A.l1idx[fc] = i;
-        } else {
-            A.l1idx[fc] = kNotListed;   // recovery_fill_kernel: no staged copy of this codeword
-        }
-    }
-}
 
 // hash of the bit patterns of the codeword's first 16 LLRs (frame_v2.cpp:1391-1396)
 __device__ inline uint32_t fast_hash16(const float* fl, const uint16_t* gather, int cw, int lane) {
@@ -778,39 +756,59 @@ __device__ inline uint32_t fast_hash16(const float* fl, const uint16_t* gather, 
     return h;
 }
 
-// one workgroup per list1 entry: the frame's soft bits come in as coalesced rows into LDS (one pass over the 10 KB
-// frame: scattered 4-byte misses to the same line are not merged on their way to HBM), the codeword is gathered from
-// LDS in register order (see kStageFloats), and the perturbation seed hash of its first 16 soft bits is kept
+// makes codeword fc, whose decoder input is in st.li / st.lp, list1 entry i: the staged row in register order (see
+// kStageFloats) and the perturbation seed hash of its first 16 soft bits
 template <class S>
-__global__ __launch_bounds__(256) void fast_stage_kernel(FastDecodeArgs A) {
-    __shared__ float fr[kStageFrameFloats];
+__device__ inline void fast_list_codeword(const FastState<S>& st, const FastDecodeArgs& A, const float* fl, unsigned fc, unsigned i,
+                                          int lane) {
+    static_assert((S::NC + S::NR) * 64 <= kStageFloats, "stage slot too small");
+    lane = opaque_lane(lane);
+    float* dst = A.staged + static_cast<size_t>(i) * kStageFloats;
+#pragma unroll
+    for (int r = 0; r < S::NC; ++r) dst[r * 64 + lane] = st.li[r];
+#pragma unroll
+    for (int r = 0; r < S::NR; ++r) dst[(S::NC + r) * 64 + lane] = st.lp[r];
+    const uint32_t h = fast_hash16(fl, A.gather, static_cast<int>(fc & 3u), lane);
+    if (lane == 0) { A.list1[i] = fc; A.l1idx[fc] = i; A.l1hash[i] = h; }
+}
+
+template <class S>
+__global__ __launch_bounds__(64) void fast_primary_kernel(FastDecodeArgs A) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = threadIdx.x;
+    const unsigned frame = blockIdx.x;   // the grid is n_frames
     const FastCode& c = A.c;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const unsigned n = A.ctl->n_list1;
-    const int nfl = A.llr_stride < kStageFrameFloats ? A.llr_stride : kStageFrameFloats;
-    for (unsigned i = blockIdx.x; i < n; i += gridDim.x) {
-        const unsigned fc = A.list1[i], cw = fc & 3u;
-        const float* fl = A.llr + static_cast<size_t>(fc >> 2) * A.llr_stride;
-        __syncthreads();
-        for (int q = tid; q < nfl; q += 256) fr[q] = fl[q];
-        __syncthreads();
-        float* dst = A.staged + static_cast<size_t>(i) * kStageFloats;
-        for (int r = wave; r < S::NC + S::NR; r += 4) {
-            float v;
-            if (r < S::NC) {
-                const uint32_t j = c.col_at[lane + 64 * r];
-                v = (j != 0xFFFFu) ? llr_canon(fr[A.gather[cw * 648 + j]]) : 0.0f;
-            } else {
-                const uint32_t k = c.check_at[lane + 64 * (r - S::NC)];
-                v = (k != 0xFFFFu) ? llr_canon(fr[A.gather[cw * 648 + c.k + k]]) : kIdleRowLlr;
+    FastState<S> st;
+    fast_load_tables(st, c, smem, lane);
+    const float* fl = A.llr + static_cast<size_t>(frame) * A.llr_stride;
+    const bool retry = (A.flags & (RIA_DECODE_PHASE0 | RIA_DECODE_PERTURB)) != 0u;   // somebody reads list1
+    const bool skip = (A.flags & RIA_DECODE_PERTURB) != 0u;                           // the decoder stays at 0.875 behind a failure
+    bool failed = false;                  // wave-uniform: a codeword of this frame has failed
+    unsigned first = 0, base = 0, skipped = 0;
+#pragma unroll 1
+    for (unsigned cw = 0; cw < 4u; ++cw) {
+        const unsigned fc = 4u * frame + cw;
+        fast_gather_llr(st, c, fl, A.gather, static_cast<int>(cw), lane);
+        if (failed && skip) ++skipped;
+        else {
+            bool ok;
+            const int it = fast_decode<S, RIA_PRIMARY_NCV>(st, c, smem, kFactors[0], c.max_iter, lane, &ok);
+            if (ok) fast_pack(st, c, smem, A.res_bytes + static_cast<size_t>(fc) * kNumFactors * c.bytes_per_cw, c.bytes_per_cw, lane);
+            fast_publish(A.res, fc, 0, ok, it, lane);
+            if (!ok && !failed) {
+                failed = true;
+                first = cw;
+                if (retry) {   // this codeword and every later one of the frame: one reservation, all-lane form (see RIA_QUEUE_GUARD)
+                    base = atomicAdd(&A.ctl->n_list1, lane == 0 ? 4u - cw : 0u);
+                    base = __builtin_amdgcn_readfirstlane(base);
+                }
             }
-            dst[r * 64 + lane] = v;
         }
-        if (wave == 0) {
-            const uint32_t h = fast_hash16(fr, A.gather, cw, lane);
-            if (lane == 0) A.l1hash[i] = h;
-        }
+        if (!retry) continue;
+        if (failed) fast_list_codeword(st, A, fl, fc, base + (cw - first), lane);
+        else if (lane == 0) A.l1idx[fc] = kNotListed;   // recovery_fill_kernel: no staged copy of this codeword
     }
+    if (skipped != 0u && lane == 0) atomicAdd(&A.ctl->skipped, skipped);
 }
 
 // ------------------------------------------------------------------------------------------------ kernel Z
@@ -868,45 +866,140 @@ __global__ __launch_bounds__(64) void fast_phase0_kernel(FastDecodeArgs A) {
 // phase 0 and left at 0.875 by phases 1-2 (frame_v2.cpp:1359-1361,1412,1447,1470), so a codeword that
 // follows one that needed phase >= 1 makes its FIRST decode at 0.875.
 // Slots read, against the slots fast_phase0_kernel may skip (slot t > 1 of a listed codeword, and only where one of
-// state[1..t-1] is 2): state[0] is the primary kernel's and always there.  state[f] with f == 1 is slot 1, which is
+// state[1..t-1] is 2) and the slot 0 fast_primary_kernel may skip (a codeword behind a failure): state[0] is read with f == 0
+// only, i.e. for codeword 0, for a codeword no failure precedes, or behind a phase-0 rescue; in the last case alone it can be
+// 0, and then the frame goes to fast_late_kernel, which computes it.  state[f] with f == 1 is slot 1, which is
 // never skipped, and f == 1 only follows a codeword that failed, so this codeword is listed.  The phase-0 walk below
 // reads state[1], state[2], ... in ascending order and stops at the first that is 2 (t*): each slot t it reaches has
 // state[1..t-1] != 2, the very condition under which unit t runs.  The bytes and iteration count are read for the
 // accepted slot only (0, 1 or t*).  So no slot read here can have been skipped, whatever the interleaving of the units.
-__global__ void fast_chain_kernel(FastDecodeArgs A) {
-    int frame = blockIdx.x * blockDim.x + threadIdx.x;
-    if (frame >= A.n_frames) return;
-    const int bpc = A.c.bytes_per_cw;
+// What the walk decides for the four codewords of a frame; fast_chain_commit writes it out.
+struct ChainPlan {
+    int accept[4];       // slot of the result table the codeword's bytes come from, -1: none
+    int attempts[4], iters[4];
+    bool cascade[4];     // the codeword becomes a cascade entry
+};
+// The walk over r, the frame's four rows of the result table.  Returns -1 when the plan is complete, else the first codeword
+// whose slot *f_missing (the decoder's factor index when it reaches that codeword) is 0 = "not computed": a first decode
+// fast_primary_kernel skipped and a phase-0 rescue of the codeword before it makes the chain read after all.
+__device__ inline int fast_chain_walk(const CwResult (&r)[4], uint32_t flags, ChainPlan& p, int* f_missing) {
     int f = 0;  // index into kFactors of the decoder's current factor (0 -> 0.9375, 1 -> 0.875)
-    ria_decode_status* s = A.status + frame;
+#pragma unroll
     for (int cw = 0; cw < 4; ++cw) {
-        const unsigned fc = static_cast<unsigned>(frame) * 4u + cw;
-        const CwResult r = A.res[fc];
-        int accept = -1, attempts = 1, iters = r.iters[f];
-        if (r.state[f] == 2) accept = f;
+        const CwResult& q = r[cw];
+        const int sf = f ? q.state[1] : q.state[0];
+        if (sf == 0) { *f_missing = f; return cw; }
+        int accept = -1, attempts = 1, iters = f ? q.iters[1] : q.iters[0];
+        bool cascade = false;
+        if (sf == 2) accept = f;
         else {
-            if (A.flags & RIA_DECODE_PHASE0) {
-                for (int t = 1; t <= 4 && accept < 0; ++t) { attempts++; if (r.state[t] == 2) { accept = t; iters = r.iters[t]; } }
+            if (flags & RIA_DECODE_PHASE0) {
+#pragma unroll
+                for (int t = 1; t <= 4; ++t)
+                    if (accept < 0) { attempts++; if (q.state[t] == 2) { accept = t; iters = q.iters[t]; } }
                 f = 0;
             }
-            if (accept < 0 && (A.flags & RIA_DECODE_PERTURB)) {
-                f = 1;
-                unsigned e = atomicAdd(&A.ctl->n_entries, 1u);
-                A.entries[e] = fc;
-                A.best[e] = 0xFFFFFFFFu;
-                A.win[e].lock = 0u;
-            }
+            if (accept < 0 && (flags & RIA_DECODE_PERTURB)) { f = 1; cascade = true; }
+        }
+        p.accept[cw] = accept; p.attempts[cw] = attempts; p.iters[cw] = iters; p.cascade[cw] = cascade;
+    }
+    return -1;
+}
+// one thread writes a frame's outputs and enqueues its cascade entries: exactly once per frame
+__device__ inline void fast_chain_commit(const FastDecodeArgs& A, unsigned frame, const ChainPlan& p) {
+    const int bpc = A.c.bytes_per_cw;
+    ria_decode_status* s = A.status + frame;
+#pragma unroll
+    for (int cw = 0; cw < 4; ++cw) {
+        const unsigned fc = frame * 4u + cw;
+        if (p.cascade[cw]) {
+            unsigned e = atomicAdd(&A.ctl->n_entries, 1u);
+            A.entries[e] = fc;
+            A.best[e] = 0xFFFFFFFFu;
+            A.win[e].lock = 0u;
         }
         uint8_t* out = A.info_out + static_cast<size_t>(fc) * bpc;
-        if (accept >= 0) {
-            const uint8_t* src = A.res_bytes + (static_cast<size_t>(fc) * kNumFactors + accept) * bpc;
+        if (p.accept[cw] >= 0) {
+            const uint8_t* src = A.res_bytes + (static_cast<size_t>(fc) * kNumFactors + p.accept[cw]) * bpc;
             for (int b = 0; b < bpc; ++b) out[b] = src[b];
         } else {
             for (int b = 0; b < bpc; ++b) out[b] = 0;
         }
-        s->cw_ok[cw] = accept >= 0 ? 1 : 0;
-        s->iterations[cw] = static_cast<uint16_t>(iters);
-        s->attempts[cw] = static_cast<uint8_t>(attempts);
+        s->cw_ok[cw] = p.accept[cw] >= 0 ? 1 : 0;
+        s->iterations[cw] = static_cast<uint16_t>(p.iters[cw]);
+        s->attempts[cw] = static_cast<uint8_t>(p.attempts[cw]);
+    }
+}
+__global__ void fast_chain_kernel(FastDecodeArgs A) {
+    const int frame = blockIdx.x * blockDim.x + threadIdx.x;
+    if (frame >= A.n_frames) return;
+    CwResult r[4];
+#pragma unroll
+    for (int cw = 0; cw < 4; ++cw) r[cw] = A.res[static_cast<unsigned>(frame) * 4u + cw];
+    ChainPlan p;
+    int f_missing;
+    if (fast_chain_walk(r, A.flags, p, &f_missing) >= 0) {   // nothing is written for this frame here: fast_late_kernel walks it again
+        A.late[atomicAdd(&A.ctl->n_late, 1u)] = static_cast<unsigned>(frame);
+        return;
+    }
+    fast_chain_commit(A, static_cast<unsigned>(frame), p);
+}
+
+// ------------------------------------------------------------------------------------------------ kernel L
+// The frames fast_chain_kernel deferred (a handful per 100 000): one wave per frame, grid-stride over the device-side count,
+// walks the frame from codeword 0 with the same function.  Where the walk stops at a slot that was never computed the wave
+// makes that decode on the spot from the codeword's staged row (a skipped codeword follows a failure, so it is listed),
+// records it in its copy of the table rows as well, and walks again: any number of rescues in one frame is served here, in
+// at most three decodes (codeword 0 is always decoded by fast_primary_kernel).  It runs between the chain and the cascade,
+// so the cascade entries it enqueues are served like the chain's.  No wave waits for another; every loop is bounded.
+template <class S>
+__global__ __launch_bounds__(64) void fast_late_kernel(FastDecodeArgs A) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = threadIdx.x;
+    const FastCode& c = A.c;
+    const unsigned n = A.ctl->n_late;
+    if (blockIdx.x >= n) return;
+    FastState<S> st;
+    fast_load_tables(st, c, smem, lane);
+    for (unsigned i = blockIdx.x; i < n; i += gridDim.x) {
+        const unsigned frame = A.late[i];
+        CwResult r[4];
+#pragma unroll
+        for (int cw = 0; cw < 4; ++cw) r[cw] = A.res[frame * 4u + cw];
+        ChainPlan p;
+        unsigned made = 0;
+        int m = 0;
+        for (int pass = 0; pass <= 4; ++pass) {   // four codewords: at most four slots can be missing, the fifth walk is complete
+            int f = 0;
+            m = fast_chain_walk(r, A.flags, p, &f);
+            m = __builtin_amdgcn_readfirstlane(m);   // every lane read the same rows: wave-uniform
+            f = __builtin_amdgcn_readfirstlane(f);
+            if (m < 0 || pass == 4) break;
+            const unsigned fc = frame * 4u + static_cast<unsigned>(m);
+            const unsigned li = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(A.l1idx[fc])));
+            if (li != kNotListed) fast_load_staged(st, A.staged + static_cast<size_t>(li) * kStageFloats, lane);
+            else fast_gather_llr(st, c, A.llr + static_cast<size_t>(frame) * A.llr_stride, A.gather, m, lane);
+            bool ok;
+            const int it = fast_decode<S, RIA_PRIMARY_NCV>(st, c, smem, kFactors[f], c.max_iter, lane, &ok);
+            if (ok) fast_pack(st, c, smem, A.res_bytes + (static_cast<size_t>(fc) * kNumFactors + f) * c.bytes_per_cw, c.bytes_per_cw, lane);
+            fast_publish(A.res, fc, f, ok, it, lane);
+#pragma unroll
+            for (int cw = 0; cw < 4; ++cw)
+                if (cw == m) {
+                    if (f) { r[cw].state[1] = ok ? 2 : 1; r[cw].iters[1] = static_cast<uint16_t>(it); }
+                    else { r[cw].state[0] = ok ? 2 : 1; r[cw].iters[0] = static_cast<uint16_t>(it); }
+                }
+            ++made;
+        }
+        if (m >= 0) {   // cannot happen: a walk after four completed slots finds none missing
+            if (lane == 0) atomicExch(&A.ctl->queue_fault, 1u);
+            continue;
+        }
+        __threadfence();   // the bytes fast_pack stored are read back through the cache below
+        if (lane == 0) {
+            fast_chain_commit(A, frame, p);
+            atomicAdd(&A.ctl->late_made, made);
+        }
     }
 }
 

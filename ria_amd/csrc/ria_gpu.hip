@@ -208,6 +208,7 @@ struct DecodeWs {
     CascadeWin* win;
     float* staged;                // [4 * n][kStageFloats]
     unsigned int *l1idx, *l1hash;
+    unsigned int* late;           // [n]
 };
 static DecodeWs decode_ws_carve(Carver& c, size_t n_frames, size_t bytes_per_cw) {
     const size_t n4 = 4 * n_frames;
@@ -221,10 +222,13 @@ static DecodeWs decode_ws_carve(Carver& c, size_t n_frames, size_t bytes_per_cw)
     w.staged = c.take<float>(n4 * kStageFloats);
     w.l1idx = c.take<unsigned int>(n4);
     w.l1hash = c.take<unsigned int>(n4);
+    w.late = c.take<unsigned int>(n_frames);
     return w;
 }
 // workgroups that own an area of d_state_ws: the persistent grid of phase 0 and the cascade, or the fill's
 constexpr int kFillGrid = 3072;
+constexpr int kTwoPartFrames = 32768;   // ria_gpu_rx_batch: from this batch size on the default split is two parts, below it three
+constexpr int kLateGrid = 256;   // workgroups of fast_late_kernel: a handful of frames per 100 000 reach it
 static int state_grid_size() { return std::max(persist_grid_size(false), kFillGrid); }
 static hipError_t ensure_decode_ws(ria_gpu_handle h, int n_frames) {
     bool state_exit_rate = false;
@@ -251,6 +255,7 @@ static void set_fast_attributes(int rate, int wb) {
         using S = decltype(s);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fast_primary_kernel<S>), hipFuncAttributeMaxDynamicSharedMemorySize, wb);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fast_phase0_kernel<S>), hipFuncAttributeMaxDynamicSharedMemorySize, wb);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fast_late_kernel<S>), hipFuncAttributeMaxDynamicSharedMemorySize, wb);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fast_cascade_kernel<S>), hipFuncAttributeMaxDynamicSharedMemorySize, wb);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fast_rows_kernel<S>), hipFuncAttributeMaxDynamicSharedMemorySize, wb);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fast_robust_kernel<S>), hipFuncAttributeMaxDynamicSharedMemorySize, wb);
@@ -725,6 +730,7 @@ static int launch_decode(ria_gpu_handle h, const float* llr_dev, int llr_stride,
     A.staged = W.staged + o4 * kStageFloats;
     A.l1idx = W.l1idx + o4;
     A.l1hash = W.l1hash + o4;
+    A.late = W.late + ws_off;
     A.seed_ws = h->d_seed_ws.as<uint32_t>() + static_cast<size_t>(slot) * persist_grid_size(false) * kSeedWsWords;
     dispatch_shape(h->cfg.code_rate, [&](auto sh) { A.state_exit = decltype(sh)::kStateExit ? h->state_exit : 0; });
     A.state_ws = h->d_state_ws ? h->d_state_ws.as<uint32_t>() + static_cast<size_t>(slot) * state_grid_size() * kStateWsWords : nullptr;
@@ -750,14 +756,8 @@ static int launch_decode(ria_gpu_handle h, const float* llr_dev, int llr_stride,
     };
     dispatch_shape(h->cfg.code_rate, [&](auto sh) {
         using S = decltype(sh);
-        hipLaunchKernelGGL(fast_primary_kernel<S>, dim3(32 * ((n_frames + 7) / 8)), dim3(64), wb, s, A);
+        hipLaunchKernelGGL(fast_primary_kernel<S>, dim3(n_frames), dim3(64), wb, s, A);
         stage("primary");
-        hipLaunchKernelGGL(fast_mark_kernel, dim3((n_frames + 255) / 256), dim3(256), 0, s, A);
-        stage("mark");
-        if (flags & (RIA_DECODE_PHASE0 | RIA_DECODE_PERTURB)) {
-            hipLaunchKernelGGL(fast_stage_kernel<S>, dim3(std::min(4 * n_frames, 8192)), dim3(256), 0, s, A);
-            stage("stage");
-        }
         if (flags & (RIA_DECODE_PHASE0 | RIA_DECODE_PERTURB)) {
 #ifdef RIA_WITH_DUAL_DECODER
             if (dual) hipLaunchKernelGGL(dual_phase0_kernel<S>, dim3(std::min(n_frames * 8, persist_grid)), dim3(64), DualInfo<S>::lds_bytes, s, A);
@@ -768,6 +768,11 @@ static int launch_decode(ria_gpu_handle h, const float* llr_dev, int llr_stride,
         stage("phase0");
         hipLaunchKernelGGL(fast_chain_kernel, dim3((n_frames + 255) / 256), dim3(256), 0, s, A);
         stage("chain");
+        // a first decode is skipped under RIA_DECODE_PERTURB only, and the chain reads a skipped one behind a phase-0 rescue only
+        if ((flags & RIA_DECODE_PERTURB) && (flags & RIA_DECODE_PHASE0)) {
+            hipLaunchKernelGGL(fast_late_kernel<S>, dim3(std::min(n_frames, kLateGrid)), dim3(64), wb, s, A);
+            stage("late");
+        }
         if (flags & RIA_DECODE_PERTURB) {
             // persistent waves over the device-side work list; sized to fill the chip (256 CUs x 12)
 #ifdef RIA_WITH_DUAL_DECODER
@@ -844,23 +849,30 @@ int ria_gpu_rx_batch(ria_gpu_handle h, const float* samples_dev, const uint64_t*
         return fail(h, RIA_ERR_INVALID, "ria_gpu_rx_batch: bad argument");
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    // Demodulate (LLRs stay in the HBM workspace / L2), then decode.  A large chunk is cut in parts (default 3) that run
+    // Demodulate (LLRs stay in the HBM workspace / L2), then decode.  A large chunk is cut in parts (default 3, 2 from kTwoPartFrames frames on) that run
     // on internal streams: the low-occupancy phases of one part (first decodes, phase 0, finalise, CRC recovery)
     // overlap with the cascade of another.  Results do not depend on the split
     // (tests/test_gpu_modes.py::test_rx_batch_split_modes_are_bit_identical_and_match_the_reference).
     const char* rh = getenv("RIA_RECOVERY_HOST");
     const bool single_stream_only = (rh && rh[0] == '1') || getenv("RIA_DEBUG_SYNC") != nullptr;   // host recovery / stage tracing own slot 0
-    int want_parts = h->split_parts;              // per handle (ria_gpu_set_option); 0: environment, else the default 3
+    // The default number of parts: a part's cascade is a persistent grid that holds the chip until it drains, so the parts'
+    // cascades run one behind the other and the recovery of the part that ends last is the step's tail.  Since the first
+    // decodes walk a frame (fast_primary_kernel) the first part reaches its cascade before the others have started their
+    // phase 0; at the bench size two parts then measure 2.4 % under three.  Batches under
+    // kTwoPartFrames were not measured again and keep three.
+    int want_parts = h->split_parts;              // per handle (ria_gpu_set_option); 0: environment, else the default
+    bool default_parts = false;
     if (want_parts == 0) {
         const char* sp = getenv("RIA_SPLIT_PARTS");
+        default_parts = !getenv("RIA_NO_SPLIT") && !sp;
         want_parts = getenv("RIA_NO_SPLIT") ? 1 : sp ? std::max(1, std::min(kMaxParts, atoi(sp))) : 3;
     }
-    if (single_stream_only) want_parts = 1;
+    if (single_stream_only) { want_parts = 1; default_parts = false; }
     for (int done = 0; done < n_frames;) {
         int nb = n_frames - done;
         if (!llr_out_dev && nb > h->cfg.max_batch) nb = h->cfg.max_batch;
         float* llr = llr_out_dev ? llr_out_dev + static_cast<size_t>(done) * h->geo.llrs_per_frame : h->d_llr_ws.as<float>();
-        const int n_parts = (nb >= 4096) ? want_parts : 1;
+        const int n_parts = (nb >= 4096) ? ((default_parts && nb >= kTwoPartFrames) ? 2 : want_parts) : 1;
         {   // grow the workspaces BEFORE anything is in flight: the parts share them
             hipError_t e = ensure_decode_ws(h, nb);
             if (e == hipSuccess && (flags & RIA_DECODE_CRC_RECOVER)) e = ensure_recovery_ws(h, std::max(nb, h->cfg.max_batch), false);
@@ -3285,6 +3297,18 @@ int ria_gpu_debug_state_exits(ria_gpu_handle h, int slot, uint32_t out[4]) {
     HIP_TRY(h, hipMemcpy(&c, h->d_ctl.as<DecodeCtl>() + slot, sizeof(c), hipMemcpyDeviceToHost));
     out[1] = c.exits[kExitsPhase0]; out[2] = c.exits[kExitsCascade]; out[3] = c.exits[kExitsFill];
     out[0] = out[1] + out[2] + out[3];
+    return RIA_OK;
+}
+
+int ria_gpu_debug_first_decodes(ria_gpu_handle h, int slot, uint32_t out[2]) {
+    if (!h || !out || slot < 0 || slot >= kMaxParts) return fail(h, RIA_ERR_INVALID, "ria_gpu_debug_first_decodes: bad argument");
+    out[0] = out[1] = 0;
+    if (!h->d_ctl) return RIA_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    DecodeCtl c;
+    HIP_TRY(h, hipDeviceSynchronize());
+    HIP_TRY(h, hipMemcpy(&c, h->d_ctl.as<DecodeCtl>() + slot, sizeof(c), hipMemcpyDeviceToHost));
+    out[0] = c.skipped; out[1] = c.late_made;
     return RIA_OK;
 }
 

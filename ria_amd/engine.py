@@ -133,6 +133,13 @@ class RxEngine:
         self._check(self.lib.ria_gpu_debug_state_exits(self.h, int(slot), out))
         return {"all": int(out[0]), "phase0": int(out[1]), "cascade": int(out[2]), "fill": int(out[3])}
 
+    def first_decodes(self, slot=0):
+        """First decodes (factor 0.9375) of the last decode call on stream slot `slot`: skipped behind a failed codeword of the
+        frame, and made late behind a phase-0 rescue.  Synchronises the device."""
+        out = (C.c_uint32 * 2)()
+        self._check(self.lib.ria_gpu_debug_first_decodes(self.h, int(slot), out))
+        return {"skipped": int(out[0]), "late": int(out[1])}
+
     # ---- helpers
     def _meta(self, n, cfo_hz, abs_pos, flags):
         if cfo_hz is None and abs_pos is None and flags is None:
