@@ -22,6 +22,7 @@
 #include "../host/link_adaptation.hpp"
 #include "frame_recovery.hpp"
 #include "ws_carve.hpp"
+#include "host_stage.hpp"
 #include "device_buffers.hpp"
 #include "ldpc_kernels.hip.h"
 #include "ldpc_fast.hip.h"
@@ -329,6 +330,14 @@ static hipError_t ensure_recovery_ws(ria_gpu_handle h, int n_frames, bool host_s
     }
     return hipSuccess;
 }
+// Everything launch_decode grows for n_frames frames under `flags`.  A reserve step does all of its stage's growing and
+// nothing else (no launch, no memset on the caller's stream): the stage's entry point calls it, and so does every composite
+// call that runs the stage later, up front, before anything is in flight - a block that grows frees the old one.
+static hipError_t decode_reserve(ria_gpu_handle h, int n_frames, uint32_t flags) {
+    hipError_t e = ensure_decode_ws(h, n_frames);
+    if (e == hipSuccess && (flags & RIA_DECODE_CRC_RECOVER)) e = ensure_recovery_ws(h, std::max(n_frames, h->cfg.max_batch), false);
+    return e;
+}
 
 __global__ void recovery_status_gather_kernel(const unsigned int* n_flagged, const unsigned int* flagged,
                                               const ria_decode_status* st, ria_decode_status* st_c) {
@@ -357,9 +366,7 @@ static int run_crc_recovery(ria_gpu_handle h, const FastDecodeArgs& D, hipStream
     const char* env = getenv("RIA_RECOVERY_HOST");   // read per call: tests flip it
     const bool on_host = env != nullptr && env[0] == '1';
     if (on_host) return run_crc_recovery_host(h, D, s);
-    const int n_frames = D.n_frames;
-    hipError_t e0 = ensure_recovery_ws(h, std::max(ws_off + n_frames, h->cfg.max_batch), false);
-    if (e0 != hipSuccess) return fail(h, RIA_ERR_HIP, "recovery workspace: %s", hipGetErrorString(e0));
+    const int n_frames = D.n_frames;   // launch_decode's decode_reserve has grown the lists for ws_off + n_frames frames
     RecoveryArgs R{};
     R.d = D;
     const RecoveryWs W = recovery_ws(h);
@@ -703,7 +710,7 @@ int ria_gpu_ldpc_decode_robust_batch(ria_gpu_handle h, const float* llr_dev, int
 // (ria_gpu_rx_batch runs the two halves of a large batch on two streams: slot 0 at offset 0, slot 1 behind it)
 static int launch_decode(ria_gpu_handle h, const float* llr_dev, int llr_stride, int n_frames, uint32_t flags,
                          uint8_t* info_out_dev, ria_decode_status* status_dev, hipStream_t s, int slot = 0, int ws_off = 0) {
-    hipError_t e = ensure_decode_ws(h, ws_off + n_frames);
+    hipError_t e = decode_reserve(h, ws_off + n_frames, flags);   // a no-op behind a caller that reserved for the whole call
     if (e != hipSuccess) return fail(h, RIA_ERR_HIP, "decode workspace: %s", hipGetErrorString(e));
     FastDecodeArgs A;
     const size_t o4 = static_cast<size_t>(ws_off) * 4, bpc = h->geo.bytes_per_codeword;
@@ -803,21 +810,21 @@ int ria_gpu_decode_batch(ria_gpu_handle h, const float* llr_dev, int llr_stride,
 }
 
 // ------------------------------------------------------------------------------------------------ demod
-static int demod_batch_slot(ria_gpu_handle h, const float* samples_dev, const uint64_t* frame_offsets_dev, const ria_frame_meta* meta_dev,
-                            int n_frames, float* llr_out_dev, ria_frame_status* status_dev, hipStream_t stream, int slot,
-                            int llr_stride = 0 /* floats between the soft-bit rows of two frames; 0 = llrs_per_frame */) {
-    DemodArgs A;
+// the demodulator's arguments: the handle's tables and one call's arrays (shared with the span form, demod_var_launch)
+static DemodArgs demod_args(ria_gpu_handle h, const float* samples_dev, const uint64_t* offsets_dev, const ria_frame_meta* meta_dev, int n_frames,
+                            float* llr_out_dev, int llr_stride, ria_frame_status* status_dev) {
+    DemodArgs A{};
     A.k = h->d_demod_const.as<const DemodConst>();
     A.twiddle = h->d_twiddle.as<const float2>();
     A.nco = h->d_nco.as<const float2>();
-    A.samples = samples_dev;
-    A.offsets = frame_offsets_dev;
-    A.meta = meta_dev;
-    A.n_frames = n_frames;
-    A.llr_out = llr_out_dev;
-    A.llr_stride = llr_stride ? llr_stride : h->geo.llrs_per_frame;
-    A.status = status_dev;
-    A.dbg = nullptr;
+    A.samples = samples_dev; A.offsets = offsets_dev; A.meta = meta_dev; A.n_frames = n_frames;
+    A.llr_out = llr_out_dev; A.llr_stride = llr_stride; A.status = status_dev; A.dbg = nullptr;
+    return A;
+}
+static int demod_batch_slot(ria_gpu_handle h, const float* samples_dev, const uint64_t* frame_offsets_dev, const ria_frame_meta* meta_dev,
+                            int n_frames, float* llr_out_dev, ria_frame_status* status_dev, hipStream_t stream, int slot,
+                            int llr_stride = 0 /* floats between the soft-bit rows of two frames; 0 = llrs_per_frame */) {
+    DemodArgs A = demod_args(h, samples_dev, frame_offsets_dev, meta_dev, n_frames, llr_out_dev, llr_stride ? llr_stride : h->geo.llrs_per_frame, status_dev);
 #ifdef RIA_DEBUG_STAMPS
     if (const char* e = getenv("RIA_DEBUG_DEMOD_STAMPS")) A.dbg = reinterpret_cast<unsigned long long*>(strtoull(e, nullptr, 0));
 #endif
@@ -873,11 +880,8 @@ int ria_gpu_rx_batch(ria_gpu_handle h, const float* samples_dev, const uint64_t*
         if (!llr_out_dev && nb > h->cfg.max_batch) nb = h->cfg.max_batch;
         float* llr = llr_out_dev ? llr_out_dev + static_cast<size_t>(done) * h->geo.llrs_per_frame : h->d_llr_ws.as<float>();
         const int n_parts = (nb >= 4096) ? ((default_parts && nb >= kTwoPartFrames) ? 2 : want_parts) : 1;
-        {   // grow the workspaces BEFORE anything is in flight: the parts share them
-            hipError_t e = ensure_decode_ws(h, nb);
-            if (e == hipSuccess && (flags & RIA_DECODE_CRC_RECOVER)) e = ensure_recovery_ws(h, std::max(nb, h->cfg.max_batch), false);
-            if (e != hipSuccess) return fail(h, RIA_ERR_HIP, "rx workspace: %s", hipGetErrorString(e));
-        }
+        // grow the workspaces BEFORE anything is in flight: the parts share them
+        if (hipError_t e = decode_reserve(h, nb, flags)) return fail(h, RIA_ERR_HIP, "rx workspace: %s", hipGetErrorString(e));
         if (n_parts > 1 && !h->aux_stream[0]) {
             for (auto& st_ : h->aux_stream) HIP_TRY(h, hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
             for (auto& ev_ : h->aux_event) HIP_TRY(h, hipEventCreateWithFlags(&ev_, hipEventDisableTiming));
@@ -923,6 +927,31 @@ static int ensure_host_stage(ria_gpu_handle h, size_t bytes) {
     HIP_TRY(h, h->p_hstage.reserve(bytes));
     return RIA_OK;
 }
+// One host-buffer call on the handle's staging block and stream.  `carve` lays the block out around the caller's host
+// pointers (host_stage.hpp); `call` is the batch form on the device block's areas.  The inputs go up in one copy, the
+// outputs from the first wanted one on come back in one copy, one stream sync, and the caller's buffers hold the results.
+extern "C++" {   // a template has no C linkage
+template <class Carve, class Call>
+static int host_staged(ria_gpu_handle h, Carve&& carve, Call&& call) {
+    StageCarver size_pass;
+    carve(size_pass);
+    if (!size_pass.valid()) return fail(h, RIA_ERR_INVALID, "staging block: an input behind an output, or too many areas");
+    if (int rc = ensure_host_stage(h, size_pass.size())) return rc;
+    unsigned char *D = h->d_hstage.as<unsigned char>(), *P = h->p_hstage.as<unsigned char>();
+    StageCarver pinned(P), device(D);
+    carve(pinned);
+    const auto on_device = carve(device);
+    hipStream_t s = h->hstream;
+    pinned.fill();
+    HIP_TRY(h, hipMemcpyAsync(D, P, pinned.upload_end(), hipMemcpyHostToDevice, s));
+    if (int rc = call(on_device, s)) return rc;
+    const size_t out0 = pinned.download_begin();
+    HIP_TRY(h, hipMemcpyAsync(P + out0, D + out0, pinned.size() - out0, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    pinned.drain();
+    return RIA_OK;
+}
+}
 
 int ria_gpu_rx_frames_host(ria_gpu_handle h, const float* samples_host, const ria_frame_meta* meta_host, int n_frames,
                            uint32_t flags, uint8_t* info_out_host, ria_decode_status* decode_status_host,
@@ -933,40 +962,19 @@ int ria_gpu_rx_frames_host(ria_gpu_handle h, const float* samples_host, const ri
     HIP_TRY(h, hipSetDevice(h->device));
     const ria_gpu_geometry& g = h->geo;
     const size_t n = static_cast<size_t>(n_frames);
-    // layout of the staging block (same offsets on the device and in pinned memory): inputs first, then outputs
-    const size_t o_s = 0, b_s = n * g.frame_samples * sizeof(float);
-    const size_t o_m = up256(o_s + b_s), b_m = n * sizeof(ria_frame_meta);
-    const size_t o_llr = up256(o_m + b_m), b_llr = n * g.llrs_per_frame * sizeof(float);
-    const size_t o_info = up256(o_llr + b_llr), b_info = n * g.info_bytes_per_frame;
-    const size_t o_ds = up256(o_info + b_info), b_ds = n * sizeof(ria_decode_status);
-    const size_t o_fs = up256(o_ds + b_ds), b_fs = n * sizeof(ria_frame_status);
-    const size_t total = up256(o_fs + b_fs);
-    int rc = ensure_host_stage(h, total);
-    if (rc != RIA_OK) return rc;
-    unsigned char *D = h->d_hstage.as<unsigned char>(), *P = h->p_hstage.as<unsigned char>();
-    hipStream_t s = h->hstream;
-    std::memcpy(P + o_s, samples_host, b_s);
-    if (meta_host) std::memcpy(P + o_m, meta_host, b_m);
-    HIP_TRY(h, hipMemcpyAsync(D, P, meta_host ? o_m + b_m : b_s, hipMemcpyHostToDevice, s));   // samples (+ meta) in one copy
-    const ria_frame_meta* d_meta = meta_host ? reinterpret_cast<const ria_frame_meta*>(D + o_m) : nullptr;
-    if (demod_only)
-        rc = ria_gpu_demod_batch(h, reinterpret_cast<const float*>(D + o_s), nullptr, d_meta, n_frames, reinterpret_cast<float*>(D + o_llr),
-                                 reinterpret_cast<ria_frame_status*>(D + o_fs), s);
-    else
-        rc = ria_gpu_rx_batch(h, reinterpret_cast<const float*>(D + o_s), nullptr, d_meta, n_frames, flags, D + o_info,
-                              reinterpret_cast<ria_decode_status*>(D + o_ds), reinterpret_cast<float*>(D + o_llr),
-                              reinterpret_cast<ria_frame_status*>(D + o_fs), s);
-    if (rc != RIA_OK) return rc;
-    // outputs back in one copy (the regions wanted are contiguous in the block), one stream sync
-    const size_t out0 = (llr_out_host ? o_llr : demod_only ? o_fs : o_info);
-    HIP_TRY(h, hipMemcpyAsync(P + out0, D + out0, total - out0, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    if (llr_out_host) std::memcpy(llr_out_host, P + o_llr, b_llr);
-    if (!demod_only) {
-        std::memcpy(info_out_host, P + o_info, b_info); std::memcpy(decode_status_host, P + o_ds, b_ds);
-        if (decode_status_host[0].reserved[1] == kDecodeFaultMarker) return fail(h, RIA_ERR_HIP, "decode work-queue fault: no frame of this call was decoded");
-    }
-    if (demod_status_host) std::memcpy(demod_status_host, P + o_fs, b_fs);
+    struct Stage { float* x; ria_frame_meta* meta; float* llr; uint8_t* info; ria_decode_status* ds; ria_frame_status* fs; };
+    auto carve = [&](StageCarver& c) {
+        Stage w;
+        w.x = c.in(n * g.frame_samples, samples_host); w.meta = c.in(n, meta_host);   // without meta only the samples go up
+        w.llr = c.out(n * g.llrs_per_frame, llr_out_host);
+        w.info = c.out(n * g.info_bytes_per_frame, demod_only ? nullptr : info_out_host); w.ds = c.out(n, demod_only ? nullptr : decode_status_host);
+        w.fs = c.out(n, demod_status_host);
+        return w;
+    };
+    if (int rc = host_staged(h, carve, [&](const Stage& d, hipStream_t s) {
+            if (demod_only) return ria_gpu_demod_batch(h, d.x, nullptr, d.meta, n_frames, d.llr, d.fs, s);
+            return ria_gpu_rx_batch(h, d.x, nullptr, d.meta, n_frames, flags, d.info, d.ds, d.llr, d.fs, s); })) return rc;
+    if (!demod_only && decode_status_host[0].reserved[1] == kDecodeFaultMarker) return fail(h, RIA_ERR_HIP, "decode work-queue fault: no frame of this call was decoded");
     return RIA_OK;
 }
 
@@ -976,21 +984,14 @@ int ria_gpu_decode_frames_host(ria_gpu_handle h, const float* llr_host, int llr_
         return fail(h, RIA_ERR_INVALID, "ria_gpu_decode_frames_host: bad argument");
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t n = static_cast<size_t>(n_frames);
-    const size_t b_llr = n * llr_stride * sizeof(float), o_info = up256(b_llr), b_info = n * h->geo.info_bytes_per_frame;
-    const size_t o_ds = up256(o_info + b_info), b_ds = n * sizeof(ria_decode_status), total = up256(o_ds + b_ds);
-    int rc = ensure_host_stage(h, total);
-    if (rc != RIA_OK) return rc;
-    unsigned char *D = h->d_hstage.as<unsigned char>(), *P = h->p_hstage.as<unsigned char>();
-    hipStream_t s = h->hstream;
-    std::memcpy(P, llr_host, b_llr);
-    HIP_TRY(h, hipMemcpyAsync(D, P, b_llr, hipMemcpyHostToDevice, s));
-    rc = ria_gpu_decode_batch(h, reinterpret_cast<const float*>(D), llr_stride, n_frames, flags, D + o_info,
-                              reinterpret_cast<ria_decode_status*>(D + o_ds), s);
-    if (rc != RIA_OK) return rc;
-    HIP_TRY(h, hipMemcpyAsync(P + o_info, D + o_info, total - o_info, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    std::memcpy(info_out_host, P + o_info, b_info);
-    std::memcpy(status_host, P + o_ds, b_ds);
+    struct Stage { float* llr; uint8_t* info; ria_decode_status* ds; };
+    auto carve = [&](StageCarver& c) {
+        Stage w;
+        w.llr = c.in(n * llr_stride, llr_host); w.info = c.out(n * h->geo.info_bytes_per_frame, info_out_host); w.ds = c.out(n, status_host);
+        return w;
+    };
+    if (int rc = host_staged(h, carve, [&](const Stage& d, hipStream_t s) {
+            return ria_gpu_decode_batch(h, d.llr, llr_stride, n_frames, flags, d.info, d.ds, s); })) return rc;
     if (status_host[0].reserved[1] == kDecodeFaultMarker) return fail(h, RIA_ERR_HIP, "decode work-queue fault: no frame of this call was decoded");
     return RIA_OK;
 }
@@ -1589,9 +1590,17 @@ static ControlWs control_carve(Carver& c, size_t n, size_t llr_row) {
     w.ctl = c.take<AcqCtl>(1);
     return w;
 }
-// grows the workspace to n rows; the caller's stream is drained first when the block has to move (an earlier call on it
-// may still read the old one)
-static int control_ensure_ws(ria_gpu_handle h, int n, hipStream_t s, ControlWs* out) {
+// The reserve step of the span demodulator (demod_var_launch), and the one place that refuses the fused kernel; `who` is
+// the public call, for the message.
+static int demod_span_reserve(ria_gpu_handle h, const char* who) {
+    if (demod_fused_selected()) return fail(h, RIA_ERR_UNSUPPORTED, "%s: RIA_DEMOD_FUSED=1 demodulates fixed frames only", who);
+    HIP_TRY(h, h->d_demod_ws[0].reserve(demod_ws_bytes(2 + h->geo.n_data_symbols)));
+    return RIA_OK;
+}
+// The reserve step of the control calls: demod_span_reserve, and the workspace grown to n rows; the caller's stream is
+// drained first when the block has to move (an earlier call on it may still read the old one)
+static int control_ensure_ws(ria_gpu_handle h, const char* who, int n, hipStream_t s, ControlWs* out) {
+    if (int rc = demod_span_reserve(h, who)) return rc;
     const size_t row = static_cast<size_t>(h->geo.llrs_per_frame);
     if (n > h->ctrl_rows) {
         if (h->ctrl_rows) HIP_TRY(h, hipStreamSynchronize(s));
@@ -1604,17 +1613,10 @@ static int control_ensure_ws(ria_gpu_handle h, int n, hipStream_t s, ControlWs* 
     return RIA_OK;
 }
 
-// spans of n_samples at offsets (never NULL here) through the split pipeline
-static int demod_var_launch(ria_gpu_handle h, const char* who, const float* samples_dev, const uint64_t* offsets_dev, const ria_frame_meta* meta_dev,
+// spans of n_samples at offsets (never NULL here) through the split pipeline; the caller has run demod_span_reserve
+static int demod_var_launch(ria_gpu_handle h, const float* samples_dev, const uint64_t* offsets_dev, const ria_frame_meta* meta_dev,
                             int n_frames, int n_samples, float* llr_out_dev, int llr_stride, ria_frame_status* status_dev, hipStream_t s) {
-    if (demod_fused_selected()) return fail(h, RIA_ERR_UNSUPPORTED, "%s: RIA_DEMOD_FUSED=1 demodulates fixed frames only", who);
-    DemodArgs A{};
-    A.k = h->d_demod_const.as<const DemodConst>();
-    A.twiddle = h->d_twiddle.as<const float2>();
-    A.nco = h->d_nco.as<const float2>();
-    A.samples = samples_dev; A.offsets = offsets_dev; A.meta = meta_dev; A.n_frames = n_frames;
-    A.llr_out = llr_out_dev; A.llr_stride = llr_stride; A.status = status_dev; A.dbg = nullptr;
-    HIP_TRY(h, h->d_demod_ws[0].reserve(demod_ws_bytes(2 + h->geo.n_data_symbols)));
+    const DemodArgs A = demod_args(h, samples_dev, offsets_dev, meta_dev, n_frames, llr_out_dev, llr_stride, status_dev);
     launch_demod<true>(A, h->geo, h->cfg.modulation, h->d_demod_ws[0].as<>(), s, n_samples / kSym);
     HIP_TRY(h, hipGetLastError());
     return RIA_OK;
@@ -1633,15 +1635,16 @@ int ria_gpu_demod_var_batch(ria_gpu_handle h, const float* samples_dev, const ui
     if (!samples_dev || !llr_out_dev) return fail(h, RIA_ERR_INVALID, "ria_gpu_demod_var_batch: null pointer");
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (demod_fused_selected()) return fail(h, RIA_ERR_UNSUPPORTED, "ria_gpu_demod_var_batch: RIA_DEMOD_FUSED=1 demodulates fixed frames only");
-    HIP_TRY(h, h->d_demod_ws[0].reserve(demod_ws_bytes(2 + h->geo.n_data_symbols)));   // before anything is in flight
-    if (!frame_offsets_dev) {
+    const char* who = "ria_gpu_demod_var_batch";
+    if (frame_offsets_dev) {
+        if (int rc = demod_span_reserve(h, who)) return rc;
+    } else {
         ControlWs W;
-        if (int rc = control_ensure_ws(h, n_frames, s, &W)) return rc;
+        if (int rc = control_ensure_ws(h, who, n_frames, s, &W)) return rc;
         hipLaunchKernelGGL(var_offsets_kernel, dim3((n_frames + 255) / 256), dim3(256), 0, s, W.offsets, n_frames, n_samples);
         frame_offsets_dev = W.offsets;
     }
-    return demod_var_launch(h, "ria_gpu_demod_var_batch", samples_dev, frame_offsets_dev, meta_dev, n_frames, n_samples, llr_out_dev, llr_stride, status_dev, s);
+    return demod_var_launch(h, samples_dev, frame_offsets_dev, meta_dev, n_frames, n_samples, llr_out_dev, llr_stride, status_dev, s);
 }
 
 int ria_gpu_demod_var_host(ria_gpu_handle h, const float* samples_host, int n_samples, const ria_frame_meta* meta_host,
@@ -1651,24 +1654,15 @@ int ria_gpu_demod_var_host(ria_gpu_handle h, const float* samples_host, int n_sa
         return fail(h, RIA_ERR_INVALID, "ria_gpu_demod_var_host: bad argument (3 * 1152 <= n_samples <= frame_samples)");
     HIP_TRY(h, hipSetDevice(h->device));
     const int made = (n_samples / kSym - 2) * h->geo.bits_per_symbol;
-    const size_t o_s = 0, b_s = static_cast<size_t>(n_samples) * sizeof(float);
-    const size_t o_m = up256(o_s + b_s), b_m = sizeof(ria_frame_meta);
-    const size_t o_llr = up256(o_m + b_m), b_llr = static_cast<size_t>(made) * sizeof(float);
-    const size_t o_fs = up256(o_llr + b_llr), total = up256(o_fs + sizeof(ria_frame_status));
-    if (int rc = ensure_host_stage(h, total)) return rc;
-    unsigned char *D = h->d_hstage.as<unsigned char>(), *P = h->p_hstage.as<unsigned char>();
-    hipStream_t s = h->hstream;
-    std::memcpy(P + o_s, samples_host, b_s);
-    if (meta_host) std::memcpy(P + o_m, meta_host, b_m);
-    HIP_TRY(h, hipMemcpyAsync(D, P, meta_host ? o_m + b_m : b_s, hipMemcpyHostToDevice, s));
-    int rc = ria_gpu_demod_var_batch(h, reinterpret_cast<const float*>(D + o_s), nullptr, meta_host ? reinterpret_cast<const ria_frame_meta*>(D + o_m) : nullptr,
-                                     1, n_samples, reinterpret_cast<float*>(D + o_llr), made, reinterpret_cast<ria_frame_status*>(D + o_fs), s);
-    if (rc != RIA_OK) return rc;
-    HIP_TRY(h, hipMemcpyAsync(P + o_llr, D + o_llr, total - o_llr, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    std::memcpy(llr_out_host, P + o_llr, static_cast<size_t>(std::min(made, max_llr)) * sizeof(float));
-    if (status_out) std::memcpy(status_out, P + o_fs, sizeof(ria_frame_status));
-    return RIA_OK;
+    struct Stage { float* x; ria_frame_meta* meta; float* llr; ria_frame_status* fs; };
+    auto carve = [&](StageCarver& c) {
+        Stage w;
+        w.x = c.in(static_cast<size_t>(n_samples), samples_host); w.meta = c.in(1, meta_host);
+        w.llr = c.out(static_cast<size_t>(made), llr_out_host, static_cast<size_t>(std::min(made, max_llr))); w.fs = c.out(1, status_out);
+        return w;
+    };
+    return host_staged(h, carve, [&](const Stage& d, hipStream_t s) {
+        return ria_gpu_demod_var_batch(h, d.x, nullptr, d.meta, 1, n_samples, d.llr, made, d.fs, s); });
 }
 
 static_assert(sizeof(ria_control_result) == 32, "ria_control_result is 32 bytes (include/ria_gpu.h)");
@@ -1695,15 +1689,13 @@ int ria_gpu_rx_control_batch(ria_gpu_handle h, const float* samples_dev, const u
     if (!samples_dev || !frame_out_dev || !result_dev) return fail(h, RIA_ERR_INVALID, "ria_gpu_rx_control_batch: null pointer");
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (demod_fused_selected()) return fail(h, RIA_ERR_UNSUPPORTED, "ria_gpu_rx_control_batch: RIA_DEMOD_FUSED=1 demodulates fixed frames only");
     ControlWs W;
-    if (int rc = control_ensure_ws(h, n_frames, s, &W)) return rc;
-    HIP_TRY(h, h->d_demod_ws[0].reserve(demod_ws_bytes(2 + h->geo.n_data_symbols)));   // before anything is in flight
+    if (int rc = control_ensure_ws(h, "ria_gpu_rx_control_batch", n_frames, s, &W)) return rc;   // before anything is in flight
     if (!frame_offsets_dev) {
         hipLaunchKernelGGL(var_offsets_kernel, dim3((n_frames + 255) / 256), dim3(256), 0, s, W.offsets, n_frames, n_samples);
         frame_offsets_dev = W.offsets;
     }
-    if (int rc = demod_var_launch(h, "ria_gpu_rx_control_batch", samples_dev, frame_offsets_dev, meta_dev, n_frames, n_samples, W.llr,
+    if (int rc = demod_var_launch(h, samples_dev, frame_offsets_dev, meta_dev, n_frames, n_samples, W.llr,
                                   h->geo.llrs_per_frame, W.fst, s)) return rc;
     ControlArgs A{};
     A.llr = W.llr; A.llr_stride = h->geo.llrs_per_frame; A.fst = W.fst; A.window = nullptr; A.n_rows = n_frames;
@@ -1727,12 +1719,10 @@ int ria_gpu_control_acquire_batch(ria_gpu_handle h, const float* samples_dev, in
         return fail(h, RIA_ERR_INVALID, "ria_gpu_control_acquire_batch: null pointer");
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (demod_fused_selected()) return fail(h, RIA_ERR_UNSUPPORTED, "ria_gpu_control_acquire_batch: RIA_DEMOD_FUSED=1 demodulates fixed frames only");
-    if (int rc = lts_prepare(h)) return rc;
     const size_t n = static_cast<size_t>(n_windows);
     ControlWs W;
-    if (int rc = control_ensure_ws(h, n_windows, s, &W)) return rc;
-    HIP_TRY(h, h->d_demod_ws[0].reserve(demod_ws_bytes(2 + h->geo.n_data_symbols)));   // before anything is in flight
+    if (int rc = control_ensure_ws(h, "ria_gpu_control_acquire_batch", n_windows, s, &W)) return rc;   // before anything is in flight
+    if (int rc = lts_prepare(h)) return rc;
     HIP_TRY(h, hipMemsetAsync(frame_out_dev, 0, n * kCtlFrameBytes, s));
     HIP_TRY(h, hipMemsetAsync(result_dev, 0, n * sizeof(ria_control_result), s));
     if (demod_status_dev) HIP_TRY(h, hipMemsetAsync(demod_status_dev, 0, n * sizeof(ria_frame_status), s));
@@ -1746,7 +1736,7 @@ int ria_gpu_control_acquire_batch(ria_gpu_handle h, const float* samples_dev, in
     const int n_list = static_cast<int>(h->p_ctrl_ctl.as<AcqCtl>()->n_list);
     if (n_list == 0) return RIA_OK;
     if (n_list > n_windows) return fail(h, RIA_ERR_HIP, "ria_gpu_control_acquire_batch: work list broke its bound (%d)", n_list);
-    if (int rc = demod_var_launch(h, "ria_gpu_control_acquire_batch", samples_dev, W.list.offset, W.list.meta, n_list, n_samples, W.llr,
+    if (int rc = demod_var_launch(h, samples_dev, W.list.offset, W.list.meta, n_list, n_samples, W.llr,
                                   h->geo.llrs_per_frame, W.fst, s)) return rc;
     A.llr = W.llr; A.llr_stride = h->geo.llrs_per_frame; A.fst = W.fst; A.window = W.list.window; A.n_rows = n_list;
     A.crc_bit = h->d_crc_bit.as<const uint16_t>(); A.crc_init = h->d_crc_init.as<const uint16_t>();
@@ -1815,12 +1805,8 @@ int ria_gpu_rx_burst_batch(ria_gpu_handle h, const float* samples_dev, int64_t s
     HIP_TRY(h, h->d_burst_ws.reserve(carved_size(carve)));
     HIP_TRY(h, h->p_burst_ctl.reserve(sizeof(BurstCtl)));
     const BurstWs B = carve_at(h->d_burst_ws.as<>(), carve);
-    {
-        const int dec_frames = static_cast<int>(n * (interleave ? N : 1));
-        hipError_t e = ensure_decode_ws(h, dec_frames);
-        if (e == hipSuccess && (flags & RIA_DECODE_CRC_RECOVER)) e = ensure_recovery_ws(h, std::max(dec_frames, h->cfg.max_batch), false);
-        if (e != hipSuccess) return fail(h, RIA_ERR_HIP, "burst workspace: %s", hipGetErrorString(e));
-    }
+    if (hipError_t e = decode_reserve(h, static_cast<int>(n * (interleave ? N : 1)), flags))
+        return fail(h, RIA_ERR_HIP, "burst workspace: %s", hipGetErrorString(e));
     HIP_TRY(h, hipMemsetAsync(info_out_dev, 0, n * kBurstSlots * ib, s));
     HIP_TRY(h, hipMemsetAsync(decode_status_dev, 0, n * kBurstSlots * sizeof(ria_decode_status), s));
     if (demod_status_dev) HIP_TRY(h, hipMemsetAsync(demod_status_dev, 0, n * kBurstSlots * sizeof(ria_frame_status), s));
@@ -1936,28 +1922,22 @@ static bool mcdpsk_config_ok(const ria_mcdpsk_config* c) {
            (c->spreading == 1 || c->spreading == 2 || c->spreading == 4);
 }
 
-// offsets_dev / bps_dev (nullable): the offset-list form (McArgs::offset, bps_list) of ria_gpu_mcdpsk_acquire_batch, whose
-// caller has checked the arguments (llr_stride for two bits per symbol)
-static int mcdpsk_demod_impl(ria_gpu_handle h, const ria_mcdpsk_config* cfg, const float* samples_dev, int64_t stride,
-                             const uint64_t* offsets_dev, const uint8_t* bps_dev,
-                             int frame_samples, int n_frames, const float* cfo_hz_dev, const float* phase0_dev,
-                             float* llr_out_dev, int llr_stride, ria_mcdpsk_status* status_dev, void* stream);
-
-int ria_gpu_mcdpsk_demod_batch(ria_gpu_handle h, const ria_mcdpsk_config* cfg, const float* samples_dev, int64_t stride,
-                               int frame_samples, int n_frames, const float* cfo_hz_dev, const float* phase0_dev,
-                               float* llr_out_dev, int llr_stride, ria_mcdpsk_status* status_dev, void* stream) {
-    if (!h) return RIA_ERR_INVALID;
-    if (n_frames == 0) return RIA_OK;
-    if (!mcdpsk_config_ok(cfg) || !samples_dev || !llr_out_dev || !status_dev || n_frames < 0 || stride < frame_samples ||
-        frame_samples < (kMcTrain + 2) * kMcSps)
-        return fail(h, RIA_ERR_INVALID, "ria_gpu_mcdpsk_demod_batch: bad arguments");
-    const int nc = cfg->num_carriers, num_rx = (frame_samples - (kMcTrain + 1) * kMcSps) / kMcSps;
-    const int nds = std::max(1, num_rx / cfg->spreading);
-    if (llr_stride < nds * nc * cfg->bits_per_symbol) return fail(h, RIA_ERR_INVALID, "ria_gpu_mcdpsk_demod_batch: llr_stride too small");
-    return mcdpsk_demod_impl(h, cfg, samples_dev, stride, nullptr, nullptr, frame_samples, n_frames, cfo_hz_dev, phase0_dev,
-                             llr_out_dev, llr_stride, status_dev, stream);
+// the tables the demodulator's kernels hand to each other for a chunk of F frames: the CFO-corrected samples and phases
+// (with a CFO array only), the symbol sums of sym_items = symbols x carriers, the three arrays of data_items = data symbols
+// x carriers, the carriers' relative gains and the frame's scale
+struct McWs { float* xc; float2* Yg; float *cph, *cmag, *pe2, *rel, *scale; };
+static McWs mc_carve(Carver& c, size_t F, size_t frame_samples, size_t sym_items, size_t data_items, bool with_cfo) {
+    McWs w;
+    w.xc = c.take<float>(with_cfo ? F * 2 * frame_samples : 0);
+    w.Yg = c.take<float2>(sym_items * F);
+    for (float** a : {&w.cph, &w.cmag, &w.pe2}) *a = c.take<float>(data_items * F);
+    w.rel = c.take<float>(static_cast<size_t>(kMcMaxCarriers) * F);
+    w.scale = c.take<float>(F);
+    return w;
 }
 
+// offsets_dev / bps_dev (nullable): the offset-list form (McArgs::offset, bps_list) of ria_gpu_mcdpsk_acquire_batch, whose
+// caller has checked the arguments (llr_stride for two bits per symbol)
 static int mcdpsk_demod_impl(ria_gpu_handle h, const ria_mcdpsk_config* cfg, const float* samples_dev, int64_t stride,
                              const uint64_t* offsets_dev, const uint8_t* bps_dev,
                              int frame_samples, int n_frames, const float* cfo_hz_dev, const float* phase0_dev,
@@ -1977,28 +1957,23 @@ static int mcdpsk_demod_impl(ria_gpu_handle h, const ria_mcdpsk_config* cfg, con
     }
     // the tables handed from kernel to kernel (and the CFO-corrected samples when a CFO array is given) live in a per-handle
     // workspace; a batch is walked in chunks of frames that fit it
-    const size_t per_frame = mcdpsk_ws_floats_per_frame(nc, frame_samples, cfg->spreading, cfo_hz_dev != nullptr);
-    const int chunk = static_cast<int>(std::min<size_t>(static_cast<size_t>(n_frames), std::max<size_t>(1, (size_t(256) << 20) / (per_frame * sizeof(float)))));
-    HIP_TRY(h, h->d_mc_ws.reserve((static_cast<size_t>(chunk) * per_frame + 64) * sizeof(float), &s));   // a growth waits for the stream's earlier users of the old block
+    const size_t n_sym = static_cast<size_t>(3 + num_rx);
+    auto carve = [&](size_t F) {
+        return [=](Carver& c) { return mc_carve(c, F, static_cast<size_t>(frame_samples), n_sym * nc, static_cast<size_t>(nds) * nc, cfo_hz_dev != nullptr); };
+    };
+    const int chunk = static_cast<int>(std::min<size_t>(static_cast<size_t>(n_frames), std::max<size_t>(1, (size_t(256) << 20) / carved_size(carve(1)))));
+    HIP_TRY(h, h->d_mc_ws.reserve(carved_size(carve(static_cast<size_t>(chunk))), &s));   // a growth waits for the stream's earlier users of the old block
     McArgs A{};
     A.samples = samples_dev; A.stride = stride; A.frame_samples = frame_samples; A.nc = nc; A.bps = cfg->bits_per_symbol;
     A.spreading = cfg->spreading; A.cfo = cfo_hz_dev; A.phase0 = phase0_dev; A.mixer = mixer.as<const float2>();
     A.hilbert = h->d_mc_hilbert.as<const float>(); A.llr = llr_out_dev;
     A.llr_stride = llr_stride; A.status = status_dev; A.chunk = mcdpsk_corr_chunk(nc, frame_samples);
     A.offset = offsets_dev; A.bps_list = bps_dev;
-    const size_t n_sym = static_cast<size_t>(3 + num_rx);
     for (int first = 0; first < n_frames; first += chunk) {
         A.first = first; A.n_frames = std::min(chunk, n_frames - first);
         const size_t F = static_cast<size_t>(A.n_frames);
-        float* p = h->d_mc_ws.as<float>();
-        A.ws = p; if (cfo_hz_dev) p += F * 2 * frame_samples;
-        p = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(p) + 15) & ~uintptr_t(15));
-        A.Yg = reinterpret_cast<float2*>(p); p += 2 * n_sym * nc * F;
-        A.cph = p; p += static_cast<size_t>(nds) * nc * F;
-        A.cmag = p; p += static_cast<size_t>(nds) * nc * F;
-        A.pe2 = p; p += static_cast<size_t>(nds) * nc * F;
-        A.rel = p; p += static_cast<size_t>(kMcMaxCarriers) * F;
-        A.scale = p;
+        const McWs W = carve_at(h->d_mc_ws.as<>(), carve(F));   // the arrays are indexed [item][frame of the chunk]
+        A.ws = W.xc; A.Yg = W.Yg; A.cph = W.cph; A.cmag = W.cmag; A.pe2 = W.pe2; A.rel = W.rel; A.scale = W.scale;
         hipLaunchKernelGGL(mcdpsk_corr_kernel, dim3(A.n_frames), dim3(256), lds, s, A);
         hipLaunchKernelGGL(mcdpsk_chain_kernel, dim3(static_cast<unsigned>((F * nc + 255) / 256)), dim3(256), 0, s, A);
         hipLaunchKernelGGL(mcdpsk_stats_kernel, dim3(static_cast<unsigned>((F + 63) / 64)), dim3(64), 0, s, A);
@@ -2006,6 +1981,21 @@ static int mcdpsk_demod_impl(ria_gpu_handle h, const ria_mcdpsk_config* cfg, con
     }
     HIP_TRY(h, hipGetLastError());
     return RIA_OK;
+}
+
+int ria_gpu_mcdpsk_demod_batch(ria_gpu_handle h, const ria_mcdpsk_config* cfg, const float* samples_dev, int64_t stride,
+                               int frame_samples, int n_frames, const float* cfo_hz_dev, const float* phase0_dev,
+                               float* llr_out_dev, int llr_stride, ria_mcdpsk_status* status_dev, void* stream) {
+    if (!h) return RIA_ERR_INVALID;
+    if (n_frames == 0) return RIA_OK;
+    if (!mcdpsk_config_ok(cfg) || !samples_dev || !llr_out_dev || !status_dev || n_frames < 0 || stride < frame_samples ||
+        frame_samples < (kMcTrain + 2) * kMcSps)
+        return fail(h, RIA_ERR_INVALID, "ria_gpu_mcdpsk_demod_batch: bad arguments");
+    const int nc = cfg->num_carriers, num_rx = (frame_samples - (kMcTrain + 1) * kMcSps) / kMcSps;
+    const int nds = std::max(1, num_rx / cfg->spreading);
+    if (llr_stride < nds * nc * cfg->bits_per_symbol) return fail(h, RIA_ERR_INVALID, "ria_gpu_mcdpsk_demod_batch: llr_stride too small");
+    return mcdpsk_demod_impl(h, cfg, samples_dev, stride, nullptr, nullptr, frame_samples, n_frames, cfo_hz_dev, phase0_dev,
+                             llr_out_dev, llr_stride, status_dev, stream);
 }
 
 // Host-buffer forms for the single-frame MC-DPSK plug-in adaptor (GpuMcDpskWaveform): staged through the handle's pinned +
@@ -2018,25 +2008,16 @@ int ria_gpu_mcdpsk_demod_host(ria_gpu_handle h, const ria_mcdpsk_config* cfg, co
     const int n_llr = std::max(1, num_rx / cfg->spreading) * cfg->num_carriers * cfg->bits_per_symbol;
     if (max_llr < n_llr) return fail(h, RIA_ERR_INVALID, "ria_gpu_mcdpsk_demod_host: llr buffer too small (%d needed)", n_llr);
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t b_s = static_cast<size_t>(n_samples) * sizeof(float), o_par = up256(b_s), o_llr = up256(o_par + 8);
-    const size_t o_st = up256(o_llr + static_cast<size_t>(n_llr) * sizeof(float)), total = up256(o_st + sizeof(ria_mcdpsk_status));
-    int rc = ensure_host_stage(h, total);
-    if (rc != RIA_OK) return rc;
-    unsigned char *D = h->d_hstage.as<unsigned char>(), *P = h->p_hstage.as<unsigned char>();
-    hipStream_t s = h->hstream;
-    std::memcpy(P, samples_host, b_s);
     const float par[2] = {cfo_hz, phase0};
-    std::memcpy(P + o_par, par, sizeof(par));
-    HIP_TRY(h, hipMemcpyAsync(D, P, o_par + 8, hipMemcpyHostToDevice, s));
-    rc = ria_gpu_mcdpsk_demod_batch(h, cfg, reinterpret_cast<const float*>(D), n_samples, n_samples, 1, reinterpret_cast<const float*>(D + o_par),
-                                    reinterpret_cast<const float*>(D + o_par) + 1, reinterpret_cast<float*>(D + o_llr), n_llr,
-                                    reinterpret_cast<ria_mcdpsk_status*>(D + o_st), s);
-    if (rc != RIA_OK) return rc;
-    HIP_TRY(h, hipMemcpyAsync(P + o_llr, D + o_llr, total - o_llr, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    std::memcpy(llr_out_host, P + o_llr, static_cast<size_t>(n_llr) * sizeof(float));
-    std::memcpy(status_out, P + o_st, sizeof(ria_mcdpsk_status));
-    return RIA_OK;
+    struct Stage { float *x, *par, *llr; ria_mcdpsk_status* st; };
+    auto carve = [&](StageCarver& c) {
+        Stage w;
+        w.x = c.in(static_cast<size_t>(n_samples), samples_host); w.par = c.in(2, par);
+        w.llr = c.out(static_cast<size_t>(n_llr), llr_out_host); w.st = c.out(1, status_out);
+        return w;
+    };
+    return host_staged(h, carve, [&](const Stage& d, hipStream_t s) {
+        return ria_gpu_mcdpsk_demod_batch(h, cfg, d.x, n_samples, n_samples, 1, d.par, d.par + 1, d.llr, n_llr, d.st, s); });
 }
 
 int ria_gpu_ldpc_decode_robust_host(ria_gpu_handle h, const float* llr_host, int n_cw, uint8_t* out_host, uint8_t* ok_host,
@@ -2044,23 +2025,15 @@ int ria_gpu_ldpc_decode_robust_host(ria_gpu_handle h, const float* llr_host, int
     if (!h || !llr_host || !out_host || !ok_host || n_cw <= 0) return fail(h, RIA_ERR_INVALID, "ria_gpu_ldpc_decode_robust_host: bad arguments");
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t n = static_cast<size_t>(n_cw), nb = static_cast<size_t>((h->code.k + 7) / 8);
-    const size_t b_llr = n * 648 * sizeof(float), o_out = up256(b_llr), o_ok = up256(o_out + n * nb), o_it = up256(o_ok + n), o_tr = up256(o_it + 2 * n);
-    const size_t total = up256(o_tr + n);
-    int rc = ensure_host_stage(h, total);
-    if (rc != RIA_OK) return rc;
-    unsigned char *D = h->d_hstage.as<unsigned char>(), *P = h->p_hstage.as<unsigned char>();
-    hipStream_t s = h->hstream;
-    std::memcpy(P, llr_host, b_llr);
-    HIP_TRY(h, hipMemcpyAsync(D, P, b_llr, hipMemcpyHostToDevice, s));
-    rc = ria_gpu_ldpc_decode_robust_batch(h, reinterpret_cast<const float*>(D), n_cw, D + o_out, D + o_ok, reinterpret_cast<uint16_t*>(D + o_it), D + o_tr, s);
-    if (rc != RIA_OK) return rc;
-    HIP_TRY(h, hipMemcpyAsync(P + o_out, D + o_out, total - o_out, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    std::memcpy(out_host, P + o_out, n * nb);
-    std::memcpy(ok_host, P + o_ok, n);
-    if (iters_host) std::memcpy(iters_host, P + o_it, 2 * n);
-    if (tries_host) std::memcpy(tries_host, P + o_tr, n);
-    return RIA_OK;
+    struct Stage { float* llr; uint8_t *out, *ok; uint16_t* it; uint8_t* tries; };
+    auto carve = [&](StageCarver& c) {
+        Stage w;
+        w.llr = c.in(n * 648, llr_host);
+        w.out = c.out(n * nb, out_host); w.ok = c.out(n, ok_host); w.it = c.out(n, iters_host); w.tries = c.out(n, tries_host);
+        return w;
+    };
+    return host_staged(h, carve, [&](const Stage& d, hipStream_t s) {
+        return ria_gpu_ldpc_decode_robust_batch(h, d.llr, n_cw, d.out, d.ok, d.it, d.tries, s); });
 }
 
 int ria_gpu_mcdpsk_modulate_batch(ria_gpu_handle h, const ria_mcdpsk_config* cfg, const uint8_t* data_dev, int n_bytes, int n_frames,
@@ -2248,6 +2221,53 @@ static int harq_stages(ria_gpu_handle h, const char* who, const MacqArgs& A, Har
     return RIA_OK;
 }
 
+// ---- one MC-DPSK round (mcdpsk_acquire_kernels.hip.h), shared by the acquire, the window and the decode-frame calls
+// the part of a round's arguments that only names workspace areas and per-handle tables
+static void macq_bind(MacqArgs& A, const MacqWs& W, ria_gpu_handle h, bool ci, int ci_step) {
+    A.ctl = W.ctl; A.mst = W.mst;
+    A.rows = W.rows; A.row_entry = W.row_entry; A.row_cw = W.row_cw;
+    A.out_a = W.out_a; A.ok_a = W.ok_a; A.out_b = W.out_b; A.ok_b = W.ok_b;
+    A.dec_bytes = (h->geo.ldpc_k + 7) / 8;
+    A.hdr_total = W.hdr; A.need_rows = W.need; A.row_base = W.base; A.done = W.done;
+    A.crc_bit = h->d_crc_bit.as<const uint16_t>(); A.crc_init = h->d_crc_init.as<const uint16_t>();
+    if (ci) { A.ci_step = ci_step; A.ci_flag = W.ci_flag; A.ci_list = W.ci_list; A.ci_ctl = W.ci_ctl; }
+}
+static unsigned macq_gather_grid(int n_rows) { return static_cast<unsigned>(std::min<size_t>((static_cast<size_t>(n_rows) * kMacqLdpcBlock + 255) / 256, 16384)); }
+// Round A on the A.n_cur entries of A.cur, their soft bits in A.llr: CW0 of every entry gathered and decoded, then with
+// `ci` the de-interleaved retry (one control read into `mirror`).  tries / tries_a2, where given, take the decoders' tries.
+static int macq_round_cw0(ria_gpu_handle h, const char* who, const MacqArgs& A, const MacqWs& W, bool ci, PinBuf& mirror, hipStream_t s,
+                          uint8_t* tries = nullptr, uint8_t* tries_a2 = nullptr) {
+    MacqArgs G = A;
+    G.row_entry = nullptr;
+    hipLaunchKernelGGL(macq_gather_kernel, dim3(macq_gather_grid(A.n_cur)), dim3(256), 0, s, G, A.n_cur);
+    if (int rc = ria_gpu_ldpc_decode_robust_batch(h, A.rows, A.n_cur, W.out_a, W.ok_a, W.it_a, tries, s)) return rc;
+    return ci ? macq_round_a2(h, who, A, W, mirror, s, tries_a2) : RIA_OK;
+}
+// The rest of the round: the headers and the round-B row list (one control read into `mirror`; with dup_noun the read is
+// also where a pool's ctl.dup is tested, and the word names the entries in the message), CW1..total_cw-1 of the entries
+// whose header asks for them, the chase stages with a pool, the finish.  max_cw bounds the codewords of an entry.
+static int macq_round_rest(ria_gpu_handle h, const char* who, const MacqArgs& A, const MacqWs& W, ria_chase_pool pool, const HarqArgs& H,
+                           const HarqWs& HW, PinBuf& mirror, int max_cw, const char* dup_noun, hipStream_t s) {
+    const unsigned waves = static_cast<unsigned>(std::min((A.n_cur + 3) / 4, 4096));
+    hipLaunchKernelGGL(macq_header_kernel, dim3(waves), dim3(256), 0, s, A);
+    hipLaunchKernelGGL(macq_rows_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A);
+    HIP_TRY(h, hipGetLastError());
+    if (int rc = read_ctl(h, mirror, A.ctl, s)) return rc;
+    const MacqCtl& ctl = *mirror.as<MacqCtl>();
+    if (pool && dup_noun && ctl.dup)
+        return fail(h, RIA_ERR_INVALID, "%s: two %s of one call use one cache id, or an id is not below n_caches; no cache was touched", who, dup_noun);
+    const int n_rows = static_cast<int>(ctl.n_rows);
+    if (n_rows < 0 || n_rows > static_cast<long long>(A.n_cur) * (max_cw - 1))
+        return fail(h, RIA_ERR_HIP, "%s: the codeword rows of a round broke their bound (%d)", who, n_rows);
+    if (n_rows > 0) {
+        hipLaunchKernelGGL(macq_gather_kernel, dim3(macq_gather_grid(n_rows)), dim3(256), 0, s, A, n_rows);
+        if (int rc = ria_gpu_ldpc_decode_robust_batch(h, A.rows, n_rows, W.out_b, W.ok_b, W.it_b, nullptr, s)) return rc;
+    }
+    if (pool) { if (int rc = harq_stages(h, who, A, H, HW, mirror, n_rows, waves, s)) return rc; }
+    hipLaunchKernelGGL(macq_finish_kernel, dim3(waves), dim3(256), 0, s, A);
+    return RIA_OK;
+}
+
 // The rounds of one list (steps 3-5): round 0 runs W.list[0] (its length in ctl.n_list) at the primary candidate, round r >= 1
 // the windows still searching at their next candidate that fits (at most 25 more rounds: each advances every window it holds by
 // at least one candidate).  A carries everything but the per-round fields; llr_ws and max_cw belong to A.frame_len.
@@ -2269,35 +2289,61 @@ static int macq_rounds(ria_gpu_handle h, const char* who, const ria_mcdpsk_confi
         A.n_cur = n_list;
         int rc = mcdpsk_demod_impl(h, &c, samples_dev, stride, A.cur.offset, A.cur.bps, frame_len, n_list, A.cur.cfo, nullptr, W.llr, llr_ws, W.mst, s);
         if (rc != RIA_OK) return rc;
-        // round A: CW0 of every entry, then the headers and the round-B row list
-        MacqArgs G = A;
-        G.row_entry = nullptr;
-        hipLaunchKernelGGL(macq_gather_kernel, dim3(static_cast<unsigned>(std::min<size_t>((static_cast<size_t>(n_list) * kMacqLdpcBlock + 255) / 256, 16384))),
-                           dim3(256), 0, s, G, n_list);
-        rc = ria_gpu_ldpc_decode_robust_batch(h, A.rows, n_list, W.out_a, W.ok_a, W.it_a, nullptr, s);
-        if (rc != RIA_OK) return rc;
-        if (ci && (rc = macq_round_a2(h, who, A, W, h->p_macq_ctl, s)) != RIA_OK) return rc;
-        const unsigned waves = static_cast<unsigned>(std::min((n_list + 3) / 4, 4096));
-        hipLaunchKernelGGL(macq_header_kernel, dim3(waves), dim3(256), 0, s, A);
-        hipLaunchKernelGGL(macq_rows_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A);
-        HIP_TRY(h, hipGetLastError());
-        if ((rc = read_ctl(h, h->p_macq_ctl, A.ctl, s)) != RIA_OK) return rc;
-        const int n_rows = static_cast<int>(ctl.n_rows);
-        if (n_rows < 0 || n_rows > n_list * (max_cw - 1))
-            return fail(h, RIA_ERR_HIP, "%s: codeword rows of round %d broke their bound (%d)", who, round, n_rows);
-        // round B: CW1..total_cw-1 of the entries whose header asks for them
-        if (n_rows > 0) {
-            hipLaunchKernelGGL(macq_gather_kernel, dim3(static_cast<unsigned>(std::min<size_t>((static_cast<size_t>(n_rows) * kMacqLdpcBlock + 255) / 256, 16384))),
-                               dim3(256), 0, s, A, n_rows);
-            rc = ria_gpu_ldpc_decode_robust_batch(h, A.rows, n_rows, W.out_b, W.ok_b, W.it_b, nullptr, s);
-            if (rc != RIA_OK) return rc;
-        }
-        if (pool && (rc = harq_stages(h, who, A, H, HW, h->p_macq_ctl, n_rows, waves, s)) != RIA_OK) return rc;
-        hipLaunchKernelGGL(macq_finish_kernel, dim3(waves), dim3(256), 0, s, A);
+        if ((rc = macq_round_cw0(h, who, A, W, ci, h->p_macq_ctl, s)) != RIA_OK) return rc;
+        if ((rc = macq_round_rest(h, who, A, W, pool, H, HW, h->p_macq_ctl, max_cw, nullptr, s)) != RIA_OK) return rc;
         hipLaunchKernelGGL(macq_next_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A);
         HIP_TRY(h, hipGetLastError());
     }
     return RIA_OK;
+}
+
+// What the acquire and the window call derive from their flags and configuration, behind the checks they share.  own_bad
+// is the call's own extra condition and bad_text the list of them all; ci_call: the entry point takes interleaver_bits.
+struct MacqSetup { bool chirp, disconnected, retry, ci; int ci_step, sym_per_cw; };
+static int macq_setup(ria_gpu_handle h, const char* who, const ria_mcdpsk_config* cfg, int64_t stride, int search_len, int window_len, int n_windows,
+                      uint32_t flags, bool own_bad, const char* bad_text, bool ci_call, int interleaver_bits, MacqSetup* out) {
+    const uint32_t known_flags = RIA_MACQ_SYNC_CHIRP | RIA_MACQ_DISCONNECTED | RIA_MACQ_NO_RETRY | RIA_MACQ_CHANNEL_INTERLEAVE;
+    MacqSetup u{};
+    u.chirp = (flags & RIA_MACQ_SYNC_CHIRP) != 0; u.disconnected = (flags & RIA_MACQ_DISCONNECTED) != 0;
+    if (!mcdpsk_config_ok(cfg) || n_windows < 0 || search_len < 0 || window_len < search_len || stride < window_len || own_bad ||
+        (flags & ~known_flags) != 0 || (u.disconnected && !u.chirp) || (!u.chirp && search_len > kZcMaxBuf))
+        return fail(h, RIA_ERR_INVALID, "%s: bad argument (%s)", who, bad_text);
+    if (h->cfg.code_rate != RIA_RATE_1_4) return fail(h, RIA_ERR_INVALID, "%s: MC-DPSK frames are R1/4: the handle's rate must be RIA_RATE_1_4", who);
+    u.ci = ci_call && (flags & RIA_MACQ_CHANNEL_INTERLEAVE) != 0;
+    if ((flags & RIA_MACQ_CHANNEL_INTERLEAVE) && !ci_call)
+        return fail(h, RIA_ERR_UNSUPPORTED, "%s: MC-DPSK channel interleaving is ria_gpu_mcdpsk_acquire_ci_batch's", who);
+    if (u.ci && !macq_ci_step(interleaver_bits, &u.ci_step)) return fail(h, RIA_ERR_INVALID, "%s: interleaver_bits %d outside 1..648", who, interleaver_bits);
+    u.retry = u.disconnected && !(flags & RIA_MACQ_NO_RETRY);
+    u.sym_per_cw = (kMacqLdpcBlock + cfg->num_carriers * cfg->bits_per_symbol - 1) / (cfg->num_carriers * cfg->bits_per_symbol);
+    *out = u;
+    return RIA_OK;
+}
+// The first launches of the two calls, on an A that names the call's own arrays and sizes; the rest of A is filled here.
+// The outputs are cleared; the chase stages begin for `rows` codeword rows (without a pool the caller's harq rows are
+// cleared); each window is searched with its own threshold (and known CFO for ZC) into W.det.
+static int macq_begin(ria_gpu_handle h, const char* who, const MacqSetup& u, const MacqWs& W, MacqArgs& A, const float* samples_dev, int search_len,
+                      ria_chase_pool pool, const int32_t* cache_id_dev, const uint64_t* now_ms_dev, ria_mcdpsk_harq_result* harq_dev, size_t rows,
+                      hipStream_t s, HarqArgs* H, HarqWs* HW) {
+    const size_t n = static_cast<size_t>(A.n_windows);
+    A.connected = !u.disconnected; A.retry = u.retry; A.llr = W.llr; A.next = W.list[0];
+    macq_bind(A, W, h, u.ci, u.ci_step);
+    HIP_TRY(h, hipMemsetAsync(A.frame_out, 0, n * static_cast<size_t>(A.frame_row), s));
+    if (A.llr_out) HIP_TRY(h, hipMemsetAsync(A.llr_out, 0, n * static_cast<size_t>(A.llr_stride) * sizeof(float), s));
+    if (pool) {
+        if (int rc = harq_begin(h, who, pool, cache_id_dev, now_ms_dev, harq_dev, A.n_windows, rows, static_cast<size_t>(A.dec_bytes), W.ctl, s, H, HW)) return rc;
+    } else if (harq_dev) {
+        HIP_TRY(h, hipMemsetAsync(harq_dev, 0, n * sizeof(ria_mcdpsk_harq_result), s));
+    }
+    const int pstride = static_cast<int>(sizeof(ria_mcdpsk_acq_params) / sizeof(float));
+    if (u.chirp) {
+        ria_chirp_result* det = reinterpret_cast<ria_chirp_result*>(W.det);
+        A.chirp = det;
+        return sync_chirp_impl(h, samples_dev, A.stride, search_len, A.n_windows, 0.15f, det, s, &A.params->detect_threshold, pstride);
+    }
+    ria_zc_result* det = reinterpret_cast<ria_zc_result*>(W.det);
+    A.zc = det;
+    return sync_zc_impl(h, samples_dev, A.stride, search_len, A.n_windows, 0.2f, 12u /* DATA | CONTROL */, &A.params->known_cfo_hz, det, s,
+                        &A.params->detect_threshold, pstride);
 }
 
 static int macq_impl(ria_gpu_handle h, const char* who, const ria_mcdpsk_config* cfg, const float* samples_dev, int64_t stride,
@@ -2307,21 +2353,12 @@ static int macq_impl(ria_gpu_handle h, const char* who, const ria_mcdpsk_config*
                      float* llr_out_dev, int llr_stride, ria_chase_pool pool, const int32_t* cache_id_dev, const uint64_t* now_ms_dev,
                      ria_mcdpsk_harq_result* harq_dev, bool ci_call, int interleaver_bits, void* stream) {
     if (!h) return RIA_ERR_INVALID;
-    const uint32_t known_flags = RIA_MACQ_SYNC_CHIRP | RIA_MACQ_DISCONNECTED | RIA_MACQ_NO_RETRY | RIA_MACQ_CHANNEL_INTERLEAVE;
-    const bool chirp = (flags & RIA_MACQ_SYNC_CHIRP) != 0, disconnected = (flags & RIA_MACQ_DISCONNECTED) != 0;
-    if (!mcdpsk_config_ok(cfg) || n_windows < 0 || search_len < 0 || window_len < search_len || stride < window_len ||
-        frame_cw < 1 || frame_cw > 8 || (flags & ~known_flags) != 0 || (disconnected && !chirp) || (!chirp && search_len > kZcMaxBuf))
-        return fail(h, RIA_ERR_INVALID, "%s: bad argument (config, 0 <= search_len <= window_len <= stride, "
-                                        "frame_cw 1..8, known flags, ZC only when connected)", who);
-    if (h->cfg.code_rate != RIA_RATE_1_4) return fail(h, RIA_ERR_INVALID, "%s: MC-DPSK frames are R1/4: the handle's rate must be RIA_RATE_1_4", who);
-    const bool ci = ci_call && (flags & RIA_MACQ_CHANNEL_INTERLEAVE) != 0;
-    if ((flags & RIA_MACQ_CHANNEL_INTERLEAVE) && !ci_call)
-        return fail(h, RIA_ERR_UNSUPPORTED, "%s: MC-DPSK channel interleaving is ria_gpu_mcdpsk_acquire_ci_batch's", who);
-    int ci_step = 0;
-    if (ci && !macq_ci_step(interleaver_bits, &ci_step)) return fail(h, RIA_ERR_INVALID, "%s: interleaver_bits %d outside 1..648", who, interleaver_bits);
-    const int nc = cfg->num_carriers, bps = cfg->bits_per_symbol, sp = cfg->spreading;
-    const bool retry = disconnected && !(flags & RIA_MACQ_NO_RETRY);
-    const int sym_per_cw = (kMacqLdpcBlock + nc * bps - 1) / (nc * bps);
+    MacqSetup u;
+    if (int rc = macq_setup(h, who, cfg, stride, search_len, window_len, n_windows, flags, frame_cw < 1 || frame_cw > 8,
+                            "config, 0 <= search_len <= window_len <= stride, frame_cw 1..8, known flags, ZC only when connected",
+                            ci_call, interleaver_bits, &u)) return rc;
+    const bool ci = u.ci, retry = u.retry;
+    const int nc = cfg->num_carriers, bps = cfg->bits_per_symbol, sp = cfg->spreading, sym_per_cw = u.sym_per_cw;
     const int frame_len = (kMcTrain + 1) * kMcSps + frame_cw * sym_per_cw * kMcSps * sp;      // getMinSamplesForCWCount
     if (mcdpsk_lds_bytes(nc, frame_len) > 160 * 1024)
         return fail(h, RIA_ERR_UNSUPPORTED, "%s: frame of %d samples too long for the MC-DPSK demodulator", who, frame_len);
@@ -2342,50 +2379,17 @@ static int macq_impl(ria_gpu_handle h, const char* who, const ria_mcdpsk_config*
     HIP_TRY(h, h->d_macq_ws.reserve(carved_size(carve)));   // nothing of an earlier call is in flight: every call ends on a stream sync
     HIP_TRY(h, h->p_macq_ctl.reserve(sizeof(MacqCtl)));
     const MacqWs W = carve_at(h->d_macq_ws.as<>(), carve);
-    const int frame_row = RIA_MACQ_FRAME_BYTES(frame_cw);
-    HIP_TRY(h, hipMemsetAsync(frame_out_dev, 0, n * frame_row, s));
-    if (llr_out_dev) HIP_TRY(h, hipMemsetAsync(llr_out_dev, 0, n * static_cast<size_t>(llr_stride) * sizeof(float), s));
+    // 1. the outputs cleared, the chase stages' begin, detection
     HarqArgs H{};
     HarqWs HW{};
-    if (pool) {
-        if (int rc = harq_begin(h, who, pool, cache_id_dev, now_ms_dev, harq_dev, n_windows, n * static_cast<size_t>(max_cw), dec_bytes, W.ctl, s, &H, &HW)) return rc;
-    } else if (harq_dev) {
-        HIP_TRY(h, hipMemsetAsync(harq_dev, 0, n * sizeof(ria_mcdpsk_harq_result), s));
-    }
-
-    // 1. detection with each window's threshold (and known CFO for ZC)
-    const int pstride = static_cast<int>(sizeof(ria_mcdpsk_acq_params) / sizeof(float));
     MacqArgs A{};
-    if (chirp) {
-        ria_chirp_result* det = reinterpret_cast<ria_chirp_result*>(W.det);
-        A.chirp = det;
-        int rc = sync_chirp_impl(h, samples_dev, stride, search_len, n_windows, 0.15f, det, s, &params_dev->detect_threshold, pstride);
-        if (rc != RIA_OK) return rc;
-    } else {
-        ria_zc_result* det = reinterpret_cast<ria_zc_result*>(W.det);
-        A.zc = det;
-        int rc = sync_zc_impl(h, samples_dev, stride, search_len, n_windows, 0.2f, 12u /* DATA | CONTROL */, &params_dev->known_cfo_hz,
-                              det, s, &params_dev->detect_threshold, pstride);
-        if (rc != RIA_OK) return rc;
-    }
-    // 2. acceptance + the round-0 list
     A.params = params_dev; A.n_windows = n_windows; A.window_len = window_len; A.frame_len = frame_len; A.stride = stride;
-    A.connected = !disconnected; A.retry = retry; A.bps = bps; A.acq = acq_dev;
-    A.ctl = W.ctl;
-    A.next = W.list[0];
+    A.bps = bps; A.acq = acq_dev; A.llr_ws = llr_ws;
+    A.frame_out = frame_out_dev; A.frame_row = RIA_MACQ_FRAME_BYTES(frame_cw); A.llr_out = llr_out_dev; A.llr_stride = llr_stride;
+    if (int rc = macq_begin(h, who, u, W, A, samples_dev, search_len, pool, cache_id_dev, now_ms_dev, harq_dev, n * static_cast<size_t>(max_cw), s, &H, &HW)) return rc;
+    // 2. acceptance + the round-0 list
     hipLaunchKernelGGL(macq_plan_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A);
     HIP_TRY(h, hipGetLastError());
-    A.mst = W.mst;
-    A.llr = W.llr; A.llr_ws = llr_ws;
-    A.rows = W.rows;
-    A.row_entry = W.row_entry; A.row_cw = W.row_cw;
-    A.out_a = W.out_a; A.ok_a = W.ok_a; A.out_b = W.out_b; A.ok_b = W.ok_b;
-    A.dec_bytes = static_cast<int>(dec_bytes);
-    A.hdr_total = W.hdr; A.need_rows = W.need;
-    A.row_base = W.base; A.done = W.done;
-    A.crc_bit = h->d_crc_bit.as<const uint16_t>(); A.crc_init = h->d_crc_init.as<const uint16_t>();
-    A.frame_out = frame_out_dev; A.frame_row = frame_row; A.llr_out = llr_out_dev; A.llr_stride = llr_stride;
-    if (ci) { A.ci_step = ci_step; A.ci_flag = W.ci_flag; A.ci_list = W.ci_list; A.ci_ctl = W.ci_ctl; }
     const ria_mcdpsk_config c = *cfg;
     // 3.-5. the rounds
     return macq_rounds(h, who, c, samples_dev, stride, A, W, pool, H, HW, ci, llr_ws, max_cw, true, s);
@@ -2452,19 +2456,12 @@ int ria_gpu_mcdpsk_window_batch(ria_gpu_handle h, const ria_mcdpsk_config* cfg, 
                                 ria_mcdpsk_harq_result* harq_dev, int interleaver_bits, void* stream) {
     const char* who = "ria_gpu_mcdpsk_window_batch";
     if (!h) return RIA_ERR_INVALID;
-    const uint32_t known_flags = RIA_MACQ_SYNC_CHIRP | RIA_MACQ_DISCONNECTED | RIA_MACQ_NO_RETRY | RIA_MACQ_CHANNEL_INTERLEAVE;
-    const bool chirp = (flags & RIA_MACQ_SYNC_CHIRP) != 0, disconnected = (flags & RIA_MACQ_DISCONNECTED) != 0;
-    if (!mcdpsk_config_ok(cfg) || n_windows < 0 || search_len < 0 || window_len < search_len || stride < window_len ||
-        (flags & ~known_flags) != 0 || (disconnected && !chirp) || (!chirp && search_len > kZcMaxBuf) || frame_row < RIA_MACQ_FRAME_BYTES(8))
-        return fail(h, RIA_ERR_INVALID, "%s: bad argument (config, 0 <= search_len <= window_len <= stride, known flags, ZC only when "
-                                        "connected, frame_row >= RIA_MACQ_FRAME_BYTES(8))", who);
-    if (h->cfg.code_rate != RIA_RATE_1_4) return fail(h, RIA_ERR_INVALID, "%s: MC-DPSK frames are R1/4: the handle's rate must be RIA_RATE_1_4", who);
-    const bool ci = (flags & RIA_MACQ_CHANNEL_INTERLEAVE) != 0;
-    int ci_step = 0;
-    if (ci && !macq_ci_step(interleaver_bits, &ci_step)) return fail(h, RIA_ERR_INVALID, "%s: interleaver_bits %d outside 1..648", who, interleaver_bits);
-    const int nc = cfg->num_carriers, bps = cfg->bits_per_symbol, sp = cfg->spreading;
-    const bool retry = disconnected && !(flags & RIA_MACQ_NO_RETRY);
-    const int sym_per_cw = (kMacqLdpcBlock + nc * bps - 1) / (nc * bps);
+    MacqSetup u;
+    if (int rc = macq_setup(h, who, cfg, stride, search_len, window_len, n_windows, flags, frame_row < RIA_MACQ_FRAME_BYTES(8),
+                            "config, 0 <= search_len <= window_len <= stride, known flags, ZC only when connected, frame_row >= RIA_MACQ_FRAME_BYTES(8)",
+                            true, interleaver_bits, &u)) return rc;
+    const bool ci = u.ci, retry = u.retry, disconnected = u.disconnected;
+    const int nc = cfg->num_carriers, bps = cfg->bits_per_symbol, sp = cfg->spreading, sym_per_cw = u.sym_per_cw;
     MwinGeom g{};
     g.window_len = window_len; g.cw_samples = sym_per_cw * kMcSps * sp; g.cw_bits = sym_per_cw * nc * bps; g.disconnected = disconnected ? 1 : 0;
     // the longest pass: 8 codewords, what the window holds (a longer span never fits), what the demodulator's workgroup holds
@@ -2492,40 +2489,16 @@ int ria_gpu_mcdpsk_window_batch(ria_gpu_handle h, const ria_mcdpsk_config* cfg, 
     HIP_TRY(h, h->p_mwin_ctl.reserve(sizeof(MwinCtl)));
     const MacqWs W = carve_at(h->d_macq_ws.as<>(), carve);
     const MwinWs WW = carve_at(h->d_mwin_ws.as<>(), wcarve);
-    HIP_TRY(h, hipMemsetAsync(frame_out_dev, 0, n * static_cast<size_t>(frame_row), s));
-    if (llr_out_dev) HIP_TRY(h, hipMemsetAsync(llr_out_dev, 0, n * static_cast<size_t>(llr_stride) * sizeof(float), s));
     HIP_TRY(h, hipMemsetAsync(WW.wctl, 0, sizeof(MwinCtl), s));
     HIP_TRY(h, hipMemsetAsync(WW.tries_deint, 0, n, s));
+    // 1. the outputs cleared, the chase stages' begin, detection
     HarqArgs H{};
     HarqWs HW{};
-    if (pool) {
-        if (int rc = harq_begin(h, who, pool, cache_id_dev, now_ms_dev, harq_dev, n_windows, n * static_cast<size_t>(top_max_cw), dec_bytes, W.ctl, s, &H, &HW)) return rc;
-    } else if (harq_dev) {
-        HIP_TRY(h, hipMemsetAsync(harq_dev, 0, n * sizeof(ria_mcdpsk_harq_result), s));
-    }
-    // 1. detection
-    const int pstride = static_cast<int>(sizeof(ria_mcdpsk_acq_params) / sizeof(float));
     MwinArgs B{};
     MacqArgs& A = B.M;
-    if (chirp) {
-        ria_chirp_result* det = reinterpret_cast<ria_chirp_result*>(W.det);
-        A.chirp = det;
-        if (int rc = sync_chirp_impl(h, samples_dev, stride, search_len, n_windows, 0.15f, det, s, &params_dev->detect_threshold, pstride)) return rc;
-    } else {
-        ria_zc_result* det = reinterpret_cast<ria_zc_result*>(W.det);
-        A.zc = det;
-        if (int rc = sync_zc_impl(h, samples_dev, stride, search_len, n_windows, 0.2f, 12u /* DATA | CONTROL */, &params_dev->known_cfo_hz,
-                                  det, s, &params_dev->detect_threshold, pstride)) return rc;
-    }
-    A.params = params_dev; A.n_windows = n_windows; A.window_len = window_len; A.stride = stride;
-    A.connected = !disconnected; A.retry = retry; A.bps = bps; A.acq = acq_dev; A.ctl = W.ctl; A.next = W.list[0];
-    A.mst = W.mst; A.llr = W.llr; A.rows = W.rows; A.row_entry = W.row_entry; A.row_cw = W.row_cw;
-    A.out_a = W.out_a; A.ok_a = W.ok_a; A.out_b = W.out_b; A.ok_b = W.ok_b;
-    A.dec_bytes = static_cast<int>(dec_bytes);
-    A.hdr_total = W.hdr; A.need_rows = W.need; A.row_base = W.base; A.done = W.done;
-    A.crc_bit = h->d_crc_bit.as<const uint16_t>(); A.crc_init = h->d_crc_init.as<const uint16_t>();
+    A.params = params_dev; A.n_windows = n_windows; A.window_len = window_len; A.stride = stride; A.bps = bps; A.acq = acq_dev;
     A.frame_out = frame_out_dev; A.frame_row = frame_row; A.llr_out = llr_out_dev; A.llr_stride = llr_stride;
-    if (ci) { A.ci_step = ci_step; A.ci_flag = W.ci_flag; A.ci_list = W.ci_list; A.ci_ctl = W.ci_ctl; }
+    if (int rc = macq_begin(h, who, u, W, A, samples_dev, search_len, pool, cache_id_dev, now_ms_dev, harq_dev, n * static_cast<size_t>(top_max_cw), s, &H, &HW)) return rc;
     B.g = g; B.samples = samples_dev; B.res = result_dev; B.st = WW.st; B.wctl = WW.wctl;
     B.tries_a = WW.tries_a; B.tries_deint = WW.tries_deint; B.tries_a2 = WW.tries_a2;
     const ria_mcdpsk_config c = *cfg;
@@ -2553,14 +2526,8 @@ int ria_gpu_mcdpsk_window_batch(ria_gpu_handle h, const ria_mcdpsk_config* cfg, 
         A.cur = W.list[0]; A.next = W.list[1]; A.n_cur = n_peek;
         int rc = mcdpsk_demod_impl(h, &c, samples_dev, stride, A.cur.offset, A.cur.bps, A.frame_len, n_peek, A.cur.cfo, nullptr, W.llr, A.llr_ws, W.mst, s);
         if (rc != RIA_OK) return rc;
-        MacqArgs G = A;
-        G.row_entry = nullptr;
-        hipLaunchKernelGGL(macq_gather_kernel, dim3(static_cast<unsigned>(std::min<size_t>((static_cast<size_t>(n_peek) * kMacqLdpcBlock + 255) / 256, 16384))),
-                           dim3(256), 0, s, G, n_peek);
-        rc = ria_gpu_ldpc_decode_robust_batch(h, A.rows, n_peek, W.out_a, W.ok_a, W.it_a, WW.tries_a, s);
-        if (rc != RIA_OK) return rc;
+        if ((rc = macq_round_cw0(h, who, A, W, ci, h->p_macq_ctl, s, WW.tries_a, WW.tries_a2)) != RIA_OK) return rc;
         if (ci) {
-            if ((rc = macq_round_a2(h, who, A, W, h->p_macq_ctl, s, WW.tries_a2)) != RIA_OK) return rc;
             hipLaunchKernelGGL(mwin_a2_tries_kernel, dim3(static_cast<unsigned>(std::min((n_peek + 255) / 256, 1024))), dim3(256), 0, s, B);
         }
         hipLaunchKernelGGL(mwin_peek_kernel, dim3(static_cast<unsigned>(std::min((n_peek + 3) / 4, 4096))), dim3(256), 0, s, B);
@@ -2590,26 +2557,16 @@ int ria_gpu_mcdpsk_window_host(ria_gpu_handle h, const ria_mcdpsk_config* cfg, c
     if (!samples_host || !params_host || !frame_out_host || !result_out || !acq_out || window_len < 1 || max_bytes < frame_row)
         return fail(h, RIA_ERR_INVALID, "ria_gpu_mcdpsk_window_host: bad argument (null pointer, window_len >= 1, max_bytes >= RIA_MACQ_FRAME_BYTES(8))");
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t b_x = static_cast<size_t>(window_len) * sizeof(float), o_p = up256(b_x), o_fr = up256(o_p + sizeof(ria_mcdpsk_acq_params));
-    const size_t o_res = up256(o_fr + frame_row), o_acq = up256(o_res + sizeof(ria_mcdpsk_window_result)), total = up256(o_acq + sizeof(ria_mcdpsk_acq_result));
-    int rc = ensure_host_stage(h, total);
-    if (rc != RIA_OK) return rc;
-    unsigned char *D = h->d_hstage.as<unsigned char>(), *P = h->p_hstage.as<unsigned char>();
-    hipStream_t s = h->hstream;
-    std::memcpy(P, samples_host, b_x);
-    std::memcpy(P + o_p, params_host, sizeof(ria_mcdpsk_acq_params));
-    HIP_TRY(h, hipMemcpyAsync(D, P, o_p + sizeof(ria_mcdpsk_acq_params), hipMemcpyHostToDevice, s));
-    rc = ria_gpu_mcdpsk_window_batch(h, cfg, reinterpret_cast<const float*>(D), window_len, search_len, window_len, 1,
-                                     reinterpret_cast<const ria_mcdpsk_acq_params*>(D + o_p), flags, D + o_fr, frame_row,
-                                     reinterpret_cast<ria_mcdpsk_window_result*>(D + o_res), reinterpret_cast<ria_mcdpsk_acq_result*>(D + o_acq),
-                                     nullptr, 0, nullptr, nullptr, nullptr, nullptr, interleaver_bits, s);
-    if (rc != RIA_OK) return rc;
-    HIP_TRY(h, hipMemcpyAsync(P + o_fr, D + o_fr, total - o_fr, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    std::memcpy(frame_out_host, P + o_fr, static_cast<size_t>(frame_row));
-    std::memcpy(result_out, P + o_res, sizeof(ria_mcdpsk_window_result));
-    std::memcpy(acq_out, P + o_acq, sizeof(ria_mcdpsk_acq_result));
-    return RIA_OK;
+    struct Stage { float* x; ria_mcdpsk_acq_params* par; uint8_t* frame; ria_mcdpsk_window_result* res; ria_mcdpsk_acq_result* acq; };
+    auto carve = [&](StageCarver& c) {
+        Stage w;
+        w.x = c.in(static_cast<size_t>(window_len), samples_host); w.par = c.in(1, params_host);
+        w.frame = c.out(static_cast<size_t>(frame_row), frame_out_host); w.res = c.out(1, result_out); w.acq = c.out(1, acq_out);
+        return w;
+    };
+    return host_staged(h, carve, [&](const Stage& d, hipStream_t s) {
+        return ria_gpu_mcdpsk_window_batch(h, cfg, d.x, window_len, search_len, window_len, 1, d.par, flags, d.frame, frame_row, d.res, d.acq,
+                                           nullptr, 0, nullptr, nullptr, nullptr, nullptr, interleaver_bits, s); });
 }
 
 int ria_gpu_mcdpsk_interleave_batch(ria_gpu_handle h, int interleaver_bits, const uint8_t* coded_dev, int n_cw, uint8_t* out_dev, void* stream) {
@@ -2741,7 +2698,6 @@ static int mdf_impl(ria_gpu_handle h, const char* who, const float* llr_dev, int
     HIP_TRY(h, h->p_mdf_ctl.reserve(sizeof(MacqCtl)));
     const MdfWs MW = carve_at(h->d_mdf_ws.as<>(), carve);
     const MacqWs& W = MW.m;
-    const MacqCtl& ctl = *h->p_mdf_ctl.as<MacqCtl>();
     HarqArgs H{};
     HarqWs HW{};
     if (pool) {
@@ -2750,42 +2706,17 @@ static int mdf_impl(ria_gpu_handle h, const char* who, const float* llr_dev, int
         HIP_TRY(h, hipMemsetAsync(harq_dev, 0, n * sizeof(ria_mcdpsk_harq_result), s));
     }
     MacqArgs A{};
-    A.n_windows = n_frames; A.retry = 0; A.bps = 1; A.acq = MW.acq; A.ctl = W.ctl;
+    A.n_windows = n_frames; A.retry = 0; A.bps = 1; A.acq = MW.acq;
     A.cur = W.list[0]; A.next = W.list[1]; A.n_cur = n_frames;
-    A.mst = W.mst; A.llr = llr_dev; A.llr_ws = llr_stride;
-    A.rows = W.rows; A.row_entry = W.row_entry; A.row_cw = W.row_cw;
-    A.out_a = W.out_a; A.ok_a = W.ok_a; A.out_b = W.out_b; A.ok_b = W.ok_b;
-    A.dec_bytes = static_cast<int>(dec_bytes);
-    A.hdr_total = W.hdr; A.need_rows = W.need; A.row_base = W.base; A.done = W.done;
-    A.crc_bit = h->d_crc_bit.as<const uint16_t>(); A.crc_init = h->d_crc_init.as<const uint16_t>();
+    macq_bind(A, W, h, ci, ci_step);
+    A.llr = llr_dev; A.llr_ws = llr_stride;
     A.frame_out = frame_out_dev; A.frame_row = frame_row;
-    if (ci) { A.ci_step = ci_step; A.ci_flag = W.ci_flag; A.ci_list = W.ci_list; A.ci_ctl = W.ci_ctl; }
-    // the rows as one round's list (every row, in order), then that round's stages
+    // the rows as one round's list (every row, in order), then that round's stages; ctl.dup is tested with the round's
+    // row-list read, the first that every call makes
     const unsigned tgrid = static_cast<unsigned>(std::min((n_frames + 255) / 256, 1024));
     hipLaunchKernelGGL(mdf_list_kernel, dim3(tgrid), dim3(256), 0, s, A, n_llr_dev, W.mst);
-    MacqArgs G = A;
-    G.row_entry = nullptr;
-    hipLaunchKernelGGL(macq_gather_kernel, dim3(static_cast<unsigned>(std::min<size_t>((n * kMacqLdpcBlock + 255) / 256, 16384))), dim3(256), 0, s, G, n_frames);
-    int rc = ria_gpu_ldpc_decode_robust_batch(h, A.rows, n_frames, W.out_a, W.ok_a, W.it_a, nullptr, s);
-    if (rc != RIA_OK) return rc;
-    if (ci && (rc = macq_round_a2(h, who, A, W, h->p_mdf_ctl, s)) != RIA_OK) return rc;
-    const unsigned waves = static_cast<unsigned>(std::min((n_frames + 3) / 4, 4096));
-    hipLaunchKernelGGL(macq_header_kernel, dim3(waves), dim3(256), 0, s, A);
-    hipLaunchKernelGGL(macq_rows_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A);
-    HIP_TRY(h, hipGetLastError());
-    if ((rc = read_ctl(h, h->p_mdf_ctl, A.ctl, s)) != RIA_OK) return rc;
-    if (pool && ctl.dup)
-        return fail(h, RIA_ERR_INVALID, "%s: two rows of one call use one cache id, or an id is not below n_caches; no cache was touched", who);
-    const int n_rows = static_cast<int>(ctl.n_rows);
-    if (n_rows < 0 || static_cast<size_t>(n_rows) > n * (max_cw - 1)) return fail(h, RIA_ERR_HIP, "%s: the codeword rows broke their bound (%d)", who, n_rows);
-    if (n_rows > 0) {
-        hipLaunchKernelGGL(macq_gather_kernel, dim3(static_cast<unsigned>(std::min<size_t>((static_cast<size_t>(n_rows) * kMacqLdpcBlock + 255) / 256, 16384))),
-                           dim3(256), 0, s, A, n_rows);
-        rc = ria_gpu_ldpc_decode_robust_batch(h, A.rows, n_rows, W.out_b, W.ok_b, W.it_b, nullptr, s);
-        if (rc != RIA_OK) return rc;
-    }
-    if (pool && (rc = harq_stages(h, who, A, H, HW, h->p_mdf_ctl, n_rows, waves, s)) != RIA_OK) return rc;
-    hipLaunchKernelGGL(macq_finish_kernel, dim3(waves), dim3(256), 0, s, A);
+    if (int rc = macq_round_cw0(h, who, A, W, ci, h->p_mdf_ctl, s)) return rc;
+    if (int rc = macq_round_rest(h, who, A, W, pool, H, HW, h->p_mdf_ctl, static_cast<int>(max_cw), "rows", s)) return rc;
     hipLaunchKernelGGL(mdf_result_kernel, dim3(tgrid), dim3(256), 0, s, MW.acq, n_frames, result_dev);
     HIP_TRY(h, hipGetLastError());
     return RIA_OK;
@@ -2850,6 +2781,24 @@ static DfWs dframe_carve(Carver& c, size_t n, size_t max_cw, size_t bpc, size_t 
     w.lg_it = c.take<uint16_t>(nr);
     return w;
 }
+// The reserve step of decodeFrame for n_frames rows of up to max_cw codewords: the R1/4 code on a handle of another rate,
+// the de-interleave table the flags select, the workspace with its control block, and decodeFixedFrame's (decode_reserve).
+// Nothing of an earlier call is in flight: every call ends on a stream sync.  `who` is the public call, for the message.
+static int dframe_reserve(ria_gpu_handle h, const char* who, int n_frames, size_t max_cw, uint32_t flags, DfWs* out) {
+    if (h->cfg.code_rate != RIA_RATE_1_4) { if (int rc = dframe_ensure_r14(h)) return rc; }
+    const bool ch_deint = (flags & RIA_DECODE_NO_CHANNEL_DEINTERLEAVE) == 0;
+    DevBuf& perm = h->d_cw_perm[ch_deint ? 1 : 0];
+    if (!perm) HIP_TRY(h, upload(perm, build_cw_deinterleave(h->geo.bits_per_symbol, ch_deint)));
+    auto carve = [&](Carver& c) {
+        return dframe_carve(c, static_cast<size_t>(n_frames), max_cw, static_cast<size_t>(h->geo.bytes_per_codeword), static_cast<size_t>((h->geo.ldpc_k + 7) / 8));
+    };
+    hipError_t e = h->d_df_ws.reserve(carved_size(carve));
+    if (e == hipSuccess) e = h->p_df_ctl.reserve(sizeof(DfCtl));
+    if (e == hipSuccess) e = decode_reserve(h, n_frames, flags);
+    if (e != hipSuccess) return fail(h, RIA_ERR_HIP, "%s workspace: %s", who, hipGetErrorString(e));
+    *out = carve_at(h->d_df_ws.as<>(), carve);
+    return RIA_OK;
+}
 
 int ria_gpu_decode_frame_batch(ria_gpu_handle h, const float* llr_dev, int llr_stride, const int32_t* n_llr_dev, int n_frames,
                                uint32_t flags, uint8_t* frame_out_dev, int frame_row, ria_dframe_result* result_dev,
@@ -2865,31 +2814,19 @@ int ria_gpu_decode_frame_batch(ria_gpu_handle h, const float* llr_dev, int llr_s
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool r14 = h->cfg.code_rate == RIA_RATE_1_4;
-    const bool ch_deint = (flags & RIA_DECODE_NO_CHANNEL_DEINTERLEAVE) == 0;
-    // everything the call may need is allocated here, before any of it is in flight
-    if (!r14) { if (int rc = dframe_ensure_r14(h)) return rc; }
-    DevBuf& perm = h->d_cw_perm[ch_deint ? 1 : 0];
-    if (!perm) HIP_TRY(h, upload(perm, build_cw_deinterleave(h->geo.bits_per_symbol, ch_deint)));
     const size_t n = static_cast<size_t>(n_frames), max_cw = static_cast<size_t>(llr_stride / kDfBlock);
-    const size_t dec_bytes = static_cast<size_t>((h->geo.ldpc_k + 7) / 8);
-    auto carve = [&](Carver& c) { return dframe_carve(c, n, max_cw, static_cast<size_t>(bpc), dec_bytes); };
-    HIP_TRY(h, h->d_df_ws.reserve(carved_size(carve)));   // nothing of an earlier call is in flight: every call ends on a stream sync
-    HIP_TRY(h, h->p_df_ctl.reserve(sizeof(DfCtl)));
-    const DfWs W = carve_at(h->d_df_ws.as<>(), carve);
+    // everything the call may need is allocated here, before any of it is in flight
+    DfWs W;
+    if (int rc = dframe_reserve(h, "ria_gpu_decode_frame_batch", n_frames, max_cw, flags, &W)) return rc;
     const DfCtl& ctl = *h->p_df_ctl.as<DfCtl>();
-    {
-        hipError_t e = ensure_decode_ws(h, n_frames);
-        if (e == hipSuccess && (flags & RIA_DECODE_CRC_RECOVER)) e = ensure_recovery_ws(h, std::max(n_frames, h->cfg.max_batch), false);
-        if (e != hipSuccess) return fail(h, RIA_ERR_HIP, "ria_gpu_decode_frame_batch workspace: %s", hipGetErrorString(e));
-    }
     DfArgs A{};
     A.llr = llr_dev; A.llr_stride = llr_stride; A.n_llr = n_llr_dev; A.n_frames = n_frames;
     A.rate_is_r14 = r14 ? 1 : 0; A.bpc = bpc; A.bpc14 = info_bits_for(RIA_RATE_1_4) / 8;
     A.row = W.row; A.probe = W.probe; A.list = W.list; A.ctl = W.ctl;
     A.fx_llr = W.fx_llr; A.fx_info = W.fx_info; A.fx_st = W.fx_st;
-    A.perm = perm.as<const uint16_t>();
+    A.perm = h->d_cw_perm[(flags & RIA_DECODE_NO_CHANNEL_DEINTERLEAVE) ? 0 : 1].as<const uint16_t>();
     A.lg_rows = W.lg_rows; A.lg_entry = W.lg_entry; A.lg_cw = W.lg_cw;
-    A.lg_out = W.lg_out; A.lg_ok = W.lg_ok; A.dec_bytes = static_cast<int>(dec_bytes);
+    A.lg_out = W.lg_out; A.lg_ok = W.lg_ok; A.dec_bytes = (h->geo.ldpc_k + 7) / 8;
     A.crc_bit = h->d_crc_bit.as<const uint16_t>(); A.crc_init = h->d_crc_init.as<const uint16_t>();
     A.frame_out = frame_out_dev; A.frame_row = frame_row; A.result = result_dev; A.st_out = decode_status_dev; A.info_out = info_out_dev;
     // control block, row state, probe records and lists in one memset (they lie in front of the bulk areas)
@@ -2960,25 +2897,18 @@ int ria_gpu_decode_frame_host(ria_gpu_handle h, const float* llr_host, int n_llr
     const int frame_row = std::max(4, stride / kDfBlock) * h->geo.bytes_per_codeword;
     if (max_bytes < frame_row) return fail(h, RIA_ERR_INVALID, "ria_gpu_decode_frame_host: max_bytes %d < %d (max(4, n_llr / 648) * bytes_per_codeword)", max_bytes, frame_row);
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t b_llr = static_cast<size_t>(stride) * sizeof(float), o_n = up256(b_llr), o_fr = up256(o_n + sizeof(int32_t));
-    const size_t o_res = up256(o_fr + frame_row), o_ds = up256(o_res + sizeof(ria_dframe_result)), total = up256(o_ds + sizeof(ria_decode_status));
-    int rc = ensure_host_stage(h, total);
-    if (rc != RIA_OK) return rc;
-    unsigned char *D = h->d_hstage.as<unsigned char>(), *P = h->p_hstage.as<unsigned char>();
-    hipStream_t s = h->hstream;
-    std::memset(P, 0, b_llr);
-    if (n_use > 0) std::memcpy(P, llr_host, static_cast<size_t>(n_use) * sizeof(float));
-    *reinterpret_cast<int32_t*>(P + o_n) = n_use;
-    HIP_TRY(h, hipMemcpyAsync(D, P, o_n + sizeof(int32_t), hipMemcpyHostToDevice, s));
-    rc = ria_gpu_decode_frame_batch(h, reinterpret_cast<const float*>(D), stride, reinterpret_cast<const int32_t*>(D + o_n), 1, flags, D + o_fr,
-                                    frame_row, reinterpret_cast<ria_dframe_result*>(D + o_res), reinterpret_cast<ria_decode_status*>(D + o_ds), nullptr, s);
-    if (rc != RIA_OK) return rc;
-    HIP_TRY(h, hipMemcpyAsync(P + o_fr, D + o_fr, total - o_fr, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    std::memcpy(frame_out_host, P + o_fr, static_cast<size_t>(frame_row));
-    std::memcpy(result_out, P + o_res, sizeof(ria_dframe_result));
-    if (decode_status_out) std::memcpy(decode_status_out, P + o_ds, sizeof(ria_decode_status));
-    return RIA_OK;
+    const int32_t n_used = n_use;
+    const float none = 0.0f;   // a row without soft bits is still a row of zeros
+    struct Stage { float* llr; int32_t* n_llr; uint8_t* frame; ria_dframe_result* res; ria_decode_status* ds; };
+    auto carve = [&](StageCarver& c) {
+        Stage w;
+        // the row is padded with zeros to a whole codeword
+        w.llr = c.in(static_cast<size_t>(stride), n_use > 0 ? llr_host : &none, static_cast<size_t>(n_use)); w.n_llr = c.in(1, &n_used);
+        w.frame = c.out(static_cast<size_t>(frame_row), frame_out_host); w.res = c.out(1, result_out); w.ds = c.out(1, decode_status_out);
+        return w;
+    };
+    return host_staged(h, carve, [&](const Stage& d, hipStream_t s) {
+        return ria_gpu_decode_frame_batch(h, d.llr, stride, d.n_llr, 1, flags, d.frame, frame_row, d.res, d.ds, nullptr, s); });
 }
 
 // ------------------------------------------------------------------------------------------------ one connected-mode window
@@ -3035,7 +2965,7 @@ static int win_demod_pass(ria_gpu_handle h, const float* samples_dev, WinArgs& A
     if (total == 0) return RIA_OK;
     for (int g = 0; g < kWinGroups; ++g) {
         if (A.cnt[g] == 0) continue;
-        if (int rc = demod_var_launch(h, "ria_gpu_rx_window_batch", samples_dev, A.list[g].offset, A.list[g].meta, A.cnt[g], A.len[g],
+        if (int rc = demod_var_launch(h, samples_dev, A.list[g].offset, A.list[g].meta, A.cnt[g], A.len[g],
                                       W.llr_c + static_cast<size_t>(A.base[g]) * A.llr_stride, A.llr_stride, W.fst_c + A.base[g], s)) return rc;
     }
     hipLaunchKernelGGL(win_scatter_kernel, dim3(static_cast<unsigned>(std::min<long long>(total, 16384))), dim3(256), 0, s, A, static_cast<int>(total));
@@ -3061,7 +2991,7 @@ int ria_gpu_rx_window_batch(ria_gpu_handle control_h, ria_gpu_handle h, const fl
     if (!samples_dev || !params_dev || !frame_out_dev || !result_dev || !acq_dev) return fail(h, RIA_ERR_INVALID, "%s: null pointer", who);
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (demod_fused_selected()) return fail(h, RIA_ERR_UNSUPPORTED, "%s: RIA_DEMOD_FUSED=1 demodulates fixed frames only", who);
+    if (int rc = demod_span_reserve(h, who)) return rc;
     const int n_ctl = ria_gpu_control_frame_samples(control_h, h);
     if (n_ctl < 0) return n_ctl;
     if (n_ctl > h->geo.frame_samples) return fail(h, RIA_ERR_UNSUPPORTED, "%s: the control span (%d samples) is longer than a frame of the data profile", who, n_ctl);
@@ -3069,23 +2999,13 @@ int ria_gpu_rx_window_batch(ria_gpu_handle control_h, ria_gpu_handle h, const fl
     const uint32_t dflags = flags & (RIA_DECODE_FULL | RIA_DECODE_NO_CHANNEL_DEINTERLEAVE);
     const size_t n = static_cast<size_t>(n_windows);
 
-    // every workspace of the call and of the calls it makes, before anything is in flight
-    if (!r14) { if (int rc = dframe_ensure_r14(h)) return rc; }
+    // every workspace of the call and of the calls it makes, before anything is in flight: the reserve steps of the span
+    // demodulator (above), of ria_gpu_control_acquire_batch on the control handle and of ria_gpu_decode_frame_batch
+    ControlWs cw;
+    DfWs dw;
+    if (int rc = control_ensure_ws(control_h, who, n_windows, s, &cw)) return fail(h, rc, "%s: %s", who, ria_gpu_last_error(control_h));
     if (int rc = lts_prepare(control_h)) return fail(h, rc, "%s: %s", who, ria_gpu_last_error(control_h));
-    {
-        DevBuf& perm = h->d_cw_perm[(flags & RIA_DECODE_NO_CHANNEL_DEINTERLEAVE) ? 0 : 1];   // decodeFrame's per-codeword de-interleave table
-        if (!perm) HIP_TRY(h, upload(perm, build_cw_deinterleave(h->geo.bits_per_symbol, (flags & RIA_DECODE_NO_CHANNEL_DEINTERLEAVE) == 0)));
-        ControlWs cw;
-        if (int rc = control_ensure_ws(control_h, n_windows, s, &cw)) return fail(h, rc, "%s: %s", who, ria_gpu_last_error(control_h));
-        hipError_t e = control_h->d_demod_ws[0].reserve(demod_ws_bytes(2 + control_h->geo.n_data_symbols));
-        if (e == hipSuccess) e = h->d_demod_ws[0].reserve(demod_ws_bytes(2 + h->geo.n_data_symbols));
-        if (e == hipSuccess) e = ensure_decode_ws(h, n_windows);
-        if (e == hipSuccess && (flags & RIA_DECODE_CRC_RECOVER)) e = ensure_recovery_ws(h, std::max(n_windows, h->cfg.max_batch), false);
-        const size_t dec_bytes = static_cast<size_t>((h->geo.ldpc_k + 7) / 8);
-        if (e == hipSuccess) e = h->d_df_ws.reserve(carved_size([&](Carver& c) { return dframe_carve(c, n, static_cast<size_t>(llr_row / kDfBlock), static_cast<size_t>(bpc), dec_bytes); }));
-        if (e == hipSuccess) e = h->p_df_ctl.reserve(sizeof(DfCtl));
-        if (e != hipSuccess) return fail(h, RIA_ERR_HIP, "%s workspace: %s", who, hipGetErrorString(e));
-    }
+    if (int rc = dframe_reserve(h, who, n_windows, static_cast<size_t>(llr_row / kDfBlock), dflags, &dw)) return rc;
     auto carve = [&](Carver& c) { return window_carve(c, n, static_cast<size_t>(llr_row), static_cast<size_t>(df_row)); };
     HIP_TRY(h, h->d_win_ws.reserve(carved_size(carve), &s));
     HIP_TRY(h, h->p_win_ctl.reserve(sizeof(WinCtl)));

@@ -182,6 +182,26 @@ def test_control_acquire_across_the_scan_tile_and_call_after_call(oracle, window
         assert np.array_equal(a.view(np.uint8) if a.dtype.names else a, b.view(np.uint8) if b.dtype.names else b)
 
 
+def test_workspace_growth_leaves_results_alone(windows):
+    """A call on 2 windows, then one on every full-length window, on a fresh handle created for 2 frames: every array of the
+    second equals the same call on another fresh handle that never ran the first, and the first equals that call's first
+    two rows."""
+    from ria_amd.engine import RxEngine
+    ws, conf = windows
+    idx = [i for i, w in enumerate(ws) if len(w) == CI.WINDOW_LEN]
+    ws, conf = [ws[i] for i in idx], [conf[i] for i in idx]
+    a, b = RxEngine("DQPSK", "R1_4", max_batch=2), RxEngine("DQPSK", "R1_4", max_batch=2)
+    small = run_windows(a, ws[:2], conf[:2], CI.CTRL_SAMPLES)
+    big = run_windows(a, ws, conf, CI.CTRL_SAMPLES)
+    ref = run_windows(b, ws, conf, CI.CTRL_SAMPLES)
+    assert len(ws) > 2 and ref[1]["tried"].any()                             # the demodulator and the decoder ran
+    for k, (s, g, r) in enumerate(zip(small, big, ref)):
+        assert g.tobytes() == r.tobytes(), k
+        assert s.tobytes() == r[:2].tobytes(), k
+    a.close()
+    b.close()
+
+
 def test_control_acquire_rejects_bad_arguments(windows):
     e = control_engine()
     w = dev(np.stack([windows[0][0]]))

@@ -129,6 +129,25 @@ def test_largest_batch_reversed_and_split(eng, expected):
             check_row(("split", call["rows"][i]["name"]), i - lo, got, exp[i])
 
 
+def test_workspace_growth_leaves_results_alone(expected):
+    """A call on 2 windows, then one on the whole largest batch, on a fresh handle created for 2 frames: every array of the
+    second equals the same call on another fresh handle that never ran the first, and the first equals that call's first
+    two rows."""
+    from ria_amd.engine import RxEngine
+    call, x, kw, _ = next(t for t in expected if t[0]["name"] == "chirp_disconnected")
+    assert len(x) > 2
+    a, b = RxEngine("DQPSK", "R1_4", max_batch=2), RxEngine("DQPSK", "R1_4", max_batch=2)
+    small = run(a, call, x[:2], {k: v[:2] for k, v in kw.items()})
+    big = run(a, call, x, kw)
+    ref = run(b, call, x, kw)
+    assert ref[2]["accepted"].sum() > 2 and ref[1]["deliver"].any()          # rounds ran behind the peek pass
+    for k, (s, g, r) in enumerate(zip(small, big, ref)):
+        assert g.tobytes() == r.tobytes(), k
+        assert s.tobytes() == r[:2].tobytes(), k
+    a.close()
+    b.close()
+
+
 def test_1030_windows_cross_the_scan_tile(eng, expected):
     """1030 windows tiled from 8 distinct one-codeword-span ZC windows: every list kernel crosses its 1024-thread tile"""
     call, x, kw, exp = next(t for t in expected if t[0]["name"] == "zc_cut_short")

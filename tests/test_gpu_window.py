@@ -33,10 +33,10 @@ def data_engine(link):
     return engine(*WI.LINK_NAMES[link])
 
 
-def run(link, ws, kws, interleave=False, retry=True):
-    """one call on windows of one length -> numpy outputs"""
-    de = data_engine(link)
-    frames, res, acq, cres, st = de.rx_window(control_engine(), dev(np.stack(ws)), WI.SEARCH_LEN,
+def run(link, ws, kws, interleave=False, retry=True, engines=None):
+    """one call on windows of one length -> numpy outputs; engines: (control, data) instead of the shared pair"""
+    ce, de = engines or (control_engine(), data_engine(link))
+    frames, res, acq, cres, st = de.rx_window(ce, dev(np.stack(ws)), WI.SEARCH_LEN,
                                               known_cfo=np.array([k["known_cfo"] for k in kws], np.float32),
                                               detect_threshold=np.array([k["detect_threshold"] for k in kws], np.float32),
                                               min_confidence=np.array([k["min_confidence"] for k in kws], np.float32),
@@ -127,6 +127,29 @@ def test_order_and_batching_do_not_change_a_row(oracle, table):
         flat = lambda t: np.ascontiguousarray(t).view(np.uint8).reshape(len(t), -1)
         assert np.array_equal(flat(x), flat(y)[::-1])
         assert np.array_equal(flat(x), np.concatenate([flat(p), flat(q)]))
+
+
+def test_workspace_growth_leaves_results_alone(oracle, table):
+    """A call on 2 windows, then one on the whole largest batch (RIA_DECODE_FULL), on fresh control and data handles created
+    for 2 frames: every array of the second equals the same call on another fresh pair that never ran the first, and the
+    first equals that call's first two rows."""
+    from ria_amd.engine import RxEngine
+    key = max(table, key=lambda k: len(table[k][0]))
+    items, got, _ = table[key]
+    link, _, il, retry = key
+    ws, kws = [w for _, w, _ in items], [kw for _, _, kw in items]
+    fresh = lambda: (RxEngine("DQPSK", "R1_4", max_batch=2), RxEngine(*WI.LINK_NAMES[link], max_batch=2))
+    a, b = fresh(), fresh()
+    small = run(link, ws[:2], kws[:2], il, retry, engines=a)
+    big = run(link, ws, kws, il, retry, engines=a)
+    ref = run(link, ws, kws, il, retry, engines=b)
+    assert len(ws) > 2 and (ref[1]["outcome"] == capi.WIN_OUTCOME["DECODED"]).sum() > 2     # decodeFrame ran on more than the first call's rows
+    flat = lambda t: np.ascontiguousarray(t).view(np.uint8).reshape(len(t), -1)
+    for k, (s, g, r, shared) in enumerate(zip(small, big, ref, got)):
+        assert np.array_equal(flat(g), flat(r)) and np.array_equal(flat(r), flat(shared)), k
+        assert np.array_equal(flat(s), flat(r)[:2]), k
+    for e in a + b:
+        e.close()
 
 
 def test_control_rows_equal_control_acquire(oracle, table):
