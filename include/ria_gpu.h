@@ -526,7 +526,8 @@ int ria_gpu_burst_interleave_batch(ria_gpu_handle h, const uint8_t* logical_byte
  * the soft bits this call can return; the control-first re-demodulation with the DQPSK R1/4 profile (:1268-1344) is
  * ria_gpu_control_acquire_batch's, run ahead of this call on a control handle; the short-span data-profile demodulation that
  * moves last_cfo_ (:1346-1434), the 1-CW peek buffer, the pending_total_cw_ escalation (:1505-1597) and the small-frame
- * recovery (:1806-1853) are ria_gpu_rx_window_batch's, which runs the whole window in one call; the weak-accept and reject-streak state (fold them into min_confidence), the PING
+ * recovery (:1806-1853) are ria_gpu_rx_window_batch's, which runs the whole window in one call; the weak-accept and reject-streak state (fold them into min_confidence, or take both from ria_gpu_search_batch, whose result
+ * names this call's window and parameters), the PING
  * energy check, burst groups and burst continuation (ria_gpu_rx_burst_batch), chase combining, Schmidl-Cox
  * acquisition, OFDM-COX, ring-buffer wrap-around, and the +-2 Hz clamp of the reported CFO the host applies before it
  * feeds it back (:1912-1918).  MC-DPSK frames (ZC and dual-chirp acquisition, the disconnected handshake fallbacks) are
@@ -1287,6 +1288,103 @@ int ria_gpu_rx_window_batch(ria_gpu_handle control_h, ria_gpu_handle data_h, con
                             uint8_t* frame_out_dev, int frame_row, ria_window_result* result_dev, ria_acq_result* acq_dev,
                             ria_control_result* control_dev /* nullable */, ria_frame_status* demod_status_dev /* nullable: the reported span's */,
                             void* stream);
+
+/* ---- from a capture to its next window: StreamingDecoder::searchForSync for a batch of captures ------------------------
+ * ria_gpu_search_batch walks n_streams captures, each from its own cursor to the next accepted sync.  It replaces
+ * gui::StreamingDecoder::searchForSync (src/gui/modem/streaming_decoder.cpp:386-941) with the part of feedAudio it depends
+ * on (:184-225, :286-291): the search-buffer sizing (:404-438), the two waits for audio (:449-481), the ZC backlog catch-up
+ * (:488-522), the 1000-sample RMS with the noise-floor tracker and the adaptive gate (:525-573), backtrack and step
+ * (:589-612), light_sync_min_confidence / weak_sync_floor with the fading and SNR hints, the reject-streak relaxation and the
+ * ZC reject-loop breaker (:662-716), the detector call with near miss, reject and weak accept (:725-783), sync_position_
+ * (:858), anti-replay (:876-889), the +-1 Hz CFO sanity rule (:903-917) and estimateSNRFromChirp (:2587-2590).  The rules
+ * are float32 with the reference's own argument order in std::max / std::min / std::clamp (ria_amd/csrc/search_rules.hpp), so
+ * a NaN noise floor becomes 0.001 at the tracker, a NaN gate passes, and every result is the reference's bit for bit.
+ *
+ * Stream s lies at samples_dev + s*stride and holds capture_len_dev[s] samples, 0 <= capture_len <= min(stride, 959 999):
+ * the 960 000-sample ring buffer never wraps, so a ring index is a capture index.  A longer capture, a state with fed outside
+ * 0..capture_len, a cursor outside 0..959 999 or a negative streak is RIA_ERR_INVALID for the whole call: the domain is checked
+ * on the device ahead of the walk, and no stream's state or result is written and no sample read.
+ *
+ * Modes.  RIA_SEARCH_OFDM_LTS: connected OFDM-CHIRP light sync (detectDataSync of OFDMChirpWaveform, min_search 67 304); the
+ * modulation class - coherent PSK 0.90 / 0.85, QAM 0.78 / 0.70, differential 0.72 / 0.55 with the hint tiers - is the
+ * handle's.  RIA_SEARCH_MCDPSK_ZC: connected MC-DPSK (ZC detectDataSync on roots DATA | CONTROL, min_search 31 120, backtrack
+ * 19 200, step 1200, catch-up, near miss, breaker).  RIA_SEARCH_MCDPSK_CHIRP: the dual-chirp detectSync of the MC-DPSK
+ * waveform (min_search 120 000, threshold 0.15, no acceptance rule): the disconnected handshake, or with
+ * RIA_SEARCH_CONNECTED the connected "weak profile" (DBPSK with spreading, :417-421), which turns the CFO sanity rule on.
+ * RIA_SEARCH_CONNECTED is implied by the first two modes.  cfg (the two MC-DPSK modes; NULL for LTS) is checked like the other
+ * MC-DPSK calls' and does not change a result: preamble, detector and rules do not depend on it.
+ *
+ * Time model.  One invocation is one searchForSync().  After every invocation that leaves the stream open, feed_step
+ * samples arrive through feedAudio's rule: count = min(feed_step, capture_len - fed); nothing happens for count 0; else a
+ * cursor ahead of fed is clamped to it with the streak cleared, and fed += count.  That is the reference's own harness
+ * (4800-sample chunks, one processBuffer() per chunk); feed_step 0 = the recording is all there.  The feed behind the last
+ * invocation of a call is applied before the state is written, so a RIA_SEARCH_LIMIT state given to a second call continues
+ * exactly as one longer call would.  A stream ends with
+ *   RIA_SEARCH_SYNC_FOUND    the reference's state_ = SYNC_FOUND;
+ *   RIA_SEARCH_NEED_SAMPLES  the invocation waits for audio (:449 or :475) and no more can arrive in this call (feed_step 0
+ *                            or fed == capture_len).  A cursor AHEAD of fed is a wait too (counted in waits): the reference
+ *                            would read ring-buffer samples that were never written; this library does not - its limit;
+ *   RIA_SEARCH_LIMIT         max_invocations (>= 1) invocations have run.
+ *
+ * ria_search_state is read and written in place: correlation_pos_, total_fed_ = write_pos_, noise_floor_,
+ * sync_reject_streak_, last_cfo_ (set to sync_cfo_ on SYNC_FOUND), last_fading_index_, last_snr_ (set to sync_snr_ on
+ * SYNC_FOUND) and last_decoded_sync_pos_ (INT32_MIN for SIZE_MAX, as in ria_mcdpsk_acq_params; the caller sets it when a
+ * frame is delivered).  A fresh decoder is {0, fed, 0.001f, 0, 0, 0, 0, INT32_MIN}.
+ *
+ * ria_search_result: the counters are this call's; search_start .. root are those of the stream's last detector run in
+ * this call (search_start 0, sync_position -1, marker -1 where none ran).  With RIA_SEARCH_SYNC_FOUND, search_start,
+ * search_len, known_cfo_hz, detect_threshold and min(min_confidence, correlation) are exactly the window geometry and the
+ * ria_acq_params / ria_mcdpsk_acq_params fields that make ria_gpu_rx_window_batch / ria_gpu_mcdpsk_window_batch repeat this
+ * detection on the window that starts at search_start (sync_start = sync_position - search_start, the same correlation):
+ * neither call needed a change.
+ *
+ * Work: rounds of walk -> list -> (gather -> detect -> accept, in chunks of the list) until no detector is due; one small
+ * device-to-host read per round (the list's length); no samples go to the host.  The walk runs a stream's invocations back
+ * to back up to the first that passes the gate, so silence costs no round.  A chunk's spans live in a workspace of at most
+ * 256 MiB on the handle (RIA_OPT_SEARCH_CHUNK: at most that many streams per chunk; 0 = the default), carved and reserved
+ * before anything of the call is in flight.  No result depends on scheduling, on chunking or on the other streams.
+ *
+ * Not covered: the ZC-miss -> chirp fallback (:785-828; wall-clock state, connected_since_), ring-buffer wrap and the
+ * overflow path of feedAudio (:227-278), disconnected OFDM (chirp) search, OFDM-COX, the frame timeout, and a one-stream
+ * host-memory form. */
+enum { RIA_SEARCH_OFDM_LTS = 0, RIA_SEARCH_MCDPSK_ZC = 1, RIA_SEARCH_MCDPSK_CHIRP = 2 };
+enum { RIA_SEARCH_SYNC_FOUND = 1, RIA_SEARCH_NEED_SAMPLES = 2, RIA_SEARCH_LIMIT = 3 };
+#define RIA_SEARCH_CONNECTED 0x1u
+/*   RIA_OPT_SEARCH_CHUNK  ria_gpu_search_batch runs the detector on at most this many streams at a time (1..65535; 0 = as
+ *                        many as 256 MiB of gathered spans hold). */
+#define RIA_OPT_SEARCH_CHUNK 5
+typedef struct ria_search_state {    /* 32 bytes, one per stream */
+    int32_t correlation_pos;
+    int32_t fed;
+    float   noise_floor;
+    int32_t reject_streak;
+    float   last_cfo_hz;
+    float   fading_hint;
+    float   snr_hint;
+    int32_t last_decoded_sync_pos;   /* INT32_MIN = none */
+} ria_search_state;
+typedef struct ria_search_result {   /* 112 bytes, one per stream */
+    int32_t  outcome;                /* RIA_SEARCH_* */
+    int32_t  search_start;
+    int32_t  search_len;             /* min_search of the mode */
+    int32_t  sync_position;          /* search_start + SyncResult::start_sample, -1 where nothing was found */
+    int64_t  abs_position;           /* ringPosToAbsolute(sync_position): equal before the wrap */
+    float    correlation;
+    float    known_cfo_hz;           /* last_cfo_ the detector was called with */
+    float    sync_cfo_hz;            /* sync_cfo_ after the CFO sanity rule (SYNC_FOUND) */
+    float    sync_snr_db;            /* sync_snr_ (SYNC_FOUND) */
+    float    detect_threshold;
+    float    min_confidence;         /* light_sync_min_confidence of that invocation */
+    int32_t  weak_accept;
+    int32_t  marker;                 /* LTS: wasBurstInterleaved(); ZC: ZCFrameType; chirp: -1 */
+    int32_t  root;                   /* ZC: root_detected; else -1 */
+    uint32_t invocations, waits, rms_skips, detector_runs, rejects, near_misses, weak_accepts, replays;
+    uint32_t catchups_moderate, catchups_severe;
+    uint32_t reserved0, reserved1, reserved2;
+} ria_search_result;
+int ria_gpu_search_batch(ria_gpu_handle h, int mode, uint32_t flags, const ria_mcdpsk_config* cfg /* NULL for RIA_SEARCH_OFDM_LTS */,
+                         const float* samples_dev, int64_t stride, const int32_t* capture_len_dev, int n_streams,
+                         ria_search_state* state_dev, int feed_step, int max_invocations, ria_search_result* result_dev, void* stream);
 
 /* ---- debug / test hooks ----------------------------------------------------------------------- */
 /* op: 0 sinf 1 cosf 2 logf 3 atan2f(a,b) 4 hypotf(a,b) 5 a/b 6 sqrtf(a); evaluates the device

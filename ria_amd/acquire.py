@@ -484,3 +484,112 @@ def make_handshake_windows(engine, n, kind, snr_db, seeds, mix=HANDSHAKE_KINDS, 
         win[idx, lead:lead + m] = tx[:m]
     engine.channel_exact_seeded_(win, kind, snr_db, np.ascontiguousarray(seeds, np.uint32))
     return win, search_len, kinds
+
+
+# ---- from a capture to its frames (ria_gpu_search_batch + the window calls)
+SEARCH_COUNTERS = tuple(f"outcome_{k.lower()}" for k in capi.SEARCH_OUTCOME) + \
+    ("invocations", "waits", "rms_skips", "detector_runs", "rejects", "near_misses", "weak_accepts", "replays", "catchups_moderate",
+     "catchups_severe")
+
+
+def search_tally(result):
+    """Counter row (SEARCH_COUNTERS) of one RxEngine.search call: streams per outcome, then the sums of the per-stream counters."""
+    row = [int((result["outcome"] == v).sum()) for v in capi.SEARCH_OUTCOME.values()]
+    row += [int(result[k].sum()) for k in SEARCH_COUNTERS[len(capi.SEARCH_OUTCOME):]]
+    return np.array(row, dtype=np.int64)
+
+
+def _gather_windows(captures, rows, starts, window_len):
+    """float32 [len(rows), window_len] on the device: captures[rows[i], starts[i] : starts[i] + window_len]"""
+    dev = captures.device
+    r = torch.as_tensor(np.asarray(rows, np.int64), device=dev)[:, None]
+    c = torch.as_tensor(np.asarray(starts, np.int64), device=dev)[:, None] + torch.arange(window_len, device=dev)[None, :]
+    return captures[r, c].contiguous()
+
+
+def rx_stream(engine, captures, capture_len, mode, control_engine=None, feed_step=0, max_invocations=1 << 20, max_events=256,
+              connected=None, carriers=10, modulation="DBPSK", spreading=1):
+    """Recordings in, frames out, as a composition of library calls: RxEngine.search on every open stream, then the window
+    call of the mode (rx_window on `engine` with control_engine for "OFDM_LTS", mcdpsk_window for the MC-DPSK modes) on the
+    window that starts at each SYNC_FOUND stream's search_start, with the parameters the search result names; then the host's
+    part as INTEGRATION.md words it - the cursor to search_start + next_pos, last_cfo_ from the window's CFO, the fading hint
+    (the SNR hint is the search's own), last_decoded_sync_pos_ on a delivered frame - and again, until every stream is at
+    NEED_SAMPLES or LIMIT.  A window holds the window call's documented minimum (search_len + a whole frame + 32 samples for
+    OFDM, search_len + an 8-codeword span for MC-DPSK), cut at the capture's end; windows of one length run in one call.
+
+    captures: float32 [n, stride] on the device; capture_len: samples per stream.  feed_step as in RxEngine.search: 0 for a
+    recording that is all there.  With feed_step > 0 a window may reach past the samples fed so far (a receiver would wait for
+    them before it decodes): after the window call `fed` is moved up to the new cursor, as if the consumed samples had arrived
+    meanwhile (not to the window's end: samples nobody consumed would count as backlog).  A connected MC-DPSK (ZC) recording longer than 2.5 x 31 120 samples should be given with
+    feed_step 4800: with everything "already arrived" the receiver's backlog catch-up jumps to the recording's end, as the
+    reference's would.  Returns, per stream, the list of events (dicts: position = sync_position, outcome = the window call's
+    outcome name, frame = the delivered bytes or None).  A window result the host would pass on to another call (BURST,
+    TOO_LONG) is an event with that outcome, and the cursor moves past the window's first frame; NEED_SAMPLES from a window
+    call ends the stream."""
+    n = captures.shape[0]
+    m = capi.SEARCH_MODE[mode] if isinstance(mode, str) else int(mode)
+    ofdm = m == capi.SEARCH_MODE["OFDM_LTS"]
+    chirp = m == capi.SEARCH_MODE["MCDPSK_CHIRP"]
+    if connected is None:
+        connected = False
+    lens = np.empty(n, np.int64)
+    lens[:] = capture_len
+    state = engine.search_state(n, fed=0 if feed_step else lens)
+    bps = {"DBPSK": 1, "DQPSK": 2}[modulation] if isinstance(modulation, str) else int(modulation)
+    search_len = capi.SEARCH_MIN_SEARCH[m]
+    first_frame = engine.geo.frame_samples if ofdm else mcdpsk_frame_len(1, carriers, bps, spreading)
+    full = search_len + (engine.geo.frame_samples + 32 if ofdm else mcdpsk_frame_len(8, carriers, bps, spreading))
+    names = {v: k for k, v in (capi.WIN_OUTCOME if ofdm else capi.MWIN_OUTCOME).items()}
+    events = [[] for _ in range(n)]
+    open_ = np.ones(n, bool)
+    while open_.any():
+        idx = np.flatnonzero(open_)
+        res, st = engine.search(captures[torch.as_tensor(idx, device=captures.device)].contiguous() if len(idx) < n else captures, lens[idx],
+                                state[idx], m, feed_step=feed_step, max_invocations=max_invocations, connected=connected, carriers=carriers,
+                                modulation=modulation, spreading=spreading)
+        state[idx] = st
+        found = res["outcome"] == capi.SEARCH_OUTCOME["SYNC_FOUND"]
+        open_[idx[~found]] = False
+        by_len = {}
+        for j in np.flatnonzero(found):
+            by_len.setdefault(int(min(full, lens[idx[j]] - res["search_start"][j])), []).append(j)
+        for wl, js in by_len.items():
+            rows, r = idx[js], res[js]
+            w = _gather_windows(captures, rows, r["search_start"], wl)
+            conf = np.minimum(r["min_confidence"], r["correlation"])
+            if ofdm:
+                frames, wres, acq, _, _ = engine.rx_window(control_engine, w, search_len, known_cfo=r["known_cfo_hz"], detect_threshold=r["detect_threshold"],
+                                                           min_confidence=conf, abs_base=r["search_start"])
+                nbytes, ok, fading = wres["frame"]["frame_bytes"], (wres["frame"]["success"] != 0) | (wres["frame"]["codewords_ok"] != 0), wres["fading_index"]
+                cfo, moved = wres["sync_cfo_hz"], (wres["outcome"] == capi.WIN_OUTCOME["DECODED"]) | (wres["outcome"] == capi.WIN_OUTCOME["CONTROL_PROFILE"])
+                last = np.where(ok, r["sync_position"], state["last_decoded_sync_pos"][rows])
+            else:
+                last_in = state["last_decoded_sync_pos"][rows].astype(np.int64)
+                rel = np.where(last_in == capi.SEARCH_NO_LAST_SYNC, capi.MWIN_NO_LAST_SYNC, np.clip(last_in - r["search_start"], -2 ** 31 + 1, 2 ** 31 - 1))
+                frames, wres, acq, _ = engine.mcdpsk_window(w, search_len, carriers=carriers, modulation=bps, spreading=spreading,
+                                                            sync="chirp" if chirp else "zc", disconnected=chirp and not connected,
+                                                            known_cfo=r["known_cfo_hz"], detect_threshold=r["detect_threshold"], min_confidence=conf,
+                                                            abs_base=r["search_start"], last_decoded_sync=rel)
+                nbytes, ok, fading = acq["frame_bytes"], wres["deliver"] != 0, acq["fading_index"]
+                cfo, moved = acq["cfo_hz"], wres["outcome"] == capi.MWIN_OUTCOME["DECODED"]
+                out_last = wres["last_decoded_sync"].astype(np.int64)
+                last = np.where(out_last == capi.MWIN_NO_LAST_SYNC, capi.SEARCH_NO_LAST_SYNC, out_last + r["search_start"])
+            frames = frames.cpu().numpy()
+            for k, s in enumerate(rows):
+                name = names[int(wres["outcome"][k])]
+                events[s].append(dict(position=int(r["sync_position"][k]), outcome=name,
+                                      frame=frames[k, :int(nbytes[k])].tobytes() if ok[k] else None))
+                if moved[k]:
+                    state["last_cfo_hz"][s] = cfo[k]
+                    state["fading_hint"][s] = fading[k]
+                state["last_decoded_sync_pos"][s] = last[k]
+                if wres["next_pos"][k] >= 0:
+                    state["correlation_pos"][s] = int(r["search_start"][k]) + int(wres["next_pos"][k])
+                elif name in ("BURST", "TOO_LONG"):
+                    state["correlation_pos"][s] = int(r["sync_position"][k]) + first_frame
+                # the samples the window call consumed have arrived (feed_step > 0: a receiver waits for them before it decodes),
+                # so the cursor it leaves behind is not ahead of the write position and the next feed does not clamp it back
+                state["fed"][s] = max(int(state["fed"][s]), min(int(lens[s]), int(state["correlation_pos"][s])))
+                if name == "NEED_SAMPLES" or len(events[s]) >= max_events or state["correlation_pos"][s] >= capi.SEARCH_MAX_CAPTURE:
+                    open_[s] = False
+    return events

@@ -15,6 +15,7 @@ OPT_SPLIT_PARTS = 1
 OPT_DUAL_DECODER = 2
 OPT_FALLBACK_QUEUE_ALL = 3
 OPT_STATE_EXIT = 4
+OPT_SEARCH_CHUNK = 5
 ACQ_NO_TIMING_RETRY = 0x400
 BURST_MAX_FRAMES = 9
 BURST_INTERLEAVE = 0x800
@@ -40,6 +41,13 @@ MPEEK_BITS = {"HANDSHAKE_FALLBACK": 0x10, "EARLY_WINDOW": 0x20, "HANDSHAKE_WINDO
 MWIN_NO_LAST_SYNC = -2 ** 31
 CHASE_MAX_CW, CHASE_MAX_ENTRIES, CHASE_MAX_COMBINES = 16, 16, 4
 HARQ_ENTRY = {"NONE": 0, "KEPT": 1, "REMOVED": 2}
+# RIA_SEARCH_*: the modes and outcomes of ria_gpu_search_batch
+SEARCH_MODE = {"OFDM_LTS": 0, "MCDPSK_ZC": 1, "MCDPSK_CHIRP": 2}
+SEARCH_OUTCOME = {"SYNC_FOUND": 1, "NEED_SAMPLES": 2, "LIMIT": 3}
+SEARCH_CONNECTED = 0x1
+SEARCH_MIN_SEARCH = {0: 67304, 1: 31120, 2: 120000}
+SEARCH_MAX_CAPTURE = 959999
+SEARCH_NO_LAST_SYNC = -2 ** 31
 
 # every symbol include/ria_gpu.h declares
 EXPORTS = [
@@ -57,7 +65,7 @@ EXPORTS = [
     "ria_gpu_mcdpsk_decode_frame_ci_batch", "ria_gpu_mcdpsk_acquire_ci_batch", "ria_gpu_mcdpsk_interleave_batch",
     "ria_gpu_var_frame_samples", "ria_gpu_control_frame_samples", "ria_gpu_tx_coded_var_batch", "ria_gpu_demod_var_batch", "ria_gpu_demod_var_host",
     "ria_gpu_rx_control_batch", "ria_gpu_control_acquire_batch", "ria_gpu_rx_window_batch",
-    "ria_gpu_mcdpsk_window_batch", "ria_gpu_mcdpsk_window_host",
+    "ria_gpu_mcdpsk_window_batch", "ria_gpu_mcdpsk_window_host", "ria_gpu_search_batch",
     "ria_link_recommend", "ria_link_data_mode", "ria_link_ofdm_code_rate", "ria_link_cap_initial_rate",
 ]
 
@@ -185,6 +193,19 @@ class WindowResult(C.Structure):
                 ("peek_cfo_hz", C.c_float), ("fading_index", C.c_float)]
 
 
+class SearchState(C.Structure):
+    _fields_ = [("correlation_pos", C.c_int32), ("fed", C.c_int32), ("noise_floor", C.c_float), ("reject_streak", C.c_int32),
+                ("last_cfo_hz", C.c_float), ("fading_hint", C.c_float), ("snr_hint", C.c_float), ("last_decoded_sync_pos", C.c_int32)]
+
+
+class SearchResult(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("outcome", "search_start", "search_len", "sync_position")] + [("abs_position", C.c_int64)] + \
+               [(n, C.c_float) for n in ("correlation", "known_cfo_hz", "sync_cfo_hz", "sync_snr_db", "detect_threshold", "min_confidence")] + \
+               [(n, C.c_int32) for n in ("weak_accept", "marker", "root")] + \
+               [(n, C.c_uint32) for n in ("invocations", "waits", "rms_skips", "detector_runs", "rejects", "near_misses", "weak_accepts",
+                                          "replays", "catchups_moderate", "catchups_severe", "reserved0", "reserved1", "reserved2")]
+
+
 def macq_frame_bytes(frame_cw):
     """RIA_MACQ_FRAME_BYTES: bytes of one frame_out row of ria_gpu_mcdpsk_acquire_batch"""
     return 40 * int(frame_cw)
@@ -288,6 +309,7 @@ def load(build_if_needed=True):
     L.ria_gpu_rx_window_batch.argtypes = [vp, vp, vp, C.c_int64, i32, i32, i32, vp, u32, vp, i32, vp, vp, vp, vp, vp]
     L.ria_gpu_mcdpsk_window_batch.argtypes = [vp, vp, vp, C.c_int64, i32, i32, i32, vp, u32, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp]
     L.ria_gpu_mcdpsk_window_host.argtypes = [vp, vp, vp, i32, i32, vp, u32, vp, i32, vp, vp, i32]
+    L.ria_gpu_search_batch.argtypes = [vp, i32, u32, vp, vp, C.c_int64, vp, i32, vp, i32, i32, vp, vp]
     L.ria_link_recommend.argtypes = [f32, f32, C.POINTER(LinkRecommendation)]
     L.ria_link_recommend.restype = None
     L.ria_link_data_mode.argtypes = [f32, i32, f32, C.POINTER(LinkRecommendation)]

@@ -90,6 +90,26 @@ __device__ inline bool macq_fits(int s, int frame_len, int window_len) {
     return s >= 0 && static_cast<long long>(s) + frame_len <= window_len;
 }
 
+// MCDPSKWaveform::detectSync / detectDataSync's SyncResult (mc_dpsk_waveform.cpp:176-292) from the detector's record;
+// start is -1 when nothing was detected.  Shared with search_accept_kernel (search_kernels.hip.h).
+struct MacqSync { bool det; int start; float corr, cfo; };
+__device__ __forceinline__ MacqSync macq_sync_of(const ria_chirp_result& r) {
+    MacqSync o;
+    o.det = r.success != 0;
+    o.start = o.det ? r.down_chirp_start + 24000 + 4800 : -1;
+    o.corr = r.up_correlation > r.down_correlation ? r.up_correlation : r.down_correlation;   // std::max(up, down)
+    o.cfo = r.cfo_hz;
+    return o;
+}
+__device__ __forceinline__ MacqSync macq_sync_of(const ria_zc_result& r) {
+    MacqSync o;
+    o.det = r.detected != 0;
+    o.start = o.det ? r.start_sample : -1;
+    o.corr = r.correlation;
+    o.cfo = r.cfo_hz;
+    return o;
+}
+
 // One block: detection results -> ria_mcdpsk_acq_result fields known before any decode, the acceptance rule and the CFO
 // every candidate of the window is demodulated with (mc_dpsk_waveform.cpp:176-292, streaming_decoder.cpp:903-917), and the
 // round-0 list of accepted windows at their primary candidate.
@@ -102,21 +122,11 @@ __global__ __launch_bounds__(kAcqScanThreads) void macq_plan_kernel(MacqArgs A) 
         float cfo = 0.0f;
         if (b < A.n_windows) {
             const ria_mcdpsk_acq_params p = A.params[b];
-            bool det;
-            float corr;
-            if (A.chirp) {
-                const ria_chirp_result r = A.chirp[b];
-                det = r.success != 0;
-                start = det ? r.down_chirp_start + 24000 + 4800 : -1;
-                corr = r.up_correlation > r.down_correlation ? r.up_correlation : r.down_correlation;   // std::max(up, down)
-                cfo = r.cfo_hz;
-            } else {
-                const ria_zc_result r = A.zc[b];
-                det = r.detected != 0;
-                start = det ? r.start_sample : -1;
-                corr = r.correlation;
-                cfo = r.cfo_hz;
-            }
+            const MacqSync sr = A.chirp ? macq_sync_of(A.chirp[b]) : macq_sync_of(A.zc[b]);
+            const bool det = sr.det;
+            const float corr = sr.corr;
+            start = sr.start;
+            cfo = sr.cfo;
             if (A.connected && fabs_(p.known_cfo_hz) > 0.01f && fabs_(cfo - p.known_cfo_hz) > 1.0f) cfo = p.known_cfo_hz;
             acc = det && !(corr < p.min_confidence) && macq_fits(start, A.frame_len, A.window_len);
             ria_mcdpsk_acq_result o;

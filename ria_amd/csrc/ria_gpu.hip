@@ -45,6 +45,7 @@
 #include "control_kernels.hip.h"
 #include "window_kernels.hip.h"
 #include "mcdpsk_window_kernels.hip.h"
+#include "search_kernels.hip.h"
 
 using namespace ria;
 
@@ -135,6 +136,10 @@ struct ria_gpu {
     // ria_gpu_mcdpsk_window_batch (mwin_carve): per-window pass state, the peek's decoder tries and the control word with its
     // pinned mirror; the rounds use d_macq_ws, carved for the longest pass
     DevBuf d_mwin_ws; PinBuf p_mwin_ctl;
+    // ria_gpu_search_batch (search_carve): the due list, one chunk's gathered spans, detector records and per-span parameters,
+    // and the control word with its pinned mirror
+    DevBuf d_search_ws; PinBuf p_search_ctl;
+    int search_chunk = 0;                 // RIA_OPT_SEARCH_CHUNK (0 = as many streams as 256 MiB of spans hold)
 };
 
 namespace {
@@ -479,6 +484,7 @@ static int run_crc_recovery_host(ria_gpu_handle h, const FastDecodeArgs& D, hipS
 static unsigned int ctl_fault(const MacqCtl&) { return 0; }   // the robust decoder has no work queue
 static unsigned int ctl_fault(const MacqCiCtl&) { return 0; }
 static unsigned int ctl_fault(const MwinCtl&) { return 0; }   // a flag of its own, read by the caller
+static unsigned int ctl_fault(const SearchCtl&) { return 0; } // a flag of its own, read by the caller
 static unsigned int ctl_fault(const WinCtl&) { return 0; }    // list lengths only: the stages behind them report their own faults
 template <class Ctl>
 static unsigned int ctl_fault(const Ctl& c) { return c.fault; }
@@ -670,6 +676,7 @@ int ria_gpu_set_option(ria_gpu_handle h, int option, int value) {
     }
     if (option == RIA_OPT_FALLBACK_QUEUE_ALL && value >= 0 && value <= 1) { h->fallback_queue_all = value; return RIA_OK; }
     if (option == RIA_OPT_STATE_EXIT && value >= 0 && value <= 1) { h->state_exit = value; return RIA_OK; }
+    if (option == RIA_OPT_SEARCH_CHUNK && value >= 0 && value <= 65535) { h->search_chunk = value; return RIA_OK; }
     return fail(h, RIA_ERR_INVALID, "ria_gpu_set_option: unknown option %d or value %d out of range", option, value);
 }
 
@@ -2582,6 +2589,114 @@ int ria_gpu_mcdpsk_interleave_batch(ria_gpu_handle h, int interleaver_bits, cons
     hipLaunchKernelGGL(macq_interleave_kernel, dim3(static_cast<unsigned>(std::min((n_cw + 3) / 4, 4096))), dim3(256), 0, static_cast<hipStream_t>(stream),
                        coded_dev, out_dev, n_cw, step_inv);
     HIP_TRY(h, hipGetLastError());
+    return RIA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ from a capture to its next window
+static_assert(sizeof(ria_search_state) == 32 && sizeof(ria_search_result) == 112 && offsetof(ria_search_result, abs_position) == 16 &&
+              offsetof(ria_search_result, invocations) == 60, "ria_gpu_search_batch record layouts (include/ria_gpu.h)");
+static_assert(RIA_SEARCH_OFDM_LTS == kSearchLts && RIA_SEARCH_MCDPSK_ZC == kSearchZc && RIA_SEARCH_MCDPSK_CHIRP == kSearchChirp &&
+              RIA_SEARCH_SYNC_FOUND == kSearchSyncFound && RIA_SEARCH_NEED_SAMPLES == kSearchNeedSamples && RIA_SEARCH_LIMIT == kSearchLimit,
+              "search_rules.hpp mirrors include/ria_gpu.h");
+struct SearchWs { uint32_t* list; SearchCtl* ctl; float* span; SearchPar* par; ria_zc_result* det; };   // det: 32 bytes for each of the three detectors
+static_assert(sizeof(ria_zc_result) == 32 && sizeof(ria_lts_result) == 32 && sizeof(ria_chirp_result) == 32, "one detector record area");
+static SearchWs search_carve(Carver& c, size_t n, size_t chunk, size_t min_search) {
+    SearchWs w;
+    w.list = c.take<uint32_t>(n);
+    w.ctl = c.take<SearchCtl>(1);
+    w.span = c.take<float>(chunk * min_search);
+    w.par = c.take<SearchPar>(chunk);
+    w.det = c.take<ria_zc_result>(chunk);
+    return w;
+}
+static int search_class(int mode, int modulation) {
+    if (mode != RIA_SEARCH_OFDM_LTS) return kSrchZc;
+    if (modulation == RIA_MOD_QPSK || modulation == RIA_MOD_BPSK) return kSrchCoherentPsk;
+    if (modulation == RIA_MOD_QAM16 || modulation == RIA_MOD_QAM32 || modulation == RIA_MOD_QAM64 || modulation == RIA_MOD_QAM256) return kSrchCoherentQam;
+    return kSrchDifferential;
+}
+
+int ria_gpu_search_batch(ria_gpu_handle h, int mode, uint32_t flags, const ria_mcdpsk_config* cfg, const float* samples_dev, int64_t stride,
+                         const int32_t* capture_len_dev, int n_streams, ria_search_state* state_dev, int feed_step, int max_invocations,
+                         ria_search_result* result_dev, void* stream) {
+    const char* who = "ria_gpu_search_batch";
+    if (!h) return RIA_ERR_INVALID;
+    const bool mc = mode == RIA_SEARCH_MCDPSK_ZC || mode == RIA_SEARCH_MCDPSK_CHIRP;
+    if ((mode != RIA_SEARCH_OFDM_LTS && !mc) || (flags & ~RIA_SEARCH_CONNECTED) != 0 || n_streams < 0 || stride < 0 || feed_step < 0 ||
+        max_invocations < 1 || (mc && !mcdpsk_config_ok(cfg)))
+        return fail(h, RIA_ERR_INVALID, "%s: bad argument (mode RIA_SEARCH_*, flags RIA_SEARCH_CONNECTED only, n_streams >= 0, stride >= 0, feed_step >= 0, "
+                                        "max_invocations >= 1, an MC-DPSK config for the MC-DPSK modes)", who);
+    if (n_streams == 0) return RIA_OK;
+    if (!samples_dev || !capture_len_dev || !state_dev || !result_dev) return fail(h, RIA_ERR_INVALID, "%s: null pointer", who);
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int min_search = srch_min_search(mode);
+    const size_t per = static_cast<size_t>(min_search) * sizeof(float);
+    int chunk = static_cast<int>(std::min<size_t>(static_cast<size_t>(n_streams), std::max<size_t>(1, (size_t(256) << 20) / per)));
+    chunk = std::min(chunk, 65535);                    // the gather's grid y extent
+    if (h->search_chunk > 0) chunk = std::min(chunk, h->search_chunk);
+    // every block of the call, before anything of it is in flight: the call's own workspace and the detector's
+    auto carve = [&](Carver& c) { return search_carve(c, static_cast<size_t>(n_streams), static_cast<size_t>(chunk), static_cast<size_t>(min_search)); };
+    HIP_TRY(h, h->d_search_ws.reserve(carved_size(carve), &s));
+    HIP_TRY(h, h->p_search_ctl.reserve(sizeof(SearchCtl)));
+    if (mode == RIA_SEARCH_OFDM_LTS) {
+        if (int rc = lts_prepare(h)) return rc;
+    } else if (mode == RIA_SEARCH_MCDPSK_ZC) {
+        const size_t zper = static_cast<size_t>(min_search) * sizeof(float2);
+        HIP_TRY(h, h->d_zc_ws.reserve(zper * std::min<size_t>(static_cast<size_t>(chunk), std::max<size_t>(1, (size_t(256) << 20) / zper)), &s));
+    } else {
+        if (int rc = chirp_prepare(h, std::min(chunk, 64), std::min(chunk, 2048), s)) return rc;
+    }
+    const SearchWs W = carve_at(h->d_search_ws.as<>(), carve);
+    HIP_TRY(h, hipMemsetAsync(W.ctl, 0, sizeof(SearchCtl), s));
+    SearchArgs A{};
+    A.samples = samples_dev; A.stride = stride; A.capture_len = capture_len_dev; A.state = state_dev; A.res = result_dev;
+    A.n_streams = n_streams; A.mode = mode; A.cls = search_class(mode, h->cfg.modulation);
+    A.connected = (mode != RIA_SEARCH_MCDPSK_CHIRP || (flags & RIA_SEARCH_CONNECTED)) ? 1 : 0;
+    A.feed_step = feed_step; A.max_invocations = max_invocations; A.min_search = min_search;
+    A.ctl = W.ctl; A.list = W.list; A.span = W.span; A.par = W.par;
+    const unsigned wgrid = static_cast<unsigned>((n_streams + kSearchWalkWaves - 1) / kSearchWalkWaves);
+    const int pstride = static_cast<int>(sizeof(SearchPar) / sizeof(float));
+    hipLaunchKernelGGL(search_check_kernel, dim3(static_cast<unsigned>((n_streams + 255) / 256)), dim3(256), 0, s, A);
+    for (int round = 0;; ++round) {
+        if (round > max_invocations) return fail(h, RIA_ERR_HIP, "%s: round %d past max_invocations", who, round);
+        hipLaunchKernelGGL(search_walk_kernel, dim3(wgrid), dim3(64 * kSearchWalkWaves), 0, s, A, round == 0 ? 1 : 0);
+        hipLaunchKernelGGL(search_list_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A);
+        HIP_TRY(h, hipGetLastError());
+        if (int rc = read_ctl(h, h->p_search_ctl, W.ctl, s)) return rc;
+        const SearchCtl ctl = *h->p_search_ctl.as<SearchCtl>();
+        if (ctl.bad)
+            return fail(h, RIA_ERR_INVALID, "%s: a stream's capture_len is above min(stride, 959999), or its state is outside the call's domain "
+                                            "(0 <= fed <= capture_len, 0 <= correlation_pos < 960000, reject_streak >= 0); no state or result was written", who);
+        const int n_list = static_cast<int>(ctl.n_list);
+        if (n_list < 0 || n_list > n_streams) return fail(h, RIA_ERR_HIP, "%s: the due list broke its bound (%d)", who, n_list);
+        if (n_list == 0) break;
+        for (int first = 0; first < n_list; first += chunk) {
+            const int nb = std::min(chunk, n_list - first);
+            A.first = first; A.n_chunk = nb; A.lts = nullptr; A.zc = nullptr; A.chirp = nullptr;
+            hipLaunchKernelGGL(search_gather_kernel, dim3(static_cast<unsigned>(std::min((min_search + 1023) / 1024, 64)), static_cast<unsigned>(nb)), dim3(256), 0, s, A);
+            HIP_TRY(h, hipGetLastError());
+            if (mode == RIA_SEARCH_OFDM_LTS) {
+                ria_lts_result* det = reinterpret_cast<ria_lts_result*>(W.det);
+                LtsArgs S{};
+                S.samples = W.span; S.stride = min_search; S.buf_len = min_search; S.n_buffers = nb;
+                S.known_cfo = &W.par->known_cfo_hz; S.threshold_dev = &W.par->detect_threshold; S.param_stride = pstride;
+                S.hilbert = h->d_hilbert65.as<const float>(); S.out = det;
+                hipLaunchKernelGGL(lts_sync_kernel, dim3(nb), dim3(kLtsThreads), lts_lds_bytes(), s, S);
+                A.lts = det;
+            } else if (mode == RIA_SEARCH_MCDPSK_ZC) {
+                A.zc = W.det;
+                if (int rc = sync_zc_impl(h, W.span, min_search, min_search, nb, 0.2f, 12u /* DATA | CONTROL */, &W.par->known_cfo_hz, W.det, s,
+                                          &W.par->detect_threshold, pstride)) return rc;
+            } else {
+                ria_chirp_result* det = reinterpret_cast<ria_chirp_result*>(W.det);
+                A.chirp = det;
+                if (int rc = sync_chirp_impl(h, W.span, min_search, min_search, nb, 0.15f, det, s, nullptr, 1)) return rc;
+            }
+            hipLaunchKernelGGL(search_accept_kernel, dim3(static_cast<unsigned>((nb + 255) / 256)), dim3(256), 0, s, A);
+            HIP_TRY(h, hipGetLastError());
+        }
+    }
     return RIA_OK;
 }
 

@@ -754,6 +754,54 @@ class RxEngine:
         out["ci_tried"] = (np.asarray(bits) >> 1) & 1
         return out
 
+    SEARCH_STATE = np.dtype([("correlation_pos", "<i4"), ("fed", "<i4"), ("noise_floor", "<f4"), ("reject_streak", "<i4"),
+                             ("last_cfo_hz", "<f4"), ("fading_hint", "<f4"), ("snr_hint", "<f4"), ("last_decoded_sync_pos", "<i4")])
+    SEARCH_RESULT = np.dtype([("outcome", "<i4"), ("search_start", "<i4"), ("search_len", "<i4"), ("sync_position", "<i4"),
+                              ("abs_position", "<i8"), ("correlation", "<f4"), ("known_cfo_hz", "<f4"), ("sync_cfo_hz", "<f4"),
+                              ("sync_snr_db", "<f4"), ("detect_threshold", "<f4"), ("min_confidence", "<f4"), ("weak_accept", "<i4"),
+                              ("marker", "<i4"), ("root", "<i4"), ("invocations", "<u4"), ("waits", "<u4"), ("rms_skips", "<u4"),
+                              ("detector_runs", "<u4"), ("rejects", "<u4"), ("near_misses", "<u4"), ("weak_accepts", "<u4"),
+                              ("replays", "<u4"), ("catchups_moderate", "<u4"), ("catchups_severe", "<u4"), ("reserved0", "<u4"), ("reserved1", "<u4"), ("reserved2", "<u4")])
+
+    @classmethod
+    def search_state(cls, n, fed=0):
+        """n fresh decoder states (SEARCH_STATE): cursor 0, `fed` samples arrived, noise floor 0.001, no decoded position"""
+        s = np.zeros(n, cls.SEARCH_STATE)
+        s["fed"] = fed
+        s["noise_floor"] = np.float32(0.001)
+        s["last_decoded_sync_pos"] = capi.SEARCH_NO_LAST_SYNC
+        return s
+
+    def set_search_chunk(self, streams):
+        """search() runs the detector on at most this many streams at a time; 0 = as many as its 256 MiB workspace holds"""
+        self._check(self.lib.ria_gpu_set_option(self.h, capi.OPT_SEARCH_CHUNK, int(streams)))
+
+    def search(self, captures, capture_len, state, mode, feed_step=0, max_invocations=1 << 20, connected=False,
+               carriers=10, modulation="DBPSK", spreading=1):
+        """StreamingDecoder::searchForSync for one capture per row of `captures` (float32 [n, stride] on the device;
+        ria_gpu_search_batch): each stream is walked from its state's cursor to its next accepted sync.  capture_len: samples
+        of each stream (scalar or one each, <= 959 999); state: SEARCH_STATE records (search_state()); mode: "OFDM_LTS" (the
+        modulation class is this engine's), "MCDPSK_ZC" or "MCDPSK_CHIRP" (connected=True: the connected weak profile); feed_step
+        samples arrive after every invocation (0: the recording is all there).  carriers / modulation / spreading: the MC-DPSK
+        configuration of the two MC-DPSK modes.  Returns (result (SEARCH_RESULT), state (SEARCH_STATE))."""
+        n, stride = captures.shape
+        assert captures.dtype == torch.float32 and captures.is_contiguous()
+        m = capi.SEARCH_MODE[mode] if isinstance(mode, str) else int(mode)
+        lens = np.empty(n, np.int32)
+        lens[:] = capture_len
+        st = np.ascontiguousarray(state, self.SEARCH_STATE)
+        assert st.shape == (n,)
+        lens_d = torch.from_numpy(lens).to(self.device)
+        st_d = torch.from_numpy(st.view(np.uint8).reshape(n, 32).copy()).to(self.device)
+        res_d = torch.empty((n, 112), dtype=torch.uint8, device=self.device)
+        cfg = None
+        if m != capi.SEARCH_MODE["OFDM_LTS"]:
+            bps = {"DBPSK": 1, "DQPSK": 2}[modulation] if isinstance(modulation, str) else int(modulation)
+            cfg = C.byref(capi.McdpskConfig(carriers, bps, spreading, 0))
+        self._check(self.lib.ria_gpu_search_batch(self.h, m, capi.SEARCH_CONNECTED if connected else 0, cfg, _ptr(captures), stride, _ptr(lens_d), n,
+                                                  _ptr(st_d), int(feed_step), int(max_invocations), _ptr(res_d), _stream_ptr()))
+        return self._status_array(res_d, self.SEARCH_RESULT), self._status_array(st_d, self.SEARCH_STATE)
+
     MCDFRAME_RESULT = np.dtype([("success", "u1"), ("codewords_ok", "u1"), ("codewords_failed", "u1"), ("frame_type", "u1"),
                                 ("header_total_cw", "<i4"), ("frame_bytes", "<i4"), ("reserved", "<i4")])
     HARQ_RESULT = np.dtype([("seq", "<u2"), ("valid", "u1"), ("entry", "u1"), ("src_hash", "<u4"), ("dst_hash", "<u4"),
