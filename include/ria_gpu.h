@@ -452,7 +452,32 @@ int ria_gpu_ldpc_encode_host(ria_gpu_handle h, const uint8_t* info, int n_cw, ui
 /* The same channel with the REFERENCE's random stream: frame f is sim::WattersonChannel(cfg, seed32) with
  * seed32 = (uint32_t)(seed + first_frame + f) (std::mt19937 + std::normal_distribution<float>, five draws per
  * sample), so the output is bit-identical to the reference channel (and to tools/test_waveform_simple.cpp's
- * "channel seed = base + frame" convention).  Any frame length; frame f at samples_dev + f*stride; in place. */
+ * "channel seed = base + frame" convention).  Any frame length; frame f at samples_dev + f*stride; in place.
+ *
+ * Input domain of the three reference-identical channel calls (this one, _seeded_batch, _cfo_batch).  Samples, snr_db and
+ * the per-frame offsets cfo_hz_dev[f] may be any float32: NaN, +-inf, denormals, +-FLT_MAX.  Seeds are any uint32;
+ * seed + first_frame + f is taken modulo 2^32 (first_frame 2^32 + 5 is first_frame 5).  None of these makes the reference
+ * undefined (it converts no sample to an index and every compare with a NaN is false), so the answer is the reference's:
+ *   - a sample counts for the signal power when |x| > 1e-6f: exactly +-1e-6f, denormals and NaN do not count, +-inf does;
+ *     a frame without a counted sample has rms 0.1; a power that overflows (one sample of 3e19) makes the noise sigma +inf
+ *     and every output sample non-finite;
+ *   - snr_db 800 gives the denormal sigma 1e-40 * rms (powf does not underflow to 0 there), 1e30 and +inf give sigma 0
+ *     (the noiseless fade), -inf and NaN leave no finite output sample;
+ *   - one NaN sample gives a NaN at its index and, in the two-path presets, delay + 1 samples later (the delay line
+ *     holds delay + 1 = 25, 49 or 97 samples), nowhere else; under applyCFO every sample from its index on is NaN;
+ *   - the channel applies its offset when |offset| > 0.001f is true and the frame has at least 256 samples: exactly
+ *     +-0.001f and NaN are NOT applied (ria_gpu_tx_cfo_batch's gate is the other way round, see there).  The phase starts
+ *     at 0, grows by float(2 pi offset / 48000) and wraps at most once per sample and only downwards (phase > 2 pi), so
+ *     a negative offset never wraps and an increment above 2 pi (48000.5 Hz, 1e6 Hz) grows without bound; cos and sin of
+ *     such phases are the correctly reduced glibc values.  An infinite offset rotates sample 0 by the phase 0 (finite)
+ *     and leaves NaN from sample 1 on;
+ *   - random_cfo_max_hz > 0 draws (2 max) * u - max in float: FLT_MAX gives +inf (or NaN for u = 0), +inf gives NaN, the
+ *     smallest denormal gives +-denormal or 0, which the gate then drops.
+ * Bits are compared wherever the reference's value is not NaN; where it is NaN the device's value is NaN, sign and payload
+ * of a NaN are not part of the contract.  Refused with RIA_ERR_INVALID, nothing launched: kind outside 0..4, n_frames < 0,
+ * frame_samples < 0, stride < frame_samples, a null samples or seeds pointer with a non-empty batch, random_cfo_max_hz
+ * negative or NaN.  n_frames == 0 or frame_samples == 0 is RIA_OK and writes nothing.  Samples between frame_samples and
+ * stride are neither read nor written.  tests/channel_domain_inputs.py holds the rows these statements are tested on. */
 int ria_gpu_channel_exact_batch(ria_gpu_handle h, int kind, float snr_db, uint32_t seed, uint64_t first_frame,
                                 float* samples_dev, int64_t stride, int frame_samples, int n_frames, void* stream);
 
@@ -478,7 +503,28 @@ int ria_gpu_channel_exact_cfo_batch(ria_gpu_handle h, int kind, float snr_db, co
  * transmissions of n_samples each (buffer b at samples_dev + b*stride, result at out_dev + b*out_stride, not in place):
  * FFT of the next power of two, frequency-domain Hilbert, inverse FFT, rotation by cfo_hz_dev[b] with the wrapped float
  * phase accumulator phase_inout_dev[b] (NULL: starts at 0, not returned), real part.  |cfo| < 0.001 Hz copies the
- * samples and leaves the accumulator alone, as the reference does.  n_samples <= 131072.  Bit-identical output. */
+ * samples and leaves the accumulator alone, as the reference does.  n_samples <= 131072.  Bit-identical output.
+ *
+ * Input domain.  cfo_hz_dev[b] and phase_inout_dev[b] may be any float32.  The gate is `|cfo| < 0.001f copies`: exactly
+ * +-0.001f and NaN ROTATE here, while the channel calls above apply their offset only when |offset| > 0.001f; the two
+ * gates are the reference's and differ at exactly +-0.001f.  Below the gate the output is a bit copy and the accumulator is
+ * not touched, whatever it holds (NaN, 100.0).  The increment is 2 * float(pi) * cfo / 48000 in float (1e38 overflows to
+ * +inf in the first product); after each sample the phase wraps once, p > float(pi) -> p - 2 float(pi), else
+ * p < -float(pi) -> p + 2 float(pi): an accumulator outside (-pi, pi] (3.2, 100.0, 1e9) or an increment above 2 pi comes
+ * back by one turn per sample only, and cos / sin are taken of the phase as it is.  A NaN or infinite accumulator or
+ * increment gives NaN output from the sample it is first used for and is returned as the reference returns it (bits
+ * compared where the reference's value is not NaN, "is NaN" where it is).  A call that continues from a returned
+ * accumulator walks the same phases as one call over both lengths.  Samples may be any finite float32 whose transform
+ * stays finite (denormals, +-FLT_MAX/4 at n <= 4, silence: bit-identical).  A NaN or infinite sample in a rotated buffer is
+ * outside bit identity: the reference's butterflies multiply with std::complex's operator* (C99 Annex G turns a NaN + NaN i
+ * product with an infinite factor into an infinity), the kernels multiply by hand.  For such a buffer every output sample
+ * is non-finite (as in the reference), the accumulator is the reference's, and every other buffer of the batch is
+ * unaffected; so is a finite buffer whose transform overflows.  Below the gate such samples are copied like any other.
+ * Refused with RIA_ERR_INVALID, nothing launched: out_dev == samples_dev, a null samples, offsets or output pointer,
+ * n_buffers < 0, n_samples < 0, stride or out_stride < n_samples; n_samples > 131072 is RIA_ERR_UNSUPPORTED.
+ * n_samples == 0 or n_buffers == 0 is RIA_OK and writes nothing.  The input is never written; output samples between
+ * n_samples and out_stride are not written.  Batches above 32 768 buffers or 256 MiB of workspace (two complex
+ * N-point arrays and one float per sample for every buffer) run as several passes with the same result. */
 int ria_gpu_tx_cfo_batch(ria_gpu_handle h, const float* samples_dev, int64_t stride, int n_samples, int n_buffers,
                          const float* cfo_hz_dev, float* phase_inout_dev, float* out_dev, int64_t out_stride, void* stream);
 

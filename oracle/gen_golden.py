@@ -427,6 +427,30 @@ def tx_domain_fixture(R):
     return rec
 
 
+def channel_domain_fixture(R):
+    """sim::WattersonChannel (with and without its CFO impairment) and SimulatedChannel::applyTxCFO of the reference over
+    their input domain (tests/channel_domain_inputs.py builds the rows; their sha256 is kept as sha).  For the recorded subset
+    (channel_domain_inputs.recorded_rows): c_labels / t_labels "family|label", c_<i> / t_<i> the samples, c_actual
+    getActualCFO() and t_phase the accumulator after, all as the reference gave them."""
+    sys.path.insert(0, os.path.join(os.path.dirname(po.HERE), "tests"))
+    import channel_domain_inputs as D
+    O = po.Oracle()
+    rc, rt = D.recorded_rows(O)
+    rec = {"sha": np.array(D.digest(O))}
+    rec["c_labels"] = np.array([f"{r['family']}|{r['label']}" for r in rc], dtype="U96")
+    rec["t_labels"] = np.array([f"{r['family']}|{r['label']}" for r in rt], dtype="U96")
+    ans_c = [D.channel_answer(R, r) for r in rc]
+    ans_t = [D.txcfo_answer(R, r) for r in rt]
+    for i, (y, _) in enumerate(ans_c):
+        rec[f"c_{i}"] = y
+    for i, (y, _) in enumerate(ans_t):
+        rec[f"t_{i}"] = y
+    rec["c_actual"] = np.array([a for _, a in ans_c], np.float32)
+    rec["t_phase"] = np.array([p for _, p in ans_t], np.float32)
+    print("channel domain: recorded", len(rc), "channel rows and", len(rt), "tx_cfo rows", flush=True)
+    return rec
+
+
 def write_reproducible(path, rec):
     """an .npz whose bytes depend on the arrays alone (np.savez stamps every member with the time of day); says whether the
     file that was there had the same bytes"""
@@ -758,6 +782,9 @@ def main():
     if only == "tx_domain":
         write_reproducible(os.path.join(OUT, "tx_domain.npz"), tx_domain_fixture(R))
         return 0
+    if only == "channel_domain":
+        write_reproducible(os.path.join(OUT, "channel_domain.npz"), channel_domain_fixture(R))
+        return 0
     if only == "sync_domain":
         np.savez_compressed(os.path.join(OUT, "sync_domain.npz"), **sync_domain_fixture(R))
         return 0
@@ -855,6 +882,7 @@ def main():
     np.savez_compressed(os.path.join(OUT, "mcdpsk_waveform.npz"), **mcwf_fixture(R))
     np.savez_compressed(os.path.join(OUT, "ref_tool_tables.npz"), **tool_tables_fixture(R))
     write_reproducible(os.path.join(OUT, "tx_domain.npz"), tx_domain_fixture(R))
+    write_reproducible(os.path.join(OUT, "channel_domain.npz"), channel_domain_fixture(R))
     print("done ->", OUT)
     return 0
 
