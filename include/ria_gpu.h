@@ -1391,8 +1391,8 @@ int ria_gpu_rx_window_batch(ria_gpu_handle control_h, ria_gpu_handle data_h, con
  * before anything of the call is in flight.  No result depends on scheduling, on chunking or on the other streams.
  *
  * Not covered: the ZC-miss -> chirp fallback (:785-828; wall-clock state, connected_since_), ring-buffer wrap and the
- * overflow path of feedAudio (:227-278), disconnected OFDM (chirp) search, OFDM-COX, the frame timeout, and a one-stream
- * host-memory form. */
+ * overflow path of feedAudio (:227-278), disconnected OFDM (chirp) search, OFDM-COX and the frame timeout.  (A one-stream
+ * host-memory form is ria_gpu_rx_stream_host's, below.) */
 enum { RIA_SEARCH_OFDM_LTS = 0, RIA_SEARCH_MCDPSK_ZC = 1, RIA_SEARCH_MCDPSK_CHIRP = 2 };
 enum { RIA_SEARCH_SYNC_FOUND = 1, RIA_SEARCH_NEED_SAMPLES = 2, RIA_SEARCH_LIMIT = 3 };
 #define RIA_SEARCH_CONNECTED 0x1u
@@ -1431,6 +1431,100 @@ typedef struct ria_search_result {   /* 112 bytes, one per stream */
 int ria_gpu_search_batch(ria_gpu_handle h, int mode, uint32_t flags, const ria_mcdpsk_config* cfg /* NULL for RIA_SEARCH_OFDM_LTS */,
                          const float* samples_dev, int64_t stride, const int32_t* capture_len_dev, int n_streams,
                          ria_search_state* state_dev, int feed_step, int max_invocations, ria_search_result* result_dev, void* stream);
+
+/* ---- recordings in, frames out: the receive loop of StreamingDecoder for a batch of captures ----------------------------------
+ * ria_gpu_rx_stream_batch runs gui::StreamingDecoder::processBuffer's loop (src/gui/modem/streaming_decoder.cpp:293-384) -
+ * searchForSync (:386-941), decodeCurrentFrame (:943-2013), the state both leave - over n_streams captures, as a composition
+ * of this library's calls with the host's part between them done on the device: ria_gpu_search_batch on the streams still
+ * open, then the window call of the mode on every stream that found a sync, then the state update, and again.  It adds no
+ * receiver arithmetic; every rule between the calls is ria_amd/csrc/stream_rules.hpp's.  Captures, capture_len_dev, state_dev,
+ * mode, flags, cfg, feed_step and max_invocations (per search leg) are ria_gpu_search_batch's, with its domain and its errors.
+ *
+ * Per round, for the open streams:
+ *   1. the search.  A stream that does not end with RIA_SEARCH_SYNC_FOUND closes with the search's outcome.
+ *   2. A found stream gets the window [search_start, search_start + min(full, capture_len - search_start)), full =
+ *      search_len + frame_samples + 32 for RIA_SEARCH_OFDM_LTS and search_len + the 8-codeword span of cfg (9 x 512 +
+ *      8 x ceil(648 / (carriers x bits)) x 512 x spreading samples) for the MC-DPSK modes: the window calls' documented minimum.
+ *   3. Its parameters are the search result's: known_cfo_hz, detect_threshold, min(min_confidence, correlation), abs_base =
+ *      search_start; for MC-DPSK last_decoded_sync = last_decoded_sync_pos - search_start (INT32_MIN kept, clipped to
+ *      -(2^31 - 1) .. 2^31 - 1), pending_total_cw 0, first_avail 0.
+ *   4. The window call: ria_gpu_rx_window_batch(control_h, h) with RIA_DECODE_FULL for OFDM; ria_gpu_mcdpsk_window_batch on h
+ *      for MC-DPSK - RIA_MACQ_SYNC_CHIRP for the chirp mode, RIA_MACQ_DISCONNECTED with it unless RIA_SEARCH_CONNECTED - with
+ *      no chase pool, no channel interleaving and no soft-bit output.
+ *   5. The state (:1994-2013, :1414-1434): last_cfo_hz = the window's CFO and fading_hint = its fading index where the outcome
+ *      is DECODED (OFDM: or CONTROL_PROFILE); last_decoded_sync_pos = sync_position of an OFDM window that delivered (success or
+ *      codewords_ok > 0), or what the MC-DPSK window call leaves, back in capture indices; the cursor = search_start + next_pos
+ *      where next_pos >= 0, sync_position + the one-frame span (frame_samples; the 1-codeword span of cfg) for RIA_WIN_BURST /
+ *      RIA_WIN_TOO_LONG / RIA_MWIN_TOO_LONG, which the host passes on to another call, else unchanged; then fed = max(fed,
+ *      min(capture_len, cursor)): the samples a window consumed have arrived, so the next feed does not clamp the cursor back.
+ *   6. The event is recorded and the stream closes on a window NEED_SAMPLES, on max_events events, or on a cursor >= 959 999.
+ * state_dev is read and written in place, the fed rule applied before it is written: a second call with the state a first
+ * call left continues exactly as one call with a larger max_events would.
+ *
+ * Event e of stream s is events_dev[s * max_events + e], its payload row (s * max_events + e) of frames_dev (frame_row bytes;
+ * frame_bytes of them where delivered, zero otherwise).  Every row of every output is written.  frame_row >= the window
+ * call's minimum: max(4, llrs_per_frame / 648) * bytes_per_codeword for OFDM, RIA_MACQ_FRAME_BYTES(8) for MC-DPSK.  control_h:
+ * ria_gpu_rx_window_batch's control handle for RIA_SEARCH_OFDM_LTS, NULL for the other modes.  The MC-DPSK modes need a handle
+ * at RIA_RATE_1_4.  max_events >= 1.  n_streams == 0 is RIA_OK.  A failure of the search's domain check fails the whole call
+ * before anything is written.
+ *
+ * Out of scope: burst groups and continuation (reported as events: RIA_WIN_BURST), chase pools and channel interleaving,
+ * re-entry of an MC-DPSK NEED_SAMPLES window (the event carries need_samples and pending_total_cw for the caller), ring
+ * wrap, the ZC-miss -> chirp fallback, OFDM-COX.
+ *
+ * Work: rounds of search -> found list -> (gather -> parameters -> window call -> apply, once per distinct window length in
+ * ascending order, in chunks of at most 256 MiB of windows) -> open list.  A stream gains an event or closes in every round,
+ * so there are at most max_events + 1 rounds.  Per round the call itself makes two small device-to-host reads - the found
+ * list with its window lengths (16 + 8 x n_streams bytes) and the number of streams still open - beside those of the search
+ * and of the window calls; most streams share `full`, only windows cut at a capture's end differ, so a round usually makes one
+ * window call.  No samples, soft bits, result records or payloads go to the host.  The search runs on the open streams through
+ * an index list, without copying their captures.  The call's workspace lives on h, is carved once per size and reserved before
+ * the call's first launch; the window calls' own workspaces grow, where they must, on a drained stream. */
+enum { RIA_STREAM_SEARCH_NEED_SAMPLES = 2, RIA_STREAM_SEARCH_LIMIT = 3,    /* = RIA_SEARCH_NEED_SAMPLES, RIA_SEARCH_LIMIT */
+       RIA_STREAM_WINDOW_NEED_SAMPLES = 4, RIA_STREAM_EVENTS_FULL = 5, RIA_STREAM_RING_END = 6 };
+typedef struct ria_stream_event {    /* 64 bytes */
+    int32_t sync_position;           /* the search's, a capture index */
+    int32_t search_start;            /* sample 0 of the window */
+    int32_t window_len;
+    int32_t outcome;                 /* RIA_WIN_* (OFDM) / RIA_MWIN_* (MC-DPSK) */
+    int32_t next_pos;                /* the window's next_pos as a capture index, -1 where nothing was consumed */
+    int32_t frame_bytes;             /* bytes of the DecodeResult's frame_data */
+    int32_t need_samples;
+    int32_t pending_total_cw;
+    uint8_t delivered;               /* the host queues the result: its frame_bytes bytes are in the payload row */
+    uint8_t success, codewords_ok, codewords_failed;
+    uint8_t frame_type;
+    uint8_t reserved0[3];
+    float   correlation;             /* the search's */
+    float   cfo_hz;                  /* ria_window_result.sync_cfo_hz / ria_mcdpsk_acq_result.cfo_hz */
+    float   fading_index;
+    float   snr_db;                  /* the search's sync_snr_db */
+    int32_t reserved[2];
+} ria_stream_event;
+typedef struct ria_stream_result {   /* 64 bytes, one per stream */
+    int32_t  n_events;
+    int32_t  closed;                 /* RIA_STREAM_* */
+    int32_t  mode;                   /* RIA_SEARCH_*: names the family of the events' outcomes */
+    int32_t  search_legs;            /* searches the stream took part in */
+    uint32_t invocations, waits, rms_skips, detector_runs, rejects, near_misses, weak_accepts, replays;   /* summed over the legs */
+    uint32_t catchups_moderate, catchups_severe;
+    uint32_t reserved[2];
+} ria_stream_result;
+int ria_gpu_rx_stream_batch(ria_gpu_handle h, ria_gpu_handle control_h /* RIA_SEARCH_OFDM_LTS only, else NULL */,
+                            int mode /* RIA_SEARCH_* */, uint32_t flags /* RIA_SEARCH_CONNECTED only */,
+                            const ria_mcdpsk_config* cfg /* NULL for RIA_SEARCH_OFDM_LTS */,
+                            const float* samples_dev, int64_t stride, const int32_t* capture_len_dev, int n_streams,
+                            ria_search_state* state_dev, int feed_step, int max_invocations, int max_events,
+                            ria_stream_event* events_dev /* n_streams * max_events */,
+                            uint8_t* frames_dev /* n_streams * max_events * frame_row */, int frame_row,
+                            ria_stream_result* result_dev /* n_streams */, void* stream);
+/* One stream from host memory: the capture (n_samples <= 959 999) and *state_host are staged through the handle's pinned block
+ * on the handle's own stream, the state, max_events events, their payload rows and the result are copied back; synchronises
+ * that stream. */
+int ria_gpu_rx_stream_host(ria_gpu_handle h, ria_gpu_handle control_h, int mode, uint32_t flags, const ria_mcdpsk_config* cfg,
+                           const float* samples_host, int n_samples, ria_search_state* state_host /* in and out */,
+                           int feed_step, int max_invocations, int max_events, ria_stream_event* events_out_host,
+                           uint8_t* frames_out_host, int frame_row, ria_stream_result* result_out_host);
 
 /* ---- debug / test hooks ----------------------------------------------------------------------- */
 /* op: 0 sinf 1 cosf 2 logf 3 atan2f(a,b) 4 hypotf(a,b) 5 a/b 6 sqrtf(a); evaluates the device

@@ -593,3 +593,35 @@ def rx_stream(engine, captures, capture_len, mode, control_engine=None, feed_ste
                 if name == "NEED_SAMPLES" or len(events[s]) >= max_events or state["correlation_pos"][s] >= capi.SEARCH_MAX_CAPTURE:
                     open_[s] = False
     return events
+
+
+# ---- the same loop in one call (ria_gpu_rx_stream_batch)
+STREAM_COUNTERS = ("streams", "events", "delivered") + tuple(f"closed_{k.lower()}" for k in capi.STREAM_CLOSED) + \
+    ("search_legs",) + SEARCH_COUNTERS[len(capi.SEARCH_OUTCOME):]
+
+
+def stream_events(results, events, frames):
+    """The records of RxEngine.rx_stream / rx_stream_host (results STREAM_RESULT [n], events STREAM_EVENT [n, max_events],
+    frames uint8 [n, max_events, row], a tensor or an array) in the form rx_stream returns: per stream the list of events,
+    dicts of position, outcome (the window call's outcome name of the result's mode) and frame (the delivered bytes or None)."""
+    if isinstance(frames, torch.Tensor):
+        frames = frames.cpu().numpy()
+    out = []
+    for s in range(len(results)):
+        ofdm = int(results["mode"][s]) == capi.SEARCH_MODE["OFDM_LTS"]
+        names = {v: k for k, v in (capi.WIN_OUTCOME if ofdm else capi.MWIN_OUTCOME).items()}
+        out.append([dict(position=int(e["sync_position"]), outcome=names[int(e["outcome"])],
+                         frame=frames[s, k, :int(e["frame_bytes"])].tobytes() if e["delivered"] else None)
+                    for k, e in enumerate(events[s, :int(results["n_events"][s])])])
+    return out
+
+
+def stream_tally(results, events):
+    """Counter row (STREAM_COUNTERS) of one RxEngine.rx_stream call: streams, events, events that delivered a frame, streams
+    per reason they closed for, search legs, then the sums of the search counters over the call's legs."""
+    n_ev = results["n_events"].astype(np.int64)
+    live = np.arange(events.shape[1])[None, :] < n_ev[:, None]
+    row = [len(results), int(n_ev.sum()), int(((events["delivered"] != 0) & live).sum())]
+    row += [int((results["closed"] == v).sum()) for v in capi.STREAM_CLOSED.values()]
+    row += [int(results["search_legs"].sum())] + [int(results[k].sum()) for k in SEARCH_COUNTERS[len(capi.SEARCH_OUTCOME):]]
+    return np.array(row, dtype=np.int64)

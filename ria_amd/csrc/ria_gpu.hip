@@ -46,6 +46,7 @@
 #include "window_kernels.hip.h"
 #include "mcdpsk_window_kernels.hip.h"
 #include "search_kernels.hip.h"
+#include "stream_kernels.hip.h"
 
 using namespace ria;
 
@@ -140,6 +141,9 @@ struct ria_gpu {
     // and the control word with its pinned mirror
     DevBuf d_search_ws; PinBuf p_search_ctl;
     int search_chunk = 0;                 // RIA_OPT_SEARCH_CHUNK (0 = as many streams as 256 MiB of spans hold)
+    // ria_gpu_rx_stream_batch (stream_carve): the control word with the found list behind it and their pinned mirror, the
+    // open and group lists, the search's result records, and one chunk's windows, parameters and window-call outputs
+    DevBuf d_stream_ws; PinBuf p_stream_ctl;
 };
 
 namespace {
@@ -2616,11 +2620,11 @@ static int search_class(int mode, int modulation) {
     return kSrchDifferential;
 }
 
-int ria_gpu_search_batch(ria_gpu_handle h, int mode, uint32_t flags, const ria_mcdpsk_config* cfg, const float* samples_dev, int64_t stride,
-                         const int32_t* capture_len_dev, int n_streams, ria_search_state* state_dev, int feed_step, int max_invocations,
-                         ria_search_result* result_dev, void* stream) {
-    const char* who = "ria_gpu_search_batch";
-    if (!h) return RIA_ERR_INVALID;
+// The search on n_streams streams: all of them, or those subset_dev lists (ascending stream indices; captures, lengths,
+// states and results stay indexed by stream, so nothing is copied).  ria_gpu_rx_stream_batch searches its open streams so.
+static int search_impl(ria_gpu_handle h, const char* who, int mode, uint32_t flags, const ria_mcdpsk_config* cfg, const float* samples_dev, int64_t stride,
+                       const int32_t* capture_len_dev, int n_streams, const uint32_t* subset_dev, ria_search_state* state_dev, int feed_step,
+                       int max_invocations, ria_search_result* result_dev, void* stream) {
     const bool mc = mode == RIA_SEARCH_MCDPSK_ZC || mode == RIA_SEARCH_MCDPSK_CHIRP;
     if ((mode != RIA_SEARCH_OFDM_LTS && !mc) || (flags & ~RIA_SEARCH_CONNECTED) != 0 || n_streams < 0 || stride < 0 || feed_step < 0 ||
         max_invocations < 1 || (mc && !mcdpsk_config_ok(cfg)))
@@ -2651,6 +2655,7 @@ int ria_gpu_search_batch(ria_gpu_handle h, int mode, uint32_t flags, const ria_m
     HIP_TRY(h, hipMemsetAsync(W.ctl, 0, sizeof(SearchCtl), s));
     SearchArgs A{};
     A.samples = samples_dev; A.stride = stride; A.capture_len = capture_len_dev; A.state = state_dev; A.res = result_dev;
+    A.subset = subset_dev;
     A.n_streams = n_streams; A.mode = mode; A.cls = search_class(mode, h->cfg.modulation);
     A.connected = (mode != RIA_SEARCH_MCDPSK_CHIRP || (flags & RIA_SEARCH_CONNECTED)) ? 1 : 0;
     A.feed_step = feed_step; A.max_invocations = max_invocations; A.min_search = min_search;
@@ -2698,6 +2703,14 @@ int ria_gpu_search_batch(ria_gpu_handle h, int mode, uint32_t flags, const ria_m
         }
     }
     return RIA_OK;
+}
+
+int ria_gpu_search_batch(ria_gpu_handle h, int mode, uint32_t flags, const ria_mcdpsk_config* cfg, const float* samples_dev, int64_t stride,
+                         const int32_t* capture_len_dev, int n_streams, ria_search_state* state_dev, int feed_step, int max_invocations,
+                         ria_search_result* result_dev, void* stream) {
+    if (!h) return RIA_ERR_INVALID;
+    return search_impl(h, "ria_gpu_search_batch", mode, flags, cfg, samples_dev, stride, capture_len_dev, n_streams, nullptr, state_dev, feed_step,
+                       max_invocations, result_dev, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ the chase pool
@@ -3227,6 +3240,215 @@ int ria_gpu_rx_window_batch(ria_gpu_handle control_h, ria_gpu_handle h, const fl
     }
     // 8. consumed samples and the receiver state
     return finish();
+}
+
+// ------------------------------------------------------------------------------------------------ recordings in, frames out
+static_assert(sizeof(ria_stream_event) == 64 && offsetof(ria_stream_event, next_pos) == 16 && offsetof(ria_stream_event, delivered) == 32 &&
+              offsetof(ria_stream_event, correlation) == 40 && sizeof(ria_stream_result) == 64 && offsetof(ria_stream_result, invocations) == 16,
+              "ria_gpu_rx_stream_batch record layouts (include/ria_gpu.h)");
+static_assert(RIA_WIN_BURST == kStrmWinBurst && RIA_WIN_CONTROL_PROFILE == kStrmWinControlProfile && RIA_WIN_DECODED == kStrmWinDecoded &&
+              RIA_WIN_NEED_SAMPLES == kStrmWinNeedSamples && RIA_WIN_TOO_LONG == kStrmWinTooLong && RIA_MWIN_DECODED == kStrmMwinDecoded &&
+              RIA_MWIN_NEED_SAMPLES == kStrmMwinNeedSamples && RIA_MWIN_TOO_LONG == kStrmMwinTooLong &&
+              RIA_STREAM_SEARCH_NEED_SAMPLES == kStreamSearchNeedSamples && RIA_STREAM_SEARCH_LIMIT == kStreamSearchLimit &&
+              RIA_STREAM_SEARCH_NEED_SAMPLES == RIA_SEARCH_NEED_SAMPLES && RIA_STREAM_SEARCH_LIMIT == RIA_SEARCH_LIMIT &&
+              RIA_STREAM_WINDOW_NEED_SAMPLES == kStreamWindowNeedSamples && RIA_STREAM_EVENTS_FULL == kStreamEventsFull &&
+              RIA_STREAM_RING_END == kStreamRingEnd && kStreamRingLast == kSrchMaxCapture,
+              "stream_rules.hpp mirrors include/ria_gpu.h");
+static_assert(sizeof(ria_acq_params) == 32 && sizeof(ria_mcdpsk_acq_params) == 32 && sizeof(ria_window_result) == 64 &&
+              sizeof(ria_mcdpsk_window_result) == 64 && sizeof(ria_acq_result) <= 64 && sizeof(ria_mcdpsk_acq_result) == 64, "one area per record kind");
+struct StreamWs {
+    uint32_t* head;               // StreamCtl (4 words), found [n], found_len [n]: what the host reads per round, in one copy
+    uint32_t *open, *group;
+    ria_search_result* sres;
+    float* win;
+    ria_acq_params* par;          // either parameter record
+    ria_window_result* wres;      // either window result
+    ria_mcdpsk_acq_result* acq;   // either acquire result
+    uint8_t* wframes;
+};
+static StreamWs stream_carve(Carver& c, size_t n, size_t chunk, size_t win_stride, size_t wframe_row) {
+    StreamWs w;
+    w.head = c.take<uint32_t>(4 + 2 * n);
+    w.open = c.take<uint32_t>(n);
+    w.group = c.take<uint32_t>(n);
+    w.sres = c.take<ria_search_result>(n);
+    w.win = c.take<float>(chunk * win_stride);
+    w.par = c.take<ria_acq_params>(chunk);
+    w.wres = c.take<ria_window_result>(chunk);
+    w.acq = c.take<ria_mcdpsk_acq_result>(chunk);
+    w.wframes = c.take<uint8_t>(chunk * wframe_row);
+    return w;
+}
+// mode / flags / cfg / handles / sizes of the two stream calls; *family, *full, *first_frame, *min_row from them
+static int stream_setup(ria_gpu_handle h, ria_gpu_handle control_h, const char* who, int mode, uint32_t flags, const ria_mcdpsk_config* cfg,
+                        int max_events, int frame_row, int* full, int* first_frame, int* min_row) {
+    const bool mc = mode == RIA_SEARCH_MCDPSK_ZC || mode == RIA_SEARCH_MCDPSK_CHIRP;
+    if ((mode != RIA_SEARCH_OFDM_LTS && !mc) || (flags & ~RIA_SEARCH_CONNECTED) != 0 || (mc && !mcdpsk_config_ok(cfg)) || max_events < 1)
+        return fail(h, RIA_ERR_INVALID, "%s: bad argument (mode RIA_SEARCH_*, flags RIA_SEARCH_CONNECTED only, an MC-DPSK config for the MC-DPSK modes, "
+                                        "max_events >= 1)", who);
+    const int min_search = srch_min_search(mode);
+    if (mc) {
+        if (control_h) return fail(h, RIA_ERR_INVALID, "%s: control_h is for RIA_SEARCH_OFDM_LTS only", who);
+        if (h->cfg.code_rate != RIA_RATE_1_4) return fail(h, RIA_ERR_INVALID, "%s: MC-DPSK frames are R1/4: the handle's rate must be RIA_RATE_1_4", who);
+        const int sym_per_cw = (kMacqLdpcBlock + cfg->num_carriers * cfg->bits_per_symbol - 1) / (cfg->num_carriers * cfg->bits_per_symbol);
+        const long long cw = static_cast<long long>(sym_per_cw) * kMcSps * cfg->spreading, pre = (kMcTrain + 1) * kMcSps;
+        if (min_search + pre + 8 * cw > kSrchRing) return fail(h, RIA_ERR_INVALID, "%s: the 8-codeword span of this configuration is longer than a capture", who);
+        *first_frame = static_cast<int>(pre + cw);
+        *full = static_cast<int>(min_search + pre + 8 * cw);
+        *min_row = RIA_MACQ_FRAME_BYTES(8);
+    } else {
+        if (!control_h || !is_control_handle(control_h) || control_h->cfg.num_carriers != h->cfg.num_carriers || control_h->device != h->device)
+            return fail(h, RIA_ERR_INVALID, "%s: RIA_SEARCH_OFDM_LTS needs the control handle: DQPSK R1/4 with the data handle's carriers, on its device", who);
+        *first_frame = h->geo.frame_samples;
+        *full = min_search + h->geo.frame_samples + 32;
+        *min_row = std::max(std::max(4, h->geo.llrs_per_frame / kDfBlock) * h->geo.bytes_per_codeword, kCtlFrameBytes);
+    }
+    if (frame_row < *min_row) return fail(h, RIA_ERR_INVALID, "%s: frame_row %d is below the window call's minimum %d", who, frame_row, *min_row);
+    return RIA_OK;
+}
+
+int ria_gpu_rx_stream_batch(ria_gpu_handle h, ria_gpu_handle control_h, int mode, uint32_t flags, const ria_mcdpsk_config* cfg,
+                            const float* samples_dev, int64_t stride, const int32_t* capture_len_dev, int n_streams,
+                            ria_search_state* state_dev, int feed_step, int max_invocations, int max_events,
+                            ria_stream_event* events_dev, uint8_t* frames_dev, int frame_row, ria_stream_result* result_dev, void* stream) {
+    const char* who = "ria_gpu_rx_stream_batch";
+    if (!h) return RIA_ERR_INVALID;
+    int full = 0, first_frame = 0, min_row = 0;
+    if (int rc = stream_setup(h, control_h, who, mode, flags, cfg, max_events, frame_row, &full, &first_frame, &min_row)) return rc;
+    if (n_streams < 0 || stride < 0 || feed_step < 0 || max_invocations < 1)
+        return fail(h, RIA_ERR_INVALID, "%s: bad argument (n_streams >= 0, stride >= 0, feed_step >= 0, max_invocations >= 1)", who);
+    if (n_streams == 0) return RIA_OK;
+    if (!samples_dev || !capture_len_dev || !state_dev || !events_dev || !frames_dev || !result_dev) return fail(h, RIA_ERR_INVALID, "%s: null pointer", who);
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool ofdm = mode == RIA_SEARCH_OFDM_LTS;
+    const size_t n = static_cast<size_t>(n_streams);
+    const int search_len = srch_min_search(mode);
+    const long long win_stride = (static_cast<long long>(full) + 3) & ~3LL;          // rows of the window workspace start on 16 bytes
+    int chunk = static_cast<int>(std::min<size_t>(n, std::max<size_t>(1, (size_t(256) << 20) / (static_cast<size_t>(win_stride) * sizeof(float)))));
+    chunk = std::min(chunk, 65535);                    // the gather's grid y extent
+    auto carve = [&](Carver& c) { return stream_carve(c, n, static_cast<size_t>(chunk), static_cast<size_t>(win_stride), static_cast<size_t>(min_row)); };
+    const size_t head_bytes = (4 + 2 * n) * sizeof(uint32_t);
+    HIP_TRY(h, h->d_stream_ws.reserve(carved_size(carve), &s));
+    HIP_TRY(h, h->p_stream_ctl.reserve(head_bytes));
+    const StreamWs W = carve_at(h->d_stream_ws.as<>(), carve);
+    uint32_t* mirror = h->p_stream_ctl.as<uint32_t>();
+
+    StreamArgs A{};
+    A.samples = samples_dev; A.stride = stride; A.capture_len = capture_len_dev; A.state = state_dev; A.sres = W.sres;
+    A.res = result_dev; A.events = events_dev; A.frames = frames_dev; A.frame_row = frame_row;
+    A.n_streams = n_streams; A.mode = mode; A.family = ofdm ? kStreamOfdm : kStreamMcdpsk; A.full = full; A.first_frame = first_frame;
+    A.max_events = max_events;
+    A.ctl = reinterpret_cast<StreamCtl*>(W.head); A.found = W.head + 4; A.found_len = reinterpret_cast<int32_t*>(W.head + 4 + n);
+    A.open = nullptr; A.group = W.group; A.n_open = n_streams;
+    A.win = W.win; A.win_stride = win_stride; A.wframes = W.wframes; A.wframe_row = min_row;
+    if (ofdm) { A.par = W.par; A.wres = W.wres; }
+    else { A.mpar = reinterpret_cast<ria_mcdpsk_acq_params*>(W.par); A.mres = reinterpret_cast<const ria_mcdpsk_window_result*>(W.wres); A.macq = W.acq; }
+    const uint32_t mflags = mode == RIA_SEARCH_MCDPSK_CHIRP ? (RIA_MACQ_SYNC_CHIRP | ((flags & RIA_SEARCH_CONNECTED) ? 0u : RIA_MACQ_DISCONNECTED)) : 0u;
+    const unsigned sgrid = static_cast<unsigned>((n_streams + 255) / 256);
+    bool window_ran = false;
+
+    for (int round = 0;; ++round) {
+        if (round > max_events) return fail(h, RIA_ERR_HIP, "%s: round %d past max_events + 1", who, round + 1);
+        // 1. the search on the open streams: in the first round all of them, and nothing of this call is written before its
+        //    domain check has passed
+        if (int rc = search_impl(h, who, mode, flags, cfg, samples_dev, stride, capture_len_dev, A.n_open, A.open, state_dev, feed_step,
+                                 max_invocations, W.sres, s)) return rc;
+        if (round == 0) {
+            HIP_TRY(h, hipMemsetAsync(events_dev, 0, n * static_cast<size_t>(max_events) * sizeof(ria_stream_event), s));
+            HIP_TRY(h, hipMemsetAsync(frames_dev, 0, n * static_cast<size_t>(max_events) * static_cast<size_t>(frame_row), s));
+            hipLaunchKernelGGL(stream_init_kernel, dim3(sgrid), dim3(256), 0, s, A);
+        }
+        // 2. the found streams and their window lengths
+        hipLaunchKernelGGL(stream_list_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A, kStreamListFound);
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(mirror, W.head, head_bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        const int n_found = static_cast<int>(mirror[1]);
+        if (n_found < 0 || n_found > A.n_open) return fail(h, RIA_ERR_HIP, "%s: the found list broke its bound (%d)", who, n_found);
+        if (n_found == 0) break;
+        A.n_found = n_found;
+        std::vector<int> lens(mirror + 4 + n, mirror + 4 + n + n_found);
+        std::sort(lens.begin(), lens.end());
+        // 3.-6. one pass per distinct window length, ascending
+        for (size_t at = 0; at < lens.size();) {
+            const int wl = lens[at];
+            size_t end = at;
+            while (end < lens.size() && lens[end] == wl) ++end;
+            const int n_group = static_cast<int>(end - at);
+            at = end;
+            if (wl < search_len || wl > full) return fail(h, RIA_ERR_HIP, "%s: a window of %d samples, outside %d..%d", who, wl, search_len, full);
+            A.window_len = wl;
+            hipLaunchKernelGGL(stream_list_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A, kStreamListGroup);
+            for (int first = 0; first < n_group; first += chunk) {
+                const int nb = std::min(chunk, n_group - first);
+                A.first = first; A.n_chunk = nb;
+                const unsigned tgrid = static_cast<unsigned>((nb + 255) / 256);
+                hipLaunchKernelGGL(stream_gather_kernel, dim3(static_cast<unsigned>(std::min((wl + 1023) / 1024, 64)), static_cast<unsigned>(nb)), dim3(256), 0, s, A);
+                hipLaunchKernelGGL(stream_params_kernel, dim3(tgrid), dim3(256), 0, s, A);
+                HIP_TRY(h, hipGetLastError());
+                // a window call may grow its workspaces: the first of the call finds the stream drained by the read above
+                if (window_ran) HIP_TRY(h, hipStreamSynchronize(s));
+                window_ran = true;
+                int rc;
+                if (ofdm)
+                    rc = ria_gpu_rx_window_batch(control_h, h, W.win, win_stride, search_len, wl, nb, W.par, RIA_DECODE_FULL, W.wframes, min_row, W.wres,
+                                                 reinterpret_cast<ria_acq_result*>(W.acq), nullptr, nullptr, s);
+                else
+                    rc = ria_gpu_mcdpsk_window_batch(h, cfg, W.win, win_stride, search_len, wl, nb, reinterpret_cast<const ria_mcdpsk_acq_params*>(W.par), mflags,
+                                                     W.wframes, min_row, reinterpret_cast<ria_mcdpsk_window_result*>(W.wres), W.acq, nullptr, 0, nullptr,
+                                                     nullptr, nullptr, nullptr, 0, s);
+                if (rc != RIA_OK) return rc;
+                hipLaunchKernelGGL(stream_apply_kernel, dim3(tgrid), dim3(256), 0, s, A);
+                HIP_TRY(h, hipGetLastError());
+            }
+        }
+        // 7. the streams still open
+        A.open = W.open;
+        hipLaunchKernelGGL(stream_list_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A, kStreamListOpen);
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(mirror, W.head, sizeof(StreamCtl), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        const int n_open = static_cast<int>(mirror[0]);
+        if (n_open < 0 || n_open > n_found) return fail(h, RIA_ERR_HIP, "%s: the open list broke its bound (%d)", who, n_open);
+        if (n_open == 0) break;
+        A.n_open = n_open;
+    }
+    return RIA_OK;
+}
+
+// One stream from host memory (the single-stream adaptor path): staged through the handle's pinned + device block on the
+// handle's own stream, like ria_gpu_mcdpsk_window_host.  The state goes up as an input and comes back as an output.
+int ria_gpu_rx_stream_host(ria_gpu_handle h, ria_gpu_handle control_h, int mode, uint32_t flags, const ria_mcdpsk_config* cfg,
+                           const float* samples_host, int n_samples, ria_search_state* state_host, int feed_step, int max_invocations,
+                           int max_events, ria_stream_event* events_out_host, uint8_t* frames_out_host, int frame_row,
+                           ria_stream_result* result_out_host) {
+    const char* who = "ria_gpu_rx_stream_host";
+    if (!h) return RIA_ERR_INVALID;
+    int full = 0, first_frame = 0, min_row = 0;
+    if (int rc = stream_setup(h, control_h, who, mode, flags, cfg, max_events, frame_row, &full, &first_frame, &min_row)) return rc;
+    if (n_samples < 0 || n_samples > kSrchMaxCapture || feed_step < 0 || max_invocations < 1)
+        return fail(h, RIA_ERR_INVALID, "%s: bad argument (0 <= n_samples <= 959999, feed_step >= 0, max_invocations >= 1)", who);
+    if (!samples_host || !state_host || !events_out_host || !frames_out_host || !result_out_host) return fail(h, RIA_ERR_INVALID, "%s: null pointer", who);
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int32_t cap = n_samples;
+    const size_t ne = static_cast<size_t>(max_events);
+    struct Stage { float* x; int32_t* cap; ria_search_state* st_in; ria_search_state* st; ria_stream_event* ev; uint8_t* frames; ria_stream_result* res; };
+    auto carve = [&](StageCarver& c) {
+        Stage w;
+        w.x = c.in(static_cast<size_t>(std::max(n_samples, 1)), samples_host, static_cast<size_t>(n_samples));
+        w.cap = c.in(1, &cap); w.st_in = c.in(1, const_cast<const ria_search_state*>(state_host));
+        w.st = c.out(1, state_host); w.ev = c.out(ne, events_out_host); w.frames = c.out(ne * static_cast<size_t>(frame_row), frames_out_host);
+        w.res = c.out(1, result_out_host);
+        return w;
+    };
+    return host_staged(h, carve, [&](const Stage& d, hipStream_t s) {
+        int rc = ria_gpu_rx_stream_batch(h, control_h, mode, flags, cfg, d.x, std::max(n_samples, 1), d.cap, 1, d.st_in, feed_step, max_invocations,
+                                         max_events, d.ev, d.frames, frame_row, d.res, s);
+        if (rc != RIA_OK) return rc;
+        if (hipMemcpyAsync(d.st, d.st_in, sizeof(ria_search_state), hipMemcpyDeviceToDevice, s) != hipSuccess)
+            return fail(h, RIA_ERR_HIP, "%s: the state's copy failed", who);
+        return static_cast<int>(RIA_OK); });
 }
 
 int ria_gpu_chase_combine_batch(ria_gpu_handle h, float* acc_dev, int32_t* count_dev, const uint8_t* decoded_dev,

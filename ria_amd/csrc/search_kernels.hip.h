@@ -38,6 +38,8 @@ struct SearchArgs {
     const int32_t* capture_len;
     ria_search_state* state;     // [n_streams], read and written in place
     ria_search_result* res;      // [n_streams]; outcome holds kSearchOpen / kSearchDue while the call runs
+    const uint32_t* subset;      // nullable: the n_streams streams to search, ascending (ria_gpu_rx_stream_batch's open streams);
+                                 // samples, capture_len, state and res stay indexed by stream.  Null: streams 0 .. n_streams - 1
     int n_streams, mode, cls, connected, feed_step, max_invocations, min_search;
     SearchCtl* ctl;
     uint32_t* list;              // [n_streams] due streams, ascending
@@ -49,6 +51,8 @@ struct SearchArgs {
 
 constexpr int kSearchWalkWaves = 4;     // 4 x 1000 floats of LDS per workgroup: 16 KB, ten workgroups per CU
 
+__device__ inline int search_stream(const SearchArgs& A, int i) { return A.subset ? static_cast<int>(A.subset[i]) : i; }
+
 __device__ inline bool search_domain_ok(const ria_search_state& s, int capture_len, long long stride) {
     return capture_len >= 0 && capture_len <= kSrchMaxCapture && capture_len <= stride && s.fed >= 0 && s.fed <= capture_len &&
            s.correlation_pos >= 0 && s.correlation_pos < kSrchRing && s.reject_streak >= 0;
@@ -57,8 +61,9 @@ __device__ inline bool search_domain_ok(const ria_search_state& s, int capture_l
 // the call's input domain, a thread per stream, ahead of the first walk: one stream outside it fails the whole call before any
 // state or result is written (the walk returns at once when the flag is set)
 __global__ __launch_bounds__(256) void search_check_kernel(SearchArgs A) {
-    const int b = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
-    if (b >= A.n_streams) return;
+    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
+    if (i >= A.n_streams) return;
+    const int b = search_stream(A, i);
     if (!search_domain_ok(A.state[b], A.capture_len[b], A.stride)) atomicOr(&A.ctl->bad, 1u);
 }
 
@@ -67,8 +72,9 @@ __global__ __launch_bounds__(256) void search_check_kernel(SearchArgs A) {
 __global__ __launch_bounds__(64 * kSearchWalkWaves) void search_walk_kernel(SearchArgs A, int first) {
     __shared__ __attribute__((aligned(16))) float sq_all[kSearchWalkWaves][kSrchRmsLen];
     const int wave = static_cast<int>(threadIdx.x) >> 6, lane = static_cast<int>(threadIdx.x) & 63;
-    const int b = static_cast<int>(blockIdx.x) * kSearchWalkWaves + wave;
-    if (b >= A.n_streams || A.ctl->bad) return;
+    const int i = static_cast<int>(blockIdx.x) * kSearchWalkWaves + wave;
+    if (i >= A.n_streams || A.ctl->bad) return;
+    const int b = search_stream(A, i);
     ria_search_state* sp = A.state + b;
     ria_search_result* rp = A.res + b;
     const int cap = A.capture_len[b];
@@ -139,8 +145,9 @@ __global__ __launch_bounds__(64 * kSearchWalkWaves) void search_walk_kernel(Sear
 __global__ __launch_bounds__(kAcqScanThreads) void search_list_kernel(SearchArgs A) {
     int running = 0;
     for (int base = 0; base < A.n_streams; base += kAcqScanThreads) {
-        const int b = base + static_cast<int>(threadIdx.x);
-        const bool due = b < A.n_streams && A.res[b].outcome == kSearchDue;
+        const int i = base + static_cast<int>(threadIdx.x);
+        const int b = i < A.n_streams ? search_stream(A, i) : 0;
+        const bool due = i < A.n_streams && A.res[b].outcome == kSearchDue;
         int total;
         const int pos = running + acq_block_scan(due, &total);
         if (due) A.list[pos] = static_cast<uint32_t>(b);

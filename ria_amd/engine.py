@@ -802,6 +802,81 @@ class RxEngine:
                                                   _ptr(st_d), int(feed_step), int(max_invocations), _ptr(res_d), _stream_ptr()))
         return self._status_array(res_d, self.SEARCH_RESULT), self._status_array(st_d, self.SEARCH_STATE)
 
+    STREAM_EVENT = np.dtype([("sync_position", "<i4"), ("search_start", "<i4"), ("window_len", "<i4"), ("outcome", "<i4"), ("next_pos", "<i4"),
+                             ("frame_bytes", "<i4"), ("need_samples", "<i4"), ("pending_total_cw", "<i4"), ("delivered", "u1"), ("success", "u1"),
+                             ("codewords_ok", "u1"), ("codewords_failed", "u1"), ("frame_type", "u1"), ("reserved0", "u1", 3),
+                             ("correlation", "<f4"), ("cfo_hz", "<f4"), ("fading_index", "<f4"), ("snr_db", "<f4"), ("reserved", "<i4", 2)])
+    STREAM_RESULT = np.dtype([("n_events", "<i4"), ("closed", "<i4"), ("mode", "<i4"), ("search_legs", "<i4"), ("invocations", "<u4"),
+                              ("waits", "<u4"), ("rms_skips", "<u4"), ("detector_runs", "<u4"), ("rejects", "<u4"), ("near_misses", "<u4"),
+                              ("weak_accepts", "<u4"), ("replays", "<u4"), ("catchups_moderate", "<u4"), ("catchups_severe", "<u4"),
+                              ("reserved", "<u4", 2)])
+
+    def stream_frame_row(self, mode):
+        """bytes of one payload row of rx_stream: the window call's minimum for the mode"""
+        m = capi.SEARCH_MODE[mode] if isinstance(mode, str) else int(mode)
+        return max(self.window_frame_row(), 20) if m == capi.SEARCH_MODE["OFDM_LTS"] else self.MCWIN_FRAME_ROW
+
+    def rx_stream(self, captures, capture_len, mode, control_engine=None, state=None, feed_step=0, max_invocations=1 << 20, max_events=256,
+                  connected=False, carriers=10, modulation="DBPSK", spreading=1):
+        """Recordings in, frames out in one call (ria_gpu_rx_stream_batch): StreamingDecoder's receive loop - search, the
+        window call of the mode, the state update - for one capture per row of `captures` (float32 [n, stride] on the
+        device), with state, windows, events and payloads on the device throughout.  Arguments as search(); control_engine:
+        rx_window's, for "OFDM_LTS" only; state: SEARCH_STATE records (default: fresh decoders with the whole recording
+        arrived for feed_step 0, nothing arrived otherwise).  A stream records at most max_events events per call; a second
+        call with the returned state goes on where the first stopped.  Returns (state (SEARCH_STATE), results
+        (STREAM_RESULT), events (STREAM_EVENT [n, max_events]), frames: uint8 [n, max_events, stream_frame_row(mode)] on the
+        device); acquire.stream_events turns the last three into rx_stream's list form."""
+        n, stride = captures.shape
+        assert captures.dtype == torch.float32 and captures.is_contiguous()
+        m = capi.SEARCH_MODE[mode] if isinstance(mode, str) else int(mode)
+        lens = np.empty(n, np.int32)
+        lens[:] = capture_len
+        if state is None:
+            state = self.search_state(n, fed=0 if feed_step else lens)
+        st = np.ascontiguousarray(state, self.SEARCH_STATE)
+        assert st.shape == (n,)
+        row, ne = self.stream_frame_row(m), int(max_events)
+        lens_d = torch.from_numpy(lens).to(self.device)
+        st_d = torch.from_numpy(st.view(np.uint8).reshape(n, 32).copy()).to(self.device)
+        res_d = torch.empty((n, 64), dtype=torch.uint8, device=self.device)
+        ev_d = torch.empty((n * max(ne, 0), 64), dtype=torch.uint8, device=self.device)
+        frames = torch.empty((n, max(ne, 0), row), dtype=torch.uint8, device=self.device)
+        cfg = None
+        if m != capi.SEARCH_MODE["OFDM_LTS"]:
+            bps = {"DBPSK": 1, "DQPSK": 2}[modulation] if isinstance(modulation, str) else int(modulation)
+            cfg = C.byref(capi.McdpskConfig(carriers, bps, spreading, 0))
+        self._check(self.lib.ria_gpu_rx_stream_batch(self.h, control_engine.h if control_engine is not None else None, m,
+                                                     capi.SEARCH_CONNECTED if connected else 0, cfg, _ptr(captures), stride, _ptr(lens_d), n,
+                                                     _ptr(st_d), int(feed_step), int(max_invocations), ne, _ptr(ev_d), _ptr(frames), row,
+                                                     _ptr(res_d), _stream_ptr()))
+        return (self._status_array(st_d, self.SEARCH_STATE), self._status_array(res_d, self.STREAM_RESULT),
+                self._status_array(ev_d, self.STREAM_EVENT).reshape(n, ne), frames)
+
+    def rx_stream_host(self, recording, mode, control_engine=None, state=None, feed_step=0, max_invocations=1 << 20, max_events=256,
+                       connected=False, carriers=10, modulation="DBPSK", spreading=1):
+        """rx_stream for one recording in host memory (ria_gpu_rx_stream_host; a float32 numpy array).  Returns (state,
+        results, events, frames) as rx_stream does for n = 1, frames as a numpy array."""
+        x = np.ascontiguousarray(recording, np.float32)
+        assert x.ndim == 1
+        m = capi.SEARCH_MODE[mode] if isinstance(mode, str) else int(mode)
+        if state is None:
+            state = self.search_state(1, fed=0 if feed_step else len(x))
+        st = np.ascontiguousarray(state, self.SEARCH_STATE).copy()
+        assert st.shape == (1,)
+        row, ne = self.stream_frame_row(m), int(max_events)
+        ev = np.zeros(max(ne, 0), self.STREAM_EVENT)
+        frames = np.zeros((1, max(ne, 0), row), np.uint8)
+        res = np.zeros(1, self.STREAM_RESULT)
+        cfg = None
+        if m != capi.SEARCH_MODE["OFDM_LTS"]:
+            bps = {"DBPSK": 1, "DQPSK": 2}[modulation] if isinstance(modulation, str) else int(modulation)
+            cfg = C.byref(capi.McdpskConfig(carriers, bps, spreading, 0))
+        self._check(self.lib.ria_gpu_rx_stream_host(self.h, control_engine.h if control_engine is not None else None, m,
+                                                    capi.SEARCH_CONNECTED if connected else 0, cfg, x.ctypes.data, len(x), st.ctypes.data,
+                                                    int(feed_step), int(max_invocations), ne, ev.ctypes.data, frames.ctypes.data, row,
+                                                    res.ctypes.data))
+        return st, res, ev.reshape(1, ne), frames
+
     MCDFRAME_RESULT = np.dtype([("success", "u1"), ("codewords_ok", "u1"), ("codewords_failed", "u1"), ("frame_type", "u1"),
                                 ("header_total_cw", "<i4"), ("frame_bytes", "<i4"), ("reserved", "<i4")])
     HARQ_RESULT = np.dtype([("seq", "<u2"), ("valid", "u1"), ("entry", "u1"), ("src_hash", "<u4"), ("dst_hash", "<u4"),
