@@ -328,9 +328,9 @@ def ldpc_domain_fixture(R):
                     rec[f"{k}_{key}"] = v
             print("ldpc domain", key, "rows", len(X), "converged at (0.9375, 200):",
                   int(rec[f"res_{key}"][:, L.CONFIGS.index((0.9375, 200)), 0].sum()), flush=True)
-    for mod, rate, shape, n, seed in L.FRAME_SETS:
+    for mod, rate, shape, n, seed in L.ALL_FRAME_SETS:      # the ten sets at two rates, then every rate and recovery step
         llr, _ = L.frames(O, mod, rate, shape, n, seed)
-        key = f"{mod}_{[k for k, v in L.RATES.items() if v == rate][0]}_{shape}"
+        key = L.set_key(mod, rate, shape)
         rec[f"sha_frm_{key}"] = np.array(L.digest(llr))
         for k, v in L.frame_answers(R, mod, rate, llr).items():
             rec[f"frm_{k}_{key}"] = v

@@ -380,6 +380,18 @@ class Oracle:
                                        ip(iters), ip(att))
         return data, ok, iters, att
 
+    # RO_REC_* of oracle/ria_oracle.h: the step of the CRC recovery that ended a decode_fixed_frame call
+    REC_STAGES = ("none", "hdr1", "hdr2", "single", "crc", "pair", "triple", "quad", "fill", "failed")
+
+    def decode_fixed_frame_stage(self, llr, rate, ch_deint, bps, flags=7):
+        """decode_fixed_frame plus the recovery step that ended it -> (data, ok, iters, attempts, stage name, detail);
+        detail is the fallback's substitution index for "fill", else -1.  The stage is this restatement's own bookkeeping
+        (kept per thread, read back on the calling thread); bytes and ok are what the reference pins."""
+        r = self.decode_fixed_frame(llr, rate, ch_deint, bps, flags)
+        detail = C.c_int(-1)
+        stage = self.lib.ro_last_recovery_stage(C.byref(detail))
+        return r + (self.REC_STAGES[stage], int(detail.value))
+
     # ---- the scenarios of the reference's own test programs, composed from the restatement (the compiled reference gives the
     # same arrays through Ref.tool_*: oracle/ref_shim_tools.cpp)
     ZC_TOOL_ROOTS = (1, 3, 5, 7)   # ZCFrameType PING, PONG, DATA, CONTROL (tools/test_zc_sync.cpp:313-323)

@@ -1426,6 +1426,9 @@ static void sus_sort(ro_suspect* a, int n) {
     else sus_insertion(a, a + n);
 }
 
+static _Thread_local int g_rec_stage = RO_REC_NONE, g_rec_detail = -1;
+int ro_last_recovery_stage(int* detail) { if (detail) *detail = g_rec_detail; return g_rec_stage; }
+
 int ro_decode_fixed_frame(const float* llr, int n, int rate, int ch_deint, int bps, int flags,
                           uint8_t* data_out, uint8_t* ok_out, int* iters_out, int* attempts_out) {
     /* frame_v2.cpp:1335-1883 */
@@ -1438,6 +1441,7 @@ int ro_decode_fixed_frame(const float* llr, int n, int rate, int ch_deint, int b
     int bpc = ro_info_bits(rate) / 8, max_iter = ro_recommended_iters(rate);
     memset(data_out, 0, (size_t)(4 * bpc));
     memset(ok_out, 0, 4);
+    g_rec_stage = RO_REC_NONE; g_rec_detail = -1;
     if (n < RO_FRAME_BITS) return 0;
 
     static const float f0[4] = { 0.875f, 0.75f, 0.625f, 0.5f };
@@ -1537,7 +1541,7 @@ int ro_decode_fixed_frame(const float* llr, int n, int rate, int ch_deint, int b
                         if (cwd[0][0] == 0x55 && cwd[0][1] == 0x4C &&
                             ro_crc16(cwd[0], 15) == (uint16_t)((cwd[0][15] << 8) | cwd[0][16])) {
                             int tl = ro_reassemble(cwd, bpc, trial);
-                            if (ro_verify_frame(trial, tl)) recovered = 1;
+                            if (ro_verify_frame(trial, tl)) { recovered = 1; g_rec_stage = RO_REC_HDR1; }
                         }
                         if (!recovered) cwd[0][by] ^= (uint8_t)(1 << bit);
                     }
@@ -1550,7 +1554,7 @@ int ro_decode_fixed_frame(const float* llr, int n, int rate, int ch_deint, int b
                             if (cwd[0][0] == 0x55 && cwd[0][1] == 0x4C &&
                                 ro_crc16(cwd[0], 15) == (uint16_t)((cwd[0][15] << 8) | cwd[0][16])) {
                                 int tl = ro_reassemble(cwd, bpc, trial);
-                                if (ro_verify_frame(trial, tl)) recovered = 1;
+                                if (ro_verify_frame(trial, tl)) { recovered = 1; g_rec_stage = RO_REC_HDR2; }
                             }
                             if (!recovered) cwd[0][b2 / 8] ^= (uint8_t)(1 << (b2 % 8));
                         }
@@ -1574,13 +1578,13 @@ int ro_decode_fixed_frame(const float* llr, int n, int rate, int ch_deint, int b
                         for (int p = 0; p < data_bits && !recovered; ++p)
                             if (deltas[p] == syn) {
                                 int fb = p / 8, ci = fb / bpc;
-                                if (ci < 4) { cwd[ci][fb % bpc] ^= (uint8_t)(1 << (p % 8)); recovered = 1; }
+                                if (ci < 4) { cwd[ci][fb % bpc] ^= (uint8_t)(1 << (p % 8)); recovered = 1; g_rec_stage = RO_REC_SINGLE; }
                             }
                         if (!recovered)
                             for (int bit = 0; bit < 16 && !recovered; ++bit)
                                 if (syn == (1u << bit)) {
                                     int fb = (bit >= 8) ? expected - 2 : expected - 1, ci = fb / bpc;
-                                    if (ci < 4) { cwd[ci][fb % bpc] ^= (uint8_t)(1 << (bit % 8)); recovered = 1; }
+                                    if (ci < 4) { cwd[ci][fb % bpc] ^= (uint8_t)(1 << (bit % 8)); recovered = 1; g_rec_stage = RO_REC_CRC; }
                                 }
                         static _Thread_local ro_suspect sus[4 * 68 * 8];
                         int nsus = 0;
@@ -1602,7 +1606,7 @@ int ro_decode_fixed_frame(const float* llr, int n, int rate, int ch_deint, int b
                                     if ((uint16_t)(sd[a] ^ sd[b2]) == syn) {
                                         RO_FIX(sus[a].frame_bit); RO_FIX(sus[b2].frame_bit);
                                         int tl = ro_reassemble(cwd, bpc, trial);
-                                        if (ro_verify_frame(trial, tl)) recovered = 1;
+                                        if (ro_verify_frame(trial, tl)) { recovered = 1; g_rec_stage = RO_REC_PAIR; }
                                         else { RO_FIX(sus[a].frame_bit); RO_FIX(sus[b2].frame_bit); }
                                     }
                         if (!recovered)
@@ -1612,7 +1616,7 @@ int ro_decode_fixed_frame(const float* llr, int n, int rate, int ch_deint, int b
                                         if ((uint16_t)(sd[a] ^ sd[b2] ^ sd[c2]) == syn) {
                                             RO_FIX(sus[a].frame_bit); RO_FIX(sus[b2].frame_bit); RO_FIX(sus[c2].frame_bit);
                                             int tl = ro_reassemble(cwd, bpc, trial);
-                                            if (ro_verify_frame(trial, tl)) recovered = 1;
+                                            if (ro_verify_frame(trial, tl)) { recovered = 1; g_rec_stage = RO_REC_TRIPLE; }
                                             else { RO_FIX(sus[a].frame_bit); RO_FIX(sus[b2].frame_bit); RO_FIX(sus[c2].frame_bit); }
                                         }
                         if (!recovered) {
@@ -1624,7 +1628,7 @@ int ro_decode_fixed_frame(const float* llr, int n, int rate, int ch_deint, int b
                                             if ((uint16_t)(sd[a] ^ sd[b2] ^ sd[c2] ^ sd[d2]) == syn) {
                                                 RO_FIX(sus[a].frame_bit); RO_FIX(sus[b2].frame_bit); RO_FIX(sus[c2].frame_bit); RO_FIX(sus[d2].frame_bit);
                                                 int tl = ro_reassemble(cwd, bpc, trial);
-                                                if (ro_verify_frame(trial, tl)) recovered = 1;
+                                                if (ro_verify_frame(trial, tl)) { recovered = 1; g_rec_stage = RO_REC_QUAD; }
                                                 else { RO_FIX(sus[a].frame_bit); RO_FIX(sus[b2].frame_bit); RO_FIX(sus[c2].frame_bit); RO_FIX(sus[d2].frame_bit); }
                                             }
                         }
@@ -1643,12 +1647,12 @@ int ro_decode_fixed_frame(const float* llr, int n, int rate, int ch_deint, int b
                             memcmp(dec, orig, (size_t)bpc) != 0) {
                             memcpy(cwd[cw], dec, (size_t)bpc);
                             int tl = ro_reassemble(cwd, bpc, trial);
-                            if (ro_verify_frame(trial, tl)) recovered = 1;
+                            if (ro_verify_frame(trial, tl)) { recovered = 1; g_rec_stage = RO_REC_FILL; g_rec_detail = at * 4 + cw; }
                             else memcpy(cwd[cw], orig, (size_t)bpc);
                         }
                     }
             }
-            if (!recovered) { memset(ok_out, 0, 4); good = 0; }
+            if (!recovered) { memset(ok_out, 0, 4); good = 0; g_rec_stage = RO_REC_FAILED; }
         }
     }
     for (int cw = 0; cw < 4; ++cw) if (ok_out[cw]) memcpy(data_out + cw * bpc, cwd[cw], (size_t)bpc);

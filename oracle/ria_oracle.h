@@ -148,6 +148,11 @@ void ro_burst_deinterleave(int n_frames, const float* physical, int stride, floa
 /* flags bit0: run retry cascade phase 0; bit1: phases 1-6; bit2: CRC false-positive recovery */
 int ro_decode_fixed_frame(const float* llr, int n, int rate, int ch_deint, int bps, int flags,
                           uint8_t* data_out, uint8_t* ok_out, int* iters_out, int* attempts_out);
+/* which step of the CRC recovery ended this thread's last ro_decode_fixed_frame (coverage bookkeeping of the tests only;
+ * the reference has no such getter).  detail: the fallback's substitution index (attempt * 4 + codeword), else -1. */
+enum { RO_REC_NONE = 0, RO_REC_HDR1, RO_REC_HDR2, RO_REC_SINGLE, RO_REC_CRC, RO_REC_PAIR, RO_REC_TRIPLE, RO_REC_QUAD,
+       RO_REC_FILL, RO_REC_FAILED };
+int ro_last_recovery_stage(int* detail);
 
 #ifdef __cplusplus
 }

@@ -141,16 +141,14 @@ def test_batch_size_and_position_do_not_change_a_row(golden, oracle, rn):
         assert np.array_equal(rti, ref_rob[idx]) and np.array_equal(out, ref_rob_bytes[idx]), f"{rn} robust n={n}"
 
 
-@pytest.mark.parametrize("mod,rate,shape,n,seed", L.FRAME_SETS)
-def test_decode_fixed_frame_families(golden, oracle, monkeypatch, mod, rate, shape, n, seed):
-    """decodeFixedFrame on real frames mapped to the erasure / ties / clamp / tiny shapes and on frames that converge to a
-    wrong codeword (CRC recovery with suspects tied on |LLR|): bytes and cw_ok against the reference, iterations,
-    attempts and frame_valid against the oracle, device recovery against the host recovery, with and without the
-    channel de-interleaver."""
+def check_frame_family(golden, oracle, monkeypatch, mod, rate, shape, n, seed):
+    """decodeFixedFrame on one set of ldpc_domain_inputs.frames: bytes and cw_ok against the reference, iterations, attempts
+    and frame_valid against the oracle, device recovery against the host recovery, with and without the channel
+    de-interleaver.  (tests/test_gpu_frame_rates.py runs the sets at all six code rates through it.)"""
     from ria_amd import capi
     rn = RATE_NAME[rate]
     e = engine(mod, rn)
-    key = f"{mod}_{rn}_{shape}"
+    key = L.set_key(mod, rate, shape)
     fx = golden("ldpc_domain")
     g = oracle.geom(getattr(po, mod), rate)
     bpc, bps = g.bytes_per_cw, g.bits_per_symbol
@@ -189,3 +187,12 @@ def test_decode_fixed_frame_families(golden, oracle, monkeypatch, mod, rate, sha
         if shape == "recovery":
             flagged = int(res["raw"][1]["needs_recovery"].sum())
             assert flagged >= 20, f"{key}: only {flagged} frames flagged for the CRC recovery"
+
+
+@pytest.mark.parametrize("mod,rate,shape,n,seed", L.FRAME_SETS)
+def test_decode_fixed_frame_families(golden, oracle, monkeypatch, mod, rate, shape, n, seed):
+    """decodeFixedFrame on real frames mapped to the erasure / ties / clamp / tiny shapes and on frames that converge to a
+    wrong codeword (CRC recovery with suspects tied on |LLR|, a search that exhausts without a repair): bytes and cw_ok
+    against the reference, iterations, attempts and frame_valid against the oracle, device recovery against the host
+    recovery, with and without the channel de-interleaver."""
+    check_frame_family(golden, oracle, monkeypatch, mod, rate, shape, n, seed)
