@@ -1432,6 +1432,85 @@ int ria_gpu_search_batch(ria_gpu_handle h, int mode, uint32_t flags, const ria_m
                          const float* samples_dev, int64_t stride, const int32_t* capture_len_dev, int n_streams,
                          ria_search_state* state_dev, int feed_step, int max_invocations, ria_search_result* result_dev, void* stream);
 
+/* ---- the same search for captures longer than the ring buffer ------------------------------------------------------------
+ * ria_gpu_search_ring_batch is ria_gpu_search_batch - its arguments, its three modes, its time model, its outcomes, its
+ * re-entrance (a RIA_SEARCH_LIMIT state continues exactly) and RIA_OPT_SEARCH_CHUNK - with the 960 000-sample ring buffer of
+ * gui::StreamingDecoder and the whole of feedAudio (src/gui/modem/streaming_decoder.cpp:184-291), so a capture may be minutes
+ * long.  Beyond what ria_gpu_search_batch replaces, it replaces the statements that depend on MAX_BUFFER_SAMPLES, write_pos_ =
+ * total_fed_ % 960000 and total_fed_ (ria_amd/csrc/ring_rules.hpp): computeUnsearched on both branches (:193-202), the pre-wrap
+ * clamp (:204, :289), the drift guard (:232-238, CORR_INVARIANT_GUARD 9600: a backlog above 950 400 after the wrap snaps the
+ * cursor to the write position), the overflow drop (:242-278, OVERFLOW_RECOVERY_KEEP 360 000, need_to_drop, overflow_events_
+ * and overflow_samples_dropped), the two waits on the circular backlog (:449, :466-481), the cursor initialisation
+ * correlation_pos_ == 0 && total_fed_ >= 960000 -> write_pos_ (:458-464, which stays done when the second wait returns), the
+ * ZC catch-up on the circular backlog (:488-522), the post-wrap backtrack (:597-605), sync_position_ modulo the ring (:858),
+ * ringPosToAbsolute (:862-874) and the circular anti-replay with its cursor (:876-889): a sync at the ring index of the last
+ * decoded frame one lap later is a replay, as in the reference.
+ *
+ * No ring is materialised.  With T = total_fed, ring index p holds x[p] for T < 960000 (0 for p >= T: never written) and
+ * x[T - 1 - ((T - 1 - p) mod 960000)] otherwise; the kernels read the capture through that form.
+ *
+ * Time model: one invocation is one searchForSync(); after every invocation that leaves the stream open, count =
+ * min(feed_step, capture_len - total_fed) samples arrive through the whole of feedAudio (count 0: nothing happens).  Before
+ * the wrap a cursor ahead of total_fed is a wait, ria_gpu_search_batch's documented limit: on a capture of at most 959 999
+ * samples the two calls give the same result and state.  After the wrap the reference's own arithmetic holds everywhere.
+ *
+ * Domain: 0 <= capture_len <= min(stride, 2^31 - 1 - 960000), 0 <= total_fed <= capture_len, correlation_pos in 0..959 999,
+ * reject_streak >= 0, last_decoded_sync_pos in 0..959 999 or INT32_MIN.  Anything else is RIA_ERR_INVALID for the whole call,
+ * checked on the device before any state or result is written or any sample read.
+ *
+ * ria_ring_state: ria_search_state's decoder with total_fed_ in 64 bits, correlation_pos and last_decoded_sync_pos as RING
+ * indices, and the running overflow_events_ / stats_.overflow_samples_dropped.  A fresh decoder is {total_fed, 0, 0, 0.001f,
+ * 0, 0, 0, INT32_MIN, 0, 0}.  ria_ring_search_result: ria_search_result's fields in its layout (search_start and
+ * sync_position are ring indices; abs_position = ringPosToAbsolute(sync_position)), then abs_search_start =
+ * ringPosToAbsolute(search_start), the capture index of span sample 0, this call's overflow_dropped, overflows, drift_snaps and
+ * cursor_inits (executions of :462), and span_wraps: 1 when the last detector run's span [search_start, search_start +
+ * search_len) modulo the ring had the write position strictly inside it.  Such a span holds the stream's newest samples
+ * followed by its oldest, so it is not a contiguous piece of the capture and the window calls cannot repeat the detection at
+ * abs_search_start; it needs a backlog above 960 000 minus the backtrack.  The search itself is exact there.
+ *
+ * Work: as ria_gpu_search_batch, on the same workspace; the gather reads the span through the closed form.
+ *
+ * Not covered: the ZC-miss -> chirp fallback (:785-828), disconnected OFDM (chirp) search, OFDM-COX and the frame timeout.
+ * The stream loop on this search is ria_gpu_rx_ring_batch, behind ria_gpu_rx_stream_batch below. */
+typedef struct ria_ring_state {      /* 48 bytes, one per stream */
+    int64_t  total_fed;
+    int32_t  correlation_pos;        /* ring index */
+    int32_t  reject_streak;
+    float    noise_floor;
+    float    last_cfo_hz;
+    float    fading_hint;
+    float    snr_hint;
+    int32_t  last_decoded_sync_pos;  /* ring index, INT32_MIN = none */
+    uint32_t overflow_events;
+    uint64_t overflow_dropped;
+} ria_ring_state;
+typedef struct ria_ring_search_result {   /* 144 bytes, one per stream: ria_search_result's 112, then the ring's */
+    int32_t  outcome;                /* RIA_SEARCH_* */
+    int32_t  search_start;           /* ring index */
+    int32_t  search_len;
+    int32_t  sync_position;          /* ring index, -1 where nothing was found */
+    int64_t  abs_position;           /* ringPosToAbsolute(sync_position) */
+    float    correlation;
+    float    known_cfo_hz;
+    float    sync_cfo_hz;
+    float    sync_snr_db;
+    float    detect_threshold;
+    float    min_confidence;
+    int32_t  weak_accept;
+    int32_t  marker;
+    int32_t  root;
+    uint32_t invocations, waits, rms_skips, detector_runs, rejects, near_misses, weak_accepts, replays;
+    uint32_t catchups_moderate, catchups_severe;
+    uint32_t reserved0, reserved1, reserved2;
+    int64_t  abs_search_start;       /* ringPosToAbsolute(search_start) */
+    uint64_t overflow_dropped;
+    uint32_t overflows, drift_snaps, cursor_inits;
+    uint32_t span_wraps;
+} ria_ring_search_result;
+int ria_gpu_search_ring_batch(ria_gpu_handle h, int mode, uint32_t flags, const ria_mcdpsk_config* cfg /* NULL for RIA_SEARCH_OFDM_LTS */,
+                              const float* samples_dev, int64_t stride, const int32_t* capture_len_dev, int n_streams,
+                              ria_ring_state* state_dev, int feed_step, int max_invocations, ria_ring_search_result* result_dev, void* stream);
+
 /* ---- recordings in, frames out: the receive loop of StreamingDecoder for a batch of captures ----------------------------------
  * ria_gpu_rx_stream_batch runs gui::StreamingDecoder::processBuffer's loop (src/gui/modem/streaming_decoder.cpp:293-384) -
  * searchForSync (:386-941), decodeCurrentFrame (:943-2013), the state both leave - over n_streams captures, as a composition
@@ -1525,6 +1604,57 @@ int ria_gpu_rx_stream_host(ria_gpu_handle h, ria_gpu_handle control_h, int mode,
                            const float* samples_host, int n_samples, ria_search_state* state_host /* in and out */,
                            int feed_step, int max_invocations, int max_events, ria_stream_event* events_out_host,
                            uint8_t* frames_out_host, int frame_row, ria_stream_result* result_out_host);
+
+/* ---- recordings longer than the ring buffer in, frames out -----------------------------------------------------------------
+ * ria_gpu_rx_ring_batch is ria_gpu_rx_stream_batch's loop on ria_gpu_search_ring_batch, with the window leg in absolute
+ * indices.  Arguments as for the stream call, with ria_ring_state; domain and errors are the ring search's.
+ *   1. the ring search on the open streams.  A stream that does not end with RIA_SEARCH_SYNC_FOUND closes with the search's
+ *      outcome; a found one whose span crossed the write position (span_wraps) closes with RIA_STREAM_SPAN_LOST: its window
+ *      is no contiguous piece of the capture (reachable only with a backlog above 960 000 minus the backtrack).
+ *   2. A found stream gets the window [abs_search_start, abs_search_start + min(full, capture_len - abs_search_start)) of
+ *      the capture; full is the stream call's.  A configuration whose full exceeds 959 999 is RIA_ERR_INVALID.
+ *   3. Parameters: the stream call's, with abs_base = abs_search_start; for MC-DPSK last_decoded_sync = the circular
+ *      difference last_decoded_sync_pos - search_start on the ring, in -480 000 .. 479 999 (INT32_MIN kept).
+ *   4. The window call of the mode, unchanged.
+ *   5. The state: last_cfo_hz / fading_hint as in the stream call; last_decoded_sync_pos a ring index (sync_position on a
+ *      delivered OFDM frame; what the MC-DPSK window call leaves, plus search_start, modulo the ring); the cursor =
+ *      (search_start + next_pos) % 960000, behind the first frame of a RIA_WIN_BURST / TOO_LONG window (sync + first frame,
+ *      modulo the ring), else where the search left it; total_fed = max(total_fed, min(capture_len, absolute cursor)) - a
+ *      direct assignment, not a feedAudio: backlog plus arrivals stay below full <= 959 999 there, so the overflow drop
+ *      could not have fired (ria_amd/csrc/ring_rules.hpp, ring_window_arrival).
+ *   6. The event: a ria_stream_event whose sync_position, search_start and next_pos are CAPTURE (absolute) indices.
+ * A stream closes with RIA_STREAM_SEARCH_NEED_SAMPLES, RIA_STREAM_SEARCH_LIMIT, RIA_STREAM_WINDOW_NEED_SAMPLES,
+ * RIA_STREAM_EVENTS_FULL or RIA_STREAM_SPAN_LOST; there is no RIA_STREAM_RING_END.  ria_ring_stream_result is
+ * ria_stream_result's 64 bytes, then the ring search's overflow_dropped, overflows, drift_snaps and cursor_inits summed over
+ * the legs.  Re-entrant through ria_ring_state as the stream call is.  The workspace is carved once and reserved before the
+ * first launch.  Feed long recordings with feed_step > 0 (4800): one that is "all there" shows the decoder only its last
+ * 960 000 samples, as the reference's would.
+ * Still out of scope: burst groups and continuation, chase pools, channel interleaving, MC-DPSK NEED_SAMPLES re-entry, the
+ * ZC-miss -> chirp fallback, OFDM-COX and the frame timeout.
+ * ria_gpu_rx_ring_host takes one recording of any length in the domain from host memory: it is copied in pieces through the
+ * handle's pinned block into a device buffer the handle owns, grown before anything is in flight. */
+#define RIA_STREAM_SPAN_LOST 7
+typedef struct ria_ring_stream_result {   /* 88 bytes, one per stream: ria_stream_result's 64, then the ring's */
+    int32_t  n_events;
+    int32_t  closed;                 /* RIA_STREAM_* */
+    int32_t  mode;
+    int32_t  search_legs;
+    uint32_t invocations, waits, rms_skips, detector_runs, rejects, near_misses, weak_accepts, replays;
+    uint32_t catchups_moderate, catchups_severe;
+    uint32_t reserved[2];
+    uint64_t overflow_dropped;
+    uint32_t overflows, drift_snaps, cursor_inits;
+    uint32_t reserved1;
+} ria_ring_stream_result;
+int ria_gpu_rx_ring_batch(ria_gpu_handle h, ria_gpu_handle control_h /* RIA_SEARCH_OFDM_LTS only, else NULL */, int mode, uint32_t flags,
+                          const ria_mcdpsk_config* cfg, const float* samples_dev, int64_t stride, const int32_t* capture_len_dev, int n_streams,
+                          ria_ring_state* state_dev, int feed_step, int max_invocations, int max_events,
+                          ria_stream_event* events_dev /* n_streams * max_events */, uint8_t* frames_dev, int frame_row,
+                          ria_ring_stream_result* result_dev, void* stream);
+int ria_gpu_rx_ring_host(ria_gpu_handle h, ria_gpu_handle control_h, int mode, uint32_t flags, const ria_mcdpsk_config* cfg,
+                         const float* samples_host, int n_samples, ria_ring_state* state_host /* in and out */,
+                         int feed_step, int max_invocations, int max_events, ria_stream_event* events_out_host,
+                         uint8_t* frames_out_host, int frame_row, ria_ring_stream_result* result_out_host);
 
 /* ---- debug / test hooks ----------------------------------------------------------------------- */
 /* op: 0 sinf 1 cosf 2 logf 3 atan2f(a,b) 4 hypotf(a,b) 5 a/b 6 sqrtf(a); evaluates the device

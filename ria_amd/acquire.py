@@ -595,6 +595,115 @@ def rx_stream(engine, captures, capture_len, mode, control_engine=None, feed_ste
     return events
 
 
+# ---- recordings longer than the ring buffer (ria_gpu_search_ring_batch + the window calls)
+RING_COUNTERS = ("overflows", "overflow_dropped", "drift_snaps", "cursor_inits")
+
+
+def rx_ring(engine, captures, capture_len, mode, control_engine=None, feed_step=4800, max_invocations=1 << 20, max_events=256,
+            connected=None, carriers=10, modulation="DBPSK", spreading=1, state=None):
+    """rx_stream for recordings of any length: RxEngine.search_ring (the decoder's 960 000-sample ring buffer wraps, with
+    feedAudio's drift guard and overflow drop) on every open stream, then the window call of the mode on the window cut from
+    the capture by ABSOLUTE index, [abs_search_start, abs_search_start + min(full, capture_len - abs_search_start)), with
+    abs_base = abs_search_start and, for MC-DPSK, last_decoded_sync_pos rebased to the window's origin by circular difference;
+    then the host's part modulo the ring: the cursor to (search_start + next_pos) % 960000 (behind the first frame of a BURST /
+    TOO_LONG window), last_decoded_sync_pos as a ring index, total_fed = max(total_fed, min(capture_len, absolute cursor)).
+    A stream whose found span crossed the write position (span_wraps: its window is no contiguous piece of the capture)
+    closes with "SPAN_LOST"; one that reaches max_events or whose window call wants samples the capture does not hold closes
+    too.  There is no end of the ring to close at.
+
+    feed_step must let the search keep up: with feed_step 0 a recording longer than the ring is "all there" and the decoder
+    sees only its last 960 000 samples, as the reference's would.  state: RING_STATE records to continue from (default:
+    fresh decoders, nothing fed for feed_step > 0).  Returns (events, state, closed, counters): per stream the list of events
+    (dicts: position = the sync's absolute index, search_start = abs_search_start, outcome, frame = the delivered bytes or
+    None), the final RING_STATE records, why each stream closed ("NEED_SAMPLES" / "LIMIT" from the search, "WINDOW_NEED_SAMPLES",
+    "EVENTS_FULL", "SPAN_LOST") and the search's RING_COUNTERS summed over the legs (int64 [n, 4])."""
+    n = captures.shape[0]
+    m = capi.SEARCH_MODE[mode] if isinstance(mode, str) else int(mode)
+    ofdm = m == capi.SEARCH_MODE["OFDM_LTS"]
+    chirp = m == capi.SEARCH_MODE["MCDPSK_CHIRP"]
+    connected = bool(connected)
+    ring = capi.RING_SAMPLES
+    lens = np.empty(n, np.int64)
+    lens[:] = capture_len
+    state = engine.ring_state(n, total_fed=0 if feed_step else lens) if state is None else np.array(state, engine.RING_STATE)
+    bps = {"DBPSK": 1, "DQPSK": 2}[modulation] if isinstance(modulation, str) else int(modulation)
+    search_len = capi.SEARCH_MIN_SEARCH[m]
+    first_frame = engine.geo.frame_samples if ofdm else mcdpsk_frame_len(1, carriers, bps, spreading)
+    full = search_len + (engine.geo.frame_samples + 32 if ofdm else mcdpsk_frame_len(8, carriers, bps, spreading))
+    if full > ring - 1:
+        raise ValueError("the window of this configuration is longer than the ring buffer")
+    names = {v: k for k, v in (capi.WIN_OUTCOME if ofdm else capi.MWIN_OUTCOME).items()}
+    search_names = {v: k for k, v in capi.SEARCH_OUTCOME.items()}
+    events = [[] for _ in range(n)]
+    closed = [None] * n
+    counters = np.zeros((n, len(RING_COUNTERS)), np.int64)
+    open_ = np.ones(n, bool)
+    while open_.any():
+        idx = np.flatnonzero(open_)
+        res, st = engine.search_ring(captures[torch.as_tensor(idx, device=captures.device)].contiguous() if len(idx) < n else captures, lens[idx],
+                                     state[idx], m, feed_step=feed_step, max_invocations=max_invocations, connected=connected, carriers=carriers,
+                                     modulation=modulation, spreading=spreading)
+        state[idx] = st
+        for c, k in enumerate(RING_COUNTERS):
+            counters[idx, c] += res[k].astype(np.int64)
+        found = res["outcome"] == capi.SEARCH_OUTCOME["SYNC_FOUND"]
+        for j in np.flatnonzero(~found):
+            open_[idx[j]], closed[idx[j]] = False, search_names[int(res["outcome"][j])]
+        by_len = {}
+        for j in np.flatnonzero(found):
+            if res["span_wraps"][j]:
+                open_[idx[j]], closed[idx[j]] = False, "SPAN_LOST"
+                continue
+            by_len.setdefault(int(min(full, lens[idx[j]] - res["abs_search_start"][j])), []).append(j)
+        for wl, js in by_len.items():
+            rows, r = idx[js], res[js]
+            w = _gather_windows(captures, rows, r["abs_search_start"], wl)
+            conf = np.minimum(r["min_confidence"], r["correlation"])
+            ss = r["search_start"].astype(np.int64)
+            if ofdm:
+                frames, wres, acq, _, _ = engine.rx_window(control_engine, w, search_len, known_cfo=r["known_cfo_hz"], detect_threshold=r["detect_threshold"],
+                                                           min_confidence=conf, abs_base=r["abs_search_start"])
+                nbytes, ok, fading = wres["frame"]["frame_bytes"], (wres["frame"]["success"] != 0) | (wres["frame"]["codewords_ok"] != 0), wres["fading_index"]
+                cfo, moved = wres["sync_cfo_hz"], (wres["outcome"] == capi.WIN_OUTCOME["DECODED"]) | (wres["outcome"] == capi.WIN_OUTCOME["CONTROL_PROFILE"])
+                last = np.where(ok, r["sync_position"], state["last_decoded_sync_pos"][rows])
+            else:
+                last_in = state["last_decoded_sync_pos"][rows].astype(np.int64)
+                d = (last_in - ss) % ring                    # the circular difference to the window's origin, in -480 000 .. 479 999
+                d = np.where(d >= ring // 2, d - ring, d)
+                rel = np.where(last_in == capi.SEARCH_NO_LAST_SYNC, capi.MWIN_NO_LAST_SYNC, d)
+                frames, wres, acq, _ = engine.mcdpsk_window(w, search_len, carriers=carriers, modulation=bps, spreading=spreading,
+                                                            sync="chirp" if chirp else "zc", disconnected=chirp and not connected,
+                                                            known_cfo=r["known_cfo_hz"], detect_threshold=r["detect_threshold"], min_confidence=conf,
+                                                            abs_base=r["abs_search_start"], last_decoded_sync=rel)
+                nbytes, ok, fading = acq["frame_bytes"], wres["deliver"] != 0, acq["fading_index"]
+                cfo, moved = acq["cfo_hz"], wres["outcome"] == capi.MWIN_OUTCOME["DECODED"]
+                out_last = wres["last_decoded_sync"].astype(np.int64)
+                last = np.where(out_last == capi.MWIN_NO_LAST_SYNC, capi.SEARCH_NO_LAST_SYNC, (out_last + ss) % ring)
+            frames = frames.cpu().numpy()
+            for k, s in enumerate(rows):
+                name = names[int(wres["outcome"][k])]
+                events[s].append(dict(position=int(r["abs_position"][k]), search_start=int(r["abs_search_start"][k]), outcome=name,
+                                      frame=frames[k, :int(nbytes[k])].tobytes() if ok[k] else None))
+                if moved[k]:
+                    state["last_cfo_hz"][s] = cfo[k]
+                    state["fading_hint"][s] = fading[k]
+                state["last_decoded_sync_pos"][s] = last[k]
+                abs_cursor = None
+                if wres["next_pos"][k] >= 0:
+                    abs_cursor = int(r["abs_search_start"][k]) + int(wres["next_pos"][k])
+                elif name in ("BURST", "TOO_LONG"):
+                    abs_cursor = int(r["abs_position"][k]) + first_frame
+                if abs_cursor is not None:
+                    # the same offset from the span's first sample in ring indices; the consumed samples have arrived
+                    state["correlation_pos"][s] = (int(ss[k]) + abs_cursor - int(r["abs_search_start"][k])) % ring
+                    state["total_fed"][s] = max(int(state["total_fed"][s]), min(int(lens[s]), abs_cursor))
+                if name == "NEED_SAMPLES":
+                    open_[s], closed[s] = False, "WINDOW_NEED_SAMPLES"
+                elif len(events[s]) >= max_events:
+                    open_[s], closed[s] = False, "EVENTS_FULL"
+    return events, state, closed, counters
+
+
 # ---- the same loop in one call (ria_gpu_rx_stream_batch)
 STREAM_COUNTERS = ("streams", "events", "delivered") + tuple(f"closed_{k.lower()}" for k in capi.STREAM_CLOSED) + \
     ("search_legs",) + SEARCH_COUNTERS[len(capi.SEARCH_OUTCOME):]

@@ -48,8 +48,13 @@ SEARCH_CONNECTED = 0x1
 SEARCH_MIN_SEARCH = {0: 67304, 1: 31120, 2: 120000}
 SEARCH_MAX_CAPTURE = 959999
 SEARCH_NO_LAST_SYNC = -2 ** 31
+# ria_gpu_search_ring_batch: the ring buffer's length and the longest capture
+RING_SAMPLES = 960000
+RING_MAX_CAPTURE = 2 ** 31 - 1 - RING_SAMPLES
 # RIA_STREAM_*: why a stream of ria_gpu_rx_stream_batch closed (2 and 3 are the search's outcomes)
 STREAM_CLOSED = {"SEARCH_NEED_SAMPLES": 2, "SEARCH_LIMIT": 3, "WINDOW_NEED_SAMPLES": 4, "EVENTS_FULL": 5, "RING_END": 6}
+# why a stream of ria_gpu_rx_ring_batch closed: no RING_END, and RIA_STREAM_SPAN_LOST
+RING_STREAM_CLOSED = {"SEARCH_NEED_SAMPLES": 2, "SEARCH_LIMIT": 3, "WINDOW_NEED_SAMPLES": 4, "EVENTS_FULL": 5, "SPAN_LOST": 7}
 
 # every symbol include/ria_gpu.h declares
 EXPORTS = [
@@ -67,8 +72,8 @@ EXPORTS = [
     "ria_gpu_mcdpsk_decode_frame_ci_batch", "ria_gpu_mcdpsk_acquire_ci_batch", "ria_gpu_mcdpsk_interleave_batch",
     "ria_gpu_var_frame_samples", "ria_gpu_control_frame_samples", "ria_gpu_tx_coded_var_batch", "ria_gpu_demod_var_batch", "ria_gpu_demod_var_host",
     "ria_gpu_rx_control_batch", "ria_gpu_control_acquire_batch", "ria_gpu_rx_window_batch",
-    "ria_gpu_mcdpsk_window_batch", "ria_gpu_mcdpsk_window_host", "ria_gpu_search_batch",
-    "ria_gpu_rx_stream_batch", "ria_gpu_rx_stream_host",
+    "ria_gpu_mcdpsk_window_batch", "ria_gpu_mcdpsk_window_host", "ria_gpu_search_batch", "ria_gpu_search_ring_batch",
+    "ria_gpu_rx_stream_batch", "ria_gpu_rx_stream_host", "ria_gpu_rx_ring_batch", "ria_gpu_rx_ring_host",
     "ria_link_recommend", "ria_link_data_mode", "ria_link_ofdm_code_rate", "ria_link_cap_initial_rate",
 ]
 
@@ -209,6 +214,17 @@ class SearchResult(C.Structure):
                                           "replays", "catchups_moderate", "catchups_severe", "reserved0", "reserved1", "reserved2")]
 
 
+class RingState(C.Structure):
+    _fields_ = [("total_fed", C.c_int64), ("correlation_pos", C.c_int32), ("reject_streak", C.c_int32), ("noise_floor", C.c_float),
+                ("last_cfo_hz", C.c_float), ("fading_hint", C.c_float), ("snr_hint", C.c_float), ("last_decoded_sync_pos", C.c_int32),
+                ("overflow_events", C.c_uint32), ("overflow_dropped", C.c_uint64)]
+
+
+class RingSearchResult(C.Structure):
+    _fields_ = SearchResult._fields_ + [("abs_search_start", C.c_int64), ("overflow_dropped", C.c_uint64)] + \
+               [(n, C.c_uint32) for n in ("overflows", "drift_snaps", "cursor_inits", "span_wraps")]
+
+
 class StreamEvent(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("sync_position", "search_start", "window_len", "outcome", "next_pos", "frame_bytes", "need_samples",
                                           "pending_total_cw")] + \
@@ -220,6 +236,11 @@ class StreamResult(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_events", "closed", "mode", "search_legs")] + \
                [(n, C.c_uint32) for n in ("invocations", "waits", "rms_skips", "detector_runs", "rejects", "near_misses", "weak_accepts", "replays",
                                           "catchups_moderate", "catchups_severe")] + [("reserved", C.c_uint32 * 2)]
+
+
+class RingStreamResult(C.Structure):
+    _fields_ = StreamResult._fields_ + [("overflow_dropped", C.c_uint64)] + \
+               [(n, C.c_uint32) for n in ("overflows", "drift_snaps", "cursor_inits", "reserved1")]
 
 
 def macq_frame_bytes(frame_cw):
@@ -326,8 +347,11 @@ def load(build_if_needed=True):
     L.ria_gpu_mcdpsk_window_batch.argtypes = [vp, vp, vp, C.c_int64, i32, i32, i32, vp, u32, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp]
     L.ria_gpu_mcdpsk_window_host.argtypes = [vp, vp, vp, i32, i32, vp, u32, vp, i32, vp, vp, i32]
     L.ria_gpu_search_batch.argtypes = [vp, i32, u32, vp, vp, C.c_int64, vp, i32, vp, i32, i32, vp, vp]
+    L.ria_gpu_search_ring_batch.argtypes = [vp, i32, u32, vp, vp, C.c_int64, vp, i32, vp, i32, i32, vp, vp]
     L.ria_gpu_rx_stream_batch.argtypes = [vp, vp, i32, u32, vp, vp, C.c_int64, vp, i32, vp, i32, i32, i32, vp, vp, i32, vp, vp]
     L.ria_gpu_rx_stream_host.argtypes = [vp, vp, i32, u32, vp, vp, i32, vp, i32, i32, i32, vp, vp, i32, vp]
+    L.ria_gpu_rx_ring_batch.argtypes = [vp, vp, i32, u32, vp, vp, C.c_int64, vp, i32, vp, i32, i32, i32, vp, vp, i32, vp, vp]
+    L.ria_gpu_rx_ring_host.argtypes = [vp, vp, i32, u32, vp, vp, i32, vp, i32, i32, i32, vp, vp, i32, vp]
     L.ria_link_recommend.argtypes = [f32, f32, C.POINTER(LinkRecommendation)]
     L.ria_link_recommend.restype = None
     L.ria_link_data_mode.argtypes = [f32, i32, f32, C.POINTER(LinkRecommendation)]

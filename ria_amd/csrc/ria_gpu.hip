@@ -45,6 +45,7 @@
 #include "control_kernels.hip.h"
 #include "window_kernels.hip.h"
 #include "mcdpsk_window_kernels.hip.h"
+#include "ring_kernels.hip.h"
 #include "search_kernels.hip.h"
 #include "stream_kernels.hip.h"
 
@@ -140,6 +141,7 @@ struct ria_gpu {
     // ria_gpu_search_batch (search_carve): the due list, one chunk's gathered spans, detector records and per-span parameters,
     // and the control word with its pinned mirror
     DevBuf d_search_ws; PinBuf p_search_ctl;
+    DevBuf d_ring_rec;                    // ria_gpu_rx_ring_host: the recording on the device
     int search_chunk = 0;                 // RIA_OPT_SEARCH_CHUNK (0 = as many streams as 256 MiB of spans hold)
     // ria_gpu_rx_stream_batch (stream_carve): the control word with the found list behind it and their pinned mirror, the
     // open and group lists, the search's result records, and one chunk's windows, parameters and window-call outputs
@@ -2620,6 +2622,53 @@ static int search_class(int mode, int modulation) {
     return kSrchDifferential;
 }
 
+// every block of a ring search call, before anything of it is in flight: the call's own workspace and the detector's
+// (search_impl's steps; that function stays as it is).
+// *chunk_out: the streams whose spans one chunk of the due list holds.
+static int search_reserve(ria_gpu_handle h, int mode, int n_streams, int min_search, hipStream_t s, int* chunk_out) {
+    const size_t per = static_cast<size_t>(min_search) * sizeof(float);
+    int chunk = static_cast<int>(std::min<size_t>(static_cast<size_t>(n_streams), std::max<size_t>(1, (size_t(256) << 20) / per)));
+    chunk = std::min(chunk, 65535);                    // the gather's grid y extent
+    if (h->search_chunk > 0) chunk = std::min(chunk, h->search_chunk);
+    auto carve = [&](Carver& c) { return search_carve(c, static_cast<size_t>(n_streams), static_cast<size_t>(chunk), static_cast<size_t>(min_search)); };
+    HIP_TRY(h, h->d_search_ws.reserve(carved_size(carve), &s));
+    HIP_TRY(h, h->p_search_ctl.reserve(sizeof(SearchCtl)));
+    if (mode == RIA_SEARCH_OFDM_LTS) {
+        if (int rc = lts_prepare(h)) return rc;
+    } else if (mode == RIA_SEARCH_MCDPSK_ZC) {
+        const size_t zper = static_cast<size_t>(min_search) * sizeof(float2);
+        HIP_TRY(h, h->d_zc_ws.reserve(zper * std::min<size_t>(static_cast<size_t>(chunk), std::max<size_t>(1, (size_t(256) << 20) / zper)), &s));
+    } else {
+        if (int rc = chirp_prepare(h, std::min(chunk, 64), std::min(chunk, 2048), s)) return rc;
+    }
+    *chunk_out = chunk;
+    return RIA_OK;
+}
+
+// the mode's detector on the nb gathered spans of W through its own launcher; the one record pointer of the mode is set
+static int search_detect(ria_gpu_handle h, int mode, const SearchWs& W, int min_search, int nb, hipStream_t s, const ria_lts_result** lts,
+                         const ria_zc_result** zc, const ria_chirp_result** chirp) {
+    const int pstride = static_cast<int>(sizeof(SearchPar) / sizeof(float));
+    if (mode == RIA_SEARCH_OFDM_LTS) {
+        ria_lts_result* det = reinterpret_cast<ria_lts_result*>(W.det);
+        LtsArgs S{};
+        S.samples = W.span; S.stride = min_search; S.buf_len = min_search; S.n_buffers = nb;
+        S.known_cfo = &W.par->known_cfo_hz; S.threshold_dev = &W.par->detect_threshold; S.param_stride = pstride;
+        S.hilbert = h->d_hilbert65.as<const float>(); S.out = det;
+        hipLaunchKernelGGL(lts_sync_kernel, dim3(nb), dim3(kLtsThreads), lts_lds_bytes(), s, S);
+        *lts = det;
+    } else if (mode == RIA_SEARCH_MCDPSK_ZC) {
+        *zc = W.det;
+        if (int rc = sync_zc_impl(h, W.span, min_search, min_search, nb, 0.2f, 12u /* DATA | CONTROL */, &W.par->known_cfo_hz, W.det, s,
+                                  &W.par->detect_threshold, pstride)) return rc;
+    } else {
+        ria_chirp_result* det = reinterpret_cast<ria_chirp_result*>(W.det);
+        *chirp = det;
+        if (int rc = sync_chirp_impl(h, W.span, min_search, min_search, nb, 0.15f, det, s, nullptr, 1)) return rc;
+    }
+    return RIA_OK;
+}
+
 // The search on n_streams streams: all of them, or those subset_dev lists (ascending stream indices; captures, lengths,
 // states and results stay indexed by stream, so nothing is copied).  ria_gpu_rx_stream_batch searches its open streams so.
 static int search_impl(ria_gpu_handle h, const char* who, int mode, uint32_t flags, const ria_mcdpsk_config* cfg, const float* samples_dev, int64_t stride,
@@ -2711,6 +2760,75 @@ int ria_gpu_search_batch(ria_gpu_handle h, int mode, uint32_t flags, const ria_m
     if (!h) return RIA_ERR_INVALID;
     return search_impl(h, "ria_gpu_search_batch", mode, flags, cfg, samples_dev, stride, capture_len_dev, n_streams, nullptr, state_dev, feed_step,
                        max_invocations, result_dev, stream);
+}
+
+// ------------------------------------------------------------------------------------------------ the search past the ring buffer's wrap
+static_assert(sizeof(ria_ring_state) == 48 && offsetof(ria_ring_state, overflow_dropped) == 40 && sizeof(ria_ring_search_result) == 144 &&
+              offsetof(ria_ring_search_result, abs_position) == 16 && offsetof(ria_ring_search_result, invocations) == 60 &&
+              offsetof(ria_ring_search_result, abs_search_start) == 112 && offsetof(ria_ring_search_result, span_wraps) == 140,
+              "ria_gpu_search_ring_batch record layouts (include/ria_gpu.h)");
+
+// The ring search on n_streams streams: all of them, or those subset_dev lists (ascending; ria_gpu_rx_ring_batch's open streams)
+static int ring_search_impl(ria_gpu_handle h, const char* who, int mode, uint32_t flags, const ria_mcdpsk_config* cfg, const float* samples_dev, int64_t stride,
+                            const int32_t* capture_len_dev, int n_streams, const uint32_t* subset_dev, ria_ring_state* state_dev, int feed_step,
+                            int max_invocations, ria_ring_search_result* result_dev, void* stream) {
+    const bool mc = mode == RIA_SEARCH_MCDPSK_ZC || mode == RIA_SEARCH_MCDPSK_CHIRP;
+    if ((mode != RIA_SEARCH_OFDM_LTS && !mc) || (flags & ~RIA_SEARCH_CONNECTED) != 0 || n_streams < 0 || stride < 0 || feed_step < 0 ||
+        max_invocations < 1 || (mc && !mcdpsk_config_ok(cfg)))
+        return fail(h, RIA_ERR_INVALID, "%s: bad argument (mode RIA_SEARCH_*, flags RIA_SEARCH_CONNECTED only, n_streams >= 0, stride >= 0, feed_step >= 0, "
+                                        "max_invocations >= 1, an MC-DPSK config for the MC-DPSK modes)", who);
+    if (n_streams == 0) return RIA_OK;
+    if (!samples_dev || !capture_len_dev || !state_dev || !result_dev) return fail(h, RIA_ERR_INVALID, "%s: null pointer", who);
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int min_search = srch_min_search(mode);
+    int chunk;
+    if (int rc = search_reserve(h, mode, n_streams, min_search, s, &chunk)) return rc;
+    auto carve = [&](Carver& c) { return search_carve(c, static_cast<size_t>(n_streams), static_cast<size_t>(chunk), static_cast<size_t>(min_search)); };
+    const SearchWs W = carve_at(h->d_search_ws.as<>(), carve);
+    HIP_TRY(h, hipMemsetAsync(W.ctl, 0, sizeof(SearchCtl), s));
+    RingArgs A{};
+    A.samples = samples_dev; A.stride = stride; A.capture_len = capture_len_dev; A.state = state_dev; A.res = result_dev;
+    A.subset = subset_dev;
+    A.n_streams = n_streams; A.mode = mode; A.cls = search_class(mode, h->cfg.modulation);
+    A.connected = (mode != RIA_SEARCH_MCDPSK_CHIRP || (flags & RIA_SEARCH_CONNECTED)) ? 1 : 0;
+    A.feed_step = feed_step; A.max_invocations = max_invocations; A.min_search = min_search;
+    A.ctl = W.ctl; A.list = W.list; A.span = W.span; A.par = W.par;
+    const unsigned wgrid = static_cast<unsigned>((n_streams + kSearchWalkWaves - 1) / kSearchWalkWaves);
+    hipLaunchKernelGGL(ring_check_kernel, dim3(static_cast<unsigned>((n_streams + 255) / 256)), dim3(256), 0, s, A);
+    for (int round = 0;; ++round) {
+        if (round > max_invocations) return fail(h, RIA_ERR_HIP, "%s: round %d past max_invocations", who, round);
+        hipLaunchKernelGGL(ring_walk_kernel, dim3(wgrid), dim3(64 * kSearchWalkWaves), 0, s, A, round == 0 ? 1 : 0);
+        hipLaunchKernelGGL(ring_list_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A);
+        HIP_TRY(h, hipGetLastError());
+        if (int rc = read_ctl(h, h->p_search_ctl, W.ctl, s)) return rc;
+        const SearchCtl ctl = *h->p_search_ctl.as<SearchCtl>();
+        if (ctl.bad)
+            return fail(h, RIA_ERR_INVALID, "%s: a stream's capture_len is above min(stride, 2^31 - 1 - 960000), or its state is outside the call's domain "
+                                            "(0 <= total_fed <= capture_len, 0 <= correlation_pos < 960000, reject_streak >= 0, last_decoded_sync_pos in "
+                                            "0..959999 or INT32_MIN); no state or result was written", who);
+        const int n_list = static_cast<int>(ctl.n_list);
+        if (n_list < 0 || n_list > n_streams) return fail(h, RIA_ERR_HIP, "%s: the due list broke its bound (%d)", who, n_list);
+        if (n_list == 0) break;
+        for (int first = 0; first < n_list; first += chunk) {
+            const int nb = std::min(chunk, n_list - first);
+            A.first = first; A.n_chunk = nb; A.lts = nullptr; A.zc = nullptr; A.chirp = nullptr;
+            hipLaunchKernelGGL(ring_gather_kernel, dim3(static_cast<unsigned>(std::min((min_search + 1023) / 1024, 64)), static_cast<unsigned>(nb)), dim3(256), 0, s, A);
+            HIP_TRY(h, hipGetLastError());
+            if (int rc = search_detect(h, mode, W, min_search, nb, s, &A.lts, &A.zc, &A.chirp)) return rc;
+            hipLaunchKernelGGL(ring_accept_kernel, dim3(static_cast<unsigned>((nb + 255) / 256)), dim3(256), 0, s, A);
+            HIP_TRY(h, hipGetLastError());
+        }
+    }
+    return RIA_OK;
+}
+
+int ria_gpu_search_ring_batch(ria_gpu_handle h, int mode, uint32_t flags, const ria_mcdpsk_config* cfg, const float* samples_dev, int64_t stride,
+                              const int32_t* capture_len_dev, int n_streams, ria_ring_state* state_dev, int feed_step, int max_invocations,
+                              ria_ring_search_result* result_dev, void* stream) {
+    if (!h) return RIA_ERR_INVALID;
+    return ring_search_impl(h, "ria_gpu_search_ring_batch", mode, flags, cfg, samples_dev, stride, capture_len_dev, n_streams, nullptr, state_dev, feed_step,
+                            max_invocations, result_dev, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ the chase pool
@@ -3447,6 +3565,191 @@ int ria_gpu_rx_stream_host(ria_gpu_handle h, ria_gpu_handle control_h, int mode,
                                          max_events, d.ev, d.frames, frame_row, d.res, s);
         if (rc != RIA_OK) return rc;
         if (hipMemcpyAsync(d.st, d.st_in, sizeof(ria_search_state), hipMemcpyDeviceToDevice, s) != hipSuccess)
+            return fail(h, RIA_ERR_HIP, "%s: the state's copy failed", who);
+        return static_cast<int>(RIA_OK); });
+}
+
+// ------------------------------------------------------------------------------------------------ the stream loop on the ring
+static_assert(sizeof(ria_ring_stream_result) == 88 && offsetof(ria_ring_stream_result, invocations) == 16 &&
+              offsetof(ria_ring_stream_result, overflow_dropped) == 64 && offsetof(ria_ring_stream_result, cursor_inits) == 80 &&
+              RIA_STREAM_SPAN_LOST == kStreamSpanLost, "ria_gpu_rx_ring_batch record layout (include/ria_gpu.h)");
+struct RingStreamWs {
+    uint32_t* head;               // StreamCtl (4 words), found [n], found_len [n]: what the host reads per round, in one copy
+    uint32_t *open, *group;
+    ria_ring_search_result* sres;
+    float* win;
+    ria_acq_params* par;          // either parameter record
+    ria_window_result* wres;      // either window result
+    ria_mcdpsk_acq_result* acq;   // either acquire result
+    uint8_t* wframes;
+};
+static RingStreamWs ring_stream_carve(Carver& c, size_t n, size_t chunk, size_t win_stride, size_t wframe_row) {
+    RingStreamWs w;
+    w.head = c.take<uint32_t>(4 + 2 * n);
+    w.open = c.take<uint32_t>(n);
+    w.group = c.take<uint32_t>(n);
+    w.sres = c.take<ria_ring_search_result>(n);
+    w.win = c.take<float>(chunk * win_stride);
+    w.par = c.take<ria_acq_params>(chunk);
+    w.wres = c.take<ria_window_result>(chunk);
+    w.acq = c.take<ria_mcdpsk_acq_result>(chunk);
+    w.wframes = c.take<uint8_t>(chunk * wframe_row);
+    return w;
+}
+
+int ria_gpu_rx_ring_batch(ria_gpu_handle h, ria_gpu_handle control_h, int mode, uint32_t flags, const ria_mcdpsk_config* cfg,
+                          const float* samples_dev, int64_t stride, const int32_t* capture_len_dev, int n_streams,
+                          ria_ring_state* state_dev, int feed_step, int max_invocations, int max_events,
+                          ria_stream_event* events_dev, uint8_t* frames_dev, int frame_row, ria_ring_stream_result* result_dev, void* stream) {
+    const char* who = "ria_gpu_rx_ring_batch";
+    if (!h) return RIA_ERR_INVALID;
+    int full = 0, first_frame = 0, min_row = 0;
+    if (int rc = stream_setup(h, control_h, who, mode, flags, cfg, max_events, frame_row, &full, &first_frame, &min_row)) return rc;
+    if (full > kSrchRing - 1) return fail(h, RIA_ERR_INVALID, "%s: the window of this configuration (%d samples) is longer than 959999", who, full);
+    if (n_streams < 0 || stride < 0 || feed_step < 0 || max_invocations < 1)
+        return fail(h, RIA_ERR_INVALID, "%s: bad argument (n_streams >= 0, stride >= 0, feed_step >= 0, max_invocations >= 1)", who);
+    if (n_streams == 0) return RIA_OK;
+    if (!samples_dev || !capture_len_dev || !state_dev || !events_dev || !frames_dev || !result_dev) return fail(h, RIA_ERR_INVALID, "%s: null pointer", who);
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool ofdm = mode == RIA_SEARCH_OFDM_LTS;
+    const size_t n = static_cast<size_t>(n_streams);
+    const int search_len = srch_min_search(mode);
+    const long long win_stride = (static_cast<long long>(full) + 3) & ~3LL;          // rows of the window workspace start on 16 bytes
+    int chunk = static_cast<int>(std::min<size_t>(n, std::max<size_t>(1, (size_t(256) << 20) / (static_cast<size_t>(win_stride) * sizeof(float)))));
+    chunk = std::min(chunk, 65535);                    // the gather's grid y extent
+    auto carve = [&](Carver& c) { return ring_stream_carve(c, n, static_cast<size_t>(chunk), static_cast<size_t>(win_stride), static_cast<size_t>(min_row)); };
+    const size_t head_bytes = (4 + 2 * n) * sizeof(uint32_t);
+    HIP_TRY(h, h->d_stream_ws.reserve(carved_size(carve), &s));
+    HIP_TRY(h, h->p_stream_ctl.reserve(head_bytes));
+    const RingStreamWs W = carve_at(h->d_stream_ws.as<>(), carve);
+    uint32_t* mirror = h->p_stream_ctl.as<uint32_t>();
+
+    RingStreamArgs A{};
+    A.samples = samples_dev; A.stride = stride; A.capture_len = capture_len_dev; A.state = state_dev; A.sres = W.sres;
+    A.res = result_dev; A.events = events_dev; A.frames = frames_dev; A.frame_row = frame_row;
+    A.n_streams = n_streams; A.mode = mode; A.family = ofdm ? kStreamOfdm : kStreamMcdpsk; A.full = full; A.first_frame = first_frame;
+    A.max_events = max_events;
+    A.ctl = reinterpret_cast<StreamCtl*>(W.head); A.found = W.head + 4; A.found_len = reinterpret_cast<int32_t*>(W.head + 4 + n);
+    A.open = nullptr; A.group = W.group; A.n_open = n_streams;
+    A.win = W.win; A.win_stride = win_stride; A.wframes = W.wframes; A.wframe_row = min_row;
+    if (ofdm) { A.par = W.par; A.wres = W.wres; }
+    else { A.mpar = reinterpret_cast<ria_mcdpsk_acq_params*>(W.par); A.mres = reinterpret_cast<const ria_mcdpsk_window_result*>(W.wres); A.macq = W.acq; }
+    const uint32_t mflags = mode == RIA_SEARCH_MCDPSK_CHIRP ? (RIA_MACQ_SYNC_CHIRP | ((flags & RIA_SEARCH_CONNECTED) ? 0u : RIA_MACQ_DISCONNECTED)) : 0u;
+    const unsigned sgrid = static_cast<unsigned>((n_streams + 255) / 256);
+    bool window_ran = false;
+
+    for (int round = 0;; ++round) {
+        if (round > max_events) return fail(h, RIA_ERR_HIP, "%s: round %d past max_events + 1", who, round + 1);
+        // 1. the ring search on the open streams: in the first round all of them, and nothing of this call is written before
+        //    its domain check has passed
+        if (int rc = ring_search_impl(h, who, mode, flags, cfg, samples_dev, stride, capture_len_dev, A.n_open, A.open, state_dev, feed_step,
+                                      max_invocations, W.sres, s)) return rc;
+        if (round == 0) {
+            HIP_TRY(h, hipMemsetAsync(events_dev, 0, n * static_cast<size_t>(max_events) * sizeof(ria_stream_event), s));
+            HIP_TRY(h, hipMemsetAsync(frames_dev, 0, n * static_cast<size_t>(max_events) * static_cast<size_t>(frame_row), s));
+            hipLaunchKernelGGL(ring_stream_init_kernel, dim3(sgrid), dim3(256), 0, s, A);
+        }
+        // 2. the found streams and their window lengths
+        hipLaunchKernelGGL(ring_stream_list_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A, kStreamListFound);
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(mirror, W.head, head_bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        const int n_found = static_cast<int>(mirror[1]);
+        if (n_found < 0 || n_found > A.n_open) return fail(h, RIA_ERR_HIP, "%s: the found list broke its bound (%d)", who, n_found);
+        if (n_found == 0) break;
+        A.n_found = n_found;
+        std::vector<int> lens(mirror + 4 + n, mirror + 4 + n + n_found);
+        std::sort(lens.begin(), lens.end());
+        // 3.-6. one pass per distinct window length, ascending
+        for (size_t at = 0; at < lens.size();) {
+            const int wl = lens[at];
+            size_t end = at;
+            while (end < lens.size() && lens[end] == wl) ++end;
+            const int n_group = static_cast<int>(end - at);
+            at = end;
+            if (wl < search_len || wl > full) return fail(h, RIA_ERR_HIP, "%s: a window of %d samples, outside %d..%d", who, wl, search_len, full);
+            A.window_len = wl;
+            hipLaunchKernelGGL(ring_stream_list_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A, kStreamListGroup);
+            for (int first = 0; first < n_group; first += chunk) {
+                const int nb = std::min(chunk, n_group - first);
+                A.first = first; A.n_chunk = nb;
+                const unsigned tgrid = static_cast<unsigned>((nb + 255) / 256);
+                hipLaunchKernelGGL(ring_stream_gather_kernel, dim3(static_cast<unsigned>(std::min((wl + 1023) / 1024, 64)), static_cast<unsigned>(nb)), dim3(256), 0, s, A);
+                hipLaunchKernelGGL(ring_stream_params_kernel, dim3(tgrid), dim3(256), 0, s, A);
+                HIP_TRY(h, hipGetLastError());
+                // a window call may grow its workspaces: the first of the call finds the stream drained by the read above
+                if (window_ran) HIP_TRY(h, hipStreamSynchronize(s));
+                window_ran = true;
+                int rc;
+                if (ofdm)
+                    rc = ria_gpu_rx_window_batch(control_h, h, W.win, win_stride, search_len, wl, nb, W.par, RIA_DECODE_FULL, W.wframes, min_row, W.wres,
+                                                 reinterpret_cast<ria_acq_result*>(W.acq), nullptr, nullptr, s);
+                else
+                    rc = ria_gpu_mcdpsk_window_batch(h, cfg, W.win, win_stride, search_len, wl, nb, reinterpret_cast<const ria_mcdpsk_acq_params*>(W.par), mflags,
+                                                     W.wframes, min_row, reinterpret_cast<ria_mcdpsk_window_result*>(W.wres), W.acq, nullptr, 0, nullptr,
+                                                     nullptr, nullptr, nullptr, 0, s);
+                if (rc != RIA_OK) return rc;
+                hipLaunchKernelGGL(ring_stream_apply_kernel, dim3(tgrid), dim3(256), 0, s, A);
+                HIP_TRY(h, hipGetLastError());
+            }
+        }
+        // 7. the streams still open
+        A.open = W.open;
+        hipLaunchKernelGGL(ring_stream_list_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A, kStreamListOpen);
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(mirror, W.head, sizeof(StreamCtl), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        const int n_open = static_cast<int>(mirror[0]);
+        if (n_open < 0 || n_open > A.n_open) return fail(h, RIA_ERR_HIP, "%s: the open list broke its bound (%d)", who, n_open);
+        if (n_open == 0) break;
+        A.n_open = n_open;
+    }
+    return RIA_OK;
+}
+
+// One recording of any length in the domain from host memory.  It goes up in pieces through the handle's pinned block into
+// a device buffer the handle owns, grown before anything is in flight; the small records are staged like
+// ria_gpu_rx_stream_host's.
+int ria_gpu_rx_ring_host(ria_gpu_handle h, ria_gpu_handle control_h, int mode, uint32_t flags, const ria_mcdpsk_config* cfg,
+                         const float* samples_host, int n_samples, ria_ring_state* state_host, int feed_step, int max_invocations,
+                         int max_events, ria_stream_event* events_out_host, uint8_t* frames_out_host, int frame_row,
+                         ria_ring_stream_result* result_out_host) {
+    const char* who = "ria_gpu_rx_ring_host";
+    if (!h) return RIA_ERR_INVALID;
+    int full = 0, first_frame = 0, min_row = 0;
+    if (int rc = stream_setup(h, control_h, who, mode, flags, cfg, max_events, frame_row, &full, &first_frame, &min_row)) return rc;
+    if (full > kSrchRing - 1) return fail(h, RIA_ERR_INVALID, "%s: the window of this configuration (%d samples) is longer than 959999", who, full);
+    if (n_samples < 0 || n_samples > kRingMaxCapture || feed_step < 0 || max_invocations < 1)
+        return fail(h, RIA_ERR_INVALID, "%s: bad argument (0 <= n_samples <= 2^31 - 1 - 960000, feed_step >= 0, max_invocations >= 1)", who);
+    if (!samples_host || !state_host || !events_out_host || !frames_out_host || !result_out_host) return fail(h, RIA_ERR_INVALID, "%s: null pointer", who);
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t piece = size_t(1) << 18;                            // samples per piece: 1 MiB of the pinned block
+    if (int rc = ensure_host_stage(h, piece * sizeof(float))) return rc;
+    hipStream_t hs = h->hstream;
+    HIP_TRY(h, h->d_ring_rec.reserve(static_cast<size_t>(std::max(n_samples, 1)) * sizeof(float), &hs));
+    float* rec = h->d_ring_rec.as<float>();
+    for (size_t at = 0; at < static_cast<size_t>(n_samples); at += piece) {
+        const size_t cnt = std::min(piece, static_cast<size_t>(n_samples) - at);
+        std::memcpy(h->p_hstage.as<unsigned char>(), samples_host + at, cnt * sizeof(float));
+        HIP_TRY(h, hipMemcpyAsync(rec + at, h->p_hstage.as<unsigned char>(), cnt * sizeof(float), hipMemcpyHostToDevice, hs));
+        HIP_TRY(h, hipStreamSynchronize(hs));                        // the pinned block is free for the next piece
+    }
+    const int32_t cap = n_samples;
+    const size_t ne = static_cast<size_t>(max_events);
+    struct Stage { int32_t* cap; ria_ring_state* st_in; ria_ring_state* st; ria_stream_event* ev; uint8_t* frames; ria_ring_stream_result* res; };
+    auto carve = [&](StageCarver& c) {
+        Stage w;
+        w.cap = c.in(1, &cap); w.st_in = c.in(1, const_cast<const ria_ring_state*>(state_host));
+        w.st = c.out(1, state_host); w.ev = c.out(ne, events_out_host); w.frames = c.out(ne * static_cast<size_t>(frame_row), frames_out_host);
+        w.res = c.out(1, result_out_host);
+        return w;
+    };
+    return host_staged(h, carve, [&](const Stage& d, hipStream_t s) {
+        int rc = ria_gpu_rx_ring_batch(h, control_h, mode, flags, cfg, rec, std::max(n_samples, 1), d.cap, 1, d.st_in, feed_step, max_invocations,
+                                       max_events, d.ev, d.frames, frame_row, d.res, s);
+        if (rc != RIA_OK) return rc;
+        if (hipMemcpyAsync(d.st, d.st_in, sizeof(ria_ring_state), hipMemcpyDeviceToDevice, s) != hipSuccess)
             return fail(h, RIA_ERR_HIP, "%s: the state's copy failed", who);
         return static_cast<int>(RIA_OK); });
 }

@@ -802,6 +802,45 @@ class RxEngine:
                                                   _ptr(st_d), int(feed_step), int(max_invocations), _ptr(res_d), _stream_ptr()))
         return self._status_array(res_d, self.SEARCH_RESULT), self._status_array(st_d, self.SEARCH_STATE)
 
+    RING_STATE = np.dtype([("total_fed", "<i8"), ("correlation_pos", "<i4"), ("reject_streak", "<i4"), ("noise_floor", "<f4"),
+                           ("last_cfo_hz", "<f4"), ("fading_hint", "<f4"), ("snr_hint", "<f4"), ("last_decoded_sync_pos", "<i4"),
+                           ("overflow_events", "<u4"), ("overflow_dropped", "<u8")])
+    RING_SEARCH_RESULT = np.dtype(SEARCH_RESULT.descr + [("abs_search_start", "<i8"), ("overflow_dropped", "<u8"), ("overflows", "<u4"),
+                                                         ("drift_snaps", "<u4"), ("cursor_inits", "<u4"), ("span_wraps", "<u4")])
+
+    @classmethod
+    def ring_state(cls, n, total_fed=0):
+        """n fresh decoder states (RING_STATE): cursor 0, `total_fed` samples arrived, noise floor 0.001, no decoded position"""
+        s = np.zeros(n, cls.RING_STATE)
+        s["total_fed"] = total_fed
+        s["noise_floor"] = np.float32(0.001)
+        s["last_decoded_sync_pos"] = capi.SEARCH_NO_LAST_SYNC
+        return s
+
+    def search_ring(self, captures, capture_len, state, mode, feed_step=0, max_invocations=1 << 20, connected=False,
+                    carriers=10, modulation="DBPSK", spreading=1):
+        """search() for captures of any length up to 2^31 - 1 - 960 000 samples (ria_gpu_search_ring_batch): the decoder's
+        960 000-sample ring buffer wraps, with feedAudio's drift guard and overflow drop.  state: RING_STATE records
+        (ring_state()), whose cursor and last decoded position are ring indices.  Other arguments as search().  Returns
+        (result (RING_SEARCH_RESULT), state (RING_STATE))."""
+        n, stride = captures.shape
+        assert captures.dtype == torch.float32 and captures.is_contiguous()
+        m = capi.SEARCH_MODE[mode] if isinstance(mode, str) else int(mode)
+        lens = np.empty(n, np.int32)
+        lens[:] = capture_len
+        st = np.ascontiguousarray(state, self.RING_STATE)
+        assert st.shape == (n,)
+        lens_d = torch.from_numpy(lens).to(self.device)
+        st_d = torch.from_numpy(st.view(np.uint8).reshape(n, 48).copy()).to(self.device)
+        res_d = torch.empty((n, 144), dtype=torch.uint8, device=self.device)
+        cfg = None
+        if m != capi.SEARCH_MODE["OFDM_LTS"]:
+            bps = {"DBPSK": 1, "DQPSK": 2}[modulation] if isinstance(modulation, str) else int(modulation)
+            cfg = C.byref(capi.McdpskConfig(carriers, bps, spreading, 0))
+        self._check(self.lib.ria_gpu_search_ring_batch(self.h, m, capi.SEARCH_CONNECTED if connected else 0, cfg, _ptr(captures), stride, _ptr(lens_d), n,
+                                                       _ptr(st_d), int(feed_step), int(max_invocations), _ptr(res_d), _stream_ptr()))
+        return self._status_array(res_d, self.RING_SEARCH_RESULT), self._status_array(st_d, self.RING_STATE)
+
     STREAM_EVENT = np.dtype([("sync_position", "<i4"), ("search_start", "<i4"), ("window_len", "<i4"), ("outcome", "<i4"), ("next_pos", "<i4"),
                              ("frame_bytes", "<i4"), ("need_samples", "<i4"), ("pending_total_cw", "<i4"), ("delivered", "u1"), ("success", "u1"),
                              ("codewords_ok", "u1"), ("codewords_failed", "u1"), ("frame_type", "u1"), ("reserved0", "u1", 3),
@@ -875,6 +914,67 @@ class RxEngine:
                                                     capi.SEARCH_CONNECTED if connected else 0, cfg, x.ctypes.data, len(x), st.ctypes.data,
                                                     int(feed_step), int(max_invocations), ne, ev.ctypes.data, frames.ctypes.data, row,
                                                     res.ctypes.data))
+        return st, res, ev.reshape(1, ne), frames
+
+    RING_STREAM_RESULT = np.dtype(STREAM_RESULT.descr + [("overflow_dropped", "<u8"), ("overflows", "<u4"), ("drift_snaps", "<u4"),
+                                                         ("cursor_inits", "<u4"), ("reserved1", "<u4")])
+
+    def rx_ring(self, captures, capture_len, mode, control_engine=None, state=None, feed_step=4800, max_invocations=1 << 20, max_events=256,
+                connected=False, carriers=10, modulation="DBPSK", spreading=1):
+        """rx_stream for recordings of any length (ria_gpu_rx_ring_batch): the loop on search_ring, with windows cut from the
+        capture by absolute index.  state: RING_STATE records (default: fresh decoders, nothing arrived for feed_step > 0).
+        The events' sync_position, search_start and next_pos are capture (absolute) indices, so acquire.stream_events and
+        stream_tally work on them.  Returns (state (RING_STATE), results (RING_STREAM_RESULT), events (STREAM_EVENT
+        [n, max_events]), frames: uint8 [n, max_events, stream_frame_row(mode)] on the device)."""
+        n, stride = captures.shape
+        assert captures.dtype == torch.float32 and captures.is_contiguous()
+        m = capi.SEARCH_MODE[mode] if isinstance(mode, str) else int(mode)
+        lens = np.empty(n, np.int32)
+        lens[:] = capture_len
+        if state is None:
+            state = self.ring_state(n, total_fed=0 if feed_step else lens)
+        st = np.ascontiguousarray(state, self.RING_STATE)
+        assert st.shape == (n,)
+        row, ne = self.stream_frame_row(m), int(max_events)
+        lens_d = torch.from_numpy(lens).to(self.device)
+        st_d = torch.from_numpy(st.view(np.uint8).reshape(n, 48).copy()).to(self.device)
+        res_d = torch.full((n, 88), 0xAB, dtype=torch.uint8, device=self.device)
+        ev_d = torch.full((n * max(ne, 0), 64), 0xAB, dtype=torch.uint8, device=self.device)
+        frames = torch.full((n, max(ne, 0), row), 0xAB, dtype=torch.uint8, device=self.device)
+        cfg = None
+        if m != capi.SEARCH_MODE["OFDM_LTS"]:
+            bps = {"DBPSK": 1, "DQPSK": 2}[modulation] if isinstance(modulation, str) else int(modulation)
+            cfg = C.byref(capi.McdpskConfig(carriers, bps, spreading, 0))
+        self._check(self.lib.ria_gpu_rx_ring_batch(self.h, control_engine.h if control_engine is not None else None, m,
+                                                   capi.SEARCH_CONNECTED if connected else 0, cfg, _ptr(captures), stride, _ptr(lens_d), n,
+                                                   _ptr(st_d), int(feed_step), int(max_invocations), ne, _ptr(ev_d), _ptr(frames), row,
+                                                   _ptr(res_d), _stream_ptr()))
+        return (self._status_array(st_d, self.RING_STATE), self._status_array(res_d, self.RING_STREAM_RESULT),
+                self._status_array(ev_d, self.STREAM_EVENT).reshape(n, ne), frames)
+
+    def rx_ring_host(self, recording, mode, control_engine=None, state=None, feed_step=4800, max_invocations=1 << 20, max_events=256,
+                     connected=False, carriers=10, modulation="DBPSK", spreading=1):
+        """rx_ring for one recording in host memory (ria_gpu_rx_ring_host; a float32 numpy array of any length in the domain).
+        Returns (state, results, events, frames) as rx_ring does for n = 1, frames as a numpy array."""
+        x = np.ascontiguousarray(recording, np.float32)
+        assert x.ndim == 1
+        m = capi.SEARCH_MODE[mode] if isinstance(mode, str) else int(mode)
+        if state is None:
+            state = self.ring_state(1, total_fed=0 if feed_step else len(x))
+        st = np.ascontiguousarray(state, self.RING_STATE).copy()
+        assert st.shape == (1,)
+        row, ne = self.stream_frame_row(m), int(max_events)
+        ev = np.zeros(max(ne, 0), self.STREAM_EVENT)
+        frames = np.zeros((1, max(ne, 0), row), np.uint8)
+        res = np.zeros(1, self.RING_STREAM_RESULT)
+        cfg = None
+        if m != capi.SEARCH_MODE["OFDM_LTS"]:
+            bps = {"DBPSK": 1, "DQPSK": 2}[modulation] if isinstance(modulation, str) else int(modulation)
+            cfg = C.byref(capi.McdpskConfig(carriers, bps, spreading, 0))
+        self._check(self.lib.ria_gpu_rx_ring_host(self.h, control_engine.h if control_engine is not None else None, m,
+                                                  capi.SEARCH_CONNECTED if connected else 0, cfg, x.ctypes.data, len(x), st.ctypes.data,
+                                                  int(feed_step), int(max_invocations), ne, ev.ctypes.data, frames.ctypes.data, row,
+                                                  res.ctypes.data))
         return st, res, ev.reshape(1, ne), frames
 
     MCDFRAME_RESULT = np.dtype([("success", "u1"), ("codewords_ok", "u1"), ("codewords_failed", "u1"), ("frame_type", "u1"),
