@@ -425,7 +425,11 @@ int ria_gpu_mcdpsk_modulate_host(ria_gpu_handle h, const ria_mcdpsk_config* cfg,
 int ria_gpu_mcdpsk_modulate_batch(ria_gpu_handle h, const ria_mcdpsk_config* cfg, const uint8_t* data_dev, int n_bytes, int n_frames,
                                   float* out_dev, int64_t out_stride, void* stream);
 /* fec::ChaseCache::store arithmetic for n_cw codeword slots of 648 LLRs (chase_cache.cpp:27-88): count 0 ->
- * copy, else add; skipped when decoded_dev[cw] != 0 or count >= 4.  stored_out_dev (nullable) gets 1/0. */
+ * copy, else add; skipped when decoded_dev[cw] != 0 or count >= 4.  stored_out_dev (nullable) gets 1/0.
+ * decoded_dev is nullable (nothing decoded); n_cw 0 returns RIA_OK without reading a pointer.  The add is one float add per
+ * element on the raw values: NaN, infinities and denormals go in and come out as IEEE arithmetic gives them (inf + -inf
+ * = NaN, no flush to zero; a NaN's sign and payload are unspecified).  The call itself only produces counts 0 .. 4; handed
+ * another one it treats a count above 4 like 4 (skipped) and a negative count like 1 .. 3 (added, count + 1). */
 int ria_gpu_chase_combine_batch(ria_gpu_handle h, float* acc_dev, int32_t* count_dev, const uint8_t* decoded_dev,
                                 const float* soft_dev, int n_cw, uint8_t* stored_out_dev, void* stream);
 
@@ -806,6 +810,17 @@ int ria_gpu_mcdpsk_acquire_batch(ria_gpu_handle h, const ria_mcdpsk_config* cfg,
  * Eviction takes the smallest last_access as the reference does.  The reference's clock advances strictly, so it never sees
  * two entries with one last_access; here one now_ms may serve several stores, and entries are ordered by (last_access_ms,
  * the cache's store sequence number at the moment last_access was set): among equal times the one touched first goes.
+ * The difference now - last_access is taken modulo 2^64 before it is read as int64, so any uint64 is a valid now_ms: a
+ * difference of 2^63 or more counts as negative and expires nothing, and ttl_ms INT64_MAX never expires an entry.
+ * An entry keeps the total_cw and frame_type of the store that created it.  A later frame with the same key and another
+ * header is stored against those: a codeword index at or above the entry's total_cw is refused, its getCombined misses and
+ * its count is 0.  A store that the entry refuses (index, decoded, MAX_COMBINES) has already set last_access (and the
+ * order) and so keeps the entry alive; a store that fails the argument checks touches nothing.
+ * Sums are raw: store copies and adds the soft bits as they are, with one IEEE float add per element and no flush of
+ * denormals.  NaN, infinities, -0.0 and denormals are kept in the pool and returned by ria_gpu_chase_export bit for bit
+ * (inf + -inf = NaN, FLT_MAX + FLT_MAX = inf; a NaN's sign and payload are unspecified).  Only the decode of a gathered sum
+ * maps its input (NaN -> +1e30, clamp to +-1e30, -0.0 -> +0.0).  A slot whose entry went keeps stale floats; the first
+ * store of a codeword into a new entry copies, and the export is zero wherever has_sum is 0.
  * Memory: n_caches * max_entries * 16 * 648 * 4 bytes of sums (41 472 bytes per entry, 663 552 per cache at 16 entries)
  * plus 1 344 bytes of metadata and 4 bytes of owner word per cache, all allocated by ria_gpu_chase_create and owned by the
  * handle (ria_gpu_destroy frees the pools still alive; a pool must not be used after its handle is destroyed). */
@@ -839,9 +854,11 @@ void ria_gpu_chase_default_config(ria_chase_config* cfg);   /* 1 cache, 16 entri
 int  ria_gpu_chase_create(ria_gpu_handle h, const ria_chase_config* cfg, ria_chase_pool* out);
 void ria_gpu_chase_destroy(ria_chase_pool pool);
 /* ChaseCache::clear (what setMode does at streaming_decoder.cpp:2206) for the n caches listed in cache_ids_dev (device,
- * int32; ids out of range are skipped) or, with NULL, for every cache of the pool (n ignored).  Counters stay. */
+ * int32; ids out of range are skipped, an id may repeat) or, with NULL, for every cache of the pool (n ignored).  With a list,
+ * n 0 clears nothing and n < 0 is RIA_ERR_INVALID.  Counters stay.  The clear is ordered on `stream` like a decode call. */
 int  ria_gpu_chase_clear(ria_chase_pool pool, const int32_t* cache_ids_dev /* nullable = all */, int n, void* stream);
-/* getStats of one cache into host memory.  Synchronises the device. */
+/* getStats of one cache into host memory.  Synchronises the device.  A cache_id outside the pool (here and in the export) and
+ * a NULL out_host are RIA_ERR_INVALID. */
 int  ria_gpu_chase_stats(ria_chase_pool pool, int cache_id, ria_chase_stats* out_host);
 /* The live entries of one cache in slot order: returns their number (size(), >= 0) or a negative ria_status.
  * entries_out_host (nullable) takes max_entries records, sums_out_host (nullable) max_entries * 16 * 648 floats: entry e's
@@ -868,7 +885,8 @@ int  ria_gpu_chase_export(ria_chase_pool pool, int cache_id, ria_chase_entry* en
  * fires here; it is implemented all the same.
  * Two rows of one call with the same cache id >= 0 (or an id >= n_caches) are RIA_ERR_INVALID: they would need an order
  * between them.  This is found on the device (an owner word per cache, atomicCAS) and read with the call's first control
- * read, before any cache is touched.  Retransmissions of one link go into successive calls.
+ * read, before any cache is touched.  Retransmissions of one link go into successive calls.  A pool created on another
+ * handle is RIA_ERR_INVALID too.  Every negative id turns chase off for its row as -1 does, and negative ids may repeat.
  * The call synchronises its stream once for the codeword-row count and, with a pool and at least one such row, once more
  * for the length of the list of sums; stage 5 is skipped when that list is empty.  Every row of every output is written. */
 typedef struct ria_mcdpsk_dframe_result {   /* 16 bytes: the DecodeResult */

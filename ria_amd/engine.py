@@ -44,10 +44,12 @@ class ChasePool:
         self.p = None
 
     def clear(self, cache_ids=None):
-        """ChaseCache::clear for the listed caches (None: all); counters stay"""
+        """ChaseCache::clear for the listed caches (None: all; an empty list: none); counters stay"""
         ids = None
         if cache_ids is not None:
             ids = torch.as_tensor(np.ascontiguousarray(cache_ids, np.int32)).to(self.engine.device)
+            if ids.numel() == 0:           # an empty tensor has no address, and a NULL list would mean every cache
+                return
         self.engine._check(self.lib.ria_gpu_chase_clear(self.p, _ptr(ids), 0 if ids is None else ids.numel(), _stream_ptr()))
 
     def stats(self, cache_id):

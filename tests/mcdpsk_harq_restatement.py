@@ -1,10 +1,12 @@
 """CPU restatement of the HARQ calls (ria_gpu_mcdpsk_decode_frame_batch, ria_gpu_mcdpsk_acquire_harq_batch):
 
 - ChaseCache: fec::ChaseCache (src/fec/chase_cache.{hpp,cpp}) in plain Python, method for method.  Time is the caller's
-  (now_ms per call); expiry is now - last_access > ttl, signed; eviction takes the smallest (last_access, store sequence
-  number), which is the reference's "smallest last_access" made definite for equal times.
+  (now_ms per call, a uint64); expiry is (int64)(now - last_access) > ttl, the difference taken modulo 2^64 as
+  include/ria_gpu.h states it; eviction takes the smallest (last_access, store sequence number), which is the reference's
+  "smallest last_access" made definite for equal times.
 - decode_mcdpsk_frame: tests/mcdpsk_acquire_restatement.py's with the chase statements (streaming_decoder.cpp:2729-2731,
-  :2766-2789, :2796-2799, :2808-2811); with cache None it is that function.
+  :2766-2789, :2796-2799, :2808-2811); with cache None it is that function.  The soft bits handed to the robust decoder go
+  through canon() (the decoder's input mapping, tests/ldpc_domain_inputs.py); what the cache stores and sums is raw.
 - acquire_window: that file's with a cache that persists across calls; every candidate goes through the cache.
 
 Test infrastructure only (not collected: no test_ prefix)."""
@@ -15,6 +17,22 @@ from mcdpsk_acquire_restatement import CONNECT, CONNECT_ACK, CONNECT_NAK, CONTRO
 
 MAX_COMBINES, LDPC_BLOCK = 4, 648
 STATS = ("cache_hits", "cache_misses", "stores", "combines", "entries_evicted", "entries_expired", "recoveries")
+
+
+def age_ms(now, last_access):
+    """now - last_access modulo 2^64, read as int64 (chase_policy.hpp's chase_expired)"""
+    d = (int(now) - int(last_access)) & (2 ** 64 - 1)
+    return d - 2 ** 64 if d >= 2 ** 63 else d
+
+
+def canon(x):
+    """the decoder's input mapping (include/ria_gpu.h; tests/ldpc_domain_inputs.canon): NaN -> +1e30, clamp to +-1e30,
+    -0.0 -> +0.0"""
+    x = np.array(x, np.float32, copy=True)
+    x[np.isnan(x)] = np.float32(1e30)
+    x = np.clip(x, np.float32(-1e30), np.float32(1e30))
+    x[x == 0] = np.float32(0.0)
+    return x
 
 
 class Entry:
@@ -62,7 +80,8 @@ class ChaseCache:
             e.soft[cw] = np.array(soft, np.float32)
             e.count[cw] = 1
         else:
-            e.soft[cw] = (e.soft[cw] + np.asarray(soft, np.float32)).astype(np.float32)   # one float add per element
+            with np.errstate(all="ignore"):            # inf + -inf and overflow are part of the domain
+                e.soft[cw] = (e.soft[cw] + np.asarray(soft, np.float32)).astype(np.float32)   # one float add per element
             e.count[cw] += 1
             self.stats["combines"] += 1
         return True
@@ -110,7 +129,7 @@ class ChaseCache:
             self.stats["entries_evicted"] += 1
 
     def prune_expired(self, now):
-        for k in [k for k, e in self.cache.items() if now - e.last_access > self.ttl]:
+        for k in [k for k, e in self.cache.items() if age_ms(now, e.last_access) > self.ttl]:
             del self.cache[k]
             self.stats["entries_expired"] += 1
 
@@ -133,7 +152,7 @@ def decode_mcdpsk_frame(checker, llr, cache=None, now=0, wrong_order=False):
     llr = np.asarray(llr, np.float32)
     if len(llr) < 648:
         return r, None
-    ok0, d0, _, _ = checker.robust_decode(po.R1_4, llr[:648])
+    ok0, d0, _, _ = checker.robust_decode(po.R1_4, canon(llr[:648]))
     if not ok0 or len(d0) < 2 or d0[0] != 0x55 or d0[1] != 0x4C:
         return r, None
     d0 = np.asarray(d0[:20], np.uint8)
@@ -166,7 +185,7 @@ def decode_mcdpsk_frame(checker, llr, cache=None, now=0, wrong_order=False):
     deferred_marks = []
     for i in range(1, total):
         soft = llr[i * 648:(i + 1) * 648]
-        ok, d, _, _ = checker.robust_decode(po.R1_4, soft)
+        ok, d, _, _ = checker.robust_decode(po.R1_4, canon(soft))
         if not ok and cache is not None:
             if cache.store(key, i, soft, total, t, now):
                 hq["stored_mask"] |= 1 << i
@@ -175,7 +194,7 @@ def decode_mcdpsk_frame(checker, llr, cache=None, now=0, wrong_order=False):
             hq["max_combine"] = max(hq["max_combine"], count)
             if combined is not None and len(combined) == 648 and count > 1:
                 hq["sum_mask"] |= 1 << i
-                ok_c, d_c, _, _ = checker.robust_decode(po.R1_4, combined)
+                ok_c, d_c, _, _ = checker.robust_decode(po.R1_4, canon(combined))
                 if ok_c and len(d_c) >= 20:
                     ok, d = True, d_c
                     cache.mark_decoded(key, i)

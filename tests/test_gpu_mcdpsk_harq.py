@@ -11,14 +11,11 @@ import torch
 
 import pyoracle as po
 from mcdpsk_acquire_restatement import ACK, CONNECT, control_frame, data_frame, encode_frame, frame_len, oracle, window
-from mcdpsk_harq_restatement import STATS, ChaseCache, acquire_window, cache_snapshot, decode_mcdpsk_frame, empty_harq
-from ria_amd.acquire import HARQ_COUNTERS, harq_tally
+from mcdpsk_harq_domain_inputs import DEAD, GOOD, HARQ_FIELDS, RES_FIELDS, WEAK2, WEAK3, Links, row   # row() and Links live there
+from mcdpsk_harq_restatement import STATS, acquire_window, decode_mcdpsk_frame
+from ria_amd.acquire import harq_tally
 
 pytestmark = pytest.mark.gpu
-
-RES_FIELDS = ("success", "codewords_ok", "codewords_failed", "frame_type", "header_total_cw")
-HARQ_FIELDS = ("valid", "seq", "src_hash", "dst_hash", "stored_mask", "sum_mask", "recovered_mask", "max_combine", "entry")
-GOOD, WEAK2, WEAK3, DEAD = 2.0, 0.6, 0.42, 0.12   # codeword amplitudes at unit noise: decodes / sum of 2 decodes / of 3 / never
 
 
 @pytest.fixture(scope="module")
@@ -27,73 +24,6 @@ def eng():
     e = RxEngine("DQPSK", "R1_4", max_batch=64)
     yield e
     e.close()
-
-
-def row(seq, amps, seed, stride=3 * 648, frame=None):
-    """coded bits of a frame (default: the 3-codeword data frame of sequence number seq), codeword c scaled by amps[c], plus
-    seeded unit Gaussian noise; noise alone behind the frame"""
-    if frame is None:
-        frame = data_frame(0x30, seq, np.arange(25, dtype=np.uint8))
-    bits = np.unpackbits(encode_frame(frame)).astype(np.float64)
-    x = np.random.default_rng(seed).standard_normal(max(stride, len(bits)))
-    x[:len(bits)] += np.repeat(np.asarray(amps, np.float64)[:len(bits) // 648], 648) * (1.0 - 2.0 * bits)
-    return x[:stride].astype(np.float32)
-
-
-class Links:
-    """A pool on the device and the restatement's caches beside it; call() runs one batch through both and compares"""
-
-    def __init__(self, eng, n_caches, max_entries=16, ttl_ms=30000):
-        self.eng, self.pool = eng, eng.chase_pool(n_caches, max_entries, ttl_ms)
-        self.caches = [ChaseCache(max_entries, ttl_ms) for _ in range(n_caches)]
-        self.tally = np.zeros(len(HARQ_COUNTERS), np.int64)
-
-    def check_tally(self):
-        """ria_amd.acquire.harq_tally summed over the calls against the sum of the caches' counters"""
-        t = dict(zip(HARQ_COUNTERS, self.tally))
-        for k in ("stores", "combines", "recoveries"):
-            assert t[k] == sum(c.stats[k] for c in self.caches), (k, t)
-        return t
-
-    def call(self, rows, ids, now, n_llr=None):
-        rows = np.stack(rows)
-        n, stride = rows.shape
-        n_llr = [stride] * n if n_llr is None else n_llr
-        now = np.broadcast_to(np.asarray(now, np.uint64), (n,))
-        frames, res, hq = self.eng.mcdpsk_decode_frame(torch.from_numpy(rows).to(self.eng.device), n_llr=n_llr, chase=self.pool, cache_id=ids,
-                                                       now_ms=now)
-        frames = frames.cpu().numpy()
-        self.tally += harq_tally(res, hq)
-        out = []
-        for i in range(n):
-            r, h = decode_mcdpsk_frame(oracle(), rows[i, :max(0, min(n_llr[i], stride))], self.caches[ids[i]] if ids[i] >= 0 else None, int(now[i]))
-            h = h or empty_harq()
-            for f in RES_FIELDS:
-                assert int(res[f][i]) == int(r[f]), (i, f, res[f][i], r[f])
-            nb = len(r["frame"])
-            assert int(res["frame_bytes"][i]) == nb and np.array_equal(frames[i, :nb], r["frame"]) and not frames[i, nb:].any(), i
-            for f in HARQ_FIELDS:
-                assert int(hq[f][i]) == int(h[f]), (i, f, hq[f][i], h[f])
-            assert int(hq["cache_id"][i]) == (ids[i] if h["valid"] else 0), i
-            out.append((r, h))
-        self.compare_caches()
-        return out
-
-    def compare_caches(self):
-        for c, cache in enumerate(self.caches):
-            assert self.pool.stats(c) == cache.stats, (c, self.pool.stats(c), cache.stats)
-            ent, sums = self.pool.export(c)
-            want = cache_snapshot(cache)
-            assert sorted((int(e["seq"]), int(e["src_hash"]), int(e["dst_hash"])) for e in ent) == sorted(want), c
-            for e, s in zip(ent, sums):
-                w = want[(int(e["seq"]), int(e["src_hash"]), int(e["dst_hash"]))]
-                assert (int(e["total_cw"]), int(e["frame_type"]), int(e["last_access_ms"]), int(e["order"]), int(e["used"])) == \
-                       (w["total_cw"], w["frame_type"], w["last_access"], w["order"], 1), (c, e, w)
-                assert e["combine_count"].tolist() == w["count"] and e["decoded"].tolist() == w["decoded"] and e["has_sum"].tolist() == w["has_sum"], (c, e, w)
-                assert np.array_equal(s.view(np.uint32), w["sums"].view(np.uint32)), c
-
-    def close(self):
-        self.pool.close()
 
 
 def test_recoveries_the_trap_refused_stores_and_rows_without_a_cache(eng):

@@ -140,6 +140,15 @@ def scripts():
         else:
             ops.append(("dump",))
     S["random_walk"] = ops + [("dump",)]
+    # time: ttl 0 (the same now keeps, now + 1 expires), ttl INT64_MAX, now stepping 2^63 - 1 -> 2^63 -> 2^64 - 1 -> 0, and
+    # last_access 0 against now 2^63, where (int64)(now - last_access) and an unbounded subtraction disagree; the steps are
+    # those of tests/mcdpsk_harq_domain_inputs.py, which the GPU domain test runs through the kernels
+    from mcdpsk_harq_domain_inputs import time_script
+    for name, (max_entries, ttl, steps) in time_script().items():
+        ops = [("cfg", max_entries, ttl)]
+        for s, now in steps:
+            ops += [("store", K[s], 1, 3, 0x30, now, 1.0), ("dump",)]
+        S[name] = ops
     return S
 
 
@@ -220,6 +229,11 @@ def test_policy_header_matches_the_python_cache(policy_exe, tmp_path):
     t = python_transcript(S["max_combines"])
     assert [l for l in t if l.startswith("store")] == ["store 1"] * 4 + ["store 0"] * 2 and t.count("count 4") == 3
     assert t[10:12] == t[13:15] == t[16:18] and t[10].startswith("get 1") and "stats 6 0 6 3 0 0 0" in t
+    from mcdpsk_harq_domain_inputs import TIME_SIZES
+    for name, sizes in TIME_SIZES.items():
+        t = python_transcript(S[name])
+        assert [int(l.split()[1]) for l in t if l.startswith("size")] == sizes, name
+    assert [l.split()[6] for l in python_transcript(S["time_ttl0"]) if l.startswith("stats")] == ["0", "0", "2", "2", "2", "5"]   # entries_expired
 
 
 # ---- (d)
