@@ -1566,8 +1566,8 @@ int ria_gpu_search_ring_batch(ria_gpu_handle h, int mode, uint32_t flags, const 
  * before anything is written.
  *
  * Out of scope: burst groups and continuation (reported as events: RIA_WIN_BURST), chase pools and channel interleaving,
- * re-entry of an MC-DPSK NEED_SAMPLES window (the event carries need_samples and pending_total_cw for the caller), ring
- * wrap, the ZC-miss -> chirp fallback, OFDM-COX.
+ * re-entry of an MC-DPSK NEED_SAMPLES window (the event carries need_samples and pending_total_cw for the caller) - these
+ * three are ria_gpu_mcdpsk_stream_batch's, below -, ring wrap, the ZC-miss -> chirp fallback, OFDM-COX.
  *
  * Work: rounds of search -> found list -> (gather -> parameters -> window call -> apply, once per distinct window length in
  * ascending order, in chunks of at most 256 MiB of windows) -> open list.  A stream gains an event or closes in every round,
@@ -1622,6 +1622,92 @@ int ria_gpu_rx_stream_host(ria_gpu_handle h, ria_gpu_handle control_h, int mode,
                            const float* samples_host, int n_samples, ria_search_state* state_host /* in and out */,
                            int feed_step, int max_invocations, int max_events, ria_stream_event* events_out_host,
                            uint8_t* frames_out_host, int frame_row, ria_stream_result* result_out_host);
+
+/* ---- the MC-DPSK stream loop with a chase pool, channel interleaving and re-entry ---------------------------------------------
+ * ria_gpu_mcdpsk_stream_batch is ria_gpu_rx_stream_batch for the two MC-DPSK modes (RIA_SEARCH_OFDM_LTS is RIA_ERR_INVALID)
+ * with the three things that call leaves out; ria_gpu_mcdpsk_window_batch has them all, and every decode is that call's.  The
+ * loop, the events, the results, the RIA_STREAM_* close reasons, the domain of captures and search states, feed_step,
+ * max_invocations, max_events and frame_row (>= RIA_MACQ_FRAME_BYTES(8)) are the stream call's; h is at RIA_RATE_1_4.  The
+ * rules it adds are ria_amd/csrc/mcdpsk_stream_rules.hpp's.  With pool NULL, window_flags 0 and no stream pending, every
+ * output - events, payload rows, results and the `search` part of the state - equals ria_gpu_rx_stream_batch's byte for byte.
+ *
+ * Time for the cache.  The caller owns the clock, the call turns it into an audio clock: every window of stream s is decoded
+ * at now_ms = t0_ms_dev[s] + (uint64)sync_position * 1000 / sample_rate (48000, the handle's), integer and modulo 2^64 as the
+ * pool's own arithmetic; a re-entered window has the same sync_position, hence the same now_ms.  Stream s uses cache
+ * cache_id_dev[s] (< 0: no chase for that stream).  Successive windows of a stream run in successive rounds, the order a
+ * cache needs: a retransmission on the same recording finds what the first reception stored.  pool NULL: no chase;
+ * cache_id_dev and t0_ms_dev are then not read.  A pool of another handle is RIA_ERR_INVALID.
+ *
+ * The up-front check runs on the device ahead of everything and is read with the call's first control read, before any state,
+ * cache or output is written.  RIA_ERR_INVALID for the whole call: a capture or search state outside ria_gpu_search_batch's
+ * domain; two streams with the same cache id >= 0 (negative ids may repeat), or an id >= n_caches - the window call's own
+ * check sees one length group of one round only; pending_total_cw outside 0..255; with pending_total_cw > 0, a negative
+ * need_samples, a pend_search_start or pend_sync_position outside the capture, or a capture that no longer holds the search
+ * span behind pend_search_start.
+ *
+ * Channel interleaving: window_flags (0 or RIA_MACQ_CHANNEL_INTERLEAVE) and interleaver_bits go to the window call unchanged;
+ * their domain and errors are the *_ci_batch calls' (another flag, or interleaver_bits outside 1..648 with the flag, is
+ * RIA_ERR_INVALID before anything is launched).
+ *
+ * Pending, written.  A window that answers RIA_MWIN_NEED_SAMPLES records its event and closes the stream with
+ * RIA_STREAM_WINDOW_NEED_SAMPLES as in the stream call, and leaves the reference's SYNC_FOUND wait (streaming_decoder.cpp:
+ * 943-1019) in the state: pending_total_cw, need_samples, pend_search_start, pend_sync_position, the three window parameters
+ * it was called with and the search's correlation.  Every other window outcome writes the eight fields as zero.  The cursor
+ * and fed follow the stream call's rules.
+ *
+ * Pending, read.  A stream that comes in with pending_total_cw > 0 is not searched in the first round.
+ *   - capture_len >= pend_sync_position + need_samples: it gets, in a round of its own ahead of the first search leg, the
+ *     window [pend_search_start, pend_search_start + min(capture_len - pend_search_start, max(full, pend_sync_position -
+ *     pend_search_start + need_samples))) with the stored parameters and pending_total_cw as the window call's re-entry
+ *     input.  fed = max(fed, pend_sync_position + need_samples) is applied first, last_decoded_sync is rebased as usual,
+ *     then the ordinary state rule runs.  The event's sync_position, search_start and correlation come from the pending
+ *     fields, snr_db from search.snr_hint (which the search set to sync_snr_ when it found this sync).  After that the
+ *     stream searches on like any other.
+ *   - otherwise it closes at once with RIA_STREAM_WINDOW_NEED_SAMPLES, no event, and its state unchanged bit for bit.
+ * A caller that gives up (the reference's frame timeout) zeroes pending_total_cw: the stream then searches from its cursor.
+ *
+ * Outputs: every row of every output is written, zero where nothing applies - events_dev, frames_dev, result_dev and
+ * harq_dev (nullable; row s * max_events + e is the ria_mcdpsk_harq_result of event e's window).  n_streams == 0 is RIA_OK.
+ * RIA_ERR_INVALID leaves everything as it was.  After any other error (RIA_ERR_HIP from a launch or a broken internal bound)
+ * state_dev is unspecified: the pending fields are written window by window, the search part only behind the last round.
+ *
+ * Work: the stream call's rounds; ahead of them the up-front check (one small device-to-host read more than the stream
+ * call's worst case) and, only when a stream comes in pending, the re-entry round (the pending list, its window calls and
+ * the open list: the reads of one more round).  Thread per stream or per window, every list an ascending scan: no result
+ * depends on chunking, grouping or scheduling.  The search works on a contiguous copy of the states' search parts, written
+ * back behind the last round.  The workspace lives on h, is carved once per size - with room for one re-entered window of a
+ * whole capture - and reserved before the call's first launch.
+ *
+ * Still out of scope: burst groups and OFDM, ring wrap (ria_gpu_rx_ring_batch is not extended), the ZC-miss -> chirp
+ * fallback, and the frame timeout (the caller's clock: it zeroes pending_total_cw). */
+typedef struct ria_mcdpsk_stream_state {   /* 64 bytes, one per stream */
+    ria_search_state search;               /* as ria_gpu_rx_stream_batch reads and writes it */
+    int32_t pending_total_cw;              /* 0: searching; n > 0: waiting at a found sync (SYNC_FOUND with pending_total_cw_ = n) */
+    int32_t need_samples;                  /* samples from pend_sync_position the next pass waits for */
+    int32_t pend_search_start;             /* sample 0 of the window that answered NEED_SAMPLES */
+    int32_t pend_sync_position;            /* capture index */
+    float   pend_known_cfo_hz, pend_detect_threshold, pend_min_confidence, pend_correlation;
+                                           /* the window parameters that repeat the detection, and the event's correlation */
+} ria_mcdpsk_stream_state;
+int ria_gpu_mcdpsk_stream_batch(ria_gpu_handle h, int mode /* RIA_SEARCH_MCDPSK_ZC | RIA_SEARCH_MCDPSK_CHIRP */,
+                                uint32_t flags /* RIA_SEARCH_CONNECTED */, uint32_t window_flags /* 0 | RIA_MACQ_CHANNEL_INTERLEAVE */,
+                                int interleaver_bits, const ria_mcdpsk_config* cfg,
+                                const float* samples_dev, int64_t stride, const int32_t* capture_len_dev, int n_streams,
+                                ria_mcdpsk_stream_state* state_dev, int feed_step, int max_invocations, int max_events,
+                                ria_chase_pool pool /* nullable */, const int32_t* cache_id_dev /* [n_streams], < 0: off */,
+                                const uint64_t* t0_ms_dev /* [n_streams] */,
+                                ria_stream_event* events_dev, uint8_t* frames_dev, int frame_row,
+                                ria_mcdpsk_harq_result* harq_dev /* nullable, [n_streams * max_events], parallel to events_dev */,
+                                ria_stream_result* result_dev, void* stream);
+/* One recording from host memory, as ria_gpu_rx_stream_host: staged through the handle's pinned block on the handle's own
+ * stream, which it synchronises.  pool (nullable) stays on the device; the stream uses cache cache_id at clock t0_ms.
+ * harq_out_host (nullable) takes max_events records. */
+int ria_gpu_mcdpsk_stream_host(ria_gpu_handle h, int mode, uint32_t flags, uint32_t window_flags, int interleaver_bits,
+                               const ria_mcdpsk_config* cfg, const float* samples_host, int n_samples,
+                               ria_mcdpsk_stream_state* state_host /* in and out */, int feed_step, int max_invocations, int max_events,
+                               ria_chase_pool pool /* nullable */, int32_t cache_id, uint64_t t0_ms,
+                               ria_stream_event* events_out_host, uint8_t* frames_out_host, int frame_row,
+                               ria_mcdpsk_harq_result* harq_out_host /* nullable */, ria_stream_result* result_out_host);
 
 /* ---- recordings longer than the ring buffer in, frames out -----------------------------------------------------------------
  * ria_gpu_rx_ring_batch is ria_gpu_rx_stream_batch's loop on ria_gpu_search_ring_batch, with the window leg in absolute

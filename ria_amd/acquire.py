@@ -595,6 +595,161 @@ def rx_stream(engine, captures, capture_len, mode, control_engine=None, feed_ste
     return events
 
 
+# ---- the MC-DPSK loop with a chase pool, channel interleaving and re-entry (ria_gpu_mcdpsk_stream_batch as a composition)
+PENDING_FIELDS = ("pending_total_cw", "need_samples", "pend_search_start", "pend_sync_position", "pend_known_cfo_hz", "pend_detect_threshold",
+                  "pend_min_confidence", "pend_correlation")
+
+
+def mcdpsk_link_stream(engine, captures, capture_len, mode, state=None, feed_step=0, max_invocations=1 << 20, max_events=256, connected=False,
+                       carriers=10, modulation="DBPSK", spreading=1, chase=None, cache_id=None, t0_ms=None, channel_interleave=False,
+                       interleaver_bits=None):
+    """RxEngine.mcdpsk_stream as a composition of RxEngine.search and RxEngine.mcdpsk_window with the host's part between
+    them in Python: rx_stream's loop for the two MC-DPSK modes, with the pool (stream s on cache cache_id[s], default s, at
+    t0_ms[s] + sync_position * 1000 // sample rate), channel interleaving, and the pending rules - a window that answers
+    NEED_SAMPLES leaves the eight pending fields in the state; a stream that comes in pending is not searched first: it gets
+    its re-entered window if the samples it waits for are there, and closes unchanged and without an event if not.
+    Returns (state (MCSTREAM_STATE), closed (RIA_STREAM_* per stream), events (STREAM_EVENT [n, max_events]), frames uint8
+    [n, max_events, 320], harq (HARQ_RESULT [n, max_events])): the records of the one-call form."""
+    n = captures.shape[0]
+    m = capi.SEARCH_MODE[mode] if isinstance(mode, str) else int(mode)
+    assert m != capi.SEARCH_MODE["OFDM_LTS"]
+    chirp = m == capi.SEARCH_MODE["MCDPSK_CHIRP"]
+    rate = int(engine.cfg.sample_rate)      # the rate of the audio clock
+    lens = np.empty(n, np.int64)
+    lens[:] = capture_len
+    state = (engine.mcdpsk_stream_state(n, fed=0 if feed_step else lens) if state is None else np.array(state, engine.MCSTREAM_STATE)).copy()
+    ids = np.arange(n, dtype=np.int32) if cache_id is None else np.broadcast_to(np.asarray(cache_id, np.int32), (n,))
+    t0 = np.broadcast_to(np.asarray(0 if t0_ms is None else t0_ms, np.uint64), (n,))
+    bps = {"DBPSK": 1, "DQPSK": 2}[modulation] if isinstance(modulation, str) else int(modulation)
+    search_len = capi.SEARCH_MIN_SEARCH[m]
+    first_frame = mcdpsk_frame_len(1, carriers, bps, spreading)
+    full = search_len + mcdpsk_frame_len(8, carriers, bps, spreading)
+    ne, row = int(max_events), engine.MCWIN_FRAME_ROW
+    events = np.zeros((n, ne), engine.STREAM_EVENT)
+    harq = np.zeros((n, ne), engine.HARQ_RESULT)
+    frames = np.zeros((n, ne, row), np.uint8)
+    n_events = np.zeros(n, np.int64)
+    closed = np.zeros(n, np.int32)
+    sfields = engine.SEARCH_STATE.names
+
+    def windows(rows, det, wl, pending):
+        """one window call on streams `rows` (one window length), det: per row search_start, sync_position, known_cfo_hz,
+        detect_threshold, min_confidence, correlation, snr_db; then the host's part"""
+        det = {k: det[k].copy() for k in det.dtype.names}       # a field of a record array is strided: torch wants it packed
+        w = _gather_windows(captures, rows, det["search_start"], wl)
+        last_in = state["last_decoded_sync_pos"][rows].astype(np.int64)
+        rel = np.where(last_in == capi.SEARCH_NO_LAST_SYNC, capi.MWIN_NO_LAST_SYNC, np.clip(last_in - det["search_start"], -2 ** 31 + 1, 2 ** 31 - 1))
+        conf = np.minimum(det["min_confidence"], det["correlation"])
+        with np.errstate(over="ignore"):
+            now = t0[rows] + det["sync_position"].astype(np.uint64) * np.uint64(1000) // np.uint64(rate)
+        f, wres, acq, hq = engine.mcdpsk_window(w, search_len, carriers=carriers, modulation=bps, spreading=spreading, sync="chirp" if chirp else "zc",
+                                                disconnected=chirp and not connected, known_cfo=det["known_cfo_hz"],
+                                                detect_threshold=det["detect_threshold"], min_confidence=conf, abs_base=det["search_start"],
+                                                last_decoded_sync=rel, pending_total_cw=pending, chase=chase,
+                                                cache_id=ids[rows] if chase is not None else -1, now_ms=now,
+                                                channel_interleave=channel_interleave, interleaver_bits=interleaver_bits)
+        f = f.cpu().numpy()
+        need = capi.MWIN_OUTCOME["NEED_SAMPLES"]
+        for k, s in enumerate(rows):
+            e = events[s, n_events[s]]
+            outcome, nxt, start, sync = int(wres["outcome"][k]), int(wres["next_pos"][k]), int(det["search_start"][k]), int(det["sync_position"][k])
+            e["sync_position"], e["search_start"], e["window_len"], e["outcome"] = sync, start, wl, outcome
+            e["next_pos"] = start + nxt if nxt >= 0 else -1
+            e["frame_bytes"], e["need_samples"], e["pending_total_cw"] = acq["frame_bytes"][k], wres["need_samples"][k], wres["pending_total_cw"][k]
+            e["delivered"] = wres["deliver"][k] != 0
+            for name in ("success", "codewords_ok", "codewords_failed", "frame_type"):
+                e[name] = acq[name][k]
+            e["correlation"], e["cfo_hz"], e["fading_index"], e["snr_db"] = det["correlation"][k], acq["cfo_hz"][k], acq["fading_index"][k], det["snr_db"][k]
+            if e["delivered"]:
+                nb = min(int(acq["frame_bytes"][k]), row)
+                frames[s, n_events[s], :nb] = f[k, :nb]
+            if chase is not None:
+                harq[s, n_events[s]] = hq[k]
+            if outcome == capi.MWIN_OUTCOME["DECODED"]:
+                state["last_cfo_hz"][s], state["fading_hint"][s] = acq["cfo_hz"][k], acq["fading_index"][k]
+            out_last = int(wres["last_decoded_sync"][k])
+            state["last_decoded_sync_pos"][s] = capi.SEARCH_NO_LAST_SYNC if out_last == capi.MWIN_NO_LAST_SYNC else out_last + start
+            if nxt >= 0:
+                state["correlation_pos"][s] = start + nxt
+            elif outcome == capi.MWIN_OUTCOME["TOO_LONG"]:
+                state["correlation_pos"][s] = sync + first_frame
+            state["fed"][s] = max(int(state["fed"][s]), min(int(lens[s]), int(state["correlation_pos"][s])))
+            keep = outcome == need
+            vals = (wres["pending_total_cw"][k], wres["need_samples"][k], start, sync, det["known_cfo_hz"][k], det["detect_threshold"][k], conf[k],
+                    det["correlation"][k])
+            for name, v in zip(PENDING_FIELDS, vals):
+                state[name][s] = v if keep else 0
+            n_events[s] += 1
+            if keep:
+                closed[s] = capi.STREAM_CLOSED["WINDOW_NEED_SAMPLES"]
+            elif n_events[s] >= ne:
+                closed[s] = capi.STREAM_CLOSED["EVENTS_FULL"]
+            elif state["correlation_pos"][s] >= capi.SEARCH_MAX_CAPTURE:
+                closed[s] = capi.STREAM_CLOSED["RING_END"]
+
+    det_dtype = np.dtype([("search_start", "<i8"), ("sync_position", "<i8"), ("known_cfo_hz", "<f4"), ("detect_threshold", "<f4"),
+                          ("min_confidence", "<f4"), ("correlation", "<f4"), ("snr_db", "<f4")])
+    # the streams that wait at a found sync: their window, if its samples are there, ahead of the first search
+    pend = np.flatnonzero(state["pending_total_cw"] > 0)
+    by_len = {}
+    for s in pend:
+        sync, need, start = int(state["pend_sync_position"][s]), int(state["need_samples"][s]), int(state["pend_search_start"][s])
+        if lens[s] >= sync + need:
+            by_len.setdefault(int(min(lens[s] - start, max(full, sync - start + need))), []).append(s)
+        else:
+            closed[s] = capi.STREAM_CLOSED["WINDOW_NEED_SAMPLES"]
+    for wl in sorted(by_len):
+        rows = np.asarray(by_len[wl])
+        det = np.zeros(len(rows), det_dtype)
+        for a, b in (("search_start", "pend_search_start"), ("sync_position", "pend_sync_position"), ("known_cfo_hz", "pend_known_cfo_hz"),
+                     ("detect_threshold", "pend_detect_threshold"), ("min_confidence", "pend_min_confidence"), ("correlation", "pend_correlation"),
+                     ("snr_db", "snr_hint")):
+            det[a] = state[b][rows]
+        state["fed"][rows] = np.maximum(state["fed"][rows], state["pend_sync_position"][rows] + state["need_samples"][rows])
+        windows(rows, det, wl, state["pending_total_cw"][rows].copy())
+    while (closed == 0).any():
+        idx = np.flatnonzero(closed == 0)
+        sstate = np.zeros(len(idx), engine.SEARCH_STATE)
+        for name in sfields:
+            sstate[name] = state[name][idx]
+        res, st = engine.search(captures[torch.as_tensor(idx, device=captures.device)].contiguous() if len(idx) < n else captures, lens[idx],
+                                sstate, m, feed_step=feed_step, max_invocations=max_invocations, connected=connected, carriers=carriers,
+                                modulation=modulation, spreading=spreading)
+        for name in sfields:
+            state[name][idx] = st[name]
+        found = res["outcome"] == capi.SEARCH_OUTCOME["SYNC_FOUND"]
+        closed[idx[~found]] = res["outcome"][~found]
+        by_len = {}
+        for j in np.flatnonzero(found):
+            by_len.setdefault(int(min(full, lens[idx[j]] - res["search_start"][j])), []).append(j)
+        for wl in sorted(by_len):
+            js = by_len[wl]
+            det = np.zeros(len(js), det_dtype)
+            for a, b in (("search_start", "search_start"), ("sync_position", "sync_position"), ("known_cfo_hz", "known_cfo_hz"),
+                         ("detect_threshold", "detect_threshold"), ("min_confidence", "min_confidence"), ("correlation", "correlation"),
+                         ("snr_db", "sync_snr_db")):
+                det[a] = res[b][js]
+            windows(idx[js], det, wl, 0)
+    return state, closed, events, frames, harq
+
+
+LINK_STREAM_COUNTERS = tuple(f"outcome_{k.lower()}" for k in capi.MWIN_OUTCOME) + ("delivered", "recovered_by_sum", "stores", "combines")
+
+
+def link_stream_tally(events, harq):
+    """Counter row (LINK_STREAM_COUNTERS) of one mcdpsk_stream / mcdpsk_link_stream call (events STREAM_EVENT [n, max_events],
+    harq HARQ_RESULT [n, max_events]; rows past a stream's events are zero and count nowhere: window_len 0): events per window
+    outcome, frames delivered, frames a combined sum recovered (success with a codeword of recovered_mask), codewords stored
+    and sums combined."""
+    live = events["window_len"] > 0
+    row = [int(((events["outcome"] == v) & live).sum()) for v in capi.MWIN_OUTCOME.values()]
+    row.append(int(((events["delivered"] != 0) & live).sum()))
+    row.append(int(((events["success"] != 0) & (harq["recovered_mask"] != 0) & live).sum()))
+    row.append(int(_popcount16(harq["stored_mask"][live]).sum()))
+    row.append(int(_popcount16(harq["sum_mask"][live]).sum()))
+    return np.array(row, dtype=np.int64)
+
+
 # ---- recordings longer than the ring buffer (ria_gpu_search_ring_batch + the window calls)
 RING_COUNTERS = ("overflows", "overflow_dropped", "drift_snaps", "cursor_inits")
 

@@ -48,6 +48,7 @@
 #include "ring_kernels.hip.h"
 #include "search_kernels.hip.h"
 #include "stream_kernels.hip.h"
+#include "mcdpsk_stream_kernels.hip.h"
 
 using namespace ria;
 
@@ -3384,17 +3385,38 @@ struct StreamWs {
     ria_mcdpsk_acq_result* acq;   // either acquire result
     uint8_t* wframes;
 };
-static StreamWs stream_carve(Carver& c, size_t n, size_t chunk, size_t win_stride, size_t wframe_row) {
+static StreamWs stream_carve(Carver& c, size_t n, size_t chunk, size_t win_floats, size_t wframe_row) {
     StreamWs w;
     w.head = c.take<uint32_t>(4 + 2 * n);
     w.open = c.take<uint32_t>(n);
     w.group = c.take<uint32_t>(n);
     w.sres = c.take<ria_search_result>(n);
-    w.win = c.take<float>(chunk * win_stride);
+    w.win = c.take<float>(win_floats);
     w.par = c.take<ria_acq_params>(chunk);
     w.wres = c.take<ria_window_result>(chunk);
     w.acq = c.take<ria_mcdpsk_acq_result>(chunk);
     w.wframes = c.take<uint8_t>(chunk * wframe_row);
+    return w;
+}
+// what ria_gpu_mcdpsk_stream_batch adds to the loop (null: ria_gpu_rx_stream_batch), and its part of the workspace
+struct McStreamExt {
+    ria_mcdpsk_stream_state* mstate;
+    uint32_t window_flags; int interleaver_bits;
+    ria_chase_pool pool; const int32_t* cache_id; const uint64_t* t0_ms;
+    ria_mcdpsk_harq_result* harq;
+};
+struct McStreamWs {
+    McStreamCtl* mctl;
+    ria_search_state* sstate;     // [n] the search part of the caller's records, contiguous: what the search reads and writes
+    int32_t* w_cache_id; uint64_t* w_now_ms; ria_mcdpsk_harq_result* w_harq;   // [chunk]
+};
+static McStreamWs mcstream_carve(Carver& c, size_t n, size_t chunk) {
+    McStreamWs w;
+    w.mctl = c.take<McStreamCtl>(1);
+    w.sstate = c.take<ria_search_state>(n);
+    w.w_cache_id = c.take<int32_t>(chunk);
+    w.w_now_ms = c.take<uint64_t>(chunk);
+    w.w_harq = c.take<ria_mcdpsk_harq_result>(chunk);
     return w;
 }
 // mode / flags / cfg / handles / sizes of the two stream calls; *family, *full, *first_frame, *min_row from them
@@ -3425,18 +3447,20 @@ static int stream_setup(ria_gpu_handle h, ria_gpu_handle control_h, const char* 
     return RIA_OK;
 }
 
-int ria_gpu_rx_stream_batch(ria_gpu_handle h, ria_gpu_handle control_h, int mode, uint32_t flags, const ria_mcdpsk_config* cfg,
-                            const float* samples_dev, int64_t stride, const int32_t* capture_len_dev, int n_streams,
-                            ria_search_state* state_dev, int feed_step, int max_invocations, int max_events,
-                            ria_stream_event* events_dev, uint8_t* frames_dev, int frame_row, ria_stream_result* result_dev, void* stream) {
-    const char* who = "ria_gpu_rx_stream_batch";
-    if (!h) return RIA_ERR_INVALID;
+// The loop of the two stream calls.  x null: ria_gpu_rx_stream_batch, on state_dev.  x set: ria_gpu_mcdpsk_stream_batch, on
+// x->mstate (state_dev is null) - the up-front check, the re-entry round ahead of the first search leg, the window call with
+// x's pool, time and interleaving, and the search part of the state written back behind the last round.
+static int stream_impl(ria_gpu_handle h, ria_gpu_handle control_h, const char* who, int mode, uint32_t flags, const ria_mcdpsk_config* cfg,
+                       const float* samples_dev, int64_t stride, const int32_t* capture_len_dev, int n_streams,
+                       ria_search_state* state_dev, int feed_step, int max_invocations, int max_events,
+                       ria_stream_event* events_dev, uint8_t* frames_dev, int frame_row, ria_stream_result* result_dev, void* stream,
+                       const McStreamExt* x) {
     int full = 0, first_frame = 0, min_row = 0;
     if (int rc = stream_setup(h, control_h, who, mode, flags, cfg, max_events, frame_row, &full, &first_frame, &min_row)) return rc;
     if (n_streams < 0 || stride < 0 || feed_step < 0 || max_invocations < 1)
         return fail(h, RIA_ERR_INVALID, "%s: bad argument (n_streams >= 0, stride >= 0, feed_step >= 0, max_invocations >= 1)", who);
     if (n_streams == 0) return RIA_OK;
-    if (!samples_dev || !capture_len_dev || !state_dev || !events_dev || !frames_dev || !result_dev) return fail(h, RIA_ERR_INVALID, "%s: null pointer", who);
+    if (!samples_dev || !capture_len_dev || (!state_dev && !x) || !events_dev || !frames_dev || !result_dev) return fail(h, RIA_ERR_INVALID, "%s: null pointer", who);
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool ofdm = mode == RIA_SEARCH_OFDM_LTS;
@@ -3445,12 +3469,22 @@ int ria_gpu_rx_stream_batch(ria_gpu_handle h, ria_gpu_handle control_h, int mode
     const long long win_stride = (static_cast<long long>(full) + 3) & ~3LL;          // rows of the window workspace start on 16 bytes
     int chunk = static_cast<int>(std::min<size_t>(n, std::max<size_t>(1, (size_t(256) << 20) / (static_cast<size_t>(win_stride) * sizeof(float)))));
     chunk = std::min(chunk, 65535);                    // the gather's grid y extent
-    auto carve = [&](Carver& c) { return stream_carve(c, n, static_cast<size_t>(chunk), static_cast<size_t>(win_stride), static_cast<size_t>(min_row)); };
+    // a re-entered window runs to the end of the span it waited for, which may lie past `full`: room for one capture at least
+    const size_t win_floats = std::max<size_t>(static_cast<size_t>(chunk) * static_cast<size_t>(win_stride), x ? static_cast<size_t>(kSrchRing) : 0);
+    auto carve = [&](Carver& c) {
+        std::pair<StreamWs, McStreamWs> w;
+        w.first = stream_carve(c, n, static_cast<size_t>(chunk), win_floats, static_cast<size_t>(min_row));
+        if (x) w.second = mcstream_carve(c, n, static_cast<size_t>(chunk));
+        return w;
+    };
     const size_t head_bytes = (4 + 2 * n) * sizeof(uint32_t);
     HIP_TRY(h, h->d_stream_ws.reserve(carved_size(carve), &s));
     HIP_TRY(h, h->p_stream_ctl.reserve(head_bytes));
-    const StreamWs W = carve_at(h->d_stream_ws.as<>(), carve);
+    const auto carved = carve_at(h->d_stream_ws.as<>(), carve);
+    const StreamWs& W = carved.first;
+    const McStreamWs& XW = carved.second;
     uint32_t* mirror = h->p_stream_ctl.as<uint32_t>();
+    if (x) state_dev = XW.sstate;
 
     StreamArgs A{};
     A.samples = samples_dev; A.stride = stride; A.capture_len = capture_len_dev; A.state = state_dev; A.sres = W.sres;
@@ -3465,14 +3499,132 @@ int ria_gpu_rx_stream_batch(ria_gpu_handle h, ria_gpu_handle control_h, int mode
     const uint32_t mflags = mode == RIA_SEARCH_MCDPSK_CHIRP ? (RIA_MACQ_SYNC_CHIRP | ((flags & RIA_SEARCH_CONNECTED) ? 0u : RIA_MACQ_DISCONNECTED)) : 0u;
     const unsigned sgrid = static_cast<unsigned>((n_streams + 255) / 256);
     bool window_ran = false;
+    McStreamArgs M{};
+    uint32_t xflags = mflags;
+    if (x) {
+        M.mstate = x->mstate; M.harq = x->harq; M.sres_w = W.sres; M.mctl = XW.mctl;
+        M.sample_rate = h->cfg.sample_rate; M.search_len = search_len;
+        M.w_cache_id = XW.w_cache_id; M.w_now_ms = XW.w_now_ms; M.w_harq = XW.w_harq;
+        if (x->pool) { M.cache_id = x->cache_id; M.t0_ms = x->t0_ms; M.owner = x->pool->d_owner.as<int32_t>(); M.n_caches = x->pool->cfg.n_caches; }
+        xflags |= x->window_flags;
+    }
 
+    // the found list as the host read it (n_found streams, their window lengths behind mirror[4 + n]): one pass per distinct
+    // window length, ascending (steps 3.-6. of a round)
+    auto run_windows = [&](int n_found, int longest) -> int {
+        A.n_found = n_found;
+        std::vector<int> lens(mirror + 4 + n, mirror + 4 + n + n_found);
+        std::sort(lens.begin(), lens.end());
+        for (size_t at = 0; at < lens.size();) {
+            const int wl = lens[at];
+            size_t end = at;
+            while (end < lens.size() && lens[end] == wl) ++end;
+            const int n_group = static_cast<int>(end - at);
+            at = end;
+            if (wl < search_len || wl > longest) return fail(h, RIA_ERR_HIP, "%s: a window of %d samples, outside %d..%d", who, wl, search_len, longest);
+            // windows up to `full` lie in rows of win_stride; a longer one (re-entry only) in rows of its own length
+            const long long row_stride = wl <= full ? win_stride : (static_cast<long long>(wl) + 3) & ~3LL;
+            const int row_chunk = wl <= full ? chunk : static_cast<int>(std::min<size_t>(static_cast<size_t>(chunk), win_floats / static_cast<size_t>(row_stride)));
+            A.window_len = wl; A.win_stride = row_stride;
+            hipLaunchKernelGGL(stream_list_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A, kStreamListGroup);
+            for (int first = 0; first < n_group; first += row_chunk) {
+                const int nb = std::min(row_chunk, n_group - first);
+                A.first = first; A.n_chunk = nb;
+                const unsigned tgrid = static_cast<unsigned>((nb + 255) / 256);
+                hipLaunchKernelGGL(stream_gather_kernel, dim3(static_cast<unsigned>(std::min((wl + 1023) / 1024, 64)), static_cast<unsigned>(nb)), dim3(256), 0, s, A);
+                if (x) { M.S = A; hipLaunchKernelGGL(mcstream_params_kernel, dim3(tgrid), dim3(256), 0, s, M); }
+                else hipLaunchKernelGGL(stream_params_kernel, dim3(tgrid), dim3(256), 0, s, A);
+                HIP_TRY(h, hipGetLastError());
+                // a window call may grow its workspaces: the first of the call finds the stream drained by the read above
+                if (window_ran) HIP_TRY(h, hipStreamSynchronize(s));
+                window_ran = true;
+                int rc;
+                if (ofdm)
+                    rc = ria_gpu_rx_window_batch(control_h, h, W.win, row_stride, search_len, wl, nb, W.par, RIA_DECODE_FULL, W.wframes, min_row, W.wres,
+                                                 reinterpret_cast<ria_acq_result*>(W.acq), nullptr, nullptr, s);
+                else if (x)
+                    rc = ria_gpu_mcdpsk_window_batch(h, cfg, W.win, row_stride, search_len, wl, nb, reinterpret_cast<const ria_mcdpsk_acq_params*>(W.par), xflags,
+                                                     W.wframes, min_row, reinterpret_cast<ria_mcdpsk_window_result*>(W.wres), W.acq, nullptr, 0, x->pool,
+                                                     XW.w_cache_id, XW.w_now_ms, XW.w_harq, x->interleaver_bits, s);
+                else
+                    rc = ria_gpu_mcdpsk_window_batch(h, cfg, W.win, row_stride, search_len, wl, nb, reinterpret_cast<const ria_mcdpsk_acq_params*>(W.par), mflags,
+                                                     W.wframes, min_row, reinterpret_cast<ria_mcdpsk_window_result*>(W.wres), W.acq, nullptr, 0, nullptr,
+                                                     nullptr, nullptr, nullptr, 0, s);
+                if (rc != RIA_OK) return rc;
+                if (x) hipLaunchKernelGGL(mcstream_apply_kernel, dim3(tgrid), dim3(256), 0, s, M);
+                else hipLaunchKernelGGL(stream_apply_kernel, dim3(tgrid), dim3(256), 0, s, A);
+                HIP_TRY(h, hipGetLastError());
+            }
+        }
+        return RIA_OK;
+    };
+    // the streams still open (step 7. of a round); *n_open_out 0: the call is over
+    auto list_open = [&](int bound, int* n_open_out) -> int {
+        A.open = W.open;
+        hipLaunchKernelGGL(stream_list_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A, kStreamListOpen);
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(mirror, W.head, sizeof(StreamCtl), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        const int n_open = static_cast<int>(mirror[0]);
+        if (n_open < 0 || n_open > bound) return fail(h, RIA_ERR_HIP, "%s: the open list broke its bound (%d)", who, n_open);
+        *n_open_out = n_open;
+        A.n_open = n_open;
+        return RIA_OK;
+    };
+    // the search part of the state back into the caller's records
+    auto finish = [&]() -> int {
+        if (x) {
+            M.S = A;
+            hipLaunchKernelGGL(mcstream_finish_kernel, dim3(sgrid), dim3(256), 0, s, M);
+            HIP_TRY(h, hipGetLastError());
+        }
+        return RIA_OK;
+    };
+
+    if (x) {
+        // 0. the up-front check - the search's domain, the pending fields', the cache ids across the whole call - read before
+        //    anything is written; then the outputs cleared, and the streams that wait at a found sync in a round of their own
+        if (x->pool) HIP_TRY(h, hipMemsetAsync(M.owner, 0xFF, static_cast<size_t>(M.n_caches) * sizeof(int32_t), s));
+        HIP_TRY(h, hipMemsetAsync(XW.mctl, 0, sizeof(McStreamCtl), s));
+        M.S = A;
+        hipLaunchKernelGGL(mcstream_check_kernel, dim3(sgrid), dim3(256), 0, s, M);
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(mirror, XW.mctl, sizeof(McStreamCtl), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        const McStreamCtl mc = *reinterpret_cast<const McStreamCtl*>(mirror);
+        if (mc.bad & kMcStreamBadDomain)
+            return fail(h, RIA_ERR_INVALID, "%s: a stream's capture_len is above min(stride, 959999), its search state is outside the search's domain, its "
+                                            "pending_total_cw is outside 0..255, or its pending fields do not lie in its capture; nothing was written", who);
+        if (mc.bad & kMcStreamBadCache)
+            return fail(h, RIA_ERR_INVALID, "%s: two streams of one call use one cache id, or an id is not below n_caches; nothing was written", who);
+        if (mc.n_pending > static_cast<unsigned>(n_streams)) return fail(h, RIA_ERR_HIP, "%s: the pending count broke its bound (%u)", who, mc.n_pending);
+        HIP_TRY(h, hipMemsetAsync(events_dev, 0, n * static_cast<size_t>(max_events) * sizeof(ria_stream_event), s));
+        HIP_TRY(h, hipMemsetAsync(frames_dev, 0, n * static_cast<size_t>(max_events) * static_cast<size_t>(frame_row), s));
+        if (x->harq) HIP_TRY(h, hipMemsetAsync(x->harq, 0, n * static_cast<size_t>(max_events) * sizeof(ria_mcdpsk_harq_result), s));
+        hipLaunchKernelGGL(mcstream_init_kernel, dim3(sgrid), dim3(256), 0, s, M);
+        if (mc.n_pending > 0) {
+            hipLaunchKernelGGL(mcstream_pending_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, M);
+            HIP_TRY(h, hipGetLastError());
+            HIP_TRY(h, hipMemcpyAsync(mirror, W.head, head_bytes, hipMemcpyDeviceToHost, s));
+            HIP_TRY(h, hipStreamSynchronize(s));
+            const int n_fit = static_cast<int>(mirror[1]);
+            if (n_fit < 0 || n_fit > static_cast<int>(mc.n_pending)) return fail(h, RIA_ERR_HIP, "%s: the pending list broke its bound (%d)", who, n_fit);
+            M.pending_round = 1;
+            if (n_fit > 0) if (int rc = run_windows(n_fit, kSrchMaxCapture)) return rc;
+            M.pending_round = 0;
+            int n_open = 0;
+            if (int rc = list_open(n_streams, &n_open)) return rc;
+            if (n_open == 0) return finish();
+        }
+        HIP_TRY(h, hipGetLastError());
+    }
     for (int round = 0;; ++round) {
         if (round > max_events) return fail(h, RIA_ERR_HIP, "%s: round %d past max_events + 1", who, round + 1);
-        // 1. the search on the open streams: in the first round all of them, and nothing of this call is written before its
-        //    domain check has passed
+        // 1. the search on the open streams: in the first round all of them (x: all that do not wait at a sync), and nothing
+        //    of this call is written before its domain check has passed
         if (int rc = search_impl(h, who, mode, flags, cfg, samples_dev, stride, capture_len_dev, A.n_open, A.open, state_dev, feed_step,
                                  max_invocations, W.sres, s)) return rc;
-        if (round == 0) {
+        if (round == 0 && !x) {
             HIP_TRY(h, hipMemsetAsync(events_dev, 0, n * static_cast<size_t>(max_events) * sizeof(ria_stream_event), s));
             HIP_TRY(h, hipMemsetAsync(frames_dev, 0, n * static_cast<size_t>(max_events) * static_cast<size_t>(frame_row), s));
             hipLaunchKernelGGL(stream_init_kernel, dim3(sgrid), dim3(256), 0, s, A);
@@ -3485,54 +3637,96 @@ int ria_gpu_rx_stream_batch(ria_gpu_handle h, ria_gpu_handle control_h, int mode
         const int n_found = static_cast<int>(mirror[1]);
         if (n_found < 0 || n_found > A.n_open) return fail(h, RIA_ERR_HIP, "%s: the found list broke its bound (%d)", who, n_found);
         if (n_found == 0) break;
-        A.n_found = n_found;
-        std::vector<int> lens(mirror + 4 + n, mirror + 4 + n + n_found);
-        std::sort(lens.begin(), lens.end());
         // 3.-6. one pass per distinct window length, ascending
-        for (size_t at = 0; at < lens.size();) {
-            const int wl = lens[at];
-            size_t end = at;
-            while (end < lens.size() && lens[end] == wl) ++end;
-            const int n_group = static_cast<int>(end - at);
-            at = end;
-            if (wl < search_len || wl > full) return fail(h, RIA_ERR_HIP, "%s: a window of %d samples, outside %d..%d", who, wl, search_len, full);
-            A.window_len = wl;
-            hipLaunchKernelGGL(stream_list_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A, kStreamListGroup);
-            for (int first = 0; first < n_group; first += chunk) {
-                const int nb = std::min(chunk, n_group - first);
-                A.first = first; A.n_chunk = nb;
-                const unsigned tgrid = static_cast<unsigned>((nb + 255) / 256);
-                hipLaunchKernelGGL(stream_gather_kernel, dim3(static_cast<unsigned>(std::min((wl + 1023) / 1024, 64)), static_cast<unsigned>(nb)), dim3(256), 0, s, A);
-                hipLaunchKernelGGL(stream_params_kernel, dim3(tgrid), dim3(256), 0, s, A);
-                HIP_TRY(h, hipGetLastError());
-                // a window call may grow its workspaces: the first of the call finds the stream drained by the read above
-                if (window_ran) HIP_TRY(h, hipStreamSynchronize(s));
-                window_ran = true;
-                int rc;
-                if (ofdm)
-                    rc = ria_gpu_rx_window_batch(control_h, h, W.win, win_stride, search_len, wl, nb, W.par, RIA_DECODE_FULL, W.wframes, min_row, W.wres,
-                                                 reinterpret_cast<ria_acq_result*>(W.acq), nullptr, nullptr, s);
-                else
-                    rc = ria_gpu_mcdpsk_window_batch(h, cfg, W.win, win_stride, search_len, wl, nb, reinterpret_cast<const ria_mcdpsk_acq_params*>(W.par), mflags,
-                                                     W.wframes, min_row, reinterpret_cast<ria_mcdpsk_window_result*>(W.wres), W.acq, nullptr, 0, nullptr,
-                                                     nullptr, nullptr, nullptr, 0, s);
-                if (rc != RIA_OK) return rc;
-                hipLaunchKernelGGL(stream_apply_kernel, dim3(tgrid), dim3(256), 0, s, A);
-                HIP_TRY(h, hipGetLastError());
-            }
-        }
+        if (int rc = run_windows(n_found, full)) return rc;
         // 7. the streams still open
-        A.open = W.open;
-        hipLaunchKernelGGL(stream_list_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A, kStreamListOpen);
-        HIP_TRY(h, hipGetLastError());
-        HIP_TRY(h, hipMemcpyAsync(mirror, W.head, sizeof(StreamCtl), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipStreamSynchronize(s));
-        const int n_open = static_cast<int>(mirror[0]);
-        if (n_open < 0 || n_open > n_found) return fail(h, RIA_ERR_HIP, "%s: the open list broke its bound (%d)", who, n_open);
+        int n_open = 0;
+        if (int rc = list_open(n_found, &n_open)) return rc;
         if (n_open == 0) break;
-        A.n_open = n_open;
     }
+    return finish();
+}
+
+int ria_gpu_rx_stream_batch(ria_gpu_handle h, ria_gpu_handle control_h, int mode, uint32_t flags, const ria_mcdpsk_config* cfg,
+                            const float* samples_dev, int64_t stride, const int32_t* capture_len_dev, int n_streams,
+                            ria_search_state* state_dev, int feed_step, int max_invocations, int max_events,
+                            ria_stream_event* events_dev, uint8_t* frames_dev, int frame_row, ria_stream_result* result_dev, void* stream) {
+    if (!h) return RIA_ERR_INVALID;
+    return stream_impl(h, control_h, "ria_gpu_rx_stream_batch", mode, flags, cfg, samples_dev, stride, capture_len_dev, n_streams, state_dev, feed_step,
+                       max_invocations, max_events, events_dev, frames_dev, frame_row, result_dev, stream, nullptr);
+}
+
+// ------------------------------------------------------------------------------------------------ the MC-DPSK stream loop: chase pool, interleaving, re-entry
+static_assert(sizeof(ria_mcdpsk_stream_state) == 64 && offsetof(ria_mcdpsk_stream_state, pending_total_cw) == 32 &&
+              offsetof(ria_mcdpsk_stream_state, pend_known_cfo_hz) == 48, "ria_gpu_mcdpsk_stream_batch record layout (include/ria_gpu.h)");
+// the arguments ria_gpu_mcdpsk_stream_batch adds, checked on the host before anything is launched
+static int mcstream_setup(ria_gpu_handle h, const char* who, int mode, uint32_t window_flags, int interleaver_bits, ria_chase_pool pool,
+                          const int32_t* cache_id, const uint64_t* t0_ms) {
+    if (mode != RIA_SEARCH_MCDPSK_ZC && mode != RIA_SEARCH_MCDPSK_CHIRP)
+        return fail(h, RIA_ERR_INVALID, "%s: mode is RIA_SEARCH_MCDPSK_ZC or RIA_SEARCH_MCDPSK_CHIRP", who);
+    if ((window_flags & ~static_cast<uint32_t>(RIA_MACQ_CHANNEL_INTERLEAVE)) != 0)
+        return fail(h, RIA_ERR_INVALID, "%s: window_flags is 0 or RIA_MACQ_CHANNEL_INTERLEAVE", who);
+    int step = 0;
+    if ((window_flags & RIA_MACQ_CHANNEL_INTERLEAVE) && !macq_ci_step(interleaver_bits, &step))
+        return fail(h, RIA_ERR_INVALID, "%s: interleaver_bits %d outside 1..648", who, interleaver_bits);
+    if (pool && !chase_pool_alive(h, pool)) return fail(h, RIA_ERR_INVALID, "%s: the pool does not belong to this handle", who);
+    if (pool && (!cache_id || !t0_ms)) return fail(h, RIA_ERR_INVALID, "%s: a pool needs cache_id_dev and t0_ms_dev", who);
     return RIA_OK;
+}
+
+int ria_gpu_mcdpsk_stream_batch(ria_gpu_handle h, int mode, uint32_t flags, uint32_t window_flags, int interleaver_bits, const ria_mcdpsk_config* cfg,
+                                const float* samples_dev, int64_t stride, const int32_t* capture_len_dev, int n_streams,
+                                ria_mcdpsk_stream_state* state_dev, int feed_step, int max_invocations, int max_events,
+                                ria_chase_pool pool, const int32_t* cache_id_dev, const uint64_t* t0_ms_dev,
+                                ria_stream_event* events_dev, uint8_t* frames_dev, int frame_row, ria_mcdpsk_harq_result* harq_dev,
+                                ria_stream_result* result_dev, void* stream) {
+    const char* who = "ria_gpu_mcdpsk_stream_batch";
+    if (!h) return RIA_ERR_INVALID;
+    if (int rc = mcstream_setup(h, who, mode, window_flags, interleaver_bits, pool, cache_id_dev, t0_ms_dev)) return rc;
+    if (n_streams > 0 && !state_dev) return fail(h, RIA_ERR_INVALID, "%s: null pointer", who);
+    McStreamExt x{};
+    x.mstate = state_dev; x.window_flags = window_flags; x.interleaver_bits = interleaver_bits;
+    x.pool = pool; x.cache_id = cache_id_dev; x.t0_ms = t0_ms_dev; x.harq = harq_dev;
+    return stream_impl(h, nullptr, who, mode, flags, cfg, samples_dev, stride, capture_len_dev, n_streams, nullptr, feed_step, max_invocations, max_events,
+                       events_dev, frames_dev, frame_row, result_dev, stream, &x);
+}
+
+// One recording from host memory, as ria_gpu_rx_stream_host; the pool's caches stay on the device.
+int ria_gpu_mcdpsk_stream_host(ria_gpu_handle h, int mode, uint32_t flags, uint32_t window_flags, int interleaver_bits, const ria_mcdpsk_config* cfg,
+                               const float* samples_host, int n_samples, ria_mcdpsk_stream_state* state_host, int feed_step, int max_invocations,
+                               int max_events, ria_chase_pool pool, int32_t cache_id, uint64_t t0_ms, ria_stream_event* events_out_host,
+                               uint8_t* frames_out_host, int frame_row, ria_mcdpsk_harq_result* harq_out_host, ria_stream_result* result_out_host) {
+    const char* who = "ria_gpu_mcdpsk_stream_host";
+    if (!h) return RIA_ERR_INVALID;
+    if (int rc = mcstream_setup(h, who, mode, window_flags, interleaver_bits, pool, &cache_id, &t0_ms)) return rc;
+    int full = 0, first_frame = 0, min_row = 0;
+    if (int rc = stream_setup(h, nullptr, who, mode, flags, cfg, max_events, frame_row, &full, &first_frame, &min_row)) return rc;
+    if (n_samples < 0 || n_samples > kSrchMaxCapture || feed_step < 0 || max_invocations < 1)
+        return fail(h, RIA_ERR_INVALID, "%s: bad argument (0 <= n_samples <= 959999, feed_step >= 0, max_invocations >= 1)", who);
+    if (!samples_host || !state_host || !events_out_host || !frames_out_host || !result_out_host) return fail(h, RIA_ERR_INVALID, "%s: null pointer", who);
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int32_t cap = n_samples;
+    const size_t ne = static_cast<size_t>(max_events);
+    struct Stage { float* x; int32_t* cap; int32_t* id; uint64_t* t0; ria_mcdpsk_stream_state* st_in; ria_mcdpsk_stream_state* st; ria_stream_event* ev;
+                   uint8_t* frames; ria_mcdpsk_harq_result* harq; ria_stream_result* res; };
+    auto carve = [&](StageCarver& c) {
+        Stage w;
+        w.x = c.in(static_cast<size_t>(std::max(n_samples, 1)), samples_host, static_cast<size_t>(n_samples));
+        w.t0 = c.in(1, const_cast<const uint64_t*>(&t0_ms));
+        w.cap = c.in(1, &cap); w.id = c.in(1, const_cast<const int32_t*>(&cache_id));
+        w.st_in = c.in(1, const_cast<const ria_mcdpsk_stream_state*>(state_host));
+        w.st = c.out(1, state_host); w.ev = c.out(ne, events_out_host); w.frames = c.out(ne * static_cast<size_t>(frame_row), frames_out_host);
+        w.harq = c.out(ne, harq_out_host);
+        w.res = c.out(1, result_out_host);
+        return w;
+    };
+    return host_staged(h, carve, [&](const Stage& d, hipStream_t s) {
+        int rc = ria_gpu_mcdpsk_stream_batch(h, mode, flags, window_flags, interleaver_bits, cfg, d.x, std::max(n_samples, 1), d.cap, 1, d.st_in, feed_step,
+                                             max_invocations, max_events, pool, d.id, d.t0, d.ev, d.frames, frame_row, d.harq, d.res, s);
+        if (rc != RIA_OK) return rc;
+        if (hipMemcpyAsync(d.st, d.st_in, sizeof(ria_mcdpsk_stream_state), hipMemcpyDeviceToDevice, s) != hipSuccess)
+            return fail(h, RIA_ERR_HIP, "%s: the state's copy failed", who);
+        return static_cast<int>(RIA_OK); });
 }
 
 // One stream from host memory (the single-stream adaptor path): staged through the handle's pinned + device block on the

@@ -85,6 +85,7 @@ class RxEngine:
         if rc != capi.RIA_OK:
             raise capi.RiaError(f"ria_gpu_create failed with status {rc}")
         self.h = h
+        self.cfg = cfg
         self.device = torch.device("cuda", device)
         self.geo = capi.Geometry()
         self._check(self.lib.ria_gpu_get_geometry(self.h, C.byref(self.geo)))
@@ -917,6 +918,81 @@ class RxEngine:
                                                     int(feed_step), int(max_invocations), ne, ev.ctypes.data, frames.ctypes.data, row,
                                                     res.ctypes.data))
         return st, res, ev.reshape(1, ne), frames
+
+    MCSTREAM_STATE = np.dtype(SEARCH_STATE.descr + [("pending_total_cw", "<i4"), ("need_samples", "<i4"), ("pend_search_start", "<i4"),
+                                                    ("pend_sync_position", "<i4"), ("pend_known_cfo_hz", "<f4"), ("pend_detect_threshold", "<f4"),
+                                                    ("pend_min_confidence", "<f4"), ("pend_correlation", "<f4")])
+
+    @classmethod
+    def mcdpsk_stream_state(cls, n, fed=0):
+        """n fresh decoder states (MCSTREAM_STATE): search_state()'s fields, then the eight pending fields, zero (searching)"""
+        s = np.zeros(n, cls.MCSTREAM_STATE)
+        for f in cls.SEARCH_STATE.names:
+            s[f] = cls.search_state(n, fed)[f]
+        return s
+
+    def _mcstream_in(self, mode, channel_interleave, interleaver_bits, carriers, modulation, spreading):
+        m = capi.SEARCH_MODE[mode] if isinstance(mode, str) else int(mode)
+        bps = {"DBPSK": 1, "DQPSK": 2}[modulation] if isinstance(modulation, str) else int(modulation)
+        bits = (carriers * bps if interleaver_bits is None else int(interleaver_bits)) if channel_interleave else 0
+        return m, capi.McdpskConfig(carriers, bps, spreading, 0), capi.MACQ_CHANNEL_INTERLEAVE if channel_interleave else 0, bits
+
+    def mcdpsk_stream(self, captures, capture_len, mode, state=None, feed_step=0, max_invocations=1 << 20, max_events=256, connected=False,
+                      carriers=10, modulation="DBPSK", spreading=1, chase=None, cache_id=None, t0_ms=None, channel_interleave=False,
+                      interleaver_bits=None):
+        """rx_stream for the two MC-DPSK modes with a chase pool, channel interleaving and re-entry of a window that waits for
+        samples (ria_gpu_mcdpsk_stream_batch).  state: MCSTREAM_STATE records (mcdpsk_stream_state(); default as rx_stream);
+        a stream whose state comes back with pending_total_cw > 0 waits at a found sync: call again with that state and a
+        longer capture.  chase: a ChasePool; stream s uses cache cache_id[s] (default s, -1 = off) and decodes a window at
+        t0_ms[s] + sync_position * 1000 // 48000.  channel_interleave / interleaver_bits as in mcdpsk_window.  Returns (state
+        (MCSTREAM_STATE), results (STREAM_RESULT), events (STREAM_EVENT [n, max_events]), frames uint8 [n, max_events, 320] on
+        the device, harq (HARQ_RESULT [n, max_events]))."""
+        n, stride = captures.shape
+        assert captures.dtype == torch.float32 and captures.is_contiguous()
+        m, cfg, wflags, bits = self._mcstream_in(mode, channel_interleave, interleaver_bits, carriers, modulation, spreading)
+        lens = np.empty(n, np.int32)
+        lens[:] = capture_len
+        if state is None:
+            state = self.mcdpsk_stream_state(n, fed=0 if feed_step else lens)
+        st = np.ascontiguousarray(state, self.MCSTREAM_STATE)
+        assert st.shape == (n,)
+        row, ne = self.MCWIN_FRAME_ROW, int(max_events)
+        lens_d = torch.from_numpy(lens).to(self.device)
+        st_d = torch.from_numpy(st.view(np.uint8).reshape(n, 64).copy()).to(self.device)
+        res_d = torch.empty((n, 64), dtype=torch.uint8, device=self.device)
+        ev_d = torch.empty((n * max(ne, 0), 64), dtype=torch.uint8, device=self.device)
+        harq_d = torch.empty((n * max(ne, 0), 32), dtype=torch.uint8, device=self.device)
+        frames = torch.empty((n, max(ne, 0), row), dtype=torch.uint8, device=self.device)
+        ids, t0, _ = self._harq_in(n, cache_id, t0_ms)
+        self._check(self.lib.ria_gpu_mcdpsk_stream_batch(self.h, m, capi.SEARCH_CONNECTED if connected else 0, wflags, bits, C.byref(cfg),
+                                                         _ptr(captures), stride, _ptr(lens_d), n, _ptr(st_d), int(feed_step), int(max_invocations), ne,
+                                                         chase.p if chase is not None else None, _ptr(ids), _ptr(t0), _ptr(ev_d), _ptr(frames), row,
+                                                         _ptr(harq_d), _ptr(res_d), _stream_ptr()))
+        return (self._status_array(st_d, self.MCSTREAM_STATE), self._status_array(res_d, self.STREAM_RESULT),
+                self._status_array(ev_d, self.STREAM_EVENT).reshape(n, ne), frames, self._status_array(harq_d, self.HARQ_RESULT).reshape(n, ne))
+
+    def mcdpsk_stream_host(self, recording, mode, state=None, feed_step=0, max_invocations=1 << 20, max_events=256, connected=False,
+                           carriers=10, modulation="DBPSK", spreading=1, chase=None, cache_id=0, t0_ms=0, channel_interleave=False,
+                           interleaver_bits=None):
+        """mcdpsk_stream for one recording in host memory (ria_gpu_mcdpsk_stream_host; a float32 numpy array).  Returns (state,
+        results, events, frames, harq) as mcdpsk_stream does for n = 1, frames as a numpy array."""
+        x = np.ascontiguousarray(recording, np.float32)
+        assert x.ndim == 1
+        m, cfg, wflags, bits = self._mcstream_in(mode, channel_interleave, interleaver_bits, carriers, modulation, spreading)
+        if state is None:
+            state = self.mcdpsk_stream_state(1, fed=0 if feed_step else len(x))
+        st = np.ascontiguousarray(state, self.MCSTREAM_STATE).copy()
+        assert st.shape == (1,)
+        row, ne = self.MCWIN_FRAME_ROW, int(max_events)
+        ev = np.zeros(max(ne, 0), self.STREAM_EVENT)
+        harq = np.zeros(max(ne, 0), self.HARQ_RESULT)
+        frames = np.zeros((1, max(ne, 0), row), np.uint8)
+        res = np.zeros(1, self.STREAM_RESULT)
+        self._check(self.lib.ria_gpu_mcdpsk_stream_host(self.h, m, capi.SEARCH_CONNECTED if connected else 0, wflags, bits, C.byref(cfg),
+                                                        x.ctypes.data, len(x), st.ctypes.data, int(feed_step), int(max_invocations), ne,
+                                                        chase.p if chase is not None else None, int(cache_id), int(t0_ms) & (2 ** 64 - 1),
+                                                        ev.ctypes.data, frames.ctypes.data, row, harq.ctypes.data, res.ctypes.data))
+        return st, res, ev.reshape(1, ne), frames, harq.reshape(1, ne)
 
     RING_STREAM_RESULT = np.dtype(STREAM_RESULT.descr + [("overflow_dropped", "<u8"), ("overflows", "<u4"), ("drift_snaps", "<u4"),
                                                          ("cursor_inits", "<u4"), ("reserved1", "<u4")])
