@@ -1678,7 +1678,7 @@ int ria_gpu_rx_stream_host(ria_gpu_handle h, ria_gpu_handle control_h, int mode,
  * back behind the last round.  The workspace lives on h, is carved once per size - with room for one re-entered window of a
  * whole capture - and reserved before the call's first launch.
  *
- * Still out of scope: burst groups and OFDM, ring wrap (ria_gpu_rx_ring_batch is not extended), the ZC-miss -> chirp
+ * Still out of scope: burst groups and OFDM, ring wrap (that is ria_gpu_mcdpsk_ring_batch, below), the ZC-miss -> chirp
  * fallback, and the frame timeout (the caller's clock: it zeroes pending_total_cw). */
 typedef struct ria_mcdpsk_stream_state {   /* 64 bytes, one per stream */
     ria_search_state search;               /* as ria_gpu_rx_stream_batch reads and writes it */
@@ -1733,8 +1733,8 @@ int ria_gpu_mcdpsk_stream_host(ria_gpu_handle h, int mode, uint32_t flags, uint3
  * the legs.  Re-entrant through ria_ring_state as the stream call is.  The workspace is carved once and reserved before the
  * first launch.  Feed long recordings with feed_step > 0 (4800): one that is "all there" shows the decoder only its last
  * 960 000 samples, as the reference's would.
- * Still out of scope: burst groups and continuation, chase pools, channel interleaving, MC-DPSK NEED_SAMPLES re-entry, the
- * ZC-miss -> chirp fallback, OFDM-COX and the frame timeout.
+ * Still out of scope: burst groups and continuation, the ZC-miss -> chirp fallback, OFDM-COX and the frame timeout; chase
+ * pools, channel interleaving and MC-DPSK NEED_SAMPLES re-entry are ria_gpu_mcdpsk_ring_batch's, below.
  * ria_gpu_rx_ring_host takes one recording of any length in the domain from host memory: it is copied in pieces through the
  * handle's pinned block into a device buffer the handle owns, grown before anything is in flight. */
 #define RIA_STREAM_SPAN_LOST 7
@@ -1759,6 +1759,93 @@ int ria_gpu_rx_ring_host(ria_gpu_handle h, ria_gpu_handle control_h, int mode, u
                          const float* samples_host, int n_samples, ria_ring_state* state_host /* in and out */,
                          int feed_step, int max_invocations, int max_events, ria_stream_event* events_out_host,
                          uint8_t* frames_out_host, int frame_row, ria_ring_stream_result* result_out_host);
+
+/* ---- the MC-DPSK link on recordings longer than the ring buffer ---------------------------------------------------------------
+ * ria_gpu_mcdpsk_ring_batch is ria_gpu_rx_ring_batch's loop for the two MC-DPSK modes (RIA_SEARCH_OFDM_LTS is RIA_ERR_INVALID)
+ * with what ria_gpu_mcdpsk_stream_batch adds to the stream call: a chase pool on the audio clock, channel interleaving, and
+ * re-entry at a NEED_SAMPLES window.  It replaces, for such recordings, gui::StreamingDecoder::processBuffer's loop
+ * (src/gui/modem/streaming_decoder.cpp:293-384) with the SYNC_FOUND wait (:943-1019, pending_total_cw_) and the ChaseCache the
+ * reference's MC-DPSK decode keeps between receptions.  Steps 1 to 6 are the ring call's: the ring search, RIA_STREAM_SPAN_LOST,
+ * windows cut from the capture by absolute index with abs_base = abs_search_start, last_decoded_sync rebased on the ring, the
+ * cursor and last_decoded_sync_pos written back as ring indices, total_fed assigned by its rule, events in capture indices,
+ * ria_ring_stream_result with its counters; every decode is ria_gpu_mcdpsk_window_batch's.  The rules it adds are
+ * ria_amd/csrc/mcdpsk_ring_rules.hpp's.  h is at RIA_RATE_1_4; frame_row >= RIA_MACQ_FRAME_BYTES(8).  With pool NULL,
+ * window_flags 0 and no stream pending, events, payload rows, results and the `ring` part of the state equal
+ * ria_gpu_rx_ring_batch's byte for byte; on captures of at most 959 999 samples the call equals ria_gpu_mcdpsk_stream_batch.
+ *
+ * Time for the cache.  Every window of stream s is decoded at now_ms = t0_ms_dev[s] + (uint64)abs_position * 1000 / sample_rate,
+ * abs_position the sync's ABSOLUTE (capture) index, never its ring index: on the ring index the cache's clock would jump back
+ * 20 s at every lap, and the pool's age (now - last access, signed) would turn negative there, so an entry past its TTL
+ * would still combine.  A re-entered window uses pend_sync_position, hence the same now_ms as before.  Cache ids, pool NULL, a pool of another handle, window_flags / interleaver_bits with their errors, and "successive
+ * windows of a stream run in successive rounds" are the MC-DPSK stream call's, unchanged.
+ *
+ * The up-front check runs on the device ahead of everything and is read with the call's first control read, before any state,
+ * cache or output is written.  RIA_ERR_INVALID for the whole call: a capture or `ring` state outside
+ * ria_gpu_search_ring_batch's domain; a configuration whose `full` window exceeds 959 999; two streams with the same cache id
+ * >= 0, or an id >= n_caches; pending_total_cw outside 0..255; with pending_total_cw > 0, a negative need_samples, a
+ * pend_search_start or pend_sync_position outside [0, capture_len), capture_len - pend_search_start < search_len, a span
+ * pend_sync_position - pend_search_start + need_samples above 959 999 (it does not fit one ring: the reference cannot wait for
+ * it), or a window whose first sample the ring no longer holds or whose search span it was never fed (ring.total_fed -
+ * pend_search_start > 960 000, or pend_search_start + search_len > ring.total_fed): no state the reference can reach.
+ *
+ * Pending, written.  A window that answers RIA_MWIN_NEED_SAMPLES records its event, closes the stream with
+ * RIA_STREAM_WINDOW_NEED_SAMPLES and writes the eight pending fields, pend_search_start = abs_search_start and
+ * pend_sync_position = abs_position (CAPTURE indices; they fit int32_t, captures end at 2^31 - 1 - 960 000), the three window
+ * parameters it was called with and the search's correlation.  Every other window outcome writes the eight fields as zero.
+ *
+ * Pending, read.  A stream that comes in with pending_total_cw > 0 is not searched in the first round.
+ *   - capture_len >= pend_sync_position + need_samples: it gets, in a round of its own ahead of the first search leg, the
+ *     window [pend_search_start, pend_search_start + min(capture_len - pend_search_start, max(full, pend_sync_position -
+ *     pend_search_start + need_samples))) with the stored parameters, abs_base = pend_search_start and pending_total_cw as
+ *     the window call's re-entry input.  total_fed = max(total_fed, pend_sync_position + need_samples) is applied first, then
+ *     last_decoded_sync is rebased against pend_search_start modulo the ring, then the ring call's state rule (its step 5)
+ *     runs.  Neither assignment of total_fed is a feedAudio: backlog plus arrivals stay below 960 000 because the re-entered
+ *     span is at most 959 999 (mcdpsk_ring_rules.hpp, mcring_reentry_arrival).  The event's positions and correlation come
+ *     from the pending fields, snr_db from ring.snr_hint.  After that the stream searches on like any other.
+ *   - otherwise it closes at once with RIA_STREAM_WINDOW_NEED_SAMPLES, no event, and its state unchanged bit for bit.
+ *
+ * Outputs: every row of every output is written, zero where nothing applies - events_dev, frames_dev, result_dev and
+ * harq_dev (nullable; row s * max_events + e is the ria_mcdpsk_harq_result of event e's window).  n_streams == 0 is RIA_OK.
+ * RIA_ERR_INVALID leaves everything as it was.  After RIA_ERR_HIP state_dev is unspecified, as in the MC-DPSK stream call.
+ *
+ * Work: ria_gpu_rx_ring_batch's rounds and reads; ahead of them the up-front check (one small device-to-host read) and, only
+ * when a stream comes in pending, the re-entry round (the pending list, its window calls and the open list).  Thread per
+ * stream or per window, every list an ascending scan: no result depends on chunking, grouping or scheduling.  The window
+ * gather indexes the captures in 64 bits and reads only inside a stream's own [0, capture_len).  The ring search works on a
+ * contiguous copy of the states' `ring` parts, written back behind the last round.  The workspace lives on h, is carved once
+ * per size - with room for one re-entered window of 959 999 samples - and reserved before the call's first launch; windows go
+ * in chunks of at most 256 MiB.
+ *
+ * Still out of scope: OFDM and burst groups on the ring, the ZC-miss -> chirp fallback, OFDM-COX, and the frame timeout (the
+ * caller's clock: it zeroes pending_total_cw, and the stream then searches from its cursor).
+ * ria_gpu_mcdpsk_ring_host takes one recording of any length in the domain from host memory, staged in pieces as
+ * ria_gpu_rx_ring_host does; pool (nullable) stays on the device, the stream uses cache cache_id at clock t0_ms; harq_out_host
+ * (nullable) takes max_events records. */
+typedef struct ria_mcdpsk_ring_state {   /* 80 bytes, one per stream */
+    ria_ring_state ring;                 /* as ria_gpu_rx_ring_batch reads and writes it */
+    int32_t pending_total_cw;            /* 0: searching; n > 0: waiting at a found sync (SYNC_FOUND with pending_total_cw_ = n) */
+    int32_t need_samples;                /* samples from pend_sync_position the next pass waits for */
+    int32_t pend_search_start;           /* CAPTURE (absolute) index of sample 0 of the window that answered NEED_SAMPLES */
+    int32_t pend_sync_position;          /* CAPTURE (absolute) index */
+    float   pend_known_cfo_hz, pend_detect_threshold, pend_min_confidence, pend_correlation;
+                                         /* the window parameters that repeat the detection, and the event's correlation */
+} ria_mcdpsk_ring_state;
+int ria_gpu_mcdpsk_ring_batch(ria_gpu_handle h, int mode /* RIA_SEARCH_MCDPSK_ZC | RIA_SEARCH_MCDPSK_CHIRP */,
+                              uint32_t flags /* RIA_SEARCH_CONNECTED */, uint32_t window_flags /* 0 | RIA_MACQ_CHANNEL_INTERLEAVE */,
+                              int interleaver_bits, const ria_mcdpsk_config* cfg,
+                              const float* samples_dev, int64_t stride, const int32_t* capture_len_dev, int n_streams,
+                              ria_mcdpsk_ring_state* state_dev, int feed_step, int max_invocations, int max_events,
+                              ria_chase_pool pool /* nullable */, const int32_t* cache_id_dev /* [n_streams], < 0: off */,
+                              const uint64_t* t0_ms_dev /* [n_streams] */,
+                              ria_stream_event* events_dev, uint8_t* frames_dev, int frame_row,
+                              ria_mcdpsk_harq_result* harq_dev /* nullable, [n_streams * max_events], parallel to events_dev */,
+                              ria_ring_stream_result* result_dev, void* stream);
+int ria_gpu_mcdpsk_ring_host(ria_gpu_handle h, int mode, uint32_t flags, uint32_t window_flags, int interleaver_bits,
+                             const ria_mcdpsk_config* cfg, const float* samples_host, int n_samples,
+                             ria_mcdpsk_ring_state* state_host /* in and out */, int feed_step, int max_invocations, int max_events,
+                             ria_chase_pool pool /* nullable */, int32_t cache_id, uint64_t t0_ms,
+                             ria_stream_event* events_out_host, uint8_t* frames_out_host, int frame_row,
+                             ria_mcdpsk_harq_result* harq_out_host /* nullable */, ria_ring_stream_result* result_out_host);
 
 /* ---- debug / test hooks ----------------------------------------------------------------------- */
 /* op: 0 sinf 1 cosf 2 logf 3 atan2f(a,b) 4 hypotf(a,b) 5 a/b 6 sqrtf(a); evaluates the device

@@ -859,6 +859,158 @@ def rx_ring(engine, captures, capture_len, mode, control_engine=None, feed_step=
     return events, state, closed, counters
 
 
+# ---- the MC-DPSK link on recordings longer than the ring buffer (ria_gpu_mcdpsk_ring_batch as a composition)
+def mcdpsk_link_ring(engine, captures, capture_len, mode, state=None, feed_step=4800, max_invocations=1 << 20, max_events=256, connected=False,
+                     carriers=10, modulation="DBPSK", spreading=1, chase=None, cache_id=None, t0_ms=None, channel_interleave=False,
+                     interleaver_bits=None):
+    """RxEngine.mcdpsk_ring as a composition of RxEngine.search_ring and RxEngine.mcdpsk_window with the host's part between
+    them in Python: rx_ring's loop for the two MC-DPSK modes - windows cut by absolute index, cursor and last decoded position
+    on the ring - with what mcdpsk_link_stream adds to rx_stream: the pool (stream s on cache cache_id[s], default s, at
+    t0_ms[s] + ABSOLUTE sync position * 1000 // sample rate), channel interleaving, and the pending rules with absolute
+    positions in the state.  It is to rx_ring what mcdpsk_link_stream is to rx_stream.  A pending state outside the call's
+    domain is a ValueError.  Returns (state (MCRING_STATE), closed (RIA_STREAM_* per stream), events (STREAM_EVENT
+    [n, max_events]), frames uint8 [n, max_events, 320], harq (HARQ_RESULT [n, max_events]), counters (RING_COUNTERS summed
+    over the legs, int64 [n, 4])): the records of the one-call form; link_stream_tally works on events and harq."""
+    n = captures.shape[0]
+    m = capi.SEARCH_MODE[mode] if isinstance(mode, str) else int(mode)
+    assert m != capi.SEARCH_MODE["OFDM_LTS"]
+    chirp = m == capi.SEARCH_MODE["MCDPSK_CHIRP"]
+    rate = int(engine.cfg.sample_rate)      # the rate of the audio clock
+    ring = capi.RING_SAMPLES
+    lens = np.empty(n, np.int64)
+    lens[:] = capture_len
+    state = (engine.mcdpsk_ring_state(n, total_fed=0 if feed_step else lens) if state is None else np.array(state, engine.MCRING_STATE)).copy()
+    ids = np.arange(n, dtype=np.int32) if cache_id is None else np.broadcast_to(np.asarray(cache_id, np.int32), (n,))
+    t0 = np.broadcast_to(np.asarray(0 if t0_ms is None else t0_ms, np.uint64), (n,))
+    bps = {"DBPSK": 1, "DQPSK": 2}[modulation] if isinstance(modulation, str) else int(modulation)
+    search_len = capi.SEARCH_MIN_SEARCH[m]
+    first_frame = mcdpsk_frame_len(1, carriers, bps, spreading)
+    full = search_len + mcdpsk_frame_len(8, carriers, bps, spreading)
+    if full > ring - 1:
+        raise ValueError("the window of this configuration is longer than the ring buffer")
+    ne, row = int(max_events), engine.MCWIN_FRAME_ROW
+    events = np.zeros((n, ne), engine.STREAM_EVENT)
+    harq = np.zeros((n, ne), engine.HARQ_RESULT)
+    frames = np.zeros((n, ne, row), np.uint8)
+    n_events = np.zeros(n, np.int64)
+    closed = np.zeros(n, np.int32)
+    counters = np.zeros((n, len(RING_COUNTERS)), np.int64)
+    rfields = engine.RING_STATE.names
+
+    def windows(rows, det, wl, pending):
+        """one window call on streams `rows` (one window length), det: per row abs_search_start, abs_position, known_cfo_hz,
+        detect_threshold, min_confidence, correlation, snr_db; then the host's part, modulo the ring"""
+        det = {k: det[k].copy() for k in det.dtype.names}
+        starts, syncs = det["abs_search_start"], det["abs_position"]
+        w = _gather_windows(captures, rows, starts, wl)
+        last_in = state["last_decoded_sync_pos"][rows].astype(np.int64)
+        d = (last_in - starts) % ring                    # the circular difference to the window's origin, in -480 000 .. 479 999
+        d = np.where(d >= ring // 2, d - ring, d)
+        rel = np.where(last_in == capi.SEARCH_NO_LAST_SYNC, capi.MWIN_NO_LAST_SYNC, d)
+        conf = np.minimum(det["min_confidence"], det["correlation"])
+        with np.errstate(over="ignore"):
+            now = t0[rows] + syncs.astype(np.uint64) * np.uint64(1000) // np.uint64(rate)
+        f, wres, acq, hq = engine.mcdpsk_window(w, search_len, carriers=carriers, modulation=bps, spreading=spreading, sync="chirp" if chirp else "zc",
+                                                disconnected=chirp and not connected, known_cfo=det["known_cfo_hz"],
+                                                detect_threshold=det["detect_threshold"], min_confidence=conf, abs_base=starts,
+                                                last_decoded_sync=rel, pending_total_cw=pending, chase=chase,
+                                                cache_id=ids[rows] if chase is not None else -1, now_ms=now,
+                                                channel_interleave=channel_interleave, interleaver_bits=interleaver_bits)
+        f = f.cpu().numpy()
+        need = capi.MWIN_OUTCOME["NEED_SAMPLES"]
+        for k, s in enumerate(rows):
+            e = events[s, n_events[s]]
+            outcome, nxt, start, sync = int(wres["outcome"][k]), int(wres["next_pos"][k]), int(starts[k]), int(syncs[k])
+            e["sync_position"], e["search_start"], e["window_len"], e["outcome"] = sync, start, wl, outcome
+            e["next_pos"] = start + nxt if nxt >= 0 else -1
+            e["frame_bytes"], e["need_samples"], e["pending_total_cw"] = acq["frame_bytes"][k], wres["need_samples"][k], wres["pending_total_cw"][k]
+            e["delivered"] = wres["deliver"][k] != 0
+            for name in ("success", "codewords_ok", "codewords_failed", "frame_type"):
+                e[name] = acq[name][k]
+            e["correlation"], e["cfo_hz"], e["fading_index"], e["snr_db"] = det["correlation"][k], acq["cfo_hz"][k], acq["fading_index"][k], det["snr_db"][k]
+            if e["delivered"]:
+                nb = min(int(acq["frame_bytes"][k]), row)
+                frames[s, n_events[s], :nb] = f[k, :nb]
+            if chase is not None:
+                harq[s, n_events[s]] = hq[k]
+            if outcome == capi.MWIN_OUTCOME["DECODED"]:
+                state["last_cfo_hz"][s], state["fading_hint"][s] = acq["cfo_hz"][k], acq["fading_index"][k]
+            out_last = int(wres["last_decoded_sync"][k])
+            state["last_decoded_sync_pos"][s] = capi.SEARCH_NO_LAST_SYNC if out_last == capi.MWIN_NO_LAST_SYNC else (out_last + start) % ring
+            abs_cursor = None
+            if nxt >= 0:
+                abs_cursor = start + nxt
+            elif outcome == capi.MWIN_OUTCOME["TOO_LONG"]:
+                abs_cursor = sync + first_frame
+            if abs_cursor is not None:
+                state["correlation_pos"][s] = abs_cursor % ring
+                state["total_fed"][s] = max(int(state["total_fed"][s]), min(int(lens[s]), abs_cursor))
+            keep = outcome == need
+            vals = (wres["pending_total_cw"][k], wres["need_samples"][k], start, sync, det["known_cfo_hz"][k], det["detect_threshold"][k], conf[k],
+                    det["correlation"][k])
+            for name, v in zip(PENDING_FIELDS, vals):
+                state[name][s] = v if keep else 0
+            n_events[s] += 1
+            if keep:
+                closed[s] = capi.RING_STREAM_CLOSED["WINDOW_NEED_SAMPLES"]
+            elif n_events[s] >= ne:
+                closed[s] = capi.RING_STREAM_CLOSED["EVENTS_FULL"]
+
+    det_dtype = np.dtype([("abs_search_start", "<i8"), ("abs_position", "<i8"), ("known_cfo_hz", "<f4"), ("detect_threshold", "<f4"),
+                          ("min_confidence", "<f4"), ("correlation", "<f4"), ("snr_db", "<f4")])
+    # the streams that wait at a found sync: their window, if its samples are there, ahead of the first search
+    pend = np.flatnonzero(state["pending_total_cw"] > 0)
+    by_len = {}
+    for s in pend:
+        sync, need, start = int(state["pend_sync_position"][s]), int(state["need_samples"][s]), int(state["pend_search_start"][s])
+        fed = int(state["total_fed"][s])
+        if not (state["pending_total_cw"][s] <= 255 and need >= 0 and 0 <= start < lens[s] and 0 <= sync < lens[s] and lens[s] - start >= search_len and
+                sync - start + need <= ring - 1 and fed - start <= ring and start + search_len <= fed):
+            raise ValueError(f"stream {s}: pending fields outside the call's domain")
+        if lens[s] >= sync + need:
+            by_len.setdefault(int(min(lens[s] - start, max(full, sync - start + need))), []).append(s)
+        else:
+            closed[s] = capi.RING_STREAM_CLOSED["WINDOW_NEED_SAMPLES"]
+    for wl in sorted(by_len):
+        rows = np.asarray(by_len[wl])
+        det = np.zeros(len(rows), det_dtype)
+        for a, b in (("abs_search_start", "pend_search_start"), ("abs_position", "pend_sync_position"), ("known_cfo_hz", "pend_known_cfo_hz"),
+                     ("detect_threshold", "pend_detect_threshold"), ("min_confidence", "pend_min_confidence"), ("correlation", "pend_correlation"),
+                     ("snr_db", "snr_hint")):
+            det[a] = state[b][rows]
+        state["total_fed"][rows] = np.maximum(state["total_fed"][rows], state["pend_sync_position"][rows].astype(np.int64) + state["need_samples"][rows])
+        windows(rows, det, wl, state["pending_total_cw"][rows].copy())
+    while (closed == 0).any():
+        idx = np.flatnonzero(closed == 0)
+        rstate = np.zeros(len(idx), engine.RING_STATE)
+        for name in rfields:
+            rstate[name] = state[name][idx]
+        res, st = engine.search_ring(captures[torch.as_tensor(idx, device=captures.device)].contiguous() if len(idx) < n else captures, lens[idx],
+                                     rstate, m, feed_step=feed_step, max_invocations=max_invocations, connected=connected, carriers=carriers,
+                                     modulation=modulation, spreading=spreading)
+        for name in rfields:
+            state[name][idx] = st[name]
+        for c, k in enumerate(RING_COUNTERS):
+            counters[idx, c] += res[k].astype(np.int64)
+        found = res["outcome"] == capi.SEARCH_OUTCOME["SYNC_FOUND"]
+        closed[idx[~found]] = res["outcome"][~found]
+        by_len = {}
+        for j in np.flatnonzero(found):
+            if res["span_wraps"][j]:
+                closed[idx[j]] = capi.RING_STREAM_CLOSED["SPAN_LOST"]
+                continue
+            by_len.setdefault(int(min(full, lens[idx[j]] - res["abs_search_start"][j])), []).append(j)
+        for wl in sorted(by_len):
+            js = by_len[wl]
+            det = np.zeros(len(js), det_dtype)
+            for a, b in (("abs_search_start", "abs_search_start"), ("abs_position", "abs_position"), ("known_cfo_hz", "known_cfo_hz"),
+                         ("detect_threshold", "detect_threshold"), ("min_confidence", "min_confidence"), ("correlation", "correlation"),
+                         ("snr_db", "sync_snr_db")):
+                det[a] = res[b][js]
+            windows(idx[js], det, wl, 0)
+    return state, closed, events, frames, harq, counters
+
+
 # ---- the same loop in one call (ria_gpu_rx_stream_batch)
 STREAM_COUNTERS = ("streams", "events", "delivered") + tuple(f"closed_{k.lower()}" for k in capi.STREAM_CLOSED) + \
     ("search_legs",) + SEARCH_COUNTERS[len(capi.SEARCH_OUTCOME):]

@@ -75,6 +75,7 @@ EXPORTS = [
     "ria_gpu_mcdpsk_window_batch", "ria_gpu_mcdpsk_window_host", "ria_gpu_search_batch", "ria_gpu_search_ring_batch",
     "ria_gpu_rx_stream_batch", "ria_gpu_rx_stream_host", "ria_gpu_rx_ring_batch", "ria_gpu_rx_ring_host",
     "ria_gpu_mcdpsk_stream_batch", "ria_gpu_mcdpsk_stream_host",
+    "ria_gpu_mcdpsk_ring_batch", "ria_gpu_mcdpsk_ring_host",
     "ria_link_recommend", "ria_link_data_mode", "ria_link_ofdm_code_rate", "ria_link_cap_initial_rate",
 ]
 
@@ -245,6 +246,10 @@ class McStreamState(C.Structure):
                [(n, C.c_float) for n in ("pend_known_cfo_hz", "pend_detect_threshold", "pend_min_confidence", "pend_correlation")]
 
 
+class McRingState(C.Structure):          # ria_mcdpsk_ring_state, 80 bytes: the pending positions are capture (absolute) indices
+    _fields_ = [("ring", RingState)] + McStreamState._fields_[1:]
+
+
 class RingStreamResult(C.Structure):
     _fields_ = StreamResult._fields_ + [("overflow_dropped", C.c_uint64)] + \
                [(n, C.c_uint32) for n in ("overflows", "drift_snaps", "cursor_inits", "reserved1")]
@@ -361,6 +366,9 @@ def load(build_if_needed=True):
     L.ria_gpu_rx_ring_host.argtypes = [vp, vp, i32, u32, vp, vp, i32, vp, i32, i32, i32, vp, vp, i32, vp]
     L.ria_gpu_mcdpsk_stream_batch.argtypes = [vp, i32, u32, u32, i32, vp, vp, C.c_int64, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp]
     L.ria_gpu_mcdpsk_stream_host.argtypes = [vp, i32, u32, u32, i32, vp, vp, i32, vp, i32, i32, i32, vp, C.c_int32, u64, vp, vp, i32, vp, vp]
+    # ria_mcdpsk_ring_state is 80 bytes: ria_ring_state's 48, then the eight pending fields (RxEngine.MCRING_STATE)
+    L.ria_gpu_mcdpsk_ring_batch.argtypes = [vp, i32, u32, u32, i32, vp, vp, C.c_int64, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp]
+    L.ria_gpu_mcdpsk_ring_host.argtypes = [vp, i32, u32, u32, i32, vp, vp, i32, vp, i32, i32, i32, vp, C.c_int32, u64, vp, vp, i32, vp, vp]
     L.ria_link_recommend.argtypes = [f32, f32, C.POINTER(LinkRecommendation)]
     L.ria_link_recommend.restype = None
     L.ria_link_data_mode.argtypes = [f32, i32, f32, C.POINTER(LinkRecommendation)]

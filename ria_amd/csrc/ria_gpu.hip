@@ -49,6 +49,7 @@
 #include "search_kernels.hip.h"
 #include "stream_kernels.hip.h"
 #include "mcdpsk_stream_kernels.hip.h"
+#include "mcdpsk_ring_kernels.hip.h"
 
 using namespace ria;
 
@@ -3777,13 +3778,13 @@ struct RingStreamWs {
     ria_mcdpsk_acq_result* acq;   // either acquire result
     uint8_t* wframes;
 };
-static RingStreamWs ring_stream_carve(Carver& c, size_t n, size_t chunk, size_t win_stride, size_t wframe_row) {
+static RingStreamWs ring_stream_carve(Carver& c, size_t n, size_t chunk, size_t win_floats, size_t wframe_row) {
     RingStreamWs w;
     w.head = c.take<uint32_t>(4 + 2 * n);
     w.open = c.take<uint32_t>(n);
     w.group = c.take<uint32_t>(n);
     w.sres = c.take<ria_ring_search_result>(n);
-    w.win = c.take<float>(chunk * win_stride);
+    w.win = c.take<float>(win_floats);
     w.par = c.take<ria_acq_params>(chunk);
     w.wres = c.take<ria_window_result>(chunk);
     w.acq = c.take<ria_mcdpsk_acq_result>(chunk);
@@ -3812,7 +3813,7 @@ int ria_gpu_rx_ring_batch(ria_gpu_handle h, ria_gpu_handle control_h, int mode, 
     const long long win_stride = (static_cast<long long>(full) + 3) & ~3LL;          // rows of the window workspace start on 16 bytes
     int chunk = static_cast<int>(std::min<size_t>(n, std::max<size_t>(1, (size_t(256) << 20) / (static_cast<size_t>(win_stride) * sizeof(float)))));
     chunk = std::min(chunk, 65535);                    // the gather's grid y extent
-    auto carve = [&](Carver& c) { return ring_stream_carve(c, n, static_cast<size_t>(chunk), static_cast<size_t>(win_stride), static_cast<size_t>(min_row)); };
+    auto carve = [&](Carver& c) { return ring_stream_carve(c, n, static_cast<size_t>(chunk), static_cast<size_t>(chunk) * static_cast<size_t>(win_stride), static_cast<size_t>(min_row)); };
     const size_t head_bytes = (4 + 2 * n) * sizeof(uint32_t);
     HIP_TRY(h, h->d_stream_ws.reserve(carved_size(carve), &s));
     HIP_TRY(h, h->p_stream_ctl.reserve(head_bytes));
@@ -3902,6 +3903,25 @@ int ria_gpu_rx_ring_batch(ria_gpu_handle h, ria_gpu_handle control_h, int mode, 
     return RIA_OK;
 }
 
+// a recording of n_samples (checked by the caller) from host memory into the handle's device buffer, in pieces through the
+// pinned block; *rec_out: where it lies.  The handle's stream is idle when this returns.
+static int ring_stage_recording(ria_gpu_handle h, const float* samples_host, int n_samples, float** rec_out) {
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t piece = size_t(1) << 18;                            // samples per piece: 1 MiB of the pinned block
+    if (int rc = ensure_host_stage(h, piece * sizeof(float))) return rc;
+    hipStream_t hs = h->hstream;
+    HIP_TRY(h, h->d_ring_rec.reserve(static_cast<size_t>(std::max(n_samples, 1)) * sizeof(float), &hs));
+    float* rec = h->d_ring_rec.as<float>();
+    for (size_t at = 0; at < static_cast<size_t>(n_samples); at += piece) {
+        const size_t cnt = std::min(piece, static_cast<size_t>(n_samples) - at);
+        std::memcpy(h->p_hstage.as<unsigned char>(), samples_host + at, cnt * sizeof(float));
+        HIP_TRY(h, hipMemcpyAsync(rec + at, h->p_hstage.as<unsigned char>(), cnt * sizeof(float), hipMemcpyHostToDevice, hs));
+        HIP_TRY(h, hipStreamSynchronize(hs));                        // the pinned block is free for the next piece
+    }
+    *rec_out = rec;
+    return RIA_OK;
+}
+
 // One recording of any length in the domain from host memory.  It goes up in pieces through the handle's pinned block into
 // a device buffer the handle owns, grown before anything is in flight; the small records are staged like
 // ria_gpu_rx_stream_host's.
@@ -3917,18 +3937,8 @@ int ria_gpu_rx_ring_host(ria_gpu_handle h, ria_gpu_handle control_h, int mode, u
     if (n_samples < 0 || n_samples > kRingMaxCapture || feed_step < 0 || max_invocations < 1)
         return fail(h, RIA_ERR_INVALID, "%s: bad argument (0 <= n_samples <= 2^31 - 1 - 960000, feed_step >= 0, max_invocations >= 1)", who);
     if (!samples_host || !state_host || !events_out_host || !frames_out_host || !result_out_host) return fail(h, RIA_ERR_INVALID, "%s: null pointer", who);
-    HIP_TRY(h, hipSetDevice(h->device));
-    const size_t piece = size_t(1) << 18;                            // samples per piece: 1 MiB of the pinned block
-    if (int rc = ensure_host_stage(h, piece * sizeof(float))) return rc;
-    hipStream_t hs = h->hstream;
-    HIP_TRY(h, h->d_ring_rec.reserve(static_cast<size_t>(std::max(n_samples, 1)) * sizeof(float), &hs));
-    float* rec = h->d_ring_rec.as<float>();
-    for (size_t at = 0; at < static_cast<size_t>(n_samples); at += piece) {
-        const size_t cnt = std::min(piece, static_cast<size_t>(n_samples) - at);
-        std::memcpy(h->p_hstage.as<unsigned char>(), samples_host + at, cnt * sizeof(float));
-        HIP_TRY(h, hipMemcpyAsync(rec + at, h->p_hstage.as<unsigned char>(), cnt * sizeof(float), hipMemcpyHostToDevice, hs));
-        HIP_TRY(h, hipStreamSynchronize(hs));                        // the pinned block is free for the next piece
-    }
+    float* rec = nullptr;
+    if (int rc = ring_stage_recording(h, samples_host, n_samples, &rec)) return rc;
     const int32_t cap = n_samples;
     const size_t ne = static_cast<size_t>(max_events);
     struct Stage { int32_t* cap; ria_ring_state* st_in; ria_ring_state* st; ria_stream_event* ev; uint8_t* frames; ria_ring_stream_result* res; };
@@ -3944,6 +3954,237 @@ int ria_gpu_rx_ring_host(ria_gpu_handle h, ria_gpu_handle control_h, int mode, u
                                        max_events, d.ev, d.frames, frame_row, d.res, s);
         if (rc != RIA_OK) return rc;
         if (hipMemcpyAsync(d.st, d.st_in, sizeof(ria_ring_state), hipMemcpyDeviceToDevice, s) != hipSuccess)
+            return fail(h, RIA_ERR_HIP, "%s: the state's copy failed", who);
+        return static_cast<int>(RIA_OK); });
+}
+
+// ------------------------------------------------------------------------------------------------ the MC-DPSK loop on the ring: chase pool, interleaving, re-entry
+static_assert(sizeof(ria_mcdpsk_ring_state) == 80 && offsetof(ria_mcdpsk_ring_state, pending_total_cw) == 48 &&
+              offsetof(ria_mcdpsk_ring_state, pend_search_start) == 56 && offsetof(ria_mcdpsk_ring_state, pend_known_cfo_hz) == 64,
+              "ria_gpu_mcdpsk_ring_batch record layout (include/ria_gpu.h)");
+struct McRingWs {
+    McStreamCtl* mctl;
+    ria_ring_state* rstate;       // [n] the `ring` part of the caller's records, contiguous: what the ring search reads and writes
+    int32_t* w_cache_id; uint64_t* w_now_ms; ria_mcdpsk_harq_result* w_harq;   // [chunk]
+};
+static McRingWs mcring_carve(Carver& c, size_t n, size_t chunk) {
+    McRingWs w;
+    w.mctl = c.take<McStreamCtl>(1);
+    w.rstate = c.take<ria_ring_state>(n);
+    w.w_cache_id = c.take<int32_t>(chunk);
+    w.w_now_ms = c.take<uint64_t>(chunk);
+    w.w_harq = c.take<ria_mcdpsk_harq_result>(chunk);
+    return w;
+}
+
+int ria_gpu_mcdpsk_ring_batch(ria_gpu_handle h, int mode, uint32_t flags, uint32_t window_flags, int interleaver_bits, const ria_mcdpsk_config* cfg,
+                              const float* samples_dev, int64_t stride, const int32_t* capture_len_dev, int n_streams,
+                              ria_mcdpsk_ring_state* state_dev, int feed_step, int max_invocations, int max_events,
+                              ria_chase_pool pool, const int32_t* cache_id_dev, const uint64_t* t0_ms_dev,
+                              ria_stream_event* events_dev, uint8_t* frames_dev, int frame_row, ria_mcdpsk_harq_result* harq_dev,
+                              ria_ring_stream_result* result_dev, void* stream) {
+    const char* who = "ria_gpu_mcdpsk_ring_batch";
+    if (!h) return RIA_ERR_INVALID;
+    if (int rc = mcstream_setup(h, who, mode, window_flags, interleaver_bits, pool, cache_id_dev, t0_ms_dev)) return rc;
+    int full = 0, first_frame = 0, min_row = 0;
+    if (int rc = stream_setup(h, nullptr, who, mode, flags, cfg, max_events, frame_row, &full, &first_frame, &min_row)) return rc;
+    if (full > kMcRingMaxSpan) return fail(h, RIA_ERR_INVALID, "%s: the window of this configuration (%d samples) is longer than 959999", who, full);
+    if (n_streams < 0 || stride < 0 || feed_step < 0 || max_invocations < 1)
+        return fail(h, RIA_ERR_INVALID, "%s: bad argument (n_streams >= 0, stride >= 0, feed_step >= 0, max_invocations >= 1)", who);
+    if (n_streams == 0) return RIA_OK;
+    if (!samples_dev || !capture_len_dev || !state_dev || !events_dev || !frames_dev || !result_dev) return fail(h, RIA_ERR_INVALID, "%s: null pointer", who);
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t n = static_cast<size_t>(n_streams);
+    const int search_len = srch_min_search(mode);
+    const long long win_stride = (static_cast<long long>(full) + 3) & ~3LL;          // rows of the window workspace start on 16 bytes
+    int chunk = static_cast<int>(std::min<size_t>(n, std::max<size_t>(1, (size_t(256) << 20) / (static_cast<size_t>(win_stride) * sizeof(float)))));
+    chunk = std::min(chunk, 65535);                    // the gather's grid y extent
+    // a re-entered window runs to the end of the span it waited for, up to 959 999 samples: room for one such row at least
+    const size_t win_floats = std::max<size_t>(static_cast<size_t>(chunk) * static_cast<size_t>(win_stride), static_cast<size_t>(kSrchRing));
+    auto carve = [&](Carver& c) {
+        std::pair<RingStreamWs, McRingWs> w;
+        w.first = ring_stream_carve(c, n, static_cast<size_t>(chunk), win_floats, static_cast<size_t>(min_row));
+        w.second = mcring_carve(c, n, static_cast<size_t>(chunk));
+        return w;
+    };
+    const size_t head_bytes = (4 + 2 * n) * sizeof(uint32_t);
+    HIP_TRY(h, h->d_stream_ws.reserve(carved_size(carve), &s));
+    HIP_TRY(h, h->p_stream_ctl.reserve(std::max(head_bytes, sizeof(McStreamCtl))));
+    const auto carved = carve_at(h->d_stream_ws.as<>(), carve);
+    const RingStreamWs& W = carved.first;
+    const McRingWs& XW = carved.second;
+    uint32_t* mirror = h->p_stream_ctl.as<uint32_t>();
+
+    McRingArgs M{};
+    RingStreamArgs& A = M.S;
+    A.samples = samples_dev; A.stride = stride; A.capture_len = capture_len_dev; A.state = XW.rstate; A.sres = W.sres;
+    A.res = result_dev; A.events = events_dev; A.frames = frames_dev; A.frame_row = frame_row;
+    A.n_streams = n_streams; A.mode = mode; A.family = kStreamMcdpsk; A.full = full; A.first_frame = first_frame;
+    A.max_events = max_events;
+    A.ctl = reinterpret_cast<StreamCtl*>(W.head); A.found = W.head + 4; A.found_len = reinterpret_cast<int32_t*>(W.head + 4 + n);
+    A.open = nullptr; A.group = W.group; A.n_open = n_streams;
+    A.win = W.win; A.win_stride = win_stride; A.wframes = W.wframes; A.wframe_row = min_row;
+    A.mpar = reinterpret_cast<ria_mcdpsk_acq_params*>(W.par); A.mres = reinterpret_cast<const ria_mcdpsk_window_result*>(W.wres); A.macq = W.acq;
+    M.mstate = state_dev; M.harq = harq_dev; M.sres_w = W.sres; M.mctl = XW.mctl;
+    M.sample_rate = h->cfg.sample_rate; M.search_len = search_len;
+    M.w_cache_id = XW.w_cache_id; M.w_now_ms = XW.w_now_ms; M.w_harq = XW.w_harq;
+    if (pool) { M.cache_id = cache_id_dev; M.t0_ms = t0_ms_dev; M.owner = pool->d_owner.as<int32_t>(); M.n_caches = pool->cfg.n_caches; }
+    const uint32_t xflags = (mode == RIA_SEARCH_MCDPSK_CHIRP ? (RIA_MACQ_SYNC_CHIRP | ((flags & RIA_SEARCH_CONNECTED) ? 0u : RIA_MACQ_DISCONNECTED)) : 0u) |
+                            window_flags;
+    const unsigned sgrid = static_cast<unsigned>((n_streams + 255) / 256);
+    bool window_ran = false;
+
+    // the found list as the host read it (n_found streams, their window lengths behind mirror[4 + n]): one pass per distinct
+    // window length, ascending (steps 2.-6. of a round)
+    auto run_windows = [&](int n_found, int longest) -> int {
+        A.n_found = n_found;
+        std::vector<int> lens(mirror + 4 + n, mirror + 4 + n + n_found);
+        std::sort(lens.begin(), lens.end());
+        for (size_t at = 0; at < lens.size();) {
+            const int wl = lens[at];
+            size_t end = at;
+            while (end < lens.size() && lens[end] == wl) ++end;
+            const int n_group = static_cast<int>(end - at);
+            at = end;
+            if (wl < search_len || wl > longest) return fail(h, RIA_ERR_HIP, "%s: a window of %d samples, outside %d..%d", who, wl, search_len, longest);
+            // windows up to `full` lie in rows of win_stride; a longer one (re-entry only) in rows of its own length
+            const long long row_stride = wl <= full ? win_stride : (static_cast<long long>(wl) + 3) & ~3LL;
+            const int row_chunk = wl <= full ? chunk : static_cast<int>(std::min<size_t>(static_cast<size_t>(chunk), win_floats / static_cast<size_t>(row_stride)));
+            A.window_len = wl; A.win_stride = row_stride;
+            hipLaunchKernelGGL(ring_stream_list_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A, kStreamListGroup);
+            for (int first = 0; first < n_group; first += row_chunk) {
+                const int nb = std::min(row_chunk, n_group - first);
+                A.first = first; A.n_chunk = nb;
+                const unsigned tgrid = static_cast<unsigned>((nb + 255) / 256);
+                hipLaunchKernelGGL(mcring_gather_kernel, dim3(static_cast<unsigned>(std::min((wl + 1023) / 1024, 64)), static_cast<unsigned>(nb)), dim3(256), 0, s, M);
+                hipLaunchKernelGGL(mcring_params_kernel, dim3(tgrid), dim3(256), 0, s, M);
+                HIP_TRY(h, hipGetLastError());
+                // a window call may grow its workspaces: the first of the call finds the stream drained by the read above
+                if (window_ran) HIP_TRY(h, hipStreamSynchronize(s));
+                window_ran = true;
+                if (int rc = ria_gpu_mcdpsk_window_batch(h, cfg, W.win, row_stride, search_len, wl, nb, reinterpret_cast<const ria_mcdpsk_acq_params*>(W.par), xflags,
+                                                         W.wframes, min_row, reinterpret_cast<ria_mcdpsk_window_result*>(W.wres), W.acq, nullptr, 0, pool,
+                                                         XW.w_cache_id, XW.w_now_ms, XW.w_harq, interleaver_bits, s)) return rc;
+                hipLaunchKernelGGL(mcring_apply_kernel, dim3(tgrid), dim3(256), 0, s, M);
+                HIP_TRY(h, hipGetLastError());
+            }
+        }
+        return RIA_OK;
+    };
+    // the streams still open (step 7. of a round); *n_open_out 0: the call is over
+    auto list_open = [&](int bound, int* n_open_out) -> int {
+        A.open = W.open;
+        hipLaunchKernelGGL(ring_stream_list_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A, kStreamListOpen);
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(mirror, W.head, sizeof(StreamCtl), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        const int n_open = static_cast<int>(mirror[0]);
+        if (n_open < 0 || n_open > bound) return fail(h, RIA_ERR_HIP, "%s: the open list broke its bound (%d)", who, n_open);
+        *n_open_out = n_open;
+        A.n_open = n_open;
+        return RIA_OK;
+    };
+    // the `ring` part of the state back into the caller's records
+    auto finish = [&]() -> int {
+        hipLaunchKernelGGL(mcring_finish_kernel, dim3(sgrid), dim3(256), 0, s, M);
+        HIP_TRY(h, hipGetLastError());
+        return RIA_OK;
+    };
+
+    // 0. the up-front check - the ring search's domain, the pending fields', the cache ids across the whole call - read before
+    //    anything is written; then the outputs cleared, and the streams that wait at a found sync in a round of their own
+    if (pool) HIP_TRY(h, hipMemsetAsync(M.owner, 0xFF, static_cast<size_t>(M.n_caches) * sizeof(int32_t), s));
+    HIP_TRY(h, hipMemsetAsync(XW.mctl, 0, sizeof(McStreamCtl), s));
+    hipLaunchKernelGGL(mcring_check_kernel, dim3(sgrid), dim3(256), 0, s, M);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(mirror, XW.mctl, sizeof(McStreamCtl), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    const McStreamCtl mc = *reinterpret_cast<const McStreamCtl*>(mirror);
+    if (mc.bad & kMcStreamBadDomain)
+        return fail(h, RIA_ERR_INVALID, "%s: a stream's capture_len is above min(stride, 2^31 - 1 - 960000), its ring state is outside the ring search's domain, "
+                                        "its pending_total_cw is outside 0..255, or its pending fields do not lie in its capture, span more than 959999 "
+                                        "samples or name a window the ring no longer holds; nothing was written", who);
+    if (mc.bad & kMcStreamBadCache)
+        return fail(h, RIA_ERR_INVALID, "%s: two streams of one call use one cache id, or an id is not below n_caches; nothing was written", who);
+    if (mc.n_pending > static_cast<unsigned>(n_streams)) return fail(h, RIA_ERR_HIP, "%s: the pending count broke its bound (%u)", who, mc.n_pending);
+    HIP_TRY(h, hipMemsetAsync(events_dev, 0, n * static_cast<size_t>(max_events) * sizeof(ria_stream_event), s));
+    HIP_TRY(h, hipMemsetAsync(frames_dev, 0, n * static_cast<size_t>(max_events) * static_cast<size_t>(frame_row), s));
+    if (harq_dev) HIP_TRY(h, hipMemsetAsync(harq_dev, 0, n * static_cast<size_t>(max_events) * sizeof(ria_mcdpsk_harq_result), s));
+    hipLaunchKernelGGL(mcring_init_kernel, dim3(sgrid), dim3(256), 0, s, M);
+    if (mc.n_pending > 0) {
+        hipLaunchKernelGGL(mcring_pending_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, M);
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(mirror, W.head, head_bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        const int n_fit = static_cast<int>(mirror[1]);
+        if (n_fit < 0 || n_fit > static_cast<int>(mc.n_pending)) return fail(h, RIA_ERR_HIP, "%s: the pending list broke its bound (%d)", who, n_fit);
+        M.pending_round = 1;
+        if (n_fit > 0) if (int rc = run_windows(n_fit, kMcRingMaxSpan)) return rc;
+        M.pending_round = 0;
+        int n_open = 0;
+        if (int rc = list_open(n_streams, &n_open)) return rc;
+        if (n_open == 0) return finish();
+    }
+    HIP_TRY(h, hipGetLastError());
+    for (int round = 0;; ++round) {
+        if (round > max_events) return fail(h, RIA_ERR_HIP, "%s: round %d past max_events + 1", who, round + 1);
+        // 1. the ring search on the open streams: all that do not wait at a sync
+        if (int rc = ring_search_impl(h, who, mode, flags, cfg, samples_dev, stride, capture_len_dev, A.n_open, A.open, XW.rstate, feed_step,
+                                      max_invocations, W.sres, s)) return rc;
+        // 2. the found streams and their window lengths
+        hipLaunchKernelGGL(ring_stream_list_kernel, dim3(1), dim3(kAcqScanThreads), 0, s, A, kStreamListFound);
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(mirror, W.head, head_bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        const int n_found = static_cast<int>(mirror[1]);
+        if (n_found < 0 || n_found > A.n_open) return fail(h, RIA_ERR_HIP, "%s: the found list broke its bound (%d)", who, n_found);
+        if (n_found == 0) break;
+        // 3.-6. one pass per distinct window length, ascending
+        if (int rc = run_windows(n_found, full)) return rc;
+        // 7. the streams still open
+        int n_open = 0;
+        if (int rc = list_open(n_found, &n_open)) return rc;
+        if (n_open == 0) break;
+    }
+    return finish();
+}
+
+// One recording of any length in the domain from host memory, as ria_gpu_rx_ring_host; the pool's caches stay on the device.
+int ria_gpu_mcdpsk_ring_host(ria_gpu_handle h, int mode, uint32_t flags, uint32_t window_flags, int interleaver_bits, const ria_mcdpsk_config* cfg,
+                             const float* samples_host, int n_samples, ria_mcdpsk_ring_state* state_host, int feed_step, int max_invocations,
+                             int max_events, ria_chase_pool pool, int32_t cache_id, uint64_t t0_ms, ria_stream_event* events_out_host,
+                             uint8_t* frames_out_host, int frame_row, ria_mcdpsk_harq_result* harq_out_host, ria_ring_stream_result* result_out_host) {
+    const char* who = "ria_gpu_mcdpsk_ring_host";
+    if (!h) return RIA_ERR_INVALID;
+    if (int rc = mcstream_setup(h, who, mode, window_flags, interleaver_bits, pool, &cache_id, &t0_ms)) return rc;
+    int full = 0, first_frame = 0, min_row = 0;
+    if (int rc = stream_setup(h, nullptr, who, mode, flags, cfg, max_events, frame_row, &full, &first_frame, &min_row)) return rc;
+    if (full > kMcRingMaxSpan) return fail(h, RIA_ERR_INVALID, "%s: the window of this configuration (%d samples) is longer than 959999", who, full);
+    if (n_samples < 0 || n_samples > kRingMaxCapture || feed_step < 0 || max_invocations < 1)
+        return fail(h, RIA_ERR_INVALID, "%s: bad argument (0 <= n_samples <= 2^31 - 1 - 960000, feed_step >= 0, max_invocations >= 1)", who);
+    if (!samples_host || !state_host || !events_out_host || !frames_out_host || !result_out_host) return fail(h, RIA_ERR_INVALID, "%s: null pointer", who);
+    float* rec = nullptr;
+    if (int rc = ring_stage_recording(h, samples_host, n_samples, &rec)) return rc;
+    const int32_t cap = n_samples;
+    const size_t ne = static_cast<size_t>(max_events);
+    struct Stage { int32_t* cap; int32_t* id; uint64_t* t0; ria_mcdpsk_ring_state* st_in; ria_mcdpsk_ring_state* st; ria_stream_event* ev;
+                   uint8_t* frames; ria_mcdpsk_harq_result* harq; ria_ring_stream_result* res; };
+    auto carve = [&](StageCarver& c) {
+        Stage w;
+        w.t0 = c.in(1, const_cast<const uint64_t*>(&t0_ms));
+        w.st_in = c.in(1, const_cast<const ria_mcdpsk_ring_state*>(state_host));
+        w.cap = c.in(1, &cap); w.id = c.in(1, const_cast<const int32_t*>(&cache_id));
+        w.st = c.out(1, state_host); w.ev = c.out(ne, events_out_host); w.frames = c.out(ne * static_cast<size_t>(frame_row), frames_out_host);
+        w.harq = c.out(ne, harq_out_host);
+        w.res = c.out(1, result_out_host);
+        return w;
+    };
+    return host_staged(h, carve, [&](const Stage& d, hipStream_t s) {
+        int rc = ria_gpu_mcdpsk_ring_batch(h, mode, flags, window_flags, interleaver_bits, cfg, rec, std::max(n_samples, 1), d.cap, 1, d.st_in, feed_step,
+                                           max_invocations, max_events, pool, d.id, d.t0, d.ev, d.frames, frame_row, d.harq, d.res, s);
+        if (rc != RIA_OK) return rc;
+        if (hipMemcpyAsync(d.st, d.st_in, sizeof(ria_mcdpsk_ring_state), hipMemcpyDeviceToDevice, s) != hipSuccess)
             return fail(h, RIA_ERR_HIP, "%s: the state's copy failed", who);
         return static_cast<int>(RIA_OK); });
 }

@@ -1055,7 +1055,75 @@ class RxEngine:
                                                   res.ctypes.data))
         return st, res, ev.reshape(1, ne), frames
 
-    MCDFRAME_RESULT = np.dtype([("success", "u1"), ("codewords_ok", "u1"), ("codewords_failed", "u1"), ("frame_type", "u1"),
+    MCRING_STATE = np.dtype(RING_STATE.descr + [("pending_total_cw", "<i4"), ("need_samples", "<i4"), ("pend_search_start", "<i4"),
+                                                ("pend_sync_position", "<i4"), ("pend_known_cfo_hz", "<f4"), ("pend_detect_threshold", "<f4"),
+                                                ("pend_min_confidence", "<f4"), ("pend_correlation", "<f4")])
+
+    @classmethod
+    def mcdpsk_ring_state(cls, n, total_fed=0):
+        """n fresh decoder states (MCRING_STATE, 80 bytes): ring_state()'s fields, then the eight pending fields, zero (searching)"""
+        s = np.zeros(n, cls.MCRING_STATE)
+        for f in cls.RING_STATE.names:
+            s[f] = cls.ring_state(n, total_fed)[f]
+        return s
+
+    def mcdpsk_ring(self, captures, capture_len, mode, state=None, feed_step=4800, max_invocations=1 << 20, max_events=256, connected=False,
+                    carriers=10, modulation="DBPSK", spreading=1, chase=None, cache_id=None, t0_ms=None, channel_interleave=False,
+                    interleaver_bits=None):
+        """mcdpsk_stream for recordings of any length (ria_gpu_mcdpsk_ring_batch): rx_ring's loop for the two MC-DPSK modes
+        with a chase pool on the audio clock (t0_ms[s] + absolute sync position * 1000 // 48000), channel interleaving and
+        re-entry of a window that waits for samples.  state: MCRING_STATE records (mcdpsk_ring_state(); default: fresh
+        decoders, nothing arrived for feed_step > 0); the pending positions and the events' positions are capture (absolute)
+        indices.  Returns (state (MCRING_STATE), results (RING_STREAM_RESULT), events (STREAM_EVENT [n, max_events]), frames
+        uint8 [n, max_events, 320] on the device, harq (HARQ_RESULT [n, max_events]))."""
+        n, stride = captures.shape
+        assert captures.dtype == torch.float32 and captures.is_contiguous()
+        m, cfg, wflags, bits = self._mcstream_in(mode, channel_interleave, interleaver_bits, carriers, modulation, spreading)
+        lens = np.empty(n, np.int32)
+        lens[:] = capture_len
+        if state is None:
+            state = self.mcdpsk_ring_state(n, total_fed=0 if feed_step else lens)
+        st = np.ascontiguousarray(state, self.MCRING_STATE)
+        assert st.shape == (n,)
+        row, ne = self.MCWIN_FRAME_ROW, int(max_events)
+        lens_d = torch.from_numpy(lens).to(self.device)
+        st_d = torch.from_numpy(st.view(np.uint8).reshape(n, 80).copy()).to(self.device)
+        res_d = torch.empty((n, 88), dtype=torch.uint8, device=self.device)
+        ev_d = torch.empty((n * max(ne, 0), 64), dtype=torch.uint8, device=self.device)
+        harq_d = torch.empty((n * max(ne, 0), 32), dtype=torch.uint8, device=self.device)
+        frames = torch.empty((n, max(ne, 0), row), dtype=torch.uint8, device=self.device)
+        ids, t0, _ = self._harq_in(n, cache_id, t0_ms)
+        self._check(self.lib.ria_gpu_mcdpsk_ring_batch(self.h, m, capi.SEARCH_CONNECTED if connected else 0, wflags, bits, C.byref(cfg),
+                                                       _ptr(captures), stride, _ptr(lens_d), n, _ptr(st_d), int(feed_step), int(max_invocations), ne,
+                                                       chase.p if chase is not None else None, _ptr(ids), _ptr(t0), _ptr(ev_d), _ptr(frames), row,
+                                                       _ptr(harq_d), _ptr(res_d), _stream_ptr()))
+        return (self._status_array(st_d, self.MCRING_STATE), self._status_array(res_d, self.RING_STREAM_RESULT),
+                self._status_array(ev_d, self.STREAM_EVENT).reshape(n, ne), frames, self._status_array(harq_d, self.HARQ_RESULT).reshape(n, ne))
+
+    def mcdpsk_ring_host(self, recording, mode, state=None, feed_step=4800, max_invocations=1 << 20, max_events=256, connected=False,
+                         carriers=10, modulation="DBPSK", spreading=1, chase=None, cache_id=0, t0_ms=0, channel_interleave=False,
+                         interleaver_bits=None):
+        """mcdpsk_ring for one recording in host memory (ria_gpu_mcdpsk_ring_host; a float32 numpy array of any length in the
+        domain).  Returns (state, results, events, frames, harq) as mcdpsk_ring does for n = 1, frames as a numpy array."""
+        x = np.ascontiguousarray(recording, np.float32)
+        assert x.ndim == 1
+        m, cfg, wflags, bits = self._mcstream_in(mode, channel_interleave, interleaver_bits, carriers, modulation, spreading)
+        if state is None:
+            state = self.mcdpsk_ring_state(1, total_fed=0 if feed_step else len(x))
+        st = np.ascontiguousarray(state, self.MCRING_STATE).copy()
+        assert st.shape == (1,)
+        row, ne = self.MCWIN_FRAME_ROW, int(max_events)
+        ev = np.zeros(max(ne, 0), self.STREAM_EVENT)
+        harq = np.zeros(max(ne, 0), self.HARQ_RESULT)
+        frames = np.zeros((1, max(ne, 0), row), np.uint8)
+        res = np.zeros(1, self.RING_STREAM_RESULT)
+        self._check(self.lib.ria_gpu_mcdpsk_ring_host(self.h, m, capi.SEARCH_CONNECTED if connected else 0, wflags, bits, C.byref(cfg),
+                                                      x.ctypes.data, len(x), st.ctypes.data, int(feed_step), int(max_invocations), ne,
+                                                      chase.p if chase is not None else None, int(cache_id), int(t0_ms) & (2 ** 64 - 1),
+                                                      ev.ctypes.data, frames.ctypes.data, row, harq.ctypes.data, res.ctypes.data))
+        return st, res, ev.reshape(1, ne), frames, harq.reshape(1, ne)
+
+    MCDFRAME_RESULT =np.dtype([("success", "u1"), ("codewords_ok", "u1"), ("codewords_failed", "u1"), ("frame_type", "u1"),
                                 ("header_total_cw", "<i4"), ("frame_bytes", "<i4"), ("reserved", "<i4")])
     HARQ_RESULT = np.dtype([("seq", "<u2"), ("valid", "u1"), ("entry", "u1"), ("src_hash", "<u4"), ("dst_hash", "<u4"),
                             ("stored_mask", "<u2"), ("sum_mask", "<u2"), ("recovered_mask", "<u2"), ("max_combine", "u1"),

@@ -483,4 +483,40 @@ inline McdpskWindowResult mcdpskWindow(GpuHandle& gpu, const ria_mcdpsk_config& 
     return r;
 }
 
+// StreamingDecoder::processBuffer's loop for the MC-DPSK modes on one recording of any length from host memory
+// (ria_gpu_mcdpsk_ring_host): the ring search, every window's decode with the chase cache `cache_id` of `pool` (null: no
+// chase) on the audio clock t0_ms + absolute sync position, channel interleaving (interleaver_bits > 0), and the wait at a
+// found sync carried in `state` from call to call (positions in capture indices).  `gpu` is an R1/4 handle.  A failure of
+// the library leaves no events and result.closed 0.
+struct McdpskRingResult {
+    ria_ring_stream_result result{};
+    std::vector<ria_stream_event> events;         // result.n_events of them
+    std::vector<ria_mcdpsk_harq_result> harq;     // parallel to events
+    std::vector<Bytes> frames;                    // parallel to events: the delivered bytes, empty where nothing was delivered
+};
+inline McdpskRingResult mcdpskRing(GpuHandle& gpu, const ria_mcdpsk_config& cfg, const float* recording, size_t n_samples, ria_mcdpsk_ring_state& state,
+                                   bool chirp_sync, bool connected, ria_chase_pool pool = nullptr, int32_t cache_id = 0, uint64_t t0_ms = 0,
+                                   int interleaver_bits = 0, int feed_step = 4800, int max_events = 64) {
+    McdpskRingResult r;
+    const size_t ne = max_events > 0 ? static_cast<size_t>(max_events) : 0, row = RIA_MACQ_FRAME_BYTES(8);
+    std::vector<ria_stream_event> ev(ne);
+    std::vector<ria_mcdpsk_harq_result> hq(ne);
+    Bytes buf(ne * row);
+    if (n_samples > size_t(2147483647)) return r;     // past the call's domain, and past its int
+    if (ria_gpu_mcdpsk_ring_host(gpu.get(), chirp_sync ? RIA_SEARCH_MCDPSK_CHIRP : RIA_SEARCH_MCDPSK_ZC, connected ? RIA_SEARCH_CONNECTED : 0u,
+                                 interleaver_bits > 0 ? RIA_MACQ_CHANNEL_INTERLEAVE : 0u, interleaver_bits, &cfg, recording, static_cast<int>(n_samples),
+                                 &state, feed_step, 1 << 20, max_events, pool, cache_id, t0_ms, ev.data(), buf.data(), static_cast<int>(row), hq.data(),
+                                 &r.result) != RIA_OK) {
+        r.result = ria_ring_stream_result{};
+        return r;
+    }
+    const size_t n = static_cast<size_t>(r.result.n_events);
+    r.events.assign(ev.begin(), ev.begin() + static_cast<std::ptrdiff_t>(n));
+    r.harq.assign(hq.begin(), hq.begin() + static_cast<std::ptrdiff_t>(n));
+    for (size_t k = 0; k < n; ++k)
+        r.frames.emplace_back(ev[k].delivered ? Bytes(buf.begin() + static_cast<std::ptrdiff_t>(k * row),
+                                                      buf.begin() + static_cast<std::ptrdiff_t>(k * row) + ev[k].frame_bytes) : Bytes());
+    return r;
+}
+
 }  // namespace ria_host
